@@ -10,6 +10,10 @@ One process per GPU.  Patches are independent, so the batch is sharded over rank
 data-path collective (weak scaling: 32 patches per GPU); the only collectives are the timing
 barrier and the MAX over ranks of the elapsed time.  A step = one PointInterpFlow.forward over
 the rank's 32 patches, inputs resident in HBM.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times exactly --steps steps and prints the line; --full adds every secondary
+measurement and check (roofline, CPU baseline and oracle parity, reduced precision, ...).  --dump-outputs DIR
+writes what the timed path returned in its last step as .npy files (inputs are seeded: same arguments, same inputs).
 """
 import argparse
 import json
@@ -74,6 +78,14 @@ def main():
     ap.add_argument("--cnf-end-times", choices=["pu1k", "init"], default="pu1k",
                     help="--mode cnf: integration end times of the six blocks - pu1k = those of the reference's trained checkpoint "
                          "(weights.CNF_PU1K_END_TIMES), init = 0.5 everywhere (cnf.py:41)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement and check after the timed steps (roofline / per-stage timings, CPU "
+                         "baseline and parity with the oracle, reduced-precision line, pipelined and zero-copy figures, strong scaling "
+                         "and collectives under --gpus N, gradient parity in --mode train); without it a run sets up, warms up, times "
+                         "--steps steps and prints the line")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float32 / "
+                         "float64, at most 64 MB in all: a larger array is replaced by a fixed seeded sample of its elements); rank 0 only")
     args = ap.parse_args()
     # torch's CPU ops default to one OpenMP thread per VISIBLE CPU (128 on the MI355X boxes); a container owns far fewer CPUs' worth of
     # quota, and a pool of spinning threads exhausts it within ms - the whole process, the thread waiting for the GPU included, is
@@ -117,7 +129,7 @@ def main():
             force_collectives(True)
         backend = os.environ.get("PF_BENCH_BACKEND", "nccl")
         rccl_log = None
-        if backend == "nccl" and os.environ.get("PF_BENCH_RCCL_DEBUG", "1") == "1" and args.mode == "infer":
+        if backend == "nccl" and os.environ.get("PF_BENCH_RCCL_DEBUG", "1") == "1" and args.mode == "infer" and args.full:
             # what RCCL says about itself goes to a per-rank file (NCCL_DEBUG_FILE), parsed after the first collective: the line
             # then carries the transport the rings really use (P2P over xGMI / SHM / NET) instead of an assumption
             import tempfile
@@ -246,7 +258,7 @@ def main():
 
     headline_graph, launch_probe = use_graph, None
     if use_graph and gmode == "auto" and pipe == 1 and not zero_copy:
-        n_probe = max(args.steps, 50)
+        n_probe = min(max(args.steps, 50), 200)                  # bounded: the probe's cost must not grow with --steps
 
         def probe_pass(g):
             r = make_runner(1, False, g)
@@ -267,30 +279,18 @@ def main():
                         "chosen": "graph" if headline_graph else "eager",
                         "note": "untimed probe before the timed region, best of two passes per mode, max over ranks; PF_BENCH_GRAPH=1 / 0 force a mode"}
     runner = make_runner(pipe, zero_copy, headline_graph)
+    # the timed region is exactly --steps steps (the caller sizes it from ms_per_step)
     el, (x, logp) = timed(runner)
-    # K steps of this path are a few tens of milliseconds at the driver's K = 20: too short a region to trust on its own.  The
-    # K-step pass is therefore REPEATED (each pass bracketed like the first: barrier + synchronize on both sides) until at least
-    # MIN_TIMED_S of timed work has accumulated; `value` / `ms_per_step` are totals over all passes, `timed_passes` says how many
-    # (every rank derives the same count from the max-over-ranks time of the first pass)
-    MIN_TIMED_S = float(os.environ.get("PF_BENCH_MIN_TIMED_S", "1.0"))
-    t1 = torch.tensor([el], dtype=torch.float64, device=dev)
-    if use_dist:
-        dist.all_reduce(t1, op=dist.ReduceOp.MAX)
-    passes = 1 + (0 if float(t1.item()) >= MIN_TIMED_S else min(int(MIN_TIMED_S / max(float(t1.item()), 1e-6)), 2000))
-    for _ in range(passes - 1):
-        torch.cuda.synchronize(); barrier(); torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        x, logp = runner(args.steps)
-        torch.cuda.synchronize(); barrier(); torch.cuda.synchronize()
-        el += time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"x": x, "logp": logp})
     # per-stage HIP-event times (the roofline's live kernel duration) straight after the timed region, before the secondary legs
     # add another few seconds of load: 5 iterations are sensitive to what ran before them (0.131 vs 0.136 ms for the dominant
     # kernel with the secondary legs in front)
-    prof_stages = net._engine(4).profile_stages(xyz, iters=5) if rank == 0 else None
+    prof_stages = net._engine(4).profile_stages(xyz, iters=5) if rank == 0 and args.full else None
     # secondary figure (never `value`): the same K steps with two of them in flight on two streams - independent batches
     # overlap; what a serving loop with more than one batch queued gets
     el_pipe = None
-    if use_graph and pipe == 1 and not args.no_pipelined:
+    if use_graph and pipe == 1 and not args.no_pipelined and args.full:
         el_pipe, _ = timed(make_runner(2))
         tp = torch.tensor([el_pipe], dtype=torch.float64, device=dev)
         if use_dist:
@@ -298,7 +298,7 @@ def main():
         el_pipe = float(tp.item())
     # secondary figure (never `value`): the batch already in the graph's own input buffer (run.input), no copy in front of the replay
     el_zc = None
-    if use_graph and pipe == 1 and not zero_copy and not args.no_pipelined:
+    if use_graph and pipe == 1 and not zero_copy and not args.no_pipelined and args.full:
         el_zc, _ = timed(make_runner(1, True))
         tz = torch.tensor([el_zc], dtype=torch.float64, device=dev)
         if use_dist:
@@ -309,85 +309,86 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     el = float(t.item())
     patches = (args.total_batch if args.scaling == "strong" else world * args.batch) * args.steps
-    value = patches * passes / el
-    el /= passes                                          # per K-step pass from here on (ms_per_step = el / K)
+    value = patches / el
 
     strong = coll = None
-    if use_dist and args.scaling == "weak":
+    if use_dist and args.scaling == "weak" and args.full:
         # one invocation, both scalings: the weak-scaling figure above is `value`; the same ranks are re-timed
         # on a fixed total of 32 patches (the metric's own batch) and 256 (32 per GPU at 8 GPUs)
         strong = strong_block(args, world, rank, dev, dist, net)
         coll = collectives_probe(args, world, rank, dev, dist)
     out = None
     if rank == 0:
-        # ---- dominant kernel: EdgeConv (units 2..5 share one kernel); live HIP-event timing on the launch stream
         eng = net._engine(4)
-        prof = prof_stages
-        T = args.batch * args.npoint
-        ec_ms = prof["edgeconv5"]                       # C=128 unit (the last one: never fused with a P|Q GEMM): avg ms per launch
-        ec_fl = edgeconv_ref_flops(T, 128, 32, 4, 128)
-        knn_ms = prof["knn"]
-        knn_bytes = T * (3 * 4 + 16 * 4)               # 155 648 B per 2048-pt patch
-        # (kernel, pipe peak, MFMAs executed per point, flops per MFMA, MFMAs per point that are not split overhead)
-        KERNELS = {
-            "f16n": ("edgeconv4_kernel<P=1,NW=16> (units 2-5, split-fp16 natural-scale low half, v_mfma_f32_16x16x32_f16)",
-                     "edgeconv4_kernel", BF16_MFMA_PEAK_TF, 132, 16384.0, 44),
-            "f32": ("edgeconv_kernel<GB=2,NCONV=4,ODIM=128> (units 2-5, v_mfma_f32_16x16x4_f32)",
-                    "edgeconv_kernel<2, 4, 128", FP32_MFMA_PEAK_TF, 352, 2048.0, 352),
-        }
-        kname, kprefix, peak, n_mfma, fl_mfma, n_useful = KERNELS[eng.ec_mode]
-        ec_exec = T * n_mfma * fl_mfma                  # MFMA flops actually issued per launch
-        # roofline.frac = EXECUTED matrix flops / dense peak of the pipe the kernel runs on (= MFMA utilisation at the
-        # nominal 2.4 GHz; rocprof's SQ_VALU_MFMA_BUSY_CYCLES / GRBM_GUI_ACTIVE gives the same ratio at the clock held).
-        # The reference-formulation figure (2 x 16 x 120 832 MAC per point, 5.4x what the P/Q fold leaves to
-        # execute) is kept as algorithmic_vs_fp16_peak; useful_frac discounts the split overhead as well (one of the
-        # three fp16 MFMAs of a product is "the" product, the other two buy fp32 accuracy).
-        roof = {"bound": "mfma", "kernel": kname,
-                "achieved": ec_exec / (ec_ms * 1e-3) / 1e12, "peak": peak, "unit": "TFLOP/s",
-                "frac": ec_exec / (ec_ms * 1e-3) / 1e12 / peak, "traffic": None,
-                "flops_basis": f"executed: {n_mfma} MFMAs x {int(fl_mfma)} flop per point x {T} points per launch; live HIP-event "
-                               "duration on the launch stream",
-                "useful_frac": ec_exec / (ec_ms * 1e-3) / 1e12 / peak * n_useful / n_mfma,
-                "algorithmic_tflops": ec_fl / (ec_ms * 1e-3) / 1e12,
-                "algorithmic_vs_fp16_peak": ec_fl / (ec_ms * 1e-3) / 1e12 / BF16_MFMA_PEAK_TF,
-                "avg_launch_ms": ec_ms}
-        # HBM traffic and the profiler's own duration of the dominant kernel: PMC counters are collected offline with
-        # rocprofv3 (bench.py cannot run under --pmc and time itself); the committed summary of the same command is read
-        # back here so that every number of this object can be recomputed from profiles/ alone.
-        try:
-            with open(os.path.join(ROOT, "profiles", "pmc_latest.json")) as f:
-                pmc = json.load(f)["kernels"]
-            key = [k for k in pmc if k.startswith(kprefix)][0]
-            roof["traffic"] = pmc[key].get("hbm_bytes_per_launch")
-            roof["profile"] = {"file": "profiles/pmc_latest.json", "kernel": key, "avg_launch_ms": pmc[key].get("avg_us", 0.0) / 1e3,
-                               "mfma_util_pct": pmc[key].get("mfma_util_pct"), "shader_clock_ghz": pmc[key].get("shader_clock_ghz")}
-            alg_bytes = T * (512 * 4 + 16 * 4 + 128 * 4)                     # P|Q row + 16 indices + the 128-channel output row, per point
-            if roof["traffic"]:
-                roof["traffic_vs_algorithmic"] = roof["traffic"] / alg_bytes
-            roof["traffic_note"] = ("bytes per launch at 32 x 2048 (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE, gfx950 correction); "
-                                    "algorithmic HBM bytes per launch = PQ 134.2 MB + idx 4.2 MB + out 33.6 MB; the measured figure is an UPPER bound: the x2 "
-                                    "is calibrated for 16-B-per-lane loads only and half of this kernel's gathers are 4-B loads, and Infinity-"
-                                    "Cache hits (the 134 MB table was written by the kernel before) are counted as traffic")
-        except Exception:
-            pass
-        # kNN: north_star asks for HBM GB/s; the kernel is ALU/selection-bound by construction (216 flop/B), so the ALU fraction
-        # is the meaningful roofline.  knn5_kernel (csrc/knn.hip) runs its two sweeps as v_mfma_f32_16x16x4_f32 - 256 pairs per
-        # instruction at 32 cycles per SIMD, i.e. the rate of the vector FMA lanes (64 FLOP / clk / SIMD: the f32 MFMA does not
-        # add throughput over VALU, it replaces 6 operations per pair by 2 lane-slots) - plus 0.5 (v_min3, sweep A) and 1
-        # (v_alignbit, sweep B) VALU lane-slots per pair: 5.5 executed lane-slots per pair against 1024 SIMDs x 16 lanes x 2.4 GHz
-        # = 39.3 T lane-ops/s.  The appends and the exact ranking of the ~22 survivors per query are not counted: the fraction
-        # is sweep arithmetic over the whole kernel time (knn4_kernel, the VALU form it replaced at this shape: 13 per pair).
-        pair_evals = float(args.batch) * args.npoint * args.npoint
-        knn5 = args.batch * ((args.npoint + 63) // 64) >= 1024 and args.npoint <= 4096
-        slots = 5.5 if knn5 else 13.0
-        roof_knn = {"kernel": "knn5_kernel<16> (f32-MFMA filter sweeps + exact ranking)" if knn5 else "knn4_kernel<16>", "bound": "valu",
-                    "avg_launch_ms": knn_ms,
-                    "hbm": {"achieved": knn_bytes / (knn_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                            "frac": knn_bytes / (knn_ms * 1e-3) / 1e9 / HBM_PEAK_GBS},
-                    "valu": {"pair_evals": pair_evals, "lane_slots_per_pair": slots, "achieved": pair_evals * slots / (knn_ms * 1e-3) / 1e12,
-                             "peak": 39.3, "unit": "T lane-ops/s", "frac": pair_evals * slots / (knn_ms * 1e-3) / 1e12 / 39.3}}
-        extra = {"stage_ms": prof, "roofline_knn": roof_knn,
-                 "model_algorithmic_tflops": model_ref_flops_per_patch() * value / world / 1e12}
+        roof = None
+        extra = {"model_algorithmic_tflops": model_ref_flops_per_patch() * value / world / 1e12}
+        if args.full:
+            # ---- dominant kernel: EdgeConv (units 2..5 share one kernel); live HIP-event timing on the launch stream
+            prof = prof_stages
+            T = args.batch * args.npoint
+            ec_ms = prof["edgeconv5"]                       # C=128 unit (the last one: never fused with a P|Q GEMM): avg ms per launch
+            ec_fl = edgeconv_ref_flops(T, 128, 32, 4, 128)
+            knn_ms = prof["knn"]
+            knn_bytes = T * (3 * 4 + 16 * 4)               # 155 648 B per 2048-pt patch
+            # (kernel, pipe peak, MFMAs executed per point, flops per MFMA, MFMAs per point that are not split overhead)
+            KERNELS = {
+                "f16n": ("edgeconv4_kernel<P=1,NW=16> (units 2-5, split-fp16 natural-scale low half, v_mfma_f32_16x16x32_f16)",
+                         "edgeconv4_kernel", BF16_MFMA_PEAK_TF, 132, 16384.0, 44),
+                "f32": ("edgeconv_kernel<GB=2,NCONV=4,ODIM=128> (units 2-5, v_mfma_f32_16x16x4_f32)",
+                        "edgeconv_kernel<2, 4, 128", FP32_MFMA_PEAK_TF, 352, 2048.0, 352),
+            }
+            kname, kprefix, peak, n_mfma, fl_mfma, n_useful = KERNELS[eng.ec_mode]
+            ec_exec = T * n_mfma * fl_mfma                  # MFMA flops actually issued per launch
+            # roofline.frac = EXECUTED matrix flops / dense peak of the pipe the kernel runs on (= MFMA utilisation at the
+            # nominal 2.4 GHz; rocprof's SQ_VALU_MFMA_BUSY_CYCLES / GRBM_GUI_ACTIVE gives the same ratio at the clock held).
+            # The reference-formulation figure (2 x 16 x 120 832 MAC per point, 5.4x what the P/Q fold leaves to
+            # execute) is kept as algorithmic_vs_fp16_peak; useful_frac discounts the split overhead as well (one of the
+            # three fp16 MFMAs of a product is "the" product, the other two buy fp32 accuracy).
+            roof = {"bound": "mfma", "kernel": kname,
+                    "achieved": ec_exec / (ec_ms * 1e-3) / 1e12, "peak": peak, "unit": "TFLOP/s",
+                    "frac": ec_exec / (ec_ms * 1e-3) / 1e12 / peak, "traffic": None,
+                    "flops_basis": f"executed: {n_mfma} MFMAs x {int(fl_mfma)} flop per point x {T} points per launch; live HIP-event "
+                                   "duration on the launch stream",
+                    "useful_frac": ec_exec / (ec_ms * 1e-3) / 1e12 / peak * n_useful / n_mfma,
+                    "algorithmic_tflops": ec_fl / (ec_ms * 1e-3) / 1e12,
+                    "algorithmic_vs_fp16_peak": ec_fl / (ec_ms * 1e-3) / 1e12 / BF16_MFMA_PEAK_TF,
+                    "avg_launch_ms": ec_ms}
+            # HBM traffic and the profiler's own duration of the dominant kernel: PMC counters are collected offline with
+            # rocprofv3 (bench.py cannot run under --pmc and time itself); the committed summary of the same command is read
+            # back here so that every number of this object can be recomputed from profiles/ alone.
+            try:
+                with open(os.path.join(ROOT, "profiles", "pmc_latest.json")) as f:
+                    pmc = json.load(f)["kernels"]
+                key = [k for k in pmc if k.startswith(kprefix)][0]
+                roof["traffic"] = pmc[key].get("hbm_bytes_per_launch")
+                roof["profile"] = {"file": "profiles/pmc_latest.json", "kernel": key, "avg_launch_ms": pmc[key].get("avg_us", 0.0) / 1e3,
+                                   "mfma_util_pct": pmc[key].get("mfma_util_pct"), "shader_clock_ghz": pmc[key].get("shader_clock_ghz")}
+                alg_bytes = T * (512 * 4 + 16 * 4 + 128 * 4)                     # P|Q row + 16 indices + the 128-channel output row, per point
+                if roof["traffic"]:
+                    roof["traffic_vs_algorithmic"] = roof["traffic"] / alg_bytes
+                roof["traffic_note"] = ("bytes per launch at 32 x 2048 (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE, gfx950 correction); "
+                                        "algorithmic HBM bytes per launch = PQ 134.2 MB + idx 4.2 MB + out 33.6 MB; the measured figure is an UPPER bound: the x2 "
+                                        "is calibrated for 16-B-per-lane loads only and half of this kernel's gathers are 4-B loads, and Infinity-"
+                                        "Cache hits (the 134 MB table was written by the kernel before) are counted as traffic")
+            except Exception:
+                pass
+            # kNN: north_star asks for HBM GB/s; the kernel is ALU/selection-bound by construction (216 flop/B), so the ALU fraction
+            # is the meaningful roofline.  knn5_kernel (csrc/knn.hip) runs its two sweeps as v_mfma_f32_16x16x4_f32 - 256 pairs per
+            # instruction at 32 cycles per SIMD, i.e. the rate of the vector FMA lanes (64 FLOP / clk / SIMD: the f32 MFMA does not
+            # add throughput over VALU, it replaces 6 operations per pair by 2 lane-slots) - plus 0.5 (v_min3, sweep A) and 1
+            # (v_alignbit, sweep B) VALU lane-slots per pair: 5.5 executed lane-slots per pair against 1024 SIMDs x 16 lanes x 2.4 GHz
+            # = 39.3 T lane-ops/s.  The appends and the exact ranking of the ~22 survivors per query are not counted: the fraction
+            # is sweep arithmetic over the whole kernel time (knn4_kernel, the VALU form it replaced at this shape: 13 per pair).
+            pair_evals = float(args.batch) * args.npoint * args.npoint
+            knn5 = args.batch * ((args.npoint + 63) // 64) >= 1024 and args.npoint <= 4096
+            slots = 5.5 if knn5 else 13.0
+            roof_knn = {"kernel": "knn5_kernel<16> (f32-MFMA filter sweeps + exact ranking)" if knn5 else "knn4_kernel<16>", "bound": "valu",
+                        "avg_launch_ms": knn_ms,
+                        "hbm": {"achieved": knn_bytes / (knn_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                "frac": knn_bytes / (knn_ms * 1e-3) / 1e9 / HBM_PEAK_GBS},
+                        "valu": {"pair_evals": pair_evals, "lane_slots_per_pair": slots, "achieved": pair_evals * slots / (knn_ms * 1e-3) / 1e12,
+                                 "peak": 39.3, "unit": "T lane-ops/s", "frac": pair_evals * slots / (knn_ms * 1e-3) / 1e12 / 39.3}}
+            extra.update({"stage_ms": prof, "roofline_knn": roof_knn})
         if el_pipe and patches / el_pipe > value:           # reported only when two steps in flight actually beat the headline on this box
             extra["pipelined"] = {"steps_in_flight": 2, "value": patches / el_pipe, "unit": "patches/s",
                                   "ms_per_step": el_pipe / args.steps * 1e3,
@@ -401,7 +402,7 @@ def main():
                                                 "input buffer beforehand (PointInterpFlow.graphed: run.input), i.e. without the device-to-device "
                                                 "copy that `value`'s step carries in front of every replay"}
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and not args.no_cpu_baseline and args.full:
             from oracle import ref_cpu as O
             # cores this process may actually use (the GPU box exposes 256 logical CPUs but a one-GPU
             # job owns a 16-core share; oversubscribing torch's pool makes the baseline meaninglessly slow)
@@ -441,11 +442,10 @@ def main():
                                "abs_cd_diff_vs_common_target": cd_diff,
                                "logp_note": "logp is a batch mean; compared in tests on equal batches"}
         reduced_lib = os.environ.get("PF_LIB_PATH", "").endswith("_f16.so")
-        if world == 1 and not args.no_cpu_baseline and not args.no_reduced and not reduced_lib:
+        if world == 1 and not args.no_cpu_baseline and not args.no_reduced and not reduced_lib and args.full:
             extra["reduced_precision"] = reduced_precision_line(args)
         out = {"metric": "patches/sec x4 2048->8192 (PU1K discrete, eval)", "value": value, "unit": "patches/s",
                "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": el / args.steps * 1e3,
-               "timed_passes": passes, "timed_steps_total": passes * args.steps,
                "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
                # the arithmetic the path computes in: fp32 values, each product as 2-term split-fp16 on the fp16 MFMA
                # with fp32 accumulation (PF_EC_MODE=f32: plain f32 MFMA in the 128-channel EdgeConv units)
@@ -595,7 +595,7 @@ def reduced_precision_line(args):
         return {"skipped": "libpuflow_hip_f16.so not built (python -m puflow_amd.build)"}
     env = dict(os.environ, PF_LIB_PATH=LIB_F16)
     cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(min(args.steps, 100)), "--warmup", str(min(args.warmup, 10)),
-           "--batch", str(args.batch), "--npoint", str(args.npoint), "--cpu-seconds", "3", "--no-reduced"]
+           "--batch", str(args.batch), "--npoint", str(args.npoint), "--cpu-seconds", "3", "--no-reduced", "--full"]
     try:
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=400)
         line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -610,6 +610,32 @@ def reduced_precision_line(args):
             "abs_cd_diff_vs_common_target": par.get("abs_cd_diff_vs_common_target"),
             "knn_idx_exact_match_rate": par.get("knn_idx_exact_match_rate"),
             "note": "same kernels, launches and weights as the headline; only the number of fp16 products per step differs"}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array the timed path returned in its last step, float64 kept, everything else as
+    float32.  If the arrays exceed DUMP_LIMIT_BYTES together, each one over its equal share of the limit is replaced by the
+    elements at a fixed, seeded, sorted sample of its flat indices (the same for the same shape), so that two builds run with
+    the same arguments can still be compared element for element."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrs = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        arrs[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    if sum(a.nbytes for a in arrs.values()) > DUMP_LIMIT_BYTES:
+        share = DUMP_LIMIT_BYTES // len(arrs)
+        for name, a in arrs.items():
+            if a.nbytes > share:
+                keep = share // a.itemsize
+                idx = np.sort(np.random.default_rng(2021).choice(a.size, size=keep, replace=False))
+                arrs[name] = a.reshape(-1)[idx]
+    for name, a in arrs.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return arrs
 
 
 def _ncpu():
@@ -706,6 +732,8 @@ def bench_train(args, world, rank, dev, dist):
     el = time.perf_counter() - t0
     grad_norm_last = float(opt.coef[1]) if hasattr(opt, "coef") else None      # of the last TIMED step (the call profile below runs more)
     tm.check_device_status()                      # EMD barrier time-outs raise, NaN substitutions of the captured steps are printed
+    if args.dump_outputs and rank == 0:           # the last timed step's loss and the parameters it left (flat, in named_parameters order)
+        dump_outputs(args.dump_outputs, {"loss": loss, "parameters": torch.cat([p.detach().reshape(-1).float() for p in tm.parameters()])})
     t = torch.tensor([el], dtype=torch.float64, device=dev)
     if use_dist:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -716,66 +744,67 @@ def bench_train(args, world, rank, dev, dist):
     # 128-channel EdgeConv units (pf_ec_train_bwd: conv_out / growth dA, one split-K launch for all weight gradients, the
     # neighbour scatter, two P|Q GEMMs), priced against the fp32 matrix pipe it runs on (v_mfma_f32_16x16x4_f32).
     # Every rank runs these steps (they contain the gradient all-reduce); rank 0 reports.
-    from puflow_amd._prof import profile_calls
-    with profile_calls() as prof:
-        for _ in range(3):
-            tm.train_step(batch, opt)
-        torch.cuda.synchronize()
-    barrier()
-    if rank == 0:
-        tab = prof.table()
-        calls_ms = {k: v[1] / 3 for k, v in sorted(tab.items(), key=lambda kv: -kv[1][1])[:8]}
-        evs = prof.events.get("pf_ec_train_bwd", [])
-        ms = sorted(a.elapsed_time(b) for a, b in evs)
-        if ms:
-            big = ms[len(ms) // 2:]                                        # 7 units per step: the upper half are the four 128-channel ones
-            ec_ms = sum(big) / len(big)
-            E = args.batch * 256 * 16
-            flops = 2.0 * EC_BWD_MAC_PER_EDGE * E
-            persist = getattr(tm.network, "train_persistent", False) and os.environ.get("PF_TRAIN_PERSIST", "1") != "0"
-            roof = {"bound": "mfma", "kernel": "pf_ec_train_bwd of a 128-channel EdgeConv unit (csrc/train_fused.hip: " +
-                                             ("ec_bwdp_kernel - the dense block's backward as one persistent launch with a grid barrier per "
-                                              "BatchNorm layer - " if persist else "ec_bwdg16_kernel x4, ec_bwd0_kernel, ") +
-                                             "ec_pq_bwd_csr_kernel, ec_dw3_kernel, two gemm2_kernel, ec_assemble_kernel)",
-                    "achieved": flops / (ec_ms * 1e-3) / 1e12, "peak": FP32_MFMA_PEAK_TF, "unit": "TFLOP/s",
-                    "frac": flops / (ec_ms * 1e-3) / 1e12 / FP32_MFMA_PEAK_TF, "traffic": None, "avg_launch_ms": ec_ms,
-                    "flops_basis": f"algorithmic: {EC_BWD_MAC_PER_EDGE} MAC per edge x {E} edges per call, each product once (split-bf16 "
-                                   "products: three v_mfma_f32_16x16x32_bf16 / 32x32x16_bf16 each; the two point GEMMs on v_mfma_f32_16x16x4_f32); live HIP-event duration of the call's launches on the launch stream",
-                    "calls_ms_per_step": calls_ms}
-            # HBM bytes of the same call from the committed PMC summary of the training kernels (collected offline over eager
-            # steps: tools/pmc_cmd.sh + tools/train_eager_steps.py): the launches of one 128-channel unit's backward
-            try:
-                with open(os.path.join(ROOT, "profiles", "pmc_train_latest.json")) as f:
-                    pk = json.load(f)
-                pk = pk.get("kernels", pk)
-                if "gemm2_kernel<2, 2, 1, 1>" in pk:                      # both point GEMMs of the call on 32 x 32 tiles (end of round 5)
-                    gemms = {"gemm2_kernel<2, 2, 1, 1>": 2}
-                elif "gemm2_kernel<2, 2, 2, 2>" in pk:
-                    gemms = {"gemm2_kernel<2, 2, 2, 2>": 2}
-                else:
-                    gemms = {"gemm_kernel<2, 2, 2, 2, true>": 2}          # before round 5
-                group = {"ec_pq_bwd_csr_kernel": 1, "ec_dw3_kernel": 1, **gemms, "ec_assemble_kernel": 1}
-                if "gemm_reduce_kernel" in pk:                            # (until ec_assemble_kernel took over dWpq's slab sums)
-                    group["gemm_reduce_kernel"] = 1
-                group.update({"ec_bwdp_kernel<32, 4, 128>": 1} if persist else {"ec_bwdg16_kernel<2, 0>": 4, "ec_bwd0_kernel": 1})
-                tot, us = 0.0, 0.0
-                for k, n in group.items():
-                    tot += n * pk[k]["hbm_bytes_per_launch"]
-                    us += n * pk[k]["avg_us"]
-                alg = E * 128 * 4 * (1 + 1 + 1) + 8192 * (256 + 512 + 128) * 4      # Y, dA read once, dA written once; dh, dPQ, dx
-                roof["traffic"] = tot
-                roof["traffic_vs_algorithmic"] = tot / alg
-                roof["profile"] = {"file": "profiles/pmc_train_latest.json", "kernels": group, "sum_avg_us": us,
-                                   "note": "FETCH_SIZE x2 + WRITE_SIZE per launch (gfx950 correction), summed over the call's launches; "
-                                           "algorithmic bytes = the [E, 128] growth outputs and their gradient read once and the "
-                                           "gradient written once + the per-point tensors; layer s of the dense block reads the gradient columns of every later layer (gather form), "
-                                           "ec_dw and the dPQ sums read the whole tensor again"}
-            except Exception:
-                pass
-        if world == 1 and not args.no_cpu_baseline:
-            cpu = train_cpu_baseline(sd, dense_cpu, args.cpu_seconds)
-        if world == 1 and not args.no_grad_parity:
-            grad_parity = train_grad_parity(args, step_grads)
+    if args.full:
+        from puflow_amd._prof import profile_calls
+        with profile_calls() as prof:
+            for _ in range(3):
+                tm.train_step(batch, opt)
+            torch.cuda.synchronize()
+        barrier()
+        if rank == 0:
+            tab = prof.table()
+            calls_ms = {k: v[1] / 3 for k, v in sorted(tab.items(), key=lambda kv: -kv[1][1])[:8]}
+            evs = prof.events.get("pf_ec_train_bwd", [])
+            ms = sorted(a.elapsed_time(b) for a, b in evs)
+            if ms:
+                big = ms[len(ms) // 2:]                                        # 7 units per step: the upper half are the four 128-channel ones
+                ec_ms = sum(big) / len(big)
+                E = args.batch * 256 * 16
+                flops = 2.0 * EC_BWD_MAC_PER_EDGE * E
+                persist = getattr(tm.network, "train_persistent", False) and os.environ.get("PF_TRAIN_PERSIST", "1") != "0"
+                roof = {"bound": "mfma", "kernel": "pf_ec_train_bwd of a 128-channel EdgeConv unit (csrc/train_fused.hip: " +
+                                                 ("ec_bwdp_kernel - the dense block's backward as one persistent launch with a grid barrier per "
+                                                  "BatchNorm layer - " if persist else "ec_bwdg16_kernel x4, ec_bwd0_kernel, ") +
+                                                 "ec_pq_bwd_csr_kernel, ec_dw3_kernel, two gemm2_kernel, ec_assemble_kernel)",
+                        "achieved": flops / (ec_ms * 1e-3) / 1e12, "peak": FP32_MFMA_PEAK_TF, "unit": "TFLOP/s",
+                        "frac": flops / (ec_ms * 1e-3) / 1e12 / FP32_MFMA_PEAK_TF, "traffic": None, "avg_launch_ms": ec_ms,
+                        "flops_basis": f"algorithmic: {EC_BWD_MAC_PER_EDGE} MAC per edge x {E} edges per call, each product once (split-bf16 "
+                                       "products: three v_mfma_f32_16x16x32_bf16 / 32x32x16_bf16 each; the two point GEMMs on v_mfma_f32_16x16x4_f32); live HIP-event duration of the call's launches on the launch stream",
+                        "calls_ms_per_step": calls_ms}
+                # HBM bytes of the same call from the committed PMC summary of the training kernels (collected offline over eager
+                # steps: tools/pmc_cmd.sh + tools/train_eager_steps.py): the launches of one 128-channel unit's backward
+                try:
+                    with open(os.path.join(ROOT, "profiles", "pmc_train_latest.json")) as f:
+                        pk = json.load(f)
+                    pk = pk.get("kernels", pk)
+                    if "gemm2_kernel<2, 2, 1, 1>" in pk:                      # both point GEMMs of the call on 32 x 32 tiles (end of round 5)
+                        gemms = {"gemm2_kernel<2, 2, 1, 1>": 2}
+                    elif "gemm2_kernel<2, 2, 2, 2>" in pk:
+                        gemms = {"gemm2_kernel<2, 2, 2, 2>": 2}
+                    else:
+                        gemms = {"gemm_kernel<2, 2, 2, 2, true>": 2}          # before round 5
+                    group = {"ec_pq_bwd_csr_kernel": 1, "ec_dw3_kernel": 1, **gemms, "ec_assemble_kernel": 1}
+                    if "gemm_reduce_kernel" in pk:                            # (until ec_assemble_kernel took over dWpq's slab sums)
+                        group["gemm_reduce_kernel"] = 1
+                    group.update({"ec_bwdp_kernel<32, 4, 128>": 1} if persist else {"ec_bwdg16_kernel<2, 0>": 4, "ec_bwd0_kernel": 1})
+                    tot, us = 0.0, 0.0
+                    for k, n in group.items():
+                        tot += n * pk[k]["hbm_bytes_per_launch"]
+                        us += n * pk[k]["avg_us"]
+                    alg = E * 128 * 4 * (1 + 1 + 1) + 8192 * (256 + 512 + 128) * 4      # Y, dA read once, dA written once; dh, dPQ, dx
+                    roof["traffic"] = tot
+                    roof["traffic_vs_algorithmic"] = tot / alg
+                    roof["profile"] = {"file": "profiles/pmc_train_latest.json", "kernels": group, "sum_avg_us": us,
+                                       "note": "FETCH_SIZE x2 + WRITE_SIZE per launch (gfx950 correction), summed over the call's launches; "
+                                               "algorithmic bytes = the [E, 128] growth outputs and their gradient read once and the "
+                                               "gradient written once + the per-point tensors; layer s of the dense block reads the gradient columns of every later layer (gather form), "
+                                               "ec_dw and the dPQ sums read the whole tensor again"}
+                except Exception:
+                    pass
+            if world == 1 and not args.no_cpu_baseline:
+                cpu = train_cpu_baseline(sd, dense_cpu, args.cpu_seconds)
+            if world == 1 and not args.no_grad_parity:
+                grad_parity = train_grad_parity(args, step_grads)
     if use_dist:
         dist.destroy_process_group()
     if rank == 0:
@@ -991,13 +1020,15 @@ def bench_cnf(args, world, rank, dev, dist):
                  note="nfe / accepted / rejected of one forward on each of the 4 rotating input sets (a fallback counts the discarded "
                       "blind attempts' evaluations too); blind: forwards enqueued without a look at a controller, how many fell back "
                       "to the look-per-batch loop (and from which of the 12 integrations), step attempts enqueued vs taken")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"x": x, "logp": logp})
     t = torch.tensor([el], dtype=torch.float64, device=dev)
     if use_dist:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     el = float(t.item())
     roof = cpu = None
     extra = {}
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- dominant kernel: one dopri5 step attempt (six fused right-hand-side evaluations) on the R-times replicated rows of
         # the inverse pass, timed THROUGH pf_cnf_steps - the entry point and kernel of the timed forward (cnf_step_dev_kernel with
         # the controller on the device; the round-4 line timed pf_cnf_step's host-stepped kernel instead): the block with the
@@ -1138,9 +1169,11 @@ def bench_pugan(args, world, rank, dev, dist):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     el = float(t.item())
     assert tuple(out.shape) == (B, N * UP, 3)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"points": out})
     roof = cpu = None
     extra = {}
-    if rank == 0:
+    if rank == 0 and args.full:
         lib = _lib.load()
 
         def ev_ms(fn, iters=3):

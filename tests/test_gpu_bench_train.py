@@ -15,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.parametrize("graph", ["1", "0"])
 def test_bench_train_fresh_process(graph):
     env = dict(os.environ, PF_BENCH_GRAPH=graph)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "train", "--steps", "4", "--warmup", "2", "--cpu-seconds", "2"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--mode", "train", "--steps", "4", "--warmup", "2", "--cpu-seconds", "2"],
                          cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
@@ -46,7 +46,7 @@ def test_bench_train_fresh_process(graph):
 def test_bench_reduced_precision_line():
     """`python bench.py`: the headline stays the fp32-parity arithmetic; the secondary single-term fp16 line (a child process on
     libpuflow_hip_f16.so) is present, faster, bit-exact in kNN and within Chamfer-distance noise of the fp32 oracle."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "3", "--cpu-seconds", "2"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "3", "--cpu-seconds", "2"],
                          cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -70,7 +70,7 @@ def test_bench_reduced_precision_line():
 def test_bench_pipeline_option_small_batch():
     """`--pipeline 3 --scaling strong --total-batch 4`: three captured graphs on three streams; the JSON line keeps the contract
     (steps, unit) and the results of every graph are the ones of the single-graph run (parity block)."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--scaling", "strong", "--total-batch", "4", "--pipeline", "3",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--scaling", "strong", "--total-batch", "4", "--pipeline", "3",
                           "--steps", "30", "--warmup", "3", "--cpu-seconds", "1", "--no-reduced"],
                          cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -86,7 +86,7 @@ def test_bench_gpus_n_starts_its_own_ranks():
     run.  Rehearsal knobs of the one-GPU box: both ranks on cuda:0, gloo instead of RCCL."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(PF_BENCH_SINGLE_DEVICE="1", PF_BENCH_BACKEND="gloo")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", "4", "--steps", "10", "--warmup", "2",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--batch", "4", "--steps", "10", "--warmup", "2",
                           "--no-pipelined"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -111,7 +111,7 @@ def test_bench_gpus_n_starts_its_own_ranks():
 def test_bench_cnf_line():
     """`bench.py --mode cnf` (BASELINE configs[4]) on a small batch: the contract fields, the solver's work on the scaled
     synthetic ODE (rejected steps included) and the same evaluation / accept / reject counts as the CPU oracle's dopri5."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "cnf", "--batch", "2", "--npoint", "256", "--steps", "2",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--mode", "cnf", "--batch", "2", "--npoint", "256", "--steps", "2",
                           "--warmup", "1", "--cpu-seconds", "1"], cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -138,7 +138,7 @@ def test_bench_train_two_ranks_self_launched():
     eager steps (they contain the gradient all-reduce, so EVERY rank must run them) and the report on rank 0."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(PF_BENCH_SINGLE_DEVICE="1", PF_BENCH_BACKEND="gloo")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--mode", "train", "--batch", "4", "--steps", "3",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--mode", "train", "--batch", "4", "--steps", "3",
                           "--warmup", "1"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -150,7 +150,7 @@ def test_bench_pugan_line():
     """`bench.py --mode pugan` (BASELINE configs[3]: clouds of 5000 -> 20000 points through the patch pipeline) on two clouds:
     contract fields, the FPS merge's latency roofline (rounds counted by the kernel, exchange floor probed live) and coverage
     parity with the CPU oracle pipeline."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "pugan", "--batch", "2", "--steps", "2", "--warmup", "1"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--mode", "pugan", "--batch", "2", "--steps", "2", "--warmup", "1"],
                          cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -165,3 +165,29 @@ def test_bench_pugan_line():
     cpu, par = rec["cpu_baseline"], rec["parity"]
     assert cpu["kind"] == "port" and cpu["value"] > 0 and rec["value"] > 10 * cpu["value"]
     assert par["rel_diff"] < 0.02
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """`python bench.py` without --full: the headline line alone (no secondary legs), and --dump-outputs writes what the timed
+    path returned in its last step - the same x / logp as a forward of the benchmark's seeded batch in this process."""
+    import numpy as np
+    import torch
+    from puflow_amd.interpflow import PointInterpFlow
+    from puflow_amd.weights import synth_patches, synth_state_dict
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "7", "--warmup", "2", "--dump-outputs", str(tmp_path)],
+                         cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert rec["steps"] == 7 and rec["unit"] == "patches/s" and rec["higher_is_better"] is True and rec["dtype"].startswith("f32")
+    assert abs(rec["value"] - 32 / (rec["ms_per_step"] * 1e-3)) < 1e-6 * rec["value"]
+    assert rec["roofline"] is None and rec["cpu_baseline"] is None
+    assert not {"parity", "reduced_precision", "zero_copy_input", "pipelined", "stage_ms", "strong"} & set(rec)
+    x, logp = np.load(tmp_path / "x.npy"), np.load(tmp_path / "logp.npy")
+    assert x.dtype == np.float32 and x.shape == (32, 4 * 2048, 3) and logp.dtype == np.float32
+    net = PointInterpFlow(3)
+    net.load_state_dict(synth_state_dict(2021))
+    net.set_to_initialized_state()
+    net = net.to("cuda:0").eval()
+    xr, lr = net(synth_patches(32, 2048, seed=2021).to("cuda:0"), 4)
+    assert np.abs(x - xr.cpu().numpy()).max() < 1e-5
+    assert abs(float(logp) - float(lr)) <= 1e-5 * abs(float(lr))

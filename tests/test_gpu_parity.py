@@ -188,7 +188,7 @@ def test_forward_matches_reference_golden(lib, golden_dir, name):
 
 
 @pytest.mark.parametrize("case", ["a", "b"])
-def test_forward_matches_reference_with_pretrained_weights(lib, golden_dir, case):
+def test_forward_matches_reference_with_pretrained_weights(lib, pretrained_pu1k, case):
     """HIP output against the REFERENCE's own Python running its own TRAINED checkpoint (pretrain/puflow-x4-pu1k.pt;
     tools/make_golden_pretrained.py): trained-scale activations (|cs| up to 480) through the split-fp16 kernels.
     The contract quantities hold their bars: kNN indices bit-exact, x within 1e-5, log-det / log-likelihood within 1e-5
@@ -196,8 +196,8 @@ def test_forward_matches_reference_with_pretrained_weights(lib, golden_dir, case
     the map cs -> z is ill-conditioned (measured on the CPU oracle: a RELATIVE perturbation of 1e-7 of cs - below fp32
     epsilon - moves z by 9e-5, 1e-6 by 4e-4), so any fp32 evaluation in another summation order, including the f32-MFMA
     mode here, differs from the reference's z by a few 1e-4; g inverts f with the same cs, which is why x does not."""
-    g = np.load(os.path.join(golden_dir, "pretrained_pu1k.npz"))
-    sd = {k[3:]: torch.from_numpy(g[k]) for k in g.files if k.startswith("sd/")}
+    g = pretrained_pu1k
+    sd = {k[3:]: torch.from_numpy(g[k]) for k in g if k.startswith("sd/")}
     B, N, seed = (int(v) for v in g[f"{case}/meta"])
     xyz = synth_patches(B, N, seed=seed, surface=True)
     net = _net(sd)

@@ -23,7 +23,7 @@ def _env():
 
 @pytest.mark.parametrize("graph", ["1", "0"])
 def test_training_step_over_rccl_one_rank(graph):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--mode", "train", "--steps", "3", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--mode", "train", "--steps", "3", "--warmup", "1",
                           "--no-cpu-baseline"], cwd=ROOT, env=dict(_env(), PF_BENCH_GRAPH=graph), capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     assert "capture failed" not in out.stderr
@@ -48,7 +48,7 @@ def test_forced_collectives_do_not_change_the_step():
         if force == "0":
             for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "PF_BENCH_FORCE_DIST"):
                 env.pop(k)
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "train", "--steps", "3", "--warmup", "0",
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--mode", "train", "--steps", "3", "--warmup", "0",
                               "--no-cpu-baseline", "--no-grad-parity"], cwd=ROOT, env=dict(env, PF_BENCH_GRAPH="0", PF_BENCH_DETERMINISTIC="1", PF_BENCH_ACTNORM_INITED="1"),
                              capture_output=True, text=True, timeout=900)
         assert out.returncode == 0, out.stderr[-3000:]
@@ -60,7 +60,7 @@ def test_forced_collectives_do_not_change_the_step():
 
 
 def test_inference_bench_over_rccl_one_rank():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "2", "--no-cpu-baseline",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "10", "--warmup", "2", "--no-cpu-baseline",
                           "--no-reduced"], cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -81,7 +81,7 @@ def test_syncbn_training_step_over_rccl_one_rank(graph):
     """cfg.sync_batchnorm on the fused kernels with RCCL: every BatchNorm layer's 257-double all-reduce (csrc/train_fused.hip
     stat_sync -> train_ops._sync_cb_impl -> dist.all_reduce) between two launches - eager, and CAPTURED into the step's hipGraph
     (graph = 1: graphed_train_step no longer refuses SyncBN when the backend is nccl).  One rank, multi-rank path forced."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--mode", "train", "--steps", "3", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--mode", "train", "--steps", "3", "--warmup", "1",
                           "--no-cpu-baseline", "--no-grad-parity"], cwd=ROOT, env=dict(_env(), PF_BENCH_GRAPH=graph, PF_BENCH_SYNCBN="1"),
                          capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]

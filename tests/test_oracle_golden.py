@@ -69,18 +69,17 @@ def test_state_dict_census(golden_dir):
     assert nparam == 806103
 
 
-def _load_pretrained(golden_dir):
-    g = np.load(os.path.join(golden_dir, "pretrained_pu1k.npz"))
-    sd = {k[3:]: torch.from_numpy(g[k]) for k in g.files if k.startswith("sd/")}
+def _load_pretrained(g):
+    sd = {k[3:]: torch.from_numpy(g[k]) for k in g if k.startswith("sd/")}
     return g, sd
 
 
 @pytest.mark.parametrize("case", ["a", "b"])
-def test_oracle_matches_reference_with_pretrained_weights(golden_dir, case):
+def test_oracle_matches_reference_with_pretrained_weights(pretrained_pu1k, case):
     """The reference's own module with its own TRAINED checkpoint (pretrain/puflow-x4-pu1k.pt, tools/make_golden_pretrained.py):
     the oracle reproduces x, z, the interpolated latent, log-det and log-likelihood on trained-scale activations too."""
     torch.set_num_threads(1)
-    g, sd = _load_pretrained(golden_dir)
+    g, sd = _load_pretrained(pretrained_pu1k)
     B, N, seed = (int(v) for v in g[f"{case}/meta"])
     xyz = synth_patches(B, N, seed=seed, surface=True)
     st = O.forward(sd, xyz, 4, stages=True)

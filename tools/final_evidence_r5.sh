@@ -11,11 +11,11 @@ OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 if [ "$PART" = a ]; then
-  timeout -k 10 400 python3 bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"; tail -1 "$OUT/bench.json" | cut -c1-200
-  timeout -k 10 400 python3 bench.py --mode train --steps 100 --warmup 10 > "$OUT/bench_train.json" 2> "$OUT/bench_train.err"; tail -1 "$OUT/bench_train.json" | cut -c1-200
+  timeout -k 10 400 python3 bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"; tail -1 "$OUT/bench.json" | cut -c1-200
+  timeout -k 10 400 python3 bench.py --full --mode train --steps 100 --warmup 10 > "$OUT/bench_train.json" 2> "$OUT/bench_train.err"; tail -1 "$OUT/bench_train.json" | cut -c1-200
   PF_TRAIN_PERSIST=0 timeout -k 10 300 python3 bench.py --mode train --steps 100 --warmup 10 --no-cpu-baseline --no-grad-parity > "$OUT/bench_train_per_layer.json" 2> /dev/null
-  timeout -k 10 400 python3 bench.py --mode cnf --steps 10 --warmup 2 > "$OUT/bench_cnf.json" 2> "$OUT/bench_cnf.err"; tail -1 "$OUT/bench_cnf.json" | cut -c1-200
-  timeout -k 10 400 python3 bench.py --mode pugan --steps 5 --warmup 2 > "$OUT/bench_pugan.json" 2> "$OUT/bench_pugan.err"; tail -1 "$OUT/bench_pugan.json" | cut -c1-200
+  timeout -k 10 400 python3 bench.py --full --mode cnf --steps 10 --warmup 2 > "$OUT/bench_cnf.json" 2> "$OUT/bench_cnf.err"; tail -1 "$OUT/bench_cnf.json" | cut -c1-200
+  timeout -k 10 400 python3 bench.py --full --mode pugan --steps 5 --warmup 2 > "$OUT/bench_pugan.json" 2> "$OUT/bench_pugan.err"; tail -1 "$OUT/bench_pugan.json" | cut -c1-200
   for B in 4 8 16 32; do
     timeout -k 10 120 python3 bench.py --scaling strong --total-batch $B --steps 100 --warmup 10 --no-cpu-baseline --no-reduced --no-pipelined 2>/dev/null | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('B=%d' % $B, d['value'], d['unit'], d['ms_per_step'], 'ms/step')"
   done > "$OUT/batch_sweep.txt"; cat "$OUT/batch_sweep.txt"

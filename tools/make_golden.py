@@ -19,6 +19,7 @@ import sys
 import types
 
 os.environ["PYTHONDONTWRITEBYTECODE"] = "1"
+os.environ["MKL_CBWR"] = "COMPATIBLE"              # the GEMM branch tests/conftest.py pins: the same rounding on every host
 sys.dont_write_bytecode = True
 
 import numpy as np

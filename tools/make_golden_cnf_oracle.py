@@ -11,6 +11,7 @@ to running the oracle when it does not match (changed seeds, changed synthetic w
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+os.environ["MKL_CBWR"] = "COMPATIBLE"              # the GEMM branch tests/conftest.py pins: the same rounding on every host
 import numpy as np
 import torch
 from oracle import cnf_ref as C

@@ -9,6 +9,7 @@ import os
 import sys
 
 os.environ["PYTHONDONTWRITEBYTECODE"] = "1"
+os.environ["MKL_CBWR"] = "COMPATIBLE"              # the GEMM branch tests/conftest.py pins: the same rounding on every host
 sys.dont_write_bytecode = True
 import numpy as np
 import torch
@@ -39,8 +40,24 @@ def main():
             arrays[f"{name}/{k}"] = a.astype(np.int16) if k == "idx16" else a
         print(name, "x range", float(out["x"].min()), float(out["x"].max()), "logp", out["logp"].numpy())
     path = os.path.join(ROOT, "tests", "golden", "pretrained_pu1k.npz")
-    np.savez_compressed(path, **arrays)
-    print("wrote", path, os.path.getsize(path))
+    if not os.path.exists(path):
+        np.savez_compressed(path, **arrays)
+        print("wrote", path, os.path.getsize(path))
+        return
+    # the committed file (3 MB of checkpoint tensors) stays as it is; the outputs of THIS capture - MKL's COMPATIBLE branch, a few
+    # ulps from the first capture's - go to pretrained_pu1k_compat.npz as exact float32 differences: base + delta == capture
+    # (tests/conftest.py::pretrained_pu1k adds them back)
+    base = np.load(path)
+    delta = {}
+    for k, a in arrays.items():
+        if k.startswith("sd/") or a.dtype != np.float32:
+            assert np.array_equal(base[k], a), f"{k} differs from the committed fixture: rewrite it (delete the file and re-run)"
+            continue
+        delta[k] = a - base[k]
+        assert np.array_equal(base[k] + delta[k], a), k
+    cpath = os.path.join(ROOT, "tests", "golden", "pretrained_pu1k_compat.npz")
+    np.savez_compressed(cpath, **delta)
+    print("wrote", cpath, os.path.getsize(cpath))
 
 
 if __name__ == "__main__":
