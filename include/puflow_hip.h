@@ -700,6 +700,27 @@ int pf_lincomb(const float* const* ptrs, const float* w, int n_terms, float* out
 int pf_scaled_sumsq(const float* a, const float* b, const float* s0, const float* s1, const float* k, const float* w,
                     int n_terms, float h, float rtol, float atol, long long n, double* ws, double* out, void* stream);
 
+/* ---- evaluation metrics (csrc/eval_metrics.hip; the reference's scoring step, evaluation/evaluate.py) ---------------------- */
+
+/* Approx-match EMD (Fan et al.; evaluation/tf_ops/approxmatch): the multi-level soft assignment of xyz1 [B,n,3] to
+ * xyz2 [B,m,3] for levels -4^j, j = top .. -1, then 0, and cost[b] = sum_kl w_kl |a_k - b_l| / n (evaluate.py:59-65).
+ * top = 7 is the CUDA op's schedule (the published numbers), 8 the CPU op's.  The match matrix is never stored: three sweeps
+ * per level recompute it.  Deterministic, and a cloud's result does not depend on B.  top in [-2, 15], n, m <= 2^22, B <= 65535.
+ * ws: pf_approxmatch_ws_floats(B, n, m, top) floats, 8-byte aligned. */
+long long pf_approxmatch_ws_floats(int B, int n, int m, int top);
+int pf_approxmatch_emd(const float* xyz1, const float* xyz2, int B, int n, int m, int top, float* cost, float* ws,
+                       long long ws_floats, void* stream);
+
+/* Point-to-mesh distance (evaluation/evaluation_code/evaluation.cpp:224-232, CGAL's AABB-tree closest point): dist[P] = the
+ * Euclidean distance of every point of pts [P,3] to the closest point of the triangle soup tris [F,9] (v0 v1 v2), face[P]
+ * (nullable) the index of that triangle (first minimum).  Exact closest point per triangle; the search prunes tiles of 64
+ * consecutive triangles by their boxes, so points and triangles in a spatially coherent (Morton) order make it fast - any
+ * order gives the same result.  seed [P] (nullable): a triangle index near each point's closest one (an upper bound to
+ * start from).  brute != 0: no pruning (the baseline the pruned search equals).  ws: pf_point_mesh_ws_floats(P, F) floats. */
+long long pf_point_mesh_ws_floats(int P, int F);
+int pf_point_mesh_dist(const float* pts, int P, const float* tris, int F, const int* seed, int brute, float* dist, int* face,
+                       float* ws, long long ws_floats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

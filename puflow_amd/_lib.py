@@ -213,6 +213,11 @@ SIGNATURES = {
     "pf_lincomb": (c_int, [POINTER(c_void_p), POINTER(c_float), c_int, c_void_p, c_longlong, c_void_p]),
     "pf_scaled_sumsq": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_float), c_int, c_float, c_float,
                                 c_float, c_longlong, c_void_p, c_void_p, c_void_p]),
+    "pf_approxmatch_ws_floats": (c_longlong, [c_int, c_int, c_int, c_int]),
+    "pf_approxmatch_emd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_longlong, c_void_p]),
+    "pf_point_mesh_ws_floats": (c_longlong, [c_int, c_int]),
+    "pf_point_mesh_dist": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_longlong,
+                                   c_void_p]),
 }
 
 
