@@ -197,10 +197,10 @@ __global__ __launch_bounds__(EMD_THREADS) void emd_auction_kernel(EmdArgs a) {
 // 3 ms on one CU.  Here a sample's points are split over G workgroups (consecutive block indices); ground truth and prices
 // are copied to LDS per iteration, bids of a workgroup's own points stay in its LDS, and only the per-object state that
 // other workgroups need (maximum increment, winner, owner, price, assignment) is global, accessed with agent-scope atomics.
-// Grid barriers per iteration: after bidding, [after the winner vote,] after assignment - an arrival counter per sample,
-// thread 0 spins on it.  With 64-bit vote words (increment bits << 32 | bidder index, one atomic max) the vote phase and its
-// barrier are gone: two barriers per iteration.  The per-object vote arrays are double-buffered by iteration parity, so an iteration's entries are
-// cleared during the NEXT iteration (by the workgroup that wrote them) instead of behind a fourth barrier.
+// Grid barriers per iteration (pf_sum_barrier, thread 0 spins): after bidding - which also sums the sample's unassigned points -,
+// after the winner vote, after assignment.  The per-object vote arrays are double-buffered by iteration parity, so an iteration's
+// entries are cleared during the NEXT iteration (by the workgroup that wrote them) instead of behind a fourth barrier.  This is
+// the kernel for callers whose scratch arrays are separate allocations; emd_repl_kernel (below) needs two of them back to back.
 // Same arithmetic and tie rules as the single-workgroup kernel: identical assignment.
 // Progress: the host launches this kernel only when the device can hold all B * G workgroups at once (pf_emd_forward_ex:
 // occupancy of this kernel x CU count); the spin is bounded anyway - on timeout the sample's distances are written as NaN,
@@ -217,9 +217,9 @@ struct EmdCoopArgs {
     const float* x; const float* y;
     float* dist; int* assignment; int* assignment_inv; float* price;
     unsigned* mb0; unsigned* mb1; int* mi0; int* mi1;     // [B,n] each: maximum increment bits / winner index, per parity
-    unsigned long long* k0; unsigned long long* k1;        // KEY64: [B,n] (increment bits << 32 | bidder) per parity, instead
-    unsigned* sync;                                        // [B,n] zeroed by the host: words [0..1] = one 64-bit barrier word per sample
-                                                           // (arrivals | running total of unassigned points << 32)
+    unsigned long long* k0; unsigned long long* k1;        // emd_repl_kernel: [B,n] bid records per parity (instead of mb / mi)
+    unsigned* sync;                                        // [B,n] zeroed by the host: words [0..3] = the sample's two 64-bit
+                                                           // pf_sum_barrier words (arrivals | sum of unassigned points << 32)
     unsigned* status;                                      // nullable: [0] += 1 for every WORKGROUP whose grid barrier timed out
     int n, iters, G;
     float eps;
@@ -295,33 +295,37 @@ __device__ __forceinline__ void emd_bid_scan(const float4* y4, int n, float x1, 
 #ifndef PF_EMD_SOLO
 #define PF_EMD_SOLO 16         // a sample with at most this many unassigned points is finished by one of its workgroups alone (0: never)
 #endif
-#ifndef PF_EMD_XCD
-#define PF_EMD_XCD 1            // 0: the linear mapping (A/B: 860 -> 843, 871 -> 850 us on the far case, the near case unchanged)
-#endif
-template <bool KEY64>
+// workgroup -> (sample b, slice w).  Consecutive workgroup ids go round-robin over the 8 XCDs, so the linear mapping spreads the G
+// workgroups of a sample over G different XCDs; when the batch divides by 8 they share one XCD (its L2) instead (A/B on the far
+// case: 860 -> 843, 871 -> 850 us; the near case unchanged)
+__device__ __forceinline__ void emd_slice(int G, int& b, int& w) {
+    const int nsamp = gridDim.x / G;
+    b = blockIdx.x / G; w = blockIdx.x % G;
+    if ((nsamp & 7) == 0) {
+        const int xc = blockIdx.x & 7, r = blockIdx.x >> 3;
+        b = xc * (nsamp >> 3) + r / G;
+        w = r % G;
+    }
+}
+// squared distance of prediction point i to its ground-truth point k (cu:217-226); NaN when k is not an object or !ok
+__device__ __forceinline__ float emd_d2(const float* x, const float4* sy4, int i, int k, int n, bool ok) {
+    float d = __builtin_nanf("");
+    if (ok && (unsigned)k < (unsigned)n) {
+        const float dx = __fsub_rn(x[i * 3 + 0], sy4[k].x), dy = __fsub_rn(x[i * 3 + 1], sy4[k].y), dz = __fsub_rn(x[i * 3 + 2], sy4[k].z);
+        d = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+    }
+    return d;
+}
+
 __global__ __launch_bounds__(EMD_THREADS) void emd_coop_kernel(EmdCoopArgs a) {
     __shared__ float4 sy4[EMDC_NMAX];                            // (y, price) of every object: one 16-byte LDS read per evaluation
     __shared__ int ulist[EMDC_NMAX], sbid[EMDC_NMAX], pbid[EMDC_NMAX];
     __shared__ float sinc[EMDC_NMAX];
-    __shared__ int ucount, dead;
-    // the one-workgroup endgame (PF_EMD_SOLO, below): the sample's whole state in this workgroup's LDS
-    __shared__ int sassign[EMDC_NMAX], sainv[EMDC_NMAX];
-    __shared__ unsigned long long skey[EMDC_NMAX];
-    // workgroup -> (sample, slice).  Consecutive workgroup ids go round-robin over the 8 XCDs, so the linear mapping spreads the
-    // G workgroups of a sample over G different XCDs; with PF_EMD_XCD the G workgroups of a sample share an XCD (its L2) when
-    // the batch divides by 8
-#if PF_EMD_XCD
+    __shared__ int ucount;
+    __shared__ PfSumBarrier bar;
     const int G = a.G;
-    const int nsamp = gridDim.x / G;
-    int b = blockIdx.x / G, w = blockIdx.x % G;
-    if ((nsamp & 7) == 0) {
-        const int x = blockIdx.x & 7, r = blockIdx.x >> 3;
-        b = x * (nsamp >> 3) + r / G;
-        w = r % G;
-    }
-#else
-    const int G = a.G, b = blockIdx.x / G, w = blockIdx.x % G;
-#endif
+    int b, w;
+    emd_slice(G, b, w);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = a.n;
     const size_t o0 = (size_t)b * n;
@@ -329,48 +333,25 @@ __global__ __launch_bounds__(EMD_THREADS) void emd_coop_kernel(EmdCoopArgs a) {
     int* assignment = a.assignment + o0;
     int* ainv = a.assignment_inv + o0;
     float* price = a.price + o0;
-    unsigned* cnt = a.sync + o0;
+    unsigned long long* words = reinterpret_cast<unsigned long long*>(a.sync + o0);
     const int i0 = (int)((long long)w * n / G), i1 = (int)((long long)(w + 1) * n / G);
     unsigned nb = 0;
-    if (tid == 0) dead = 0;
-    // The barrier word is 64 bits: arrivals in the low half, the running total of unassigned points in the high half - a
-    // workgroup adds (its count << 32 | 1) in ONE atomic, and the poll that sees every arrival has the sample's total with it
-    // (a separate counter cost one more dependent memory round trip per iteration; a round trip is ~1.2 us, an iteration ~17).
-    unsigned long long* cnt64 = reinterpret_cast<unsigned long long*>(cnt);
-    __shared__ unsigned utot;
-    auto barrier = [&](unsigned add_u) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        ++nb;
-        if (tid == 0) {
-            atomicAdd(cnt64, ((unsigned long long)add_u << 32) | 1ull);
-            const unsigned target = nb * (unsigned)G;
-            int budget = 1 << 18;                       // ~0.2 s: a barrier normally completes in microseconds
-            unsigned long long w = ald(cnt64);
-            while ((unsigned)w < target && --budget > 0) { __builtin_amdgcn_s_sleep(2); w = ald(cnt64); }
-            if (budget <= 0) dead = 1;
-            utot = (unsigned)(w >> 32);
-        }
-        __syncthreads();
-    };
+    if (tid == 0) bar = PfSumBarrier{};
+    auto barrier = [&](unsigned add_u) { return pf_sum_barrier<1 << 18, 2>(words, ++nb, (unsigned)G, add_u, bar); };   // ~0.2 s budget
     for (int i = tid; i < n; i += EMD_THREADS)
         sy4[i] = make_float4(a.y[(o0 + i) * 3 + 0], a.y[(o0 + i) * 3 + 1], a.y[(o0 + i) * 3 + 2], 0.f);
     for (int i = i0 + tid; i < i1; i += EMD_THREADS) {
-        if (KEY64) { ast(a.k0 + o0 + i, 0ull); ast(a.k1 + o0 + i, 0ull); }
-        else { ast(a.mb0 + o0 + i, 0u); ast(a.mb1 + o0 + i, 0u); ast(a.mi0 + o0 + i, -1); ast(a.mi1 + o0 + i, -1); }
+        ast(a.mb0 + o0 + i, 0u); ast(a.mb1 + o0 + i, 0u); ast(a.mi0 + o0 + i, -1); ast(a.mi1 + o0 + i, -1);
     }
     barrier(0u);
-    int pU = 0, solo_from = -1;
-    unsigned uprev = 0;
-    for (int it = 0; it < a.iters && !dead; ++it) {
+    int pU = 0;
+    for (int it = 0; it < a.iters && !bar.dead; ++it) {
         const bool last = it == a.iters - 1;
         const int par = it & 1;
-        unsigned* mb = KEY64 ? nullptr : (par ? a.mb1 : a.mb0) + o0;
-        int* mi = KEY64 ? nullptr : (par ? a.mi1 : a.mi0) + o0;
-        unsigned* mbo = KEY64 ? nullptr : (par ? a.mb0 : a.mb1) + o0;
-        int* mio = KEY64 ? nullptr : (par ? a.mi0 : a.mi1) + o0;
-        unsigned long long* key = KEY64 ? (par ? a.k1 : a.k0) + o0 : nullptr;
-        unsigned long long* keyo = KEY64 ? (par ? a.k0 : a.k1) + o0 : nullptr;
+        unsigned* mb = (par ? a.mb1 : a.mb0) + o0;
+        int* mi = (par ? a.mi1 : a.mi0) + o0;
+        unsigned* mbo = (par ? a.mb0 : a.mb1) + o0;
+        int* mio = (par ? a.mi0 : a.mi1) + o0;
         // the slice's assignments are fetched together with the prices (one memory round trip, not two)
         const int as0 = i0 + tid < i1 ? ald(assignment + i0 + tid) : 0;
         for (int i = tid; i < n; i += EMD_THREADS) sy4[i].w = ald(price + i);
@@ -393,30 +374,20 @@ __global__ __launch_bounds__(EMD_THREADS) void emd_coop_kernel(EmdCoopArgs a) {
                 const float inc = __fadd_rn(__fsub_rn(tbest, tbetter), a.eps);
                 sbid[u] = tidx;
                 sinc[u] = inc;
-                // KEY64: one 64-bit max decides the object's winner - largest increment (positive floats order like their
-                // bits), then largest bidder index: the vote phase and its barrier disappear
-                if (KEY64) atomicMax(key + tidx, ((unsigned long long)__float_as_uint(inc) << 32) | (unsigned)i);
-                else atomicMax(mb + tidx, __float_as_uint(inc));
+                atomicMax(mb + tidx, __float_as_uint(inc));
             }
         }
-        barrier((unsigned)U);
-        const unsigned ucur = utot;                              // every workgroup reads the same total: its poll saw all arrivals
-        if (ucur == uprev) break;                                // nothing left to assign in the whole sample (uniform)
-        const unsigned u_it = ucur - uprev;                      // the sample's unassigned points at the start of this iteration
-        uprev = ucur;
-        if (!KEY64) {
-            // ---- winner of each object: largest index among the bidders holding the exact maximum increment
-            for (int u = tid; u < U; u += EMD_THREADS) {
-                const int o = sbid[u];
-                if (__float_as_uint(sinc[u]) == ald(mb + o)) atomicMax(mi + o, ulist[u]);
-            }
-            barrier(0u);
+        if (barrier((unsigned)U) == 0) break;                    // nothing left to assign in the whole sample (uniform)
+        // ---- winner of each object: largest index among the bidders holding the exact maximum increment
+        for (int u = tid; u < U; u += EMD_THREADS) {
+            const int o = sbid[u];
+            if (__float_as_uint(sinc[u]) == ald(mb + o)) atomicMax(mi + o, ulist[u]);
         }
+        barrier(0u);
         // ---- assign; clear the OTHER parity's entries this workgroup wrote in the previous iteration
         for (int u = tid; u < U; u += EMD_THREADS) {
             const int i = ulist[u], o = sbid[u];
-            const bool won = KEY64 ? (int)(unsigned)(ald(key + o) & 0xffffffffull) == i : ald(mi + o) == i;
-            if (last || won) {
+            if (last || ald(mi + o) == i) {
                 if (!last) {
                     const int prev = ald(ainv + o);
                     if (prev != -1) ast(assignment + prev, -1);
@@ -426,94 +397,16 @@ __global__ __launch_bounds__(EMD_THREADS) void emd_coop_kernel(EmdCoopArgs a) {
                 atomicAdd(price + o, sinc[u]);
             }
         }
-        for (int u = tid; u < pU; u += EMD_THREADS) {
-            if (KEY64) ast(keyo + pbid[u], 0ull);
-            else { ast(mbo + pbid[u], 0u); ast(mio + pbid[u], -1); }
-        }
+        for (int u = tid; u < pU; u += EMD_THREADS) { ast(mbo + pbid[u], 0u); ast(mio + pbid[u], -1); }
         for (int u = tid; u < U; u += EMD_THREADS) pbid[u] = sbid[u];
         pU = U;
         barrier(0u);
-        // The unassigned count of a sample never grows (a winner takes one point off the list and evicts at most one), and once
-        // it is small an iteration is nothing but its fixed cost: the price copy, the list build and TWO grid barriers - 9 us
-        // for a handful of bids (a prediction near its target has <= 40 unassigned points from the fifth iteration on and
-        // still runs all 50).  From here on ONE workgroup finishes the sample out of its own LDS with workgroup barriers only.
-        if (KEY64 && PF_EMD_SOLO > 0 && !last && u_it <= (unsigned)PF_EMD_SOLO) { solo_from = it + 1; break; }
     }
-    if (solo_from >= 0 && !dead) {                               // uniform over the sample's workgroups (u_it is the barrier's total)
-        if (w != 0) return;                                      // every write of the iterations so far is behind the barrier above
-        for (int i = tid; i < n; i += EMD_THREADS) {
-            sassign[i] = ald(assignment + i); sainv[i] = ald(ainv + i); sy4[i].w = ald(price + i); skey[i] = 0ull;
-        }
-        __syncthreads();
-        for (int it = solo_from; it < a.iters; ++it) {
-            const bool last = it == a.iters - 1;
-            if (tid == 0) ucount = 0;
-            __syncthreads();
-            for (int i = tid; i < n; i += EMD_THREADS)
-                if (sassign[i] == -1) ulist[atomicAdd(&ucount, 1)] = i;
-            __syncthreads();
-            const int U = ucount;
-            if (U == 0) break;
-            for (int u = wave; u < U; u += EMD_THREADS / 64) {     // the same bid, vote word and tie rules as above
-                const int i = ulist[u];
-                const float x1 = x[i * 3 + 0], y1 = x[i * 3 + 1], z1 = x[i * 3 + 2];
-                float tbest, tbetter;
-                int tidx;
-                emd_bid_scan(sy4, n, x1, y1, z1, lane, tbest, tbetter, tidx);
-                if (lane == 0) {
-                    if ((unsigned)tidx >= (unsigned)n) { tidx = i; tbest = tbetter = 0.f; }
-                    const float inc = __fadd_rn(__fsub_rn(tbest, tbetter), a.eps);
-                    sbid[u] = tidx;
-                    sinc[u] = inc;
-                    atomicMax(skey + tidx, ((unsigned long long)__float_as_uint(inc) << 32) | (unsigned)i);
-                }
-            }
-            __syncthreads();
-            for (int u = tid; u < U; u += EMD_THREADS) {
-                const int i = ulist[u], o = sbid[u];
-                const bool won = (int)(unsigned)(skey[o] & 0xffffffffull) == i;
-                if (last || won) {
-                    if (!last) {
-                        const int prev = sainv[o];
-                        if (prev != -1) sassign[prev] = -1;
-                    }
-                    sainv[o] = i;
-                    sassign[i] = o;
-                    atomicAdd(&sy4[o].w, sinc[u]);
-                }
-            }
-            __syncthreads();
-            for (int u = tid; u < U; u += EMD_THREADS) skey[sbid[u]] = 0ull;      // read again only behind the next iteration's barriers
-        }
-        __syncthreads();
-        for (int i = tid; i < n; i += EMD_THREADS) {
-            const int k = sassign[i];
-            assignment[i] = k; ainv[i] = sainv[i]; price[i] = sy4[i].w;
-            float d = __builtin_nanf("");
-            if ((unsigned)k < (unsigned)n) {
-                const float dx = __fsub_rn(x[i * 3 + 0], sy4[k].x), dy = __fsub_rn(x[i * 3 + 1], sy4[k].y),
-                            dz = __fsub_rn(x[i * 3 + 2], sy4[k].z);
-                d = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-            }
-            a.dist[o0 + i] = d;
-        }
-        return;
-    }
-    // ---- squared distance to the assigned ground-truth point (cu:217-226)
-    for (int i = i0 + tid; i < i1; i += EMD_THREADS) {
-        const int k = ald(assignment + i);
-        float d = __builtin_nanf("");
-        if (!dead && (unsigned)k < (unsigned)n) {
-            const float dx = __fsub_rn(x[i * 3 + 0], sy4[k].x), dy = __fsub_rn(x[i * 3 + 1], sy4[k].y),
-                        dz = __fsub_rn(x[i * 3 + 2], sy4[k].z);
-            d = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-        }
-        a.dist[o0 + i] = d;
-    }
+    for (int i = i0 + tid; i < i1; i += EMD_THREADS) a.dist[o0 + i] = emd_d2(x, sy4, i, ald(assignment + i), n, !bar.dead);
     // a timed-out barrier is REPORTED by EVERY workgroup that saw it (workgroup 0 of the sample may have got through its last
     // barrier while a peer timed out: that peer's slice of dist is NaN): the host raises on any non-zero count at its next
     // synchronisation point; the NaN distances above only keep a consumer from using the partial assignment silently
-    if (dead && tid == 0 && a.status) atomicAdd(a.status, 1u);
+    if (bar.dead && tid == 0 && a.status) atomicAdd(a.status, 1u);
 }
 
 // ---- round 5: the multi-workgroup auction with REPLICATED state - one grid barrier per iteration instead of two ---------------
@@ -527,25 +420,17 @@ __global__ __launch_bounds__(EMD_THREADS) void emd_coop_kernel(EmdCoopArgs a) {
 // cleared), meets the others at ONE barrier, reads the sample's n record slots (8 bytes per thread) and resolves winners and
 // assignments in LDS.  No price reload, no global atomics, no second barrier.  Same bids, vote words and tie rules as the
 // other kernels: identical assignment (tests/test_gpu_losses.py compares all three with the oracle).
-#ifndef PF_EMD_REPL
-#define PF_EMD_REPL 1
-#endif
 __global__ __launch_bounds__(EMD_THREADS) void emd_repl_kernel(EmdCoopArgs a) {
     __shared__ float4 sy4[EMDC_NMAX];
     __shared__ int ulist[EMDC_NMAX], sbid[EMDC_NMAX];
     __shared__ float sinc[EMDC_NMAX];
     __shared__ int sassign[EMDC_NMAX], sainv[EMDC_NMAX];
     __shared__ unsigned long long skey[EMDC_NMAX];
-    __shared__ int ucount, dead;
-    __shared__ unsigned utot;
+    __shared__ int ucount;
+    __shared__ PfSumBarrier bar;
     const int G = a.G;
-    const int nsamp = gridDim.x / G;
-    int b = blockIdx.x / G, w = blockIdx.x % G;
-    if ((nsamp & 7) == 0) {                                      // a sample's workgroups on one XCD (speed only)
-        const int xc = blockIdx.x & 7, r = blockIdx.x >> 3;
-        b = xc * (nsamp >> 3) + r / G;
-        w = r % G;
-    }
+    int b, w;
+    emd_slice(G, b, w);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = a.n;
     const size_t o0 = (size_t)b * n;
@@ -553,25 +438,11 @@ __global__ __launch_bounds__(EMD_THREADS) void emd_repl_kernel(EmdCoopArgs a) {
     int* assignment = a.assignment + o0;
     int* ainv = a.assignment_inv + o0;
     float* price = a.price + o0;
-    unsigned long long* cnt64 = reinterpret_cast<unsigned long long*>(a.sync + o0);
+    unsigned long long* words = reinterpret_cast<unsigned long long*>(a.sync + o0);
     const int i0 = (int)((long long)w * n / G), i1 = (int)((long long)(w + 1) * n / G);
     unsigned nb = 0;
-    if (tid == 0) dead = 0;
-    auto barrier = [&](unsigned add_u) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        ++nb;
-        if (tid == 0) {
-            atomicAdd(cnt64, ((unsigned long long)add_u << 32) | 1ull);
-            const unsigned target = nb * (unsigned)G;
-            int budget = 1 << 18;
-            unsigned long long v = ald(cnt64);
-            while ((unsigned)v < target && --budget > 0) { __builtin_amdgcn_s_sleep(1); v = ald(cnt64); }
-            if (budget <= 0) dead = 1;
-            utot = (unsigned)(v >> 32);
-        }
-        __syncthreads();
-    };
+    if (tid == 0) bar = PfSumBarrier{};
+    auto barrier = [&](unsigned add_u) { return pf_sum_barrier<1 << 18, 1>(words, ++nb, (unsigned)G, add_u, bar); };
     for (int i = tid; i < n; i += EMD_THREADS) {
         sy4[i] = make_float4(a.y[(o0 + i) * 3 + 0], a.y[(o0 + i) * 3 + 1], a.y[(o0 + i) * 3 + 2], price[i]);
         sassign[i] = assignment[i]; sainv[i] = ainv[i]; skey[i] = 0ull;
@@ -579,9 +450,7 @@ __global__ __launch_bounds__(EMD_THREADS) void emd_repl_kernel(EmdCoopArgs a) {
     for (int i = i0 + tid; i < i1; i += EMD_THREADS) { ast(a.k0 + o0 + i, 0ull); ast(a.k1 + o0 + i, 0ull); }
     barrier(0u);
     int pU0 = 0, pU1 = 0, solo_from = -1;
-    unsigned uprev = 0;
-    bool done = false;
-    for (int it = 0; it < a.iters && !dead; ++it) {
+    for (int it = 0; it < a.iters && !bar.dead; ++it) {
         const bool last = it == a.iters - 1;
         const int par = it & 1;
         unsigned long long* rec = (par ? a.k1 : a.k0) + o0;
@@ -606,11 +475,8 @@ __global__ __launch_bounds__(EMD_THREADS) void emd_repl_kernel(EmdCoopArgs a) {
         const int pUp = par ? pU1 : pU0;                          // slots this workgroup filled two iterations ago and does not refill
         for (int u = U + tid; u < pUp; u += EMD_THREADS) ast(rec + i0 + u, 0ull);
         if (par) pU1 = U; else pU0 = U;
-        barrier((unsigned)U);
-        const unsigned ucur = utot;
-        if (ucur == uprev) { done = true; break; }               // nothing left to assign in the whole sample (uniform)
-        const unsigned u_it = ucur - uprev;
-        uprev = ucur;
+        const unsigned u_it = barrier((unsigned)U);             // the sample's unassigned points at the start of this iteration
+        if (u_it == 0) break;                                    // nothing left to assign in the whole sample (uniform)
         // ---- every workgroup applies every bid of the sample to its own copy of the state
         unsigned long long r[(EMDC_NMAX + EMD_THREADS - 1) / EMD_THREADS];
 #pragma unroll
@@ -645,9 +511,8 @@ __global__ __launch_bounds__(EMD_THREADS) void emd_repl_kernel(EmdCoopArgs a) {
         // few unassigned points left in the sample (their number never grows): workgroup 0 finishes alone, without grid barriers
         if (PF_EMD_SOLO > 0 && !last && u_it <= (unsigned)PF_EMD_SOLO) { solo_from = it + 1; break; }
     }
-    (void)done;
     int w0 = i0, w1 = i1;                                        // the slice of the outputs this workgroup writes
-    if (solo_from >= 0 && !dead) {
+    if (solo_from >= 0 && !bar.dead) {
         if (w != 0) return;
         w0 = 0; w1 = n;
         for (int it = solo_from; it < a.iters; ++it) {
@@ -694,15 +559,9 @@ __global__ __launch_bounds__(EMD_THREADS) void emd_repl_kernel(EmdCoopArgs a) {
     for (int i = w0 + tid; i < w1; i += EMD_THREADS) {
         const int k = sassign[i];
         assignment[i] = k; ainv[i] = sainv[i]; price[i] = sy4[i].w;
-        float d = __builtin_nanf("");
-        if (!dead && (unsigned)k < (unsigned)n) {
-            const float dx = __fsub_rn(x[i * 3 + 0], sy4[k].x), dy = __fsub_rn(x[i * 3 + 1], sy4[k].y),
-                        dz = __fsub_rn(x[i * 3 + 2], sy4[k].z);
-            d = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-        }
-        a.dist[o0 + i] = d;
+        a.dist[o0 + i] = emd_d2(x, sy4, i, k, n, !bar.dead);
     }
-    if (dead && tid == 0 && a.status) atomicAdd(a.status, 1u);
+    if (bar.dead && tid == 0 && a.status) atomicAdd(a.status, 1u);
 }
 
 __global__ __launch_bounds__(256) void emd_grad_kernel(const float* __restrict__ x, const float* __restrict__ y,
@@ -745,21 +604,16 @@ extern "C" int pf_emd_forward_ex(const float* xyz1, const float* xyz2, float* di
     EmdArgs a{xyz1, xyz2, dist, assignment, assignment_inv, price, bid, bid_increments,
               reinterpret_cast<unsigned*>(max_increments), max_idx, unass_idx, n, iters, eps};
     hipStream_t s = (hipStream_t)stream;
-    // 64-bit vote words need two of the caller's [B,n] scratch arrays back to back (8-byte aligned): true when they are
-    // slices of one allocation, as puflow_amd.loss.emdFunction passes them; otherwise the three-barrier protocol
+    // emd_repl_kernel's 64-bit records need two of the caller's [B,n] scratch arrays back to back (8-byte aligned): true when
+    // they are slices of one allocation, as puflow_amd.loss.emdFunction passes them; otherwise emd_coop_kernel
     const size_t bn = (size_t)B * n;
     const bool pair0 = bid_increments == max_increments + bn && (reinterpret_cast<size_t>(max_increments) & 7) == 0;
     const bool pair1 = bid == max_idx + bn && (reinterpret_cast<size_t>(max_idx) & 7) == 0;
     const bool key64 = pair0 && pair1;
     int G = 1;
-    if (groups != 1 && n <= EMDC_NMAX && (n & 1) == 0 && (reinterpret_cast<size_t>(unass_idx) & 7) == 0) {   // 64-bit barrier word per sample
-        int ncu = 0, dev = 0, per_cu = 0;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-        const hipError_t oc = key64
-            ? (PF_EMD_REPL ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, emd_repl_kernel, EMD_THREADS, 0)
-                           : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, emd_coop_kernel<true>, EMD_THREADS, 0))
-            : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, emd_coop_kernel<false>, EMD_THREADS, 0);
-        if (oc != hipSuccess) { (void)hipGetLastError(); per_cu = 0; }
+    if (groups != 1 && n <= EMDC_NMAX && (n & 1) == 0 && (reinterpret_cast<size_t>(unass_idx) & 7) == 0) {   // 64-bit barrier words per sample
+        int ncu = 0;
+        const int per_cu = key64 ? resident_per_cu(emd_repl_kernel, EMD_THREADS, 0, &ncu) : resident_per_cu(emd_coop_kernel, EMD_THREADS, 0, &ncu);
         const long long resident = per_cu >= 1 ? (long long)ncu : 0;        // one workgroup per CU at most: each wants a whole CU's issue slots
         const int cap = groups > 1 ? groups : 16;
         while (2 * G <= cap && (long long)B * (2 * G) <= resident && n / (2 * G) >= 64) G *= 2;
@@ -773,10 +627,9 @@ extern "C" int pf_emd_forward_ex(const float* xyz1, const float* xyz2, float* di
             c.k0 = reinterpret_cast<unsigned long long*>(max_increments);
             c.k1 = reinterpret_cast<unsigned long long*>(max_idx);
             // each array pair holds 2 B n 32-bit words = B n 64-bit words: sample b's keys at word offset b n
-            if (PF_EMD_REPL) hipLaunchKernelGGL(emd_repl_kernel, dim3(B * G), dim3(EMD_THREADS), 0, s, c);
-            else hipLaunchKernelGGL(emd_coop_kernel<true>, dim3(B * G), dim3(EMD_THREADS), 0, s, c);
+            hipLaunchKernelGGL(emd_repl_kernel, dim3(B * G), dim3(EMD_THREADS), 0, s, c);
         } else
-            hipLaunchKernelGGL(emd_coop_kernel<false>, dim3(B * G), dim3(EMD_THREADS), 0, s, c);
+            hipLaunchKernelGGL(emd_coop_kernel, dim3(B * G), dim3(EMD_THREADS), 0, s, c);
         return pf_last_launch_status();
     }
     if (n <= EMD_NMAX_ALL) hipLaunchKernelGGL(emd_auction_kernel<2>, dim3(B), dim3(EMD_THREADS), 0, s, a);

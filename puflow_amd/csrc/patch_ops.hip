@@ -67,13 +67,13 @@ __global__ __launch_bounds__(FPS_T) void fps_kernel(const float* __restrict__ xy
 // The single-workgroup kernel above re-reads 16 B per point from L2 on every one of the npoint sequential steps
 // (99 840 points -> 1.6 MB per step through ONE CU's 64 B/clk texture path: 19 us per step, 388 ms for the CLI's
 // 99 840 -> 20 024 merge, 99.7 % of its per-cloud GPU time).  Here a cloud is split over G <= 32 workgroups
-// (<= 32 points per thread), a step is: local arg-max in registers -> one 64-bit candidate per WAVE
+// (<= 32 points per thread), a step is: local arg-max in registers -> 64-bit candidates from every WAVE
 // (distance bits << 32 | ~index, so an integer max is "farthest, then smallest index") published with an
 // agent-scope atomic store into a 4-deep ring of G x 4 slots -> wave 0 of every workgroup polls the slots of the
 // step (agent-scope atomic loads) and reduces them.  The 64-bit word IS the whole message (coordinates are re-read
 // from the read-only input), so relaxed ordering suffices: no L2 write-back / invalidate per step, which is what an
 // acquire / release pair costs at agent scope on this chip.  No read-modify-write atomics, no counters: a slot is
-// "filled" when it carries the current step's 2-bit tag (the same slot held step j-4's word before): see the kernel.
+// "filled" when it carries the current step's 2-bit tag (the same slot held step j-4's word before): see the exchange below.
 // Progress: blocks are dispatched in index order and a cloud's workgroups are contiguous, so the lowest
 // unfinished cloud always has all its workgroups resident; a bounded spin + abort guarantees the grid drains
 // even if that assumption were ever violated.  A cloud's status word is 0 only after all of its steps completed -
@@ -84,15 +84,9 @@ __global__ __launch_bounds__(FPS_T) void fps_kernel(const float* __restrict__ xy
 constexpr int FPSC_T = PF_FPSC_T;
 constexpr int FPSC_GMAX = 32;
 constexpr int FPSC_SLOTS = FPSC_GMAX * (FPSC_T / 64);    // one slot per wave of a cloud
-constexpr int FPSC_RING = 4 * FPSC_SLOTS;                // 64-bit words per cloud, then the status word
-static_assert(FPSC_SLOTS <= 128, "a lane polls two slots");
-constexpr unsigned FPSC_SPIN_MAX = 1u << 24;
-// status word of a cloud (ring[FPSC_RING]): 2 = not finished (set by fps_init_kernel), 1 = aborted, 0 = complete
-constexpr unsigned long long FPSC_ST_DONE = 0ull, FPSC_ST_ABORT = 1ull, FPSC_ST_INIT = 2ull;
-
-__device__ __forceinline__ unsigned long long fps_ld(const unsigned long long* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
+static_assert(FPSC_SLOTS <= 128, "a lane of wave 0 polls two words per word a wave publishes");
+// status word of a cloud (after its ring): 2 = not finished (set by fps_init_kernel), 1 = aborted, 0 = complete
+constexpr unsigned long long FPSC_ST_DONE = 0ull, FPSC_ST_ABORT = PF_RING_ABORT, FPSC_ST_INIT = 2ull;
 __device__ __forceinline__ void fps_st(unsigned long long* p, unsigned long long v) {
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -113,14 +107,19 @@ __device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
                max((unsigned)__builtin_amdgcn_readlane((int)v, 32), (unsigned)__builtin_amdgcn_readlane((int)v, 48)));
 }
 
-// A step: every WAVE reduces its own points in registers (DPP) and publishes one 64-bit word (distance bits << 32 | tag |
-// ~index: an integer max is "farthest, then smallest index") into its slot of a 4-deep ring; wave 0 of every workgroup reads
-// the G x 4 slots of the step (two per lane), reduces them and hands the winner's coordinates to the other waves through LDS
-// (double-buffered: ONE barrier per step).  Measured on the CLI's merge (99 840 -> 20 024, 25 workgroups), per step:
+// The exchange: every WAVE reduces its own points in registers (DPP) and publishes 64-bit words (distance bits << 32 | tag |
+// ~index: an integer max is "farthest, then smallest index") into its slots of a 4-deep ring; wave 0 of every workgroup reads
+// the slots of the round (pf_ring_poll), reduces them and hands the result to the other waves through LDS.  The 2-bit tag
+// (r / 4) & 3 tells a word of THIS round from the one the same slot held four rounds ago, so a consumer can never take a stale
+// candidate whatever order two relaxed stores to different addresses become visible in (no slot clearing, no release /
+// acquire); within a round every word carries the same tag, so the integer max is unchanged.  The LDS words are
+// double-buffered: wave 0 rewrites a round's half only after the NEXT round's barrier, which every wave reaches after it has
+// read the half - ONE workgroup barrier per round.  Measured with one word per wave (the first cooperative kernel, up to
+// commit b35a33c) on the CLI's merge (99 840 -> 20 024, 25 workgroups), per step:
 //   one word per workgroup, shuffles through LDS, two barriers (round 2's first version)   2.86 us
 //   one word per wave, every wave reads all slots itself (no barrier at all)               2.95-3.1 us  (100 readers of the
 //                                                                          same lines: the reads get in each other's way)
-//   one word per wave, wave 0 reads (this kernel)                                          2.2-2.3 us
+//   one word per wave, wave 0 reads (the protocol kept)                                    2.2-2.3 us
 //   the same with the workgroup's four words merged in LDS first (25 slots)                2.56 us
 //   ... waiting for the OWN slots only (wrong results, timing experiment)                  1.65 us  = what the store -> load
 //                                                                          round trip through the fabric leaves of a step
@@ -128,97 +127,9 @@ __device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
 // atomics bypass the XCD's L2 wherever the peers run (2.5 us), workgroup-scope loads are served by the CU's own L1 and never
 // see the peers' stores, and an L1 invalidate (buffer_inv sc1) per read costs 6.3 us per step; two staggered reads in flight
 // (2.37 us); s_sleep between reads (no change); touching the whole cloud once per XCD before the loop (-0.06 us).
-template <int PPT>
-__global__ __launch_bounds__(FPSC_T) void fps_coop_kernel(const float* __restrict__ xyz, int N, int npoint, int G,
-                                                          unsigned long long* __restrict__ ringbuf, long long ring_stride,
-                                                          int* __restrict__ out) {
-    constexpr int NW = FPSC_T / 64;
-    __shared__ float s_l[2][4];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int b = blockIdx.x / G, g = blockIdx.x % G;
-    const float* p = xyz + (size_t)b * N * 3;
-    unsigned long long* ring = ringbuf + (size_t)b * ring_stride;       // [4][FPSC_SLOTS] + status word
-    unsigned long long* abort_w = ring + FPSC_RING;
-    int* o = out + (size_t)b * npoint;
-    const int S = G * NW;                                               // slots = waves of the cloud (<= 128: two per lane)
 
-    float px[PPT], py[PPT], pz[PPT], md[PPT];
-    int pi[PPT];
-#pragma unroll
-    for (int k = 0; k < PPT; ++k) {
-        const int i = (g * PPT + k) * FPSC_T + tid;                     // increasing in k: first maximum = smallest index
-        pi[k] = i;
-        const bool in = i < N;
-        const int ic = in ? i : N - 1;
-        px[k] = p[ic * 3 + 0]; py[k] = p[ic * 3 + 1]; pz[k] = p[ic * 3 + 2];
-        md[k] = in ? 1e10f : -1.f;                                      // padding can never be the farthest point
-    }
-    if (g == 0 && tid == 0) o[0] = 0;
-    float lx = p[0], ly = p[1], lz = p[2];
-    for (int j = 1; j < npoint; ++j) {
-        float best = -1.f;
-        int besti = 0x7fffffff;
-#pragma unroll
-        for (int k = 0; k < PPT; ++k) {
-            const float d = fminf(md[k], sqd(px[k], py[k], pz[k], lx, ly, lz));
-            md[k] = d;
-            if (d > best) { best = d; besti = pi[k]; }
-        }
-        // distances are >= 0 or the -1 of padding: their bit patterns order like signed integers
-        const int vb = __float_as_int(best);
-        const int vmax = wave_max_i32(vb);
-        const unsigned imin = ~wave_max_u32(vb == vmax ? ~(unsigned)besti : 0u);      // smallest index among the maxima
-        unsigned long long* slot = ring + (j & 3) * FPSC_SLOTS;
-        // word = distance bits << 32 | step tag (2 bits) | valid bit | ~index (29 bits).  The tag (j / 4) & 3 tells a
-        // word of THIS step from the one the same slot held four steps ago, so a consumer can never take a stale
-        // candidate whatever order two relaxed stores to different addresses become visible in (no slot clearing,
-        // no release / acquire); within a step every word carries the same tag, so the integer max is unchanged.
-        const unsigned tag = ((unsigned)(((j >> 2) & 3) << 1) | 1u) << 29;
-        if (lane == 0) {
-            const unsigned long long key =
-                vmax < 0 ? (unsigned long long)tag : (((unsigned long long)(unsigned)vmax << 32) | tag | ((~imin) & 0x1fffffffu));
-            fps_st(slot + g * NW + wave, key);
-        }
-        if (wave == 0) {
-            unsigned long long k0, k1;
-            unsigned spins = 0;
-            bool dead = false;
-            for (;;) {
-                k0 = lane < S ? fps_ld(slot + lane) : (unsigned long long)tag;
-                k1 = lane + 64 < S ? fps_ld(slot + lane + 64) : (unsigned long long)tag;
-                if (!__any(((unsigned)k0 & (7u << 29)) != tag || ((unsigned)k1 & (7u << 29)) != tag)) break;
-                if (++spins > FPSC_SPIN_MAX || (spins % 1024 == 0 && fps_ld(abort_w) == FPSC_ST_ABORT)) { dead = true; break; }
-            }
-            if (dead) {                                                     // uniform over the wave
-                if (lane == 0) { fps_st(abort_w, FPSC_ST_ABORT); s_l[j & 1][3] = -1.f; }
-            } else {
-                const unsigned long long km = k0 > k1 ? k0 : k1;
-                // every lane fetches ITS candidate's coordinates while the maximum is being reduced: the winner's are then
-                // already in registers (one dependent L2 round trip less per step)
-                const unsigned ci = (~(unsigned)km) & 0x1fffffffu;
-                const unsigned cic = ci < (unsigned)N ? ci : 0u;
-                const float cx = p[cic * 3 + 0], cy = p[cic * 3 + 1], cz = p[cic * 3 + 2];
-                const unsigned hi = (unsigned)(km >> 32), lo = (unsigned)km;
-                const unsigned hmax = wave_max_u32(hi);
-                const unsigned lmax = wave_max_u32(hi == hmax ? lo : 0u);
-                const int wl = __builtin_ctzll(__ballot(hi == hmax && lo == lmax));       // keys are distinct: one lane matches
-                if (lane == wl) { s_l[j & 1][0] = cx; s_l[j & 1][1] = cy; s_l[j & 1][2] = cz; s_l[j & 1][3] = 1.f; }
-                if (g == 0 && lane == 0) o[j] = (int)((~lmax) & 0x1fffffffu);
-            }
-        }
-        // s_l is double-buffered: wave 0 rewrites this step's half only after the NEXT step's barrier, which every wave
-        // reaches after it has read the half here
-        __syncthreads();
-        lx = s_l[j & 1][0]; ly = s_l[j & 1][1]; lz = s_l[j & 1][2];
-        if (s_l[j & 1][3] < 0.f) return;                                  // uniform over the workgroup: aborted
-    }
-    // every step of this cloud completed (a step completes only when all of its waves published): mark the row valid
-    if (g == 0 && tid == 0) fps_st(abort_w, FPSC_ST_DONE);
-}
-
-// ---- two samples per exchange ------------------------------------------------------------------------------------------
-// A step of fps_coop_kernel is ~0.4 us of arithmetic and ~1.8 us of waiting for the words to cross the fabric.  Here every wave
+// ---- two samples per exchange (rounds 2 - 4; the kernel is retired, the probe below still measures its exchange) ------------
+// A step of the one-word kernel is ~0.4 us of arithmetic and ~1.8 us of waiting for the words to cross the fabric.  Here every wave
 // publishes its TWO best points (keys K_a > K_b), so a round knows the global best c1 AND the best of the rest c2.  After c1
 // has been added, every min-distance can only shrink, i.e. every key can only fall; points nobody published lie below their
 // wave's K_b, which lies below K2 = key(c2).  So if c2 itself is not touched by c1 - d(c2, c1) >= md(c2), computed exactly as
@@ -228,13 +139,12 @@ __global__ __launch_bounds__(FPSC_T) void fps_coop_kernel(const float* __restric
 // emits c1 alone, as before.  Every workgroup takes the same decision from the same words.  Bit-identical output; on the CLI's
 // merge (99 840 -> 20 024) 1.59 samples per round: 46.0 -> 30.4 ms per cloud.
 constexpr int FPSC_SLOTS2 = 2 * FPSC_SLOTS;
-constexpr int FPSC_RING2 = 4 * FPSC_SLOTS2;              // status word of the two-sample kernel's ring
+constexpr int FPSC_RING2 = 4 * FPSC_SLOTS2;              // status word of the probe's ring
 
 __device__ __forceinline__ unsigned long long fps_key(int vbits, unsigned idx, unsigned tag) {
     return vbits < 0 ? (unsigned long long)tag : (((unsigned long long)(unsigned)vbits << 32) | tag | ((~idx) & 0x1fffffffu));
 }
 __device__ __forceinline__ unsigned long long u64max(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
-__device__ __forceinline__ unsigned long long u64min(unsigned long long a, unsigned long long b) { return a < b ? a : b; }
 __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long k) {       // two 32-bit passes: high word, then low
     const unsigned hi = (unsigned)(k >> 32), lo = (unsigned)k;
     const unsigned hmax = wave_max_u32(hi);
@@ -242,135 +152,8 @@ __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long k)
     return ((unsigned long long)hmax << 32) | lmax;
 }
 
-template <int PPT>
-__global__ __launch_bounds__(FPSC_T) void fps_coop2_kernel(const float* __restrict__ xyz, int N, int npoint, int G,
-                                                           unsigned long long* __restrict__ ringbuf, long long ring_stride,
-                                                           int* __restrict__ out) {
-    constexpr int NW = FPSC_T / 64;
-    __shared__ float s_l[2][8];                                         // c1 xyz, c2 xyz, accepted-2 flag, alive flag
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int b = blockIdx.x / G, g = blockIdx.x % G;
-    const float* p = xyz + (size_t)b * N * 3;
-    unsigned long long* ring = ringbuf + (size_t)b * ring_stride;       // [4][FPSC_SLOTS2] + status word
-    unsigned long long* abort_w = ring + FPSC_RING2;
-    int* o = out + (size_t)b * npoint;
-    const int S2 = 2 * G * NW;                                          // words per round (<= 256: four per lane)
-
-    float px[PPT], py[PPT], pz[PPT], md[PPT];
-    int pi[PPT];
-#pragma unroll
-    for (int k = 0; k < PPT; ++k) {
-        const int i = (g * PPT + k) * FPSC_T + tid;                     // increasing in k: first maximum = smallest index
-        pi[k] = i;
-        const bool in = i < N;
-        const int ic = in ? i : N - 1;
-        px[k] = p[ic * 3 + 0]; py[k] = p[ic * 3 + 1]; pz[k] = p[ic * 3 + 2];
-        md[k] = in ? 1e10f : -1.f;                                      // padding can never be the farthest point
-    }
-    if (g == 0 && tid == 0) o[0] = 0;
-    float l1x = p[0], l1y = p[1], l1z = p[2], l2x = 0.f, l2y = 0.f, l2z = 0.f;
-    bool have2 = false;
-    int j = 1, rounds = 0;
-    for (int r = 0; j < npoint; ++r) {
-        // update with the sample(s) of the previous round; per-lane best two by (distance, then smaller index)
-        float b1 = -1.f, b2 = -1.f;
-        int i1 = 0x7fffffff, i2 = 0x7fffffff;
-#pragma unroll
-        for (int k = 0; k < PPT; ++k) {
-            float d = fminf(md[k], sqd(px[k], py[k], pz[k], l1x, l1y, l1z));
-            if (have2) d = fminf(d, sqd(px[k], py[k], pz[k], l2x, l2y, l2z));
-            md[k] = d;
-            const bool gt1 = d > b1, gt2 = d > b2;                      // indices grow with k: strict comparisons keep the smaller
-            b2 = gt1 ? b1 : (gt2 ? d : b2);
-            i2 = gt1 ? i1 : (gt2 ? pi[k] : i2);
-            b1 = gt1 ? d : b1;
-            i1 = gt1 ? pi[k] : i1;
-        }
-        // the wave's best two (distances are >= 0 or the -1 of padding: their bit patterns order like signed integers)
-        const int vb = __float_as_int(b1);
-        const int vmax = wave_max_i32(vb);
-        const unsigned imin = ~wave_max_u32(vb == vmax ? ~(unsigned)i1 : 0u);
-        const bool mine = vb == vmax && (unsigned)i1 == imin;           // the lane that holds the wave's best
-        const int cb = mine ? __float_as_int(b2) : vb;
-        const unsigned ci = mine ? (unsigned)i2 : (unsigned)i1;
-        const int v2 = wave_max_i32(cb);
-        const unsigned i2m = ~wave_max_u32(cb == v2 ? ~ci : 0u);
-        unsigned long long* slot = ring + (r & 3) * FPSC_SLOTS2;
-        const unsigned tag = ((unsigned)(((r >> 2) & 3) << 1) | 1u) << 29;      // see fps_coop_kernel
-        if (lane == 0) {
-            fps_st(slot + 2 * (g * NW + wave), fps_key(vmax, imin, tag));
-            fps_st(slot + 2 * (g * NW + wave) + 1, fps_key(v2, i2m, tag));
-        }
-        if (wave == 0) {
-            unsigned long long k[4];
-            unsigned spins = 0;
-            bool dead = false;
-            for (;;) {
-                bool ok = true;
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    k[t] = lane + 64 * t < S2 ? fps_ld(slot + lane + 64 * t) : (unsigned long long)tag;
-                    ok = ok && ((unsigned)k[t] & (7u << 29)) == tag;
-                }
-                if (!__any(!ok)) break;
-                if (++spins > FPSC_SPIN_MAX || (spins % 1024 == 0 && fps_ld(abort_w) == FPSC_ST_ABORT)) { dead = true; break; }
-            }
-            if (dead) {                                                     // uniform over the wave
-                if (lane == 0) { fps_st(abort_w, FPSC_ST_ABORT); s_l[r & 1][7] = -1.f; }
-            } else {
-                // this lane's best two of its four words, then the wave's best two
-                const unsigned long long a0 = u64max(k[0], k[1]), a1 = u64min(k[0], k[1]);
-                const unsigned long long c0 = u64max(k[2], k[3]), c1m = u64min(k[2], k[3]);
-                const unsigned long long f1 = u64max(a0, c0);
-                const unsigned long long f2 = u64max(u64min(a0, c0), a0 > c0 ? a1 : c1m);
-                // both candidates' coordinates are fetched while the maxima are reduced
-                const unsigned q1 = (~(unsigned)f1) & 0x1fffffffu, q2 = (~(unsigned)f2) & 0x1fffffffu;
-                const unsigned q1c = q1 < (unsigned)N ? q1 : 0u, q2c = q2 < (unsigned)N ? q2 : 0u;
-                const float ax = p[q1c * 3 + 0], ay = p[q1c * 3 + 1], az = p[q1c * 3 + 2];
-                const float bx = p[q2c * 3 + 0], by = p[q2c * 3 + 1], bz = p[q2c * 3 + 2];
-                const unsigned long long K1 = wave_max_u64(f1);
-                const bool own1 = f1 == K1;                                  // keys are distinct: one lane
-                const unsigned long long K2 = wave_max_u64(own1 ? f2 : f1);
-                const int w1 = __builtin_ctzll(__ballot(own1));
-                const bool own2 = (own1 ? f2 : f1) == K2;
-                const int w2 = __builtin_ctzll(__ballot(own2));
-                const bool k2_second = w2 == w1;                             // K2 is the second word of the lane that owns K1
-                auto rl = [](float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); };
-                const float c1x = rl(ax, w1), c1y = rl(ay, w1), c1z = rl(az, w1);
-                const float c2x = k2_second ? rl(bx, w2) : rl(ax, w2), c2y = k2_second ? rl(by, w2) : rl(ay, w2),
-                            c2z = k2_second ? rl(bz, w2) : rl(az, w2);
-                const unsigned idx1 = (~(unsigned)K1) & 0x1fffffffu, idx2 = (~(unsigned)K2) & 0x1fffffffu;
-                // c2 follows c1 at once iff adding c1 leaves its min-distance (the high word of K2) untouched
-                const float md2 = __uint_as_float((unsigned)(K2 >> 32));
-                // (md2 > 0: once every min-distance is 0 - more samples than distinct points - c1 keeps the largest key
-                // (0, smallest index) after it has been added, and the sequential algorithm picks it again, not c2)
-                const bool two = j + 1 < npoint && idx2 < (unsigned)N && idx1 < (unsigned)N && md2 > 0.f &&
-                                 sqd(c2x, c2y, c2z, c1x, c1y, c1z) >= md2;
-                if (lane == 0) {
-                    float* sl = s_l[r & 1];
-                    sl[0] = c1x; sl[1] = c1y; sl[2] = c1z; sl[3] = c2x; sl[4] = c2y; sl[5] = c2z;
-                    sl[6] = two ? 1.f : 0.f; sl[7] = 1.f;
-                    if (g == 0) { o[j] = (int)idx1; if (two) o[j + 1] = (int)idx2; }
-                }
-            }
-        }
-        // s_l is double-buffered (see fps_coop_kernel): one barrier per round
-        __syncthreads();
-        const float* sl = s_l[r & 1];
-        if (sl[7] < 0.f) return;                                          // uniform over the workgroup: aborted
-        l1x = sl[0]; l1y = sl[1]; l1z = sl[2]; l2x = sl[3]; l2y = sl[4]; l2z = sl[5];
-        have2 = sl[6] > 0.f;
-        j += have2 ? 2 : 1;
-        rounds = r + 1;
-    }
-    // the word after the status word: exchange rounds this cloud took (measurement only: bench.py --mode pugan reports
-    // samples per round and the time per round next to the exchange floor of pf_fps_exchange_probe)
-    if (g == 0 && tid == 0) { fps_st(abort_w + 1, (unsigned long long)rounds); fps_st(abort_w, FPSC_ST_DONE); }
-}
-
-// ---- many samples per exchange (the shipped kernel; -DPF_FPS_TWO_SAMPLE / -DPF_FPS_ONE_SAMPLE build the predecessors) -------
-// A round of fps_coop2_kernel knows more than it uses.  Every wave publishes its KW best points; wave 0 of every workgroup
+// ---- many samples per exchange --------------------------------------------------------------------------------------------
+// A round of the two-sample kernel knows more than it uses.  Every wave publishes its KW best points; wave 0 of every workgroup
 // holds ALL published candidates (keys and, after one gather, coordinates).  Let B = the largest of the waves' LAST published
 // keys: every point nobody published lies below its own wave's last key, hence below B - and adding samples only lowers
 // min-distances, i.e. keys.  So wave 0 can run the sequential algorithm on the published candidates alone: take the largest
@@ -381,7 +164,7 @@ __global__ __launch_bounds__(FPSC_T) void fps_coop2_kernel(const float* __restri
 // fails or MS samples are out.  Unlike the two-sample rule a TOUCHED candidate may still be taken (its lowered key is exact),
 // and so may the third, fourth, ... .  Every workgroup runs the same chain on the same words and reaches the same samples.
 // CPU simulation of the CLI's merge shape (99 840 -> 20 024, 100 waves): KW = 2, MS = 8: 7.3 samples per round (cap reached
-// in 76 % of the rounds); KW = 2, MS = 16: 11.3; KW = 4, MS = 16: 15.5 - against 1.6-1.7 of fps_coop2_kernel.
+// in 76 % of the rounds); KW = 2, MS = 16: 11.3; KW = 4, MS = 16: 15.5 - against 1.6-1.7 of the two-sample kernel.
 #ifndef PF_FPS_KW
 #define PF_FPS_KW 4                                      // words (best points) a wave publishes per round: 2 or 4
 #endif
@@ -485,7 +268,7 @@ __global__ __launch_bounds__(FPSC_T, (PPT <= 16 ? 4 : (PPT <= 24 ? 3 : 2))) void
             }
         }
         unsigned long long* slot = ring + (r & 3) * FPSC_SLOTSM;
-        const unsigned tag = ((unsigned)(((r >> 2) & 3) << 1) | 1u) << 29;      // see fps_coop_kernel
+        const unsigned tag = ((unsigned)(((r >> 2) & 3) << 1) | 1u) << 29;      // see the exchange above
         if (touched) {                                                  // uniform over the wave
             // per-lane best KW by (distance, then smaller index): indices grow with k, strict comparisons keep the smaller
             float bv[KW];
@@ -526,18 +309,7 @@ __global__ __launch_bounds__(FPSC_T, (PPT <= 16 ? 4 : (PPT <= 24 ? 3 : 2))) void
         }
         if (wave == 0) {
             unsigned long long kk[NT];
-            unsigned spins = 0;
-            bool dead = false;
-            for (;;) {
-                bool ok = true;
-#pragma unroll
-                for (int t = 0; t < NT; ++t) {
-                    kk[t] = lane + 64 * t < SW ? fps_ld(slot + lane + 64 * t) : (unsigned long long)tag;
-                    ok = ok && ((unsigned)kk[t] & (7u << 29)) == tag;
-                }
-                if (!__any(!ok)) break;
-                if (++spins > FPSC_SPIN_MAX || (spins % 1024 == 0 && fps_ld(abort_w) == FPSC_ST_ABORT)) { dead = true; break; }
-            }
+            const bool dead = !pf_ring_poll<NT>(slot, SW, tag, abort_w, kk);
             float* sl = s_l[r & 1];
             if (dead) {                                                     // uniform over the wave
                 if (lane == 0) { fps_st(abort_w, FPSC_ST_ABORT); sl[3 * MS + 1] = -1.f; }
@@ -646,7 +418,7 @@ __global__ __launch_bounds__(FPSC_T, (PPT <= 16 ? 4 : (PPT <= 24 ? 3 : 2))) void
                 if (lane == 0) { sl[3 * MS] = (float)m; sl[3 * MS + 1] = 1.f; }
             }
         }
-        // s_l is double-buffered (see fps_coop_kernel): one barrier per round
+        // s_l is double-buffered (see the exchange above): one barrier per round
         __syncthreads();
         const float* sl = s_l[r & 1];
         if (sl[3 * MS + 1] < 0.f) return;                                 // uniform over the workgroup: aborted
@@ -658,7 +430,7 @@ __global__ __launch_bounds__(FPSC_T, (PPT <= 16 ? 4 : (PPT <= 24 ? 3 : 2))) void
     if (g == 0 && tid == 0) { fps_st(abort_w + 1, (unsigned long long)rounds); fps_st(abort_w, FPSC_ST_DONE); }
 }
 
-// ---- the exchange alone: what a round of fps_coop2_kernel costs with NO points to update ------------------------------
+// ---- the exchange alone: what a round of the two-sample kernel costs with NO points to update ------------------------------
 // Same protocol, same ring, same shapes (G workgroups of FPSC_T threads, two words per wave, wave 0 polls 4 words per lane,
 // reduces them and hands a result to the other waves through the double-buffered LDS words, one barrier per round) - only the
 // per-point min-distance update and the candidate's coordinate fetch are missing.  Timed with HIP events it is the floor of a
@@ -681,18 +453,7 @@ __global__ __launch_bounds__(FPSC_T) void fps_exchange_probe_kernel(int G, int r
         }
         if (wave == 0) {
             unsigned long long k[4];
-            unsigned spins = 0;
-            bool dead = false;
-            for (;;) {
-                bool ok = true;
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    k[t] = lane + 64 * t < S2 ? fps_ld(slot + lane + 64 * t) : (unsigned long long)tag;
-                    ok = ok && ((unsigned)k[t] & (7u << 29)) == tag;
-                }
-                if (!__any(!ok)) break;
-                if (++spins > FPSC_SPIN_MAX || (spins % 1024 == 0 && fps_ld(abort_w) == FPSC_ST_ABORT)) { dead = true; break; }
-            }
+            const bool dead = !pf_ring_poll<4>(slot, S2, tag, abort_w, k);
             if (dead) {
                 if (lane == 0) { fps_st(abort_w, FPSC_ST_ABORT); s_l[r & 1][1] = -1.f; }
             } else {
@@ -822,22 +583,11 @@ __global__ __launch_bounds__(256) void fps_init_kernel(float* p, long long n, in
 }
 }  // namespace
 
-// 1 when pf_fps runs the cooperative kernel for clouds of N points (its scratch row then holds the candidate ring):
-// stride_words = 64-bit words between the rings of consecutive clouds, abort_word = index of the abort word in a ring
-// two samples per exchange (fps_coop2_kernel, the shipped kernel); -DPF_FPS_ONE_SAMPLE builds the one-sample kernel instead
-// (tools/time_fps.py A/B) - a compile-time choice: pf_fps and pf_fps_scratch_layout must agree
-#if defined(PF_FPS_ONE_SAMPLE)
-static constexpr int fps_mode() { return 1; }
-#elif defined(PF_FPS_TWO_SAMPLE)
-static constexpr int fps_mode() { return 2; }
-#else
-static constexpr int fps_mode() { return 3; }                             // fps_coopm_kernel
-#endif
-static constexpr int fps_status_word() { return fps_mode() == 1 ? FPSC_RING : fps_mode() == 2 ? FPSC_RING2 : FPSC_RINGM; }
-
+// 1 when pf_fps runs the cooperative kernel (fps_coopm_kernel) for clouds of N points (its scratch row then holds the candidate
+// ring): stride_words = 64-bit words between the rings of consecutive clouds, abort_word = index of the status word in a ring
 extern "C" int pf_fps_scratch_layout(int N, long long* stride_words, long long* abort_word) {
     if (stride_words) *stride_words = ((long long)N / 2) & ~1ll;
-    if (abort_word) *abort_word = fps_status_word();
+    if (abort_word) *abort_word = FPSC_RINGM;
     return N >= 8192 && N <= FPSC_GMAX * 1024 * 8 ? 1 : 0;
 }
 
@@ -846,7 +596,7 @@ extern "C" int pf_fps_scratch_layout(int N, long long* stride_words, long long* 
 // spatial neighbourhood (the CLI's merge: 1280 candidates per patch); when a wave can hold exactly one group (64 x 12 / 20 / 24
 // points) its bounding box is that neighbourhood's, which is what the culling of fps_coopm_kernel lives on.
 static int fps_ppt(int N, int group) {
-    if (fps_mode() == 3 && group > 0 && group % 64 == 0) {
+    if (group > 0 && group % 64 == 0) {
         const int p = group / 64;
         if ((p == 12 || p == 20 || p == 24) && (N + FPSC_T * p - 1) / (FPSC_T * p) <= FPSC_GMAX && N >= FPSC_T * p * 2) return p;
     }
@@ -872,25 +622,19 @@ extern "C" int pf_fps_grouped(const float* xyz, int B, int N, int npoint, int gr
         unsigned long long* ring = reinterpret_cast<unsigned long long*>(mind);
         // cleared by a kernel, not hipMemsetAsync: a memset node inside a captured hipGraph was observed to race with the
         // kernel node that follows it (csrc/emd.hip)
-        hipLaunchKernelGGL(fps_init_kernel, dim3(256), dim3(256), 0, s, mind, (long long)B * N, B, stride,
-                           fps_status_word());
+        hipLaunchKernelGGL(fps_init_kernel, dim3(256), dim3(256), 0, s, mind, (long long)B * N, B, stride, FPSC_RINGM);
         const dim3 grid(B * G), block(FPSC_T);
-#define PF_FPS_LAUNCH(PPT)                                                                                                  \
-        if (fps_mode() == 3) hipLaunchKernelGGL(fps_coopm_kernel<PPT>, grid, block, 0, s, xyz, N, npoint, G, ring, stride, idx_out); \
-        else if (fps_mode() == 2) hipLaunchKernelGGL(fps_coop2_kernel<PPT>, grid, block, 0, s, xyz, N, npoint, G, ring, stride, idx_out); \
-        else hipLaunchKernelGGL(fps_coop_kernel<PPT>, grid, block, 0, s, xyz, N, npoint, G, ring, stride, idx_out)
-#define PF_FPS_LAUNCHM(PPT) hipLaunchKernelGGL(fps_coopm_kernel<PPT>, grid, block, 0, s, xyz, N, npoint, G, ring, stride, idx_out)
+#define PF_FPS_LAUNCH(PPT) hipLaunchKernelGGL(fps_coopm_kernel<PPT>, grid, block, 0, s, xyz, N, npoint, G, ring, stride, idx_out)
         switch (ppt) {
             case 1: PF_FPS_LAUNCH(1); break;
             case 4: PF_FPS_LAUNCH(4); break;
             case 8: PF_FPS_LAUNCH(8); break;
-            case 12: PF_FPS_LAUNCHM(12); break;                                        // (group-aligned shapes: fps_mode() == 3 only)
+            case 12: PF_FPS_LAUNCH(12); break;                                         // (group-aligned shapes)
             case 16: PF_FPS_LAUNCH(16); break;
-            case 20: PF_FPS_LAUNCHM(20); break;
-            case 24: PF_FPS_LAUNCHM(24); break;
+            case 20: PF_FPS_LAUNCH(20); break;
+            case 24: PF_FPS_LAUNCH(24); break;
             default: PF_FPS_LAUNCH(32); break;
         }
-#undef PF_FPS_LAUNCHM
 #undef PF_FPS_LAUNCH
         return pf_last_launch_status();
     }
@@ -899,7 +643,7 @@ extern "C" int pf_fps_grouped(const float* xyz, int B, int N, int npoint, int gr
 }
 
 // `rounds` exchange rounds of the cooperative FPS protocol between G workgroups (2 <= G <= 32) with no points to update: the
-// floor of a round of fps_coop2_kernel.  ring: >= 1032 64-bit words of scratch (cleared here); its word 1024 is 0 afterwards
+// floor of a round of the two-sample protocol.  ring: >= 1032 64-bit words of scratch (cleared here); its word 1024 is 0 afterwards
 // when every round completed (1 = the bounded spin gave up).  Measurement aid of bench.py --mode pugan.
 extern "C" int pf_fps_exchange_probe(int G, int rounds, unsigned long long* ring, void* stream) {
     if (!ring) return PF_ERR_NULL;
@@ -926,7 +670,7 @@ extern "C" int pf_knn_large(const float* ref, const float* query, int B, int N, 
         while (kp < K) kp <<= 1;
     }
     const size_t lds = (size_t)np * 8;
-    pf_allow_lds(reinterpret_cast<const void*>(knn_sort_kernel), lds);
+    allow_lds(knn_sort_kernel, lds);
     hipLaunchKernelGGL(knn_sort_kernel, dim3(M, B), dim3(KS_T), lds, (hipStream_t)stream, ref, query, N, M, K, np, kp,
                        idx_out, dist_out);
     return pf_last_launch_status();

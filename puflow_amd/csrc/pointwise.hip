@@ -307,11 +307,6 @@ __global__ __launch_bounds__(COND_NW * 64) void cond_all_kernel(CondAllArgs g) {
     }
 }
 
-template <class KERNEL>
-void cond_allow_lds(KERNEL k, int bytes) {
-    pf_allow_lds(reinterpret_cast<const void*>(k), (size_t)bytes);
-}
-
 // the five LDS-resident matrices of a unit back to back in the blob, in LDS order?  (fragment pair = 512 floats)
 inline int cond_contiguous(const long long* off, int odim) {
     const int HB = odim / 16, MB = odim / 32, HP = (HB + 1) / 2, MP = (MB + 1) / 2;
@@ -337,7 +332,7 @@ int launch_cond(CondArgs a, hipStream_t s) {
     if (per_cu < 1) per_cu = 1;
     const int cap = 256 * per_cu;
     const int grid = wgt < cap ? wgt : cap;
-    cond_allow_lds(cond_kernel<ODIM, CDIM>, lds);
+    allow_lds(cond_kernel<ODIM, CDIM>, lds);
     hipLaunchKernelGGL((cond_kernel<ODIM, CDIM>), dim3(grid), dim3(NW * 64), lds, s, a);
     return pf_last_launch_status();
 }
@@ -419,7 +414,7 @@ extern "C" int pf_cond_all(const float* const* h, const float* w, const long lon
         g.first[u + 1] = g.first[u] + n;
     }
     constexpr int lds = cond_lds_bytes<128>();
-    cond_allow_lds(cond_all_kernel, lds);
+    allow_lds(cond_all_kernel, lds);
     hipLaunchKernelGGL(cond_all_kernel, dim3(g.first[6]), dim3(COND_NW * 64), lds, (hipStream_t)stream, g);
     return pf_last_launch_status();
 }

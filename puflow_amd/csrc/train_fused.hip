@@ -536,26 +536,10 @@ __device__ __forceinline__ int ecp_rowmin16(int v) {
     return v;
 }
 
-// grid barrier number `gen` (1, 2, ...) of this launch: pure arrival counting - the workgroup that arrives last publishes
-// the generation word at once (what follows a barrier is done by every workgroup for itself).  Returns false when the spin gave
-// up (uniform over the workgroup).
+// grid barrier number `gen` (1, 2, ...) of this launch (pf_grid.h); false when the spin gave up (uniform over the workgroup)
 __device__ __forceinline__ bool ecp_barrier(unsigned* sync, unsigned gen, int* flag) {
     if (PF_ECP_DBG & 2) { __syncthreads(); return true; }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int fl = 0;
-        if (atomicAdd(sync, 1u) == gen * gridDim.x - 1)
-            __hip_atomic_store(sync + 1, gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else {
-            int budget = ECP_SPIN;
-            while (__hip_atomic_load(sync + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < gen && --budget > 0) __builtin_amdgcn_s_sleep(1);
-            if (budget <= 0) { fl = 2; __hip_atomic_store(sync + 3, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-        }
-        *flag = fl;
-    }
-    __syncthreads();
-    return *flag != 2;
+    return pf_grid_barrier<ECP_SPIN>(sync, gen, flag);
 }
 
 template <int G, int NC, int ODIM>
@@ -2740,11 +2724,6 @@ __global__ __launch_bounds__(256) void ec_zero_kernel(f4* p, long long n4) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) p[i] = pf_splat(0.f);
 }
 
-template <typename KERNEL>
-void allow_lds(KERNEL k, size_t bytes) {
-    pf_allow_lds(reinterpret_cast<const void*>(k), bytes);
-}
-
 // SyncBN on the fused kernels: after a launch whose StatFin defers (the local sums sit in fin.defer), the caller's callback
 // all-reduces them over the ranks (stream-ordered, e.g. torch.distributed.all_reduce on the tensor behind the pointer) and
 // one small launch finishes the layer with the global sums.
@@ -2827,27 +2806,12 @@ size_t ecp_lds_bytes() {
     for (int t = 1; t < 4; ++t) fl += (size_t)((G + 15) / 16) * 16 * (((G * t + 15) & ~15) + 4);
     return fl * sizeof(float) + (size_t)(ODIM / 16) * (G * 4 / 32) * 2 * 64 * 16;
 }
-// (the occupancy answers are cached per device: the queries ran on every call of the 1 ms step and inside graph captures - ADVICE r4)
-constexpr int ECP_MAXDEV = 16;
 template <int G, int ODIM>
 int ecp_capacity() {
-    static int cache[ECP_MAXDEV];                   // 0 = not asked yet, -1 = does not fit, > 0 = workgroups that can be resident
-    static std::mutex mu;
-    int ncu = 0, dev = 0, per_cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-    std::lock_guard<std::mutex> lock(mu);
-    if (dev >= 0 && dev < ECP_MAXDEV && cache[dev] != 0) return cache[dev] > 0 ? cache[dev] : 0;
-    const size_t lds = ecp_lds_bytes<G, ODIM>();
-    allow_lds(ec_fwdp_kernel<G, 4, ODIM>, lds);
-    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    int cap = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, ec_fwdp_kernel<G, 4, ODIM>, ECP_T, lds) != hipSuccess) (void)hipGetLastError();
-    else {
-        const int want = ECP_TPW / ecp_tpw(G);      // workgroups per CU the unit's grid needs resident (2 for the narrow units)
-        cap = (per_cu < want ? per_cu : want) * ncu;
-    }
-    if (dev >= 0 && dev < ECP_MAXDEV) cache[dev] = cap > 0 ? cap : -1;
-    return cap;
+    int ncu = 0;
+    const int per_cu = resident_per_cu(ec_fwdp_kernel<G, 4, ODIM>, ECP_T, ecp_lds_bytes<G, ODIM>(), &ncu);
+    const int want = ECP_TPW / ecp_tpw(G);          // workgroups per CU the unit's grid needs resident (2 for the narrow units)
+    return (per_cu < want ? per_cu : want) * ncu;
 }
 bool ec_persistent_ok(const PfEcTrain* p, const Dims& d) {
     if (!(p->flags & PF_EC_PERSISTENT) || (p->flags & PF_TRAIN_DETERMINISTIC) || !p->sync || !p->pooling || p->K != 16 || p->nconv != 4 ||
@@ -2871,19 +2835,7 @@ size_t ecpb_lds_bytes() {
 }
 template <int G, int ODIM>
 bool ecpb_fits() {
-    static int cache[ECP_MAXDEV];                   // 0 = not asked yet, 1 = fits, -1 = does not
-    static std::mutex mu;
-    int dev = 0, per_cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return false;
-    std::lock_guard<std::mutex> lock(mu);
-    if (dev >= 0 && dev < ECP_MAXDEV && cache[dev] != 0) return cache[dev] > 0;
-    const size_t lds = ecpb_lds_bytes<G, ODIM>();
-    allow_lds(ec_bwdp_kernel<G, 4, ODIM>, lds);
-    bool fits = false;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, ec_bwdp_kernel<G, 4, ODIM>, ECP_T, lds) != hipSuccess) (void)hipGetLastError();
-    else fits = per_cu >= ECP_TPW / ecp_tpw(G);
-    if (dev >= 0 && dev < ECP_MAXDEV) cache[dev] = fits ? 1 : -1;
-    return fits;
+    return resident_per_cu(ec_bwdp_kernel<G, 4, ODIM>, ECP_T, ecpb_lds_bytes<G, ODIM>(), nullptr) >= ECP_TPW / ecp_tpw(G);
 }
 bool ec_bwd_persistent_fits(const PfEcTrain* p) {
     return p->growth == 8 ? ecpb_fits<8, 32>() : (p->growth == 16 ? ecpb_fits<16, 64>() : ecpb_fits<32, 128>());
@@ -3258,7 +3210,7 @@ extern "C" int pf_ec_train_bwd(const PfEcTrain* p, void* stream) {
         } else {
             const int ramax = p->odim > d.GT ? p->odim : d.GT;
             const size_t lds = sizeof(float) * (size_t)DW_EB * ((ramax + 16) + (d.GT + 16));
-            pf_allow_lds(reinterpret_cast<const void*>(ec_dw_kernel<EC_DW_WAVES>), lds);
+            allow_lds(ec_dw_kernel<EC_DW_WAVES>, lds);
             hipLaunchKernelGGL(ec_dw_kernel<EC_DW_WAVES>, dim3(d.nchunk, 2), dim3(64 * EC_DW_WAVES), lds, s, a);
         }
     }

@@ -709,11 +709,6 @@ __global__ __launch_bounds__(64 * MLP_RG) void mlp_dw_reduce_kernel(MlpBatch bb)
 
 static inline MlpBatch mlp_one(const PfMlpTrain& p) { MlpBatch b; b.p[0] = p; return b; }
 
-template <typename KERNEL>
-void allow_lds(KERNEL k, size_t bytes) {
-    pf_allow_lds(reinterpret_cast<const void*>(k), bytes);
-}
-
 int mlp_check(const PfMlpTrain* p) {
     if (!p) return PF_ERR_NULL;
     if (p->rows <= 0 || (p->nl != 2 && p->nl != 3) || p->td < 0 || p->td > 3 || p->cdiv < 1) return PF_ERR_SHAPE;

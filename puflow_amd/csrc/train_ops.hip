@@ -340,7 +340,7 @@ void gemm2_launch(const GemmArgs& g, int split, hipStream_t s) {
     constexpr int LDA = BM % 32 == 0 ? BM + 16 : BM + 32, LDB = BN % 32 == 0 ? BN + 16 : BN + 32;
     constexpr int loop_floats = 2 * 32 * (LDA + LDB), out_floats = BM * (BN + 4);
     constexpr size_t lds = sizeof(float) * (size_t)(loop_floats > out_floats ? loop_floats : out_floats);
-    pf_allow_lds(reinterpret_cast<const void*>(gemm2_kernel<WAVES_M, WAVES_N, TM, TN>), lds);
+    allow_lds(gemm2_kernel<WAVES_M, WAVES_N, TM, TN>, lds);
     auto al16 = [](const void* p) { return (reinterpret_cast<unsigned long long>(p) & 15ull) == 0; };
     const long long ldc = g.ldc;
     const int cvec = (ldc % 4 == 0) && al16(g.C) && (!g.bias || al16(g.bias)) && (!g.add || al16(g.add)) && (((long long)g.M * ldc) % 4 == 0);

@@ -7,6 +7,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import emd_ref as E
 from oracle import ref_cpu as O
+from kernel_trace import launched, ran
 from puflow_amd.weights import synth_patches
 
 DEV = "cuda:0"
@@ -156,9 +157,12 @@ def test_emd_groups_argument_and_status_word():
     g = torch.Generator().manual_seed(3)
     x = torch.rand(4, 1024, 3, generator=g).cuda()
     y = torch.rand(4, 1024, 3, generator=g).cuda()
-    outs = [emdFunction.apply(x, y, 0.005, 50, grp) for grp in (0, 1, 4)]
+    runs = [launched(lambda: emdFunction.apply(x, y, 0.005, 50, grp)) for grp in (0, 1, 4)]
+    outs = [r[0] for r in runs]
     for d, a in outs[1:]:
         assert torch.equal(a, outs[0][1]) and torch.equal(d, outs[0][0])
+    for (_, names), kernel in zip(runs, ("emd_repl_kernel", "emd_auction_kernel", "emd_repl_kernel")):
+        assert ran(names, kernel), sorted(names)
     check_emd_status()                                       # nothing timed out
     st = _emd_status(x.device)
     assert int(st[0]) == 0
@@ -166,3 +170,42 @@ def test_emd_groups_argument_and_status_word():
     with pytest.raises(_lib.PuflowHipError):
         check_emd_status()
     check_emd_status()                                       # cleared by the report
+
+
+def test_emd_unpaired_scratch_runs_the_coop_kernel():
+    """pf_emd_forward_ex with bid / bid_increments / max_increments / max_idx as separate arrays (not back to back, as the
+    reference's emd.forward argument list may pass them): emd_repl_kernel needs two of them adjacent for its 64-bit records, so
+    emd_coop_kernel runs.  Same arithmetic and tie rules: the assignment and distances equal the paired path's (emd_repl_kernel)
+    and one workgroup per sample's (emd_auction_kernel) bit for bit, and the status word stays 0."""
+    from puflow_amd import _lib, ops
+    from puflow_amd.loss import _emd_status, check_emd_status, emdFunction
+    lib = _lib.load()
+    B, n = 4, 1024
+    g = torch.Generator().manual_seed(5)
+    x = torch.rand(B, n, 3, generator=g).to(DEV)
+    y = torch.rand(B, n, 3, generator=g).to(DEV)
+    st = _emd_status(x.device)
+
+    def unpaired():
+        price = torch.zeros(B, n, device=DEV)
+        assignment = torch.full((B, n), -1, device=DEV, dtype=torch.int32)
+        assignment_inv = torch.full((B, n), -1, device=DEV, dtype=torch.int32)
+        gap = B * n + 64                                      # 64 spare words between the arrays: never adjacent, 8-byte aligned
+        buf = torch.empty(5 * gap, device=DEV, dtype=torch.int32)
+        max_inc, bid_inc, max_idx, bid, unass = (buf[k * gap:k * gap + B * n] for k in range(5))
+        dist = torch.empty(B, n, device=DEV)
+        _lib.check(lib.pf_emd_forward_ex(x.data_ptr(), y.data_ptr(), dist.data_ptr(), assignment.data_ptr(), price.data_ptr(),
+                                         assignment_inv.data_ptr(), bid.data_ptr(), bid_inc.data_ptr(), max_inc.data_ptr(),
+                                         unass.data_ptr(), max_idx.data_ptr(), 0.005, 50, B, n, 0, st.data_ptr(), ops._stream()),
+                   "pf_emd_forward")
+        return dist, assignment
+
+    (d_u, a_u), names_u = launched(unpaired)
+    (d_p, a_p), names_p = launched(lambda: emdFunction.apply(x, y, 0.005, 50, 0))
+    d_1, a_1 = emdFunction.apply(x, y, 0.005, 50, 1)
+    assert ran(names_u, "emd_coop_kernel") and not ran(names_u, "emd_repl_kernel"), sorted(names_u)
+    assert ran(names_p, "emd_repl_kernel"), sorted(names_p)
+    assert int(st[0]) == 0
+    assert torch.equal(a_u, a_p) and torch.equal(d_u, d_p)
+    assert torch.equal(a_u, a_1) and torch.equal(d_u, d_1)
+    check_emd_status()

@@ -9,6 +9,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import patch_ref as P
 from oracle import ref_cpu as O
+from kernel_trace import launched, ran
 from puflow_amd.weights import synth_patches, synth_state_dict
 
 DEV = "cuda:0"
@@ -24,9 +25,11 @@ def test_fps_bit_exact(B, N, npoint):
         xyz[0, 5] = xyz[0, 9]                          # duplicates: ties resolve to the first maximum
         xyz[0, N - 1] = xyz[0, 3]
     ref = P.fps(xyz, npoint)
-    got = ops.furthest_point_sample(xyz.to(DEV), npoint)
+    got, names = launched(lambda: ops.furthest_point_sample(xyz.to(DEV), npoint))
     assert torch.equal(got.cpu().long(), ref)
     assert got[:, 0].eq(0).all()
+    if N == 40960:                                     # one cooperative shape: the many-samples-per-round kernel ran
+        assert ran(names, "fps_coopm_kernel"), sorted(names)
 
 
 @pytest.mark.parametrize("group,N,npoint", [(768, 30720, 3001), (1280, 99840, 1500), (1280, 20480, 2048), (1536, 36864, 777), (640, 20480, 500)])

@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+from kernel_trace import launched, ran
+
 pytestmark = pytest.mark.gpu
 
 
@@ -457,10 +459,14 @@ def test_edgeconv_unit_persistent_forward_matches_the_per_layer_kernels(cin, odi
         train_ops.edgeconv_train_fused(p, x, idx, True, csr, False)
     rmeans = [seq[1].running_mean.clone() * (0.97 / seq[1].momentum) for seq in p.convs]
     assert train_ops._PERSIST
-    o_p, dx_p, g_p, st_p, Y_p, aff_p, arg_p = run(True)
+    (o_p, dx_p, g_p, st_p, Y_p, aff_p, arg_p), k_p = launched(lambda: run(True))
     sync = train_ops._sync_words(xyz.device)
     assert sync.tolist() == [0, 0, 0, 0]                               # barrier words back to zero, no timeout
-    o_l, dx_l, g_l, st_l, Y_l, aff_l, arg_l = run(False)
+    (o_l, dx_l, g_l, st_l, Y_l, aff_l, arg_l), k_l = launched(lambda: run(False))
+    # the persistent run really ran the grid-barrier kernels (a residency check that wrongly says "does not fit" falls back to
+    # the per-layer kernels, and the comparison below would pass against itself)
+    assert ran(k_p, "ec_fwdp_kernel") and ran(k_p, "ec_bwdp_kernel"), sorted(k_p)
+    assert not ran(k_l, "ec_fwdp_kernel") and not ran(k_l, "ec_bwdp_kernel"), sorted(k_l)
     g = growth
     assert torch.equal(Y_p[:, :g], Y_l[:, :g])                         # layer 0: P[i] + Q[j], no statistics involved yet
     _close(Y_p, Y_l, "Y", 2e-6)
