@@ -77,27 +77,48 @@ struct StatFin {
                                       // defer[0 .. ncol) / defer[STAT_W ..] and the local row count in defer[2 STAT_W] (mode 2: dbeta /
                                       // dgamma are written from the local sums, as torch.nn.SyncBatchNorm does); the host all-reduces
                                       // the 2 STAT_W + 1 doubles over the ranks and stat_finalize_kernel finishes with the global sums
-    int det;                          // PF_TRAIN_DETERMINISTIC: the accumulators hold 64-bit FIXED-POINT sums (quantum 2^-28) added with
-                                      // integer atomics - exact, so independent of the order in which the workgroups arrive; the
-                                      // default (double atomics) rounds in arrival order once a sum needs more than 53 bits
+    int det;                          // PF_TRAIN_DETERMINISTIC: the accumulators hold 64-bit FIXED-POINT sums (two words per value:
+                                      // quanta 2^-28 and 2^-60) added with integer atomics - exact, so independent of the order in
+                                      // which the workgroups arrive; the default (double atomics) rounds in arrival order once a sum
+                                      // needs more than 53 bits
 };
 
 constexpr int STAT_COPIES = 16;       // workgroups spread their atomics over this many accumulator sets (same-address atomics serialise)
 constexpr int STAT_W = 128;           // statistics columns per launch (EdgeConv layers use <= 32, the BatchNorm MLPs up to 128)
 constexpr int STAT_DOUBLES = STAT_COPIES * 2 * STAT_W + 1;
-// deterministic accumulation (StatFin::det): a workgroup's float partial as a multiple of 2^-28 in a 64-bit integer (|sum| < 3.4e10);
-// the same 8-byte accumulator words, zero in either reading
+// deterministic accumulation (StatFin::det): a workgroup's float partial v split into two 64-bit integers, hi = v rounded to a
+// multiple of 2^-28 (|sum| < 3.4e10) and lo = the remainder as a multiple of 2^-60 (|lo| <= 2^31 per partial) - the sum is
+// exact to ~4e-19 per partial, whatever the size of the sum (one coarse quantum alone put an absolute error of up to 1.9e-9 on
+// every partial: BatchNorm gradients of 1e-5 missed float64 by 3.3e-3 to 1.0e-2, tests/test_gpu_deterministic.py case (b)).
+// The same 8-byte accumulator words, zero in either reading: copies [0, STAT_DET_COPIES) hold hi, the copies behind them lo.
 #define PF_DET(p) (((p)->flags & PF_TRAIN_DETERMINISTIC) ? 1 : 0)
-constexpr double STAT_FIX = 268435456.0, STAT_FIX_INV = 1.0 / 268435456.0;
+constexpr int STAT_DET_COPIES = STAT_COPIES / 2;
+constexpr double STAT_FIX = 268435456.0, STAT_FIX_INV = 1.0 / 268435456.0;                 // 2^28
+constexpr double STAT_FIX_LO = 4294967296.0, STAT_FIX_LO_INV = 1.0 / (268435456.0 * 4294967296.0);   // 2^32 more
 __device__ __forceinline__ void stat_add(double* acc, float v, int det) {
-    if (det) atomicAdd(reinterpret_cast<unsigned long long*>(acc), (unsigned long long)(long long)__double2ll_rn((double)v * STAT_FIX));
-    else unsafeAtomicAdd(acc, (double)v);
+    if (det) {
+        const double s = (double)v * STAT_FIX;                          // exact (a float times a power of two)
+        const long long hi = __double2ll_rn(s);
+        const long long lo = __double2ll_rn((s - (double)hi) * STAT_FIX_LO);   // s - hi exact: |s - hi| <= 1/2, hi within 2x of s
+        atomicAdd(reinterpret_cast<unsigned long long*>(acc), (unsigned long long)hi);
+        atomicAdd(reinterpret_cast<unsigned long long*>(acc + STAT_DET_COPIES * 2 * STAT_W), (unsigned long long)lo);
+    } else
+        unsafeAtomicAdd(acc, (double)v);
 }
-__device__ __forceinline__ double stat_load(const double* acc, int det) {
-    if (det)
-        return (double)(long long)__hip_atomic_load(reinterpret_cast<const unsigned long long*>(acc), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) *
-               STAT_FIX_INV;
+__device__ __forceinline__ double stat_load(const double* acc) {
     return __hip_atomic_load(acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ long long stat_load_fix(const double* acc) {
+    return (long long)__hip_atomic_load(reinterpret_cast<const unsigned long long*>(acc), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// det: one column's sum from its hi / lo words - integer sums first (exact, any order), then one fixed conversion
+__device__ __forceinline__ double stat_load_det(const double* acc) {
+    long long hi = 0, lo = 0;
+    for (int k = 0; k < STAT_DET_COPIES; ++k) {
+        hi += stat_load_fix(acc + k * 2 * STAT_W);
+        lo += stat_load_fix(acc + (k + STAT_DET_COPIES) * 2 * STAT_W);
+    }
+    return (double)hi * STAT_FIX_INV + (double)lo * STAT_FIX_LO_INV;
 }
 
 // sums of one column -> the layer's constants.  R: rows the sums run over (the GLOBAL count under SyncBN); param_grads: mode 2
@@ -149,7 +170,8 @@ __device__ __forceinline__ void stat_flush(float (&s0)[NT], float (&s1)[NT], int
     if ((threadIdx.x & (STAT_W - 1)) < ncol) {                        // 256 threads = 2 x STAT_W sums
         const int t = threadIdx.x;
         const float v = (red[t] + red[2 * STAT_W + t]) + (red[4 * STAT_W + t] + red[6 * STAT_W + t]);
-        stat_add(f.acc + (blockIdx.x % STAT_COPIES) * 2 * STAT_W + t, v, f.det);
+        if (f.det) stat_add(f.acc + (blockIdx.x % STAT_DET_COPIES) * 2 * STAT_W + t, v, 1);
+        else stat_add(f.acc + (blockIdx.x % STAT_COPIES) * 2 * STAT_W + t, v, 0);
     }
     // order the accumulator atomics before the arrival count WITHOUT a release fence: a device-scope fence writes the whole
     // L2 back on this multi-die part (tens of microseconds per launch); the atomics themselves are performed at the coherent
@@ -163,11 +185,16 @@ __device__ __forceinline__ void stat_flush(float (&s0)[NT], float (&s1)[NT], int
     const int c = threadIdx.x;
     if (c < ncol) {
         double a0 = 0.0, a1 = 0.0;
-        for (int k = 0; k < STAT_COPIES; ++k) {
-            a0 += stat_load(f.acc + k * 2 * STAT_W + c, f.det);          // (16 multiples of 2^-28: exact in double, any order)
-            a1 += stat_load(f.acc + k * 2 * STAT_W + STAT_W + c, f.det);
-            f.acc[k * 2 * STAT_W + c] = 0.0; f.acc[k * 2 * STAT_W + STAT_W + c] = 0.0;
-        }
+        if (f.det) {
+            a0 = stat_load_det(f.acc + c);
+            a1 = stat_load_det(f.acc + STAT_W + c);
+            for (int k = 0; k < STAT_COPIES; ++k) { f.acc[k * 2 * STAT_W + c] = 0.0; f.acc[k * 2 * STAT_W + STAT_W + c] = 0.0; }
+        } else
+            for (int k = 0; k < STAT_COPIES; ++k) {
+                a0 += stat_load(f.acc + k * 2 * STAT_W + c);
+                a1 += stat_load(f.acc + k * 2 * STAT_W + STAT_W + c);
+                f.acc[k * 2 * STAT_W + c] = 0.0; f.acc[k * 2 * STAT_W + STAT_W + c] = 0.0;
+            }
         if (f.defer) {                                                // SyncBN: local sums out, the layer is finished after the all-reduce
             f.defer[c] = a0;
             f.defer[STAT_W + c] = a1;

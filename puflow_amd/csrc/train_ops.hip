@@ -1172,7 +1172,9 @@ extern "C" int pf_scatter_rows(const float* g, const int* idx, int B, int N, int
 }
 
 // the same sum as a gather over the transposed lists (pf_knn_csr of idx, lists sorted): one order, run after run - the
-// deterministic form (PF_TRAIN_DETERMINISTIC) of the un-fused latent gather's backward
+// deterministic form (PF_TRAIN_DETERMINISTIC) of the un-fused latent gather's backward.  Accumulated in double and rounded
+// once: a hub row's list holds every edge of its cloud (100 in tests/test_gpu_deterministic.py), and the fp32 sum of such a
+// list missed float64 by 1.2e-6 on one element, past that test's bar
 __global__ __launch_bounds__(256) void scatter_rows_det_kernel(const float* __restrict__ g, const int* __restrict__ off,
                                                               const int* __restrict__ edge, int C, long long total,
                                                               float* __restrict__ out) {
@@ -1180,9 +1182,9 @@ __global__ __launch_bounds__(256) void scatter_rows_det_kernel(const float* __re
     if (t >= total) return;
     const long long j = t / C;
     const int c = (int)(t - j * C);
-    float s = 0.f;
-    for (int q = off[j]; q < off[j + 1]; ++q) s += g[(long long)edge[q] * C + c];
-    out[t] = s;
+    double s = 0.0;
+    for (int q = off[j]; q < off[j + 1]; ++q) s += (double)g[(long long)edge[q] * C + c];
+    out[t] = (float)s;
 }
 extern "C" int pf_scatter_rows_det(const float* g, const int* csr_off, const int* csr_edge, long long T, int C, float* out, void* stream) {
     if (!g || !csr_off || !csr_edge || !out) return PF_ERR_NULL;

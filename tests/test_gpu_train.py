@@ -130,6 +130,12 @@ def _assert_grads_elementwise(params, ref_grad, tol=1e-2):
 
 
 def test_training_step_matches_reference_golden(golden_dir):
+    _golden_step(golden_dir)
+
+
+def _golden_step(golden_dir, deterministic=False):
+    """The step of tests/golden/train_step.npz against the golden vectors and the oracle; deterministic: net.deterministic
+    (tests/test_gpu_deterministic.py), every assertion and bar the same."""
     from puflow_amd import ops
     from puflow_amd.interpflow import PointInterpFlow
     g = np.load(os.path.join(golden_dir, "train_step.npz"))
@@ -140,6 +146,7 @@ def test_training_step_matches_reference_golden(golden_dir):
     net = PointInterpFlow(3)
     net.load_state_dict(sd)
     net = net.to(DEV).train()                            # ActNorm not initialised: first-batch init, like the reference
+    net.deterministic = deterministic
     x, logp = net(sparse.to(DEV), R)
     cd, _ = ops.chamfer_distance(x, dense.to(DEV))
     loss = logp * 1e-4 + cd * 1e-1
@@ -242,6 +249,11 @@ def test_training_step_at_the_real_batch_size_matches_the_oracle():
     """BASELINE configs[2] shape: 32 patches of 256 -> 1024 points per rank.  The HIP train-mode forward + backward
     against the train-mode oracle (oracle/ref_cpu.py::forward_train, itself pinned to the reference's own training
     step at B = 4 by tests/golden/train_step.npz): x, logp, CD, loss and the gradient norm of every parameter."""
+    _real_batch_step()
+
+
+def _real_batch_step(deterministic=False):
+    """test_training_step_at_the_real_batch_size_matches_the_oracle's body; deterministic: net.deterministic, bars unchanged."""
     from puflow_amd import ops
     from puflow_amd.interpflow import PointInterpFlow
     B, N, R = 32, 256, 4
@@ -257,6 +269,7 @@ def test_training_step_at_the_real_batch_size_matches_the_oracle():
     net = PointInterpFlow(3)
     net.load_state_dict(sd)
     net = net.to(DEV).train()
+    net.deterministic = deterministic
     x, logp = net(sparse.to(DEV), R)
     cd, _ = ops.chamfer_distance(x, dense.to(DEV))
     loss = logp * 1e-4 + cd * 1e-1
