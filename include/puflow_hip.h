@@ -621,6 +621,35 @@ int pf_fps_exchange_probe(int G, int rounds, unsigned long long* ring, void* str
  * summation order: a cloud's result does not depend on B. */
 int pf_normalize_pc(const float* x, int B, int N, float* out, float* centroid, float* fdist, void* stream);
 
+/* ---- ragged ("packed") forms of the patch operators: B clouds of n[i] points stored back to back as one [sum n, 3] array.
+ * n, npoint, m are HOST arrays of B ints (the per-cloud tables travel to the kernels as launch arguments: nothing is uploaded,
+ * nothing synchronises).  Contract: every cloud gets, bit for bit, what the dense entry point above gives it when it runs
+ * alone (B = 1); a cloud's result depends on no other cloud of the batch. */
+/* pf_normalize_pc per cloud: out [sum n, 3] (may alias x), centroid [B,3], fdist [B]. */
+int pf_normalize_pc_ragged(const float* x, const int* n, int B, float* out, float* centroid, float* fdist, void* stream);
+/* Scratch of pf_fps_ragged for these sizes and this group hint (HOST function, no GPU work): scratch_off[i] = first float of
+ * cloud i's row (even: a cooperative cloud's candidate ring is read there as 64-bit words), wgs[i] = workgroups cloud i gets
+ * in the cooperative launch (0 = fewer than 8192 points: single-workgroup kernel), total_floats = size of the scratch array;
+ * cloud i's status word is the 64-bit word status_word + i * status_stride of the scratch (values as pf_fps_scratch_layout:
+ * 0 = complete; here EVERY cloud has one, whichever kernel ran it), followed by its exchange-round count.  All outputs
+ * nullable.  Returns the points per thread of the cooperative launch (0: none needed) or a negative PF_ERR_* code. */
+int pf_fps_ragged_layout(const int* n, int B, int group, long long* scratch_off, int* wgs, long long* total_floats,
+                         long long* status_word, long long* status_stride);
+/* pf_fps_grouped per cloud: npoint[i] <= n[i] samples of cloud i -> idx_out [sum npoint] int32 (indices inside the cloud).
+ * scratch: pf_fps_ragged_layout's total_floats, 8-byte aligned.  At most two kernel families per pass - the cooperative one
+ * for the clouds of >= 8192 points (one launch per 64 clouds: workgroups cloud-major in ascending order, G_i = wgs[i] each, so
+ * in-order dispatch keeps every workgroup of the lowest unfinished cloud resident, as in pf_fps), one workgroup per cloud
+ * for the others - with one points-per-thread shape per pass (chosen for the largest cloud; it changes no index). */
+int pf_fps_ragged(const float* xyz, const int* n, const int* npoint, int B, int group, float* scratch, int* idx_out,
+                  void* stream);
+/* pf_knn_large per cloud: ref [sum n, 3], query [sum m, 3] (m[i] queries against cloud i) -> idx_out [sum m, K] (indices
+ * inside the cloud), dist_out [sum m, K] (nullable).  K <= every n[i]; clouds beyond 16384 points stream as in pf_knn_large. */
+int pf_knn_large_ragged(const float* ref, const float* query, const int* n, const int* m, int B, int K, int* idx_out,
+                        float* dist_out, void* stream);
+/* pf_nn1 per cloud: p1 [sum n, 3] queries, p2 [sum m, 3] references -> dist_out [sum n], idx_out [sum n] (nullable). */
+int pf_nn1_ragged(const float* p1, const float* p2, const int* n, const int* m, int B, float* dist_out, int* idx_out,
+                  void* stream);
+
 /* Text format of the CLI's output clouds (HOST memory, no GPU work): the bytes np.savetxt(path, cloud, fmt='%.6f') writes
  * (modules/discrete/upsample.py:57) - rows of c "%.6f" values separated by one blank, '\n' after every row.  pts [n,c]
  * float32; out must hold pf_format_xyz_bound(n, c) bytes.  Returns the bytes written or a negative PF_ERR_* code. */

@@ -201,6 +201,12 @@ SIGNATURES = {
                              c_float, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "pf_knn_large": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "pf_normalize_pc": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pf_normalize_pc_ragged": (c_int, [c_void_p, POINTER(c_int), c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pf_fps_ragged_layout": (c_int, [POINTER(c_int), c_int, c_int, POINTER(c_longlong), POINTER(c_int), POINTER(c_longlong),
+                                     POINTER(c_longlong), POINTER(c_longlong)]),
+    "pf_fps_ragged": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "pf_knn_large_ragged": (c_int, [c_void_p, c_void_p, POINTER(c_int), POINTER(c_int), c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "pf_nn1_ragged": (c_int, [c_void_p, c_void_p, POINTER(c_int), POINTER(c_int), c_int, c_void_p, c_void_p, c_void_p]),
     "pf_format_xyz_bound": (c_longlong, [c_longlong, c_int]),
     "pf_format_xyz": (c_longlong, [c_void_p, c_longlong, c_int, c_void_p, c_longlong]),
     "pf_parse_xyz": (c_longlong, [c_void_p, c_longlong, c_void_p, c_longlong, POINTER(c_int)]),
@@ -250,3 +256,8 @@ def check(rc: int, what: str = "") -> None:
 
 def offsets(vals):
     return (c_longlong * len(vals))(*[int(v) for v in vals])
+
+
+def counts(vals):
+    """host int array of the ragged entry points (per-cloud point counts)"""
+    return (c_int * len(vals))(*[int(v) for v in vals])

@@ -773,15 +773,12 @@ __global__ __launch_bounds__(NW * 64) void knn5_kernel(const float* __restrict__
 }
 
 // K = 1: nearest neighbour distance + index (first minimum wins ties).
-__global__ __launch_bounds__(256) void nn1_kernel(const float* __restrict__ p1, const float* __restrict__ p2,
-                                                  int N, int M, float* __restrict__ dist_out,
-                                                  int* __restrict__ idx_out) {
-    const int b = blockIdx.y;
-    const int n = blockIdx.x * 256 + threadIdx.x;
+// query n of one cloud: q1 [N,3] queries, r [M,3] references (uniform over the workgroup), dout / iout [N]
+__device__ __forceinline__ void nn1_body(const float* __restrict__ q1, const float* __restrict__ r, int N, int M, int n,
+                                         float* __restrict__ dout, int* __restrict__ iout) {
     const bool live = n < N;
-    const float* q = p1 + ((size_t)b * N + (live ? n : N - 1)) * 3;
+    const float* q = q1 + (size_t)(live ? n : N - 1) * 3;
     const float qx = q[0], qy = q[1], qz = q[2];
-    const float* __restrict__ r = p2 + (size_t)b * M * 3;
     // references are wave-uniform: scalar loads, SGPR operands (see knn4_kernel)
     float best = __builtin_inff(), thr = __builtin_inff();
     int besti = 0;
@@ -817,9 +814,34 @@ __global__ __launch_bounds__(256) void nn1_kernel(const float* __restrict__ p1, 
     }
     for (int j = mfull; j < M; ++j) visit(j);
     if (live) {
-        dist_out[(size_t)b * N + n] = best;
-        if (idx_out) idx_out[(size_t)b * N + n] = besti;
+        dout[n] = best;
+        if (iout) iout[n] = besti;
     }
+}
+
+__global__ __launch_bounds__(256) void nn1_kernel(const float* __restrict__ p1, const float* __restrict__ p2,
+                                                  int N, int M, float* __restrict__ dist_out,
+                                                  int* __restrict__ idx_out) {
+    const int b = blockIdx.y;
+    nn1_body(p1 + (size_t)b * N * 3, p2 + (size_t)b * M * 3, N, M, blockIdx.x * 256 + threadIdx.x, dist_out + (size_t)b * N,
+             idx_out ? idx_out + (size_t)b * N : nullptr);
+}
+
+// ragged batch (clouds of different sizes stored back to back): the table travels as a kernel argument, a workgroup is one
+// 256-query tile of one cloud
+constexpr int NN1_RAGGED_MAXB = 64;
+struct Nn1RaggedTab {
+    int xoff[NN1_RAGGED_MAXB], n[NN1_RAGGED_MAXB];        // queries of the cloud: first row, count (outputs have the same rows)
+    int yoff[NN1_RAGGED_MAXB], m[NN1_RAGGED_MAXB];        // its references
+    int t0[NN1_RAGGED_MAXB + 1];                          // its first tile (prefix sum of ceil(n / 256))
+};
+__global__ __launch_bounds__(256) void nn1_ragged_kernel(const float* __restrict__ p1, const float* __restrict__ p2,
+                                                         const Nn1RaggedTab t, int nc, float* __restrict__ dist_out,
+                                                         int* __restrict__ idx_out) {
+    int c = 0;
+    while (c + 1 < nc && (int)blockIdx.x >= t.t0[c + 1]) ++c;            // uniform
+    nn1_body(p1 + (size_t)t.xoff[c] * 3, p2 + (size_t)t.yoff[c] * 3, t.n[c], t.m[c], ((int)blockIdx.x - t.t0[c]) * 256 + threadIdx.x,
+             dist_out + t.xoff[c], idx_out ? idx_out + t.xoff[c] : nullptr);
 }
 
 
@@ -918,5 +940,43 @@ extern "C" int pf_nn1(const float* p1, const float* p2, int B, int N, int M, flo
     }
     hipLaunchKernelGGL(nn1_kernel, dim3((N + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, p1, p2, N, M, dist_out,
                        idx_out);
+    return pf_last_launch_status();
+}
+
+// pf_nn1 for B clouds of different sizes stored back to back: p1 [sum n, 3], p2 [sum m, 3] -> dist_out / idx_out [sum n];
+// n, m: HOST arrays.  Every cloud runs on the kernel pf_nn1 picks for it ALONE (B = 1), so its result is that call's bit for
+// bit: the clouds pf_nn1 scans with nn1_kernel share ragged launches (up to 64 clouds each), the ones it sends to the
+// MFMA-filter kernel (1024 <= m <= 4096 references and >= 64 query tiles: a table per cloud in LDS) get one launch each.
+extern "C" int pf_nn1_ragged(const float* p1, const float* p2, const int* n, const int* m, int B, float* dist_out, int* idx_out,
+                             void* stream) {
+    if (!p1 || !p2 || !n || !m || !dist_out) return PF_ERR_NULL;
+    if (B <= 0) return PF_ERR_SHAPE;
+    long long nt = 0, mt = 0;
+    for (int i = 0; i < B; ++i) {
+        if (n[i] <= 0 || m[i] <= 0) return PF_ERR_SHAPE;
+        nt += n[i]; mt += m[i];
+    }
+    if (nt * 3 > 0x7fffffffll || mt * 3 > 0x7fffffffll) return PF_ERR_SHAPE;
+    hipStream_t s = (hipStream_t)stream;
+    Nn1RaggedTab t;
+    int nc = 0;
+    auto launch = [&]() {
+        if (!nc) return;
+        hipLaunchKernelGGL(nn1_ragged_kernel, dim3(t.t0[nc]), dim3(256), 0, s, p1, p2, t, nc, dist_out, idx_out);
+        nc = 0;
+    };
+    long long xoff = 0, yoff = 0;
+    for (int i = 0; i < B; ++i) {
+        if (use_knn5(1, n[i], m[i])) {
+            launch_knn5<1>(p1 + xoff * 3, p2 + yoff * 3, 1, n[i], m[i], idx_out ? idx_out + xoff : nullptr, dist_out + xoff, s);
+        } else {
+            if (nc == 0) t.t0[0] = 0;
+            t.xoff[nc] = (int)xoff; t.n[nc] = n[i]; t.yoff[nc] = (int)yoff; t.m[nc] = m[i];
+            t.t0[nc + 1] = t.t0[nc] + (n[i] + 255) / 256;
+            if (++nc == NN1_RAGGED_MAXB) launch();
+        }
+        xoff += n[i]; yoff += m[i];
+    }
+    launch();
     return pf_last_launch_status();
 }

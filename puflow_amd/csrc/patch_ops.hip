@@ -21,15 +21,13 @@ __device__ __forceinline__ float sqd(float ax, float ay, float az, float bx, flo
 // sequential in npoint by nature: per step = one strided sweep + one workgroup arg-max.
 constexpr int FPS_T = 1024;
 
-__global__ __launch_bounds__(FPS_T) void fps_kernel(const float* __restrict__ xyz, int N, int npoint,
-                                                    float* __restrict__ mind, int* __restrict__ out) {
+// one cloud: p [N,3], md [N] scratch, o [npoint] (the dense and the ragged kernel differ only in where these come from)
+__device__ __forceinline__ void fps_body(const float* __restrict__ p, int N, int npoint, float* __restrict__ md,
+                                         int* __restrict__ o) {
     __shared__ float sv[FPS_T / 64];
     __shared__ int si[FPS_T / 64];
     __shared__ int cur;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float* p = xyz + (size_t)b * N * 3;
-    float* md = mind + (size_t)b * N;
-    int* o = out + (size_t)b * npoint;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     for (int k = tid; k < N; k += FPS_T) md[k] = 1e10f;
     if (tid == 0) { cur = 0; o[0] = 0; }
     __syncthreads();
@@ -61,6 +59,12 @@ __global__ __launch_bounds__(FPS_T) void fps_kernel(const float* __restrict__ xy
         }
         __syncthreads();
     }
+}
+
+__global__ __launch_bounds__(FPS_T) void fps_kernel(const float* __restrict__ xyz, int N, int npoint,
+                                                    float* __restrict__ mind, int* __restrict__ out) {
+    const int b = blockIdx.x;
+    fps_body(xyz + (size_t)b * N * 3, N, npoint, mind + (size_t)b * N, out + (size_t)b * npoint);
 }
 
 // ---- cooperative FPS: G workgroups per cloud, every point and its running min-distance live in REGISTERS ----
@@ -190,21 +194,18 @@ __device__ __forceinline__ fps_f2 sqd2(fps_f2 ax, fps_f2 ay, fps_f2 az, float bx
     return (dx * dx + dy * dy) + dz * dz;
 }
 
+// Workgroup g of the G that share one cloud: p [N,3], ring [4][FPSC_SLOTSM], abort_w = the cloud's status word (+ 1: rounds),
+// o [npoint].  fps_coopm_kernel (dense batch) and fps_coopm_ragged_kernel (clouds of different sizes) differ only in where
+// these come from.
 template <int PPT>
-__global__ __launch_bounds__(FPSC_T, (PPT <= 16 ? 4 : (PPT <= 24 ? 3 : 2))) void fps_coopm_kernel(const float* __restrict__ xyz, int N,
-                                                                                 int npoint, int G,
-                                                                                 unsigned long long* __restrict__ ringbuf,
-                                                                                 long long ring_stride, int* __restrict__ out) {
+__device__ __forceinline__ void fps_coopm_body(const float* __restrict__ p, int N, int npoint, int G, int g,
+                                               unsigned long long* __restrict__ ring, unsigned long long* __restrict__ abort_w,
+                                               int* __restrict__ o) {
     constexpr int NW = FPSC_T / 64, KW = FPSM_KW, MS = FPSM_MS, NT = FPSM_NT, PH = (PPT + 1) / 2, NC = FPSM_NC, CAP = 64 * NC;
     __shared__ unsigned long long s_ck[CAP];                            // wave 0: the round's compacted candidates
     __shared__ float s_l[2][3 * MS + 4];                                // samples of a round, [3 MS] = count, [3 MS + 1] = alive
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int b = blockIdx.x / G, g = blockIdx.x % G;
-    const float* p = xyz + (size_t)b * N * 3;
-    unsigned long long* ring = ringbuf + (size_t)b * ring_stride;       // [4][FPSC_SLOTSM] + status word
-    unsigned long long* abort_w = ring + FPSC_RINGM;
-    int* o = out + (size_t)b * npoint;
     const int SW = KW * G * NW;                                         // words per round
 
     // a thread holds PPT CONSECUTIVE points, a wave 64 PPT consecutive points: indices grow with k (first maximum = smallest
@@ -430,6 +431,54 @@ __global__ __launch_bounds__(FPSC_T, (PPT <= 16 ? 4 : (PPT <= 24 ? 3 : 2))) void
     if (g == 0 && tid == 0) { fps_st(abort_w + 1, (unsigned long long)rounds); fps_st(abort_w, FPSC_ST_DONE); }
 }
 
+template <int PPT>
+__global__ __launch_bounds__(FPSC_T, (PPT <= 16 ? 4 : (PPT <= 24 ? 3 : 2))) void fps_coopm_kernel(const float* __restrict__ xyz, int N,
+                                                                                 int npoint, int G,
+                                                                                 unsigned long long* __restrict__ ringbuf,
+                                                                                 long long ring_stride, int* __restrict__ out) {
+    const int b = blockIdx.x / G, g = blockIdx.x % G;
+    unsigned long long* ring = ringbuf + (size_t)b * ring_stride;       // [4][FPSC_SLOTSM] + status word
+    fps_coopm_body<PPT>(xyz + (size_t)b * N * 3, N, npoint, G, g, ring, ring + FPSC_RINGM, out + (size_t)b * npoint);
+}
+
+// ---- ragged batches: clouds of different sizes stored back to back --------------------------------------------------------
+// The per-cloud tables travel as kernel arguments (at most PF_RAGGED_MAXB clouds per launch; the entry points split longer
+// lists): no device-side table to build, upload or keep alive, and the host validates every offset it hands out.
+// Cooperative FPS with unequal G_i keeps the progress argument of the dense launch: workgroup ids are cloud-major and
+// ascending (wg0 is a prefix sum), workgroups are dispatched in id order, so when a workgroup of cloud c is resident every
+// workgroup of the clouds before c has been dispatched; the lowest unfinished cloud either has all of its G_c <= 32
+// workgroups resident or is the only cloud still holding CUs, and one cloud always fits the chip.
+constexpr int PF_RAGGED_MAXB = 64;
+struct FpsRaggedTab {
+    int off[PF_RAGGED_MAXB];          // first point of the cloud in xyz
+    int n[PF_RAGGED_MAXB];            // its points
+    int npoint[PF_RAGGED_MAXB];       // its samples
+    int ooff[PF_RAGGED_MAXB];         // first sample in idx_out
+    int cloud[PF_RAGGED_MAXB];        // its number in the batch (status word)
+    int wg0[PF_RAGGED_MAXB + 1];      // cooperative launch: first workgroup of the cloud (prefix sum of G_i)
+    long long soff[PF_RAGGED_MAXB];   // its scratch row, in floats (even: the ring is read as 64-bit words)
+};
+
+template <int PPT>
+__global__ __launch_bounds__(FPSC_T, (PPT <= 16 ? 4 : (PPT <= 24 ? 3 : 2))) void fps_coopm_ragged_kernel(
+    const float* __restrict__ xyz, const FpsRaggedTab t, int nc, float* __restrict__ scratch, unsigned long long* __restrict__ status,
+    int* __restrict__ out) {
+    int c = 0;
+    while (c + 1 < nc && (int)blockIdx.x >= t.wg0[c + 1]) ++c;         // uniform: nc <= 64 table entries
+    const int g = (int)blockIdx.x - t.wg0[c], G = t.wg0[c + 1] - t.wg0[c];
+    unsigned long long* ring = reinterpret_cast<unsigned long long*>(scratch + t.soff[c]);
+    fps_coopm_body<PPT>(xyz + (size_t)t.off[c] * 3, t.n[c], t.npoint[c], G, g, ring, status + 2 * t.cloud[c], out + t.ooff[c]);
+}
+
+// clouds below the cooperative threshold: fps_kernel's workgroup per cloud; the status word only says "ran to the end"
+__global__ __launch_bounds__(FPS_T) void fps_ragged_kernel(const float* __restrict__ xyz, const FpsRaggedTab t,
+                                                           float* __restrict__ scratch, unsigned long long* __restrict__ status,
+                                                           int* __restrict__ out) {
+    const int c = blockIdx.x;
+    fps_body(xyz + (size_t)t.off[c] * 3, t.n[c], t.npoint[c], scratch + t.soff[c], out + t.ooff[c]);
+    if (threadIdx.x == 0) fps_st(status + 2 * t.cloud[c], FPSC_ST_DONE);
+}
+
 // ---- the exchange alone: what a round of the two-sample kernel costs with NO points to update ------------------------------
 // Same protocol, same ring, same shapes (G workgroups of FPSC_T threads, two words per wave, wave 0 polls 4 words per lane,
 // reduces them and hands a result to the other waves through the double-buffered LDS words, one barrier per round) - only the
@@ -478,14 +527,12 @@ constexpr int KS_T = 1024;
 constexpr int KS_NMAX = 16384;          // 128 KiB of 64-bit keys
 constexpr int KS_KMAX = 8192;           // chunked path: at least half of the LDS keys are fresh references per pass
 
-__global__ __launch_bounds__(KS_T) void knn_sort_kernel(const float* __restrict__ ref, const float* __restrict__ query,
-                                                       int N, int M, int K, int NP /*pow2: keys sorted per pass*/,
-                                                       int KP /*0: single pass; else pow2 >= K kept between passes*/,
-                                                       int* __restrict__ idx_out, float* __restrict__ dist_out) {
-    extern __shared__ unsigned long long keys[];
-    const int b = blockIdx.y, q = blockIdx.x, tid = threadIdx.x;
-    const float* r = ref + (size_t)b * N * 3;
-    const float* qq = query + ((size_t)b * M + q) * 3;
+// one query qq [3] against its cloud r [N,3]; irow / drow: the query's K outputs
+__device__ __forceinline__ void knn_sort_body(unsigned long long* keys, const float* __restrict__ r, const float* __restrict__ qq,
+                                              int N, int K, int NP /*pow2: keys sorted per pass*/,
+                                              int KP /*0: single pass; else pow2 >= K kept between passes*/,
+                                              int* __restrict__ irow, float* __restrict__ drow) {
+    const int tid = threadIdx.x;
     const float qx = qq[0], qy = qq[1], qz = qq[2];
     const int C = NP - KP;                                              // fresh references per pass
     for (int i = tid; i < KP; i += KS_T) keys[i] = ~0ull;
@@ -512,9 +559,52 @@ __global__ __launch_bounds__(KS_T) void knn_sort_kernel(const float* __restrict_
     }
     for (int i = tid; i < K; i += KS_T) {
         const unsigned long long key = keys[i];
-        idx_out[((size_t)b * M + q) * K + i] = (int)(key & 0xffffffffu);
-        if (dist_out) dist_out[((size_t)b * M + q) * K + i] = __uint_as_float((unsigned)(key >> 32));
+        irow[i] = (int)(key & 0xffffffffu);
+        if (drow) drow[i] = __uint_as_float((unsigned)(key >> 32));
     }
+}
+
+__global__ __launch_bounds__(KS_T) void knn_sort_kernel(const float* __restrict__ ref, const float* __restrict__ query,
+                                                       int N, int M, int K, int NP, int KP,
+                                                       int* __restrict__ idx_out, float* __restrict__ dist_out) {
+    extern __shared__ unsigned long long keys[];
+    const int b = blockIdx.y, q = blockIdx.x;
+    const size_t row = ((size_t)b * M + q) * K;
+    knn_sort_body(keys, ref + (size_t)b * N * 3, query + ((size_t)b * M + q) * 3, N, K, NP, KP, idx_out + row,
+                  dist_out ? dist_out + row : nullptr);
+}
+
+// sort shape of a cloud of N references (the host's choice in pf_knn_large, per cloud here)
+__host__ __device__ __forceinline__ void knn_sort_shape(int N, int K, int* np, int* kp) {
+    int a = 1, k = 0;
+    if (N <= KS_NMAX) {
+        while (a < N) a <<= 1;
+    } else {
+        a = KS_NMAX;
+        k = 1;
+        while (k < K) k <<= 1;
+    }
+    *np = a; *kp = k;
+}
+
+struct KnnRaggedTab {
+    int roff[PF_RAGGED_MAXB];         // first reference of the cloud
+    int n[PF_RAGGED_MAXB];            // its references
+    int q0[PF_RAGGED_MAXB + 1];       // its first query (queries of all clouds are stored back to back, as the outputs)
+};
+// one workgroup per query of the launch; every query looks up its own cloud
+__global__ __launch_bounds__(KS_T) void knn_sort_ragged_kernel(const float* __restrict__ ref, const float* __restrict__ query,
+                                                              const KnnRaggedTab t, int nc, int K, int* __restrict__ idx_out,
+                                                              float* __restrict__ dist_out) {
+    extern __shared__ unsigned long long keys[];
+    const int q = t.q0[0] + (int)blockIdx.x;
+    int c = 0;
+    while (c + 1 < nc && q >= t.q0[c + 1]) ++c;                         // uniform
+    int np, kp;
+    knn_sort_shape(t.n[c], K, &np, &kp);
+    const size_t row = (size_t)q * K;
+    knn_sort_body(keys, ref + (size_t)t.roff[c] * 3, query + (size_t)q * 3, t.n[c], K, np, kp, idx_out + row,
+                  dist_out ? dist_out + row : nullptr);
 }
 
 // ---- normalize_pc (modules/utils/patch.py:168-178): centroid = mean over the points, pc - centroid, divided by the largest
@@ -522,13 +612,11 @@ __global__ __launch_bounds__(KS_T) void knn_sort_kernel(const float* __restrict_
 // binary tree over the 256 partial sums), so a cloud's result does not depend on how many clouds share the launch - torch's
 // mean picks its reduction tree from the whole tensor shape.  All arithmetic unfused fp32, IEEE sqrt and division.
 constexpr int NRM_T = 256;
-__global__ __launch_bounds__(NRM_T) void normalize_pc_kernel(const float* __restrict__ x, int N, float* __restrict__ out,
-                                                             float* __restrict__ centroid, float* __restrict__ fdist) {
+// one cloud: p [N,3] -> o [N,3], cen [3], fdp [1]
+__device__ __forceinline__ void normalize_pc_body(const float* p, int N, float* o, float* __restrict__ cen, float* __restrict__ fdp) {
 #pragma clang fp contract(off)
     __shared__ float red[3][NRM_T];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const float* p = x + (size_t)b * N * 3;
-    float* o = out + (size_t)b * N * 3;
+    const int tid = threadIdx.x;
     float sx = 0.f, sy = 0.f, sz = 0.f;
     for (int i = tid; i < N; i += NRM_T) {
         sx = __fadd_rn(sx, p[i * 3 + 0]); sy = __fadd_rn(sy, p[i * 3 + 1]); sz = __fadd_rn(sz, p[i * 3 + 2]);
@@ -563,9 +651,24 @@ __global__ __launch_bounds__(NRM_T) void normalize_pc_kernel(const float* __rest
         o[i * 3 + 2] = __fdiv_rn(__fsub_rn(p[i * 3 + 2], cz), fd);
     }
     if (tid == 0) {
-        centroid[b * 3 + 0] = cx; centroid[b * 3 + 1] = cy; centroid[b * 3 + 2] = cz;
-        fdist[b] = fd;
+        cen[0] = cx; cen[1] = cy; cen[2] = cz;
+        fdp[0] = fd;
     }
+}
+
+__global__ __launch_bounds__(NRM_T) void normalize_pc_kernel(const float* __restrict__ x, int N, float* __restrict__ out,
+                                                             float* __restrict__ centroid, float* __restrict__ fdist) {
+    const int b = blockIdx.x;
+    normalize_pc_body(x + (size_t)b * N * 3, N, out + (size_t)b * N * 3, centroid + b * 3, fdist + b);
+}
+
+struct NrmRaggedTab { int off[PF_RAGGED_MAXB + 1]; };                   // cloud c = points [off[c], off[c + 1])
+// the same workgroup per cloud, the same summation order for the cloud's own N: a cloud's result depends on nothing else
+__global__ __launch_bounds__(NRM_T) void normalize_pc_ragged_kernel(const float* __restrict__ x, const NrmRaggedTab t,
+                                                                    float* __restrict__ out, float* __restrict__ centroid,
+                                                                    float* __restrict__ fdist) {
+    const int c = blockIdx.x;
+    normalize_pc_body(x + (size_t)t.off[c] * 3, t.off[c + 1] - t.off[c], out + (size_t)t.off[c] * 3, centroid + c * 3, fdist + c);
 }
 
 }  // namespace
@@ -681,5 +784,159 @@ extern "C" int pf_normalize_pc(const float* x, int B, int N, float* out, float* 
     if (!x || !out || !centroid || !fdist) return PF_ERR_NULL;
     if (B <= 0 || N <= 0 || (long long)N * 3 > 0x7fffffffll) return PF_ERR_SHAPE;
     hipLaunchKernelGGL(normalize_pc_kernel, dim3(B), dim3(NRM_T), 0, (hipStream_t)stream, x, N, out, centroid, fdist);
+    return pf_last_launch_status();
+}
+
+// ---- ragged entry points: B clouds of n[i] points stored back to back ([sum n, 3]); n / npoint / m are HOST arrays --------------
+namespace {
+bool fps_coop_size(int N) { return N >= 8192 && N <= FPSC_GMAX * 1024 * 8; }
+
+// Shared by pf_fps_ragged_layout and pf_fps_ragged: the points per thread of the cooperative launch (0: no cooperative cloud)
+// and the scratch rows.  One PPT per pass, chosen for the largest cooperative cloud (FPS is exact: the choice changes no index);
+// a cloud that would need more than FPSC_GMAX workgroups at that PPT cannot occur, since G grows with N.
+int fps_ragged_ppt(const int* n, int B, int group) {
+    int nmax = 0;
+    for (int i = 0; i < B; ++i)
+        if (fps_coop_size(n[i]) && n[i] > nmax) nmax = n[i];
+    return nmax ? fps_ppt(nmax, group) : 0;
+}
+long long fps_ragged_row(int n) { return ((long long)n + 1) & ~1ll; }      // floats: every row starts 64-bit aligned
+
+__global__ __launch_bounds__(256) void fps_ragged_init_kernel(float* p, long long n, long long status_word) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const long long w = i >> 1;
+        p[i] = ((i & 1) == 0 && w >= status_word && ((w - status_word) & 1) == 0) ? __uint_as_float((unsigned)FPSC_ST_INIT) : 0.f;
+    }
+}
+}  // namespace
+
+extern "C" int pf_fps_ragged_layout(const int* n, int B, int group, long long* scratch_off, int* wgs, long long* total_floats,
+                                    long long* status_word, long long* status_stride) {
+    if (!n) return PF_ERR_NULL;
+    if (B <= 0 || group < 0) return PF_ERR_SHAPE;
+    long long tot = 0;
+    for (int i = 0; i < B; ++i) {
+        if (n[i] <= 0) return PF_ERR_SHAPE;
+        tot += n[i];
+    }
+    if (tot * 3 > 0x7fffffffll) return PF_ERR_SHAPE;
+    const int ppt = fps_ragged_ppt(n, B, group);
+    long long off = 0;
+    for (int i = 0; i < B; ++i) {
+        if (scratch_off) scratch_off[i] = off;
+        if (wgs) wgs[i] = fps_coop_size(n[i]) ? (n[i] + FPSC_T * ppt - 1) / (FPSC_T * ppt) : 0;
+        off += fps_ragged_row(n[i]);
+    }
+    if (total_floats) *total_floats = off + 4ll * B;                     // + {status, rounds} per cloud
+    if (status_word) *status_word = off / 2;
+    if (status_stride) *status_stride = 2;
+    return ppt;
+}
+
+extern "C" int pf_fps_ragged(const float* xyz, const int* n, const int* npoint, int B, int group, float* scratch, int* idx_out,
+                             void* stream) {
+    if (!xyz || !n || !npoint || !scratch || !idx_out) return PF_ERR_NULL;
+    long long total = 0, sw = 0;
+    const int ppt = pf_fps_ragged_layout(n, B, group, nullptr, nullptr, &total, &sw, nullptr);
+    if (ppt < 0) return ppt;
+    if (((size_t)scratch & 7) != 0) return PF_ERR_SHAPE;
+    for (int i = 0; i < B; ++i)
+        if (npoint[i] <= 0 || npoint[i] > n[i]) return PF_ERR_SHAPE;
+    hipStream_t s = (hipStream_t)stream;
+    unsigned long long* status = reinterpret_cast<unsigned long long*>(scratch) + sw;
+    hipLaunchKernelGGL(fps_ragged_init_kernel, dim3(256), dim3(256), 0, s, scratch, total, sw);
+    // two kernel families, each in launches of up to PF_RAGGED_MAXB clouds in batch order: cooperative, then single-workgroup
+    for (int fam = 0; fam < 2; ++fam) {
+        FpsRaggedTab t;
+        int nc = 0;
+        long long poff = 0, ooff = 0, soff = 0;
+        auto launch = [&]() {
+            if (!nc) return;
+            if (fam == 0) {
+                const dim3 grid(t.wg0[nc]), block(FPSC_T);
+#define PF_FPS_LAUNCH(PPT) hipLaunchKernelGGL(fps_coopm_ragged_kernel<PPT>, grid, block, 0, s, xyz, t, nc, scratch, status, idx_out)
+                switch (ppt) {
+                    case 1: PF_FPS_LAUNCH(1); break;
+                    case 4: PF_FPS_LAUNCH(4); break;
+                    case 8: PF_FPS_LAUNCH(8); break;
+                    case 12: PF_FPS_LAUNCH(12); break;
+                    case 16: PF_FPS_LAUNCH(16); break;
+                    case 20: PF_FPS_LAUNCH(20); break;
+                    case 24: PF_FPS_LAUNCH(24); break;
+                    default: PF_FPS_LAUNCH(32); break;
+                }
+#undef PF_FPS_LAUNCH
+            } else {
+                hipLaunchKernelGGL(fps_ragged_kernel, dim3(nc), dim3(FPS_T), 0, s, xyz, t, scratch, status, idx_out);
+            }
+            nc = 0;
+        };
+        for (int i = 0; i < B; ++i) {
+            // a cloud larger than the cooperative kernel's 32 workgroups x 8192 points runs on one workgroup, as in pf_fps
+            if ((fps_coop_size(n[i]) ? 0 : 1) == fam) {
+                if (nc == 0) t.wg0[0] = 0;
+                t.off[nc] = (int)poff; t.n[nc] = n[i]; t.npoint[nc] = npoint[i]; t.ooff[nc] = (int)ooff; t.cloud[nc] = i;
+                t.soff[nc] = soff;
+                t.wg0[nc + 1] = t.wg0[nc] + (fam == 0 ? (n[i] + FPSC_T * ppt - 1) / (FPSC_T * ppt) : 1);
+                if (++nc == PF_RAGGED_MAXB) launch();
+            }
+            poff += n[i]; ooff += npoint[i]; soff += fps_ragged_row(n[i]);
+        }
+        launch();
+    }
+    return pf_last_launch_status();
+}
+
+extern "C" int pf_knn_large_ragged(const float* ref, const float* query, const int* n, const int* m, int B, int K, int* idx_out,
+                                   float* dist_out, void* stream) {
+    if (!ref || !query || !n || !m || !idx_out) return PF_ERR_NULL;
+    if (B <= 0 || K <= 0) return PF_ERR_SHAPE;
+    long long nt = 0, mt = 0;
+    int npmax = 1;
+    for (int i = 0; i < B; ++i) {
+        if (n[i] <= 0 || m[i] <= 0 || K > n[i]) return PF_ERR_SHAPE;
+        if (n[i] > KS_NMAX && K > KS_KMAX) return PF_ERR_UNSUPPORTED;
+        int np, kp;
+        knn_sort_shape(n[i], K, &np, &kp);
+        if (np > npmax) npmax = np;
+        nt += n[i]; mt += m[i];
+    }
+    if (nt * 3 > 0x7fffffffll || mt * 3 > 0x7fffffffll) return PF_ERR_SHAPE;
+    const size_t lds = (size_t)npmax * 8;
+    allow_lds(knn_sort_ragged_kernel, lds);
+    long long roff = 0, q = 0;
+    for (int c0 = 0; c0 < B; c0 += PF_RAGGED_MAXB) {
+        KnnRaggedTab t;
+        const int nc = B - c0 < PF_RAGGED_MAXB ? B - c0 : PF_RAGGED_MAXB;
+        t.q0[0] = (int)q;
+        for (int c = 0; c < nc; ++c) {
+            t.roff[c] = (int)roff; t.n[c] = n[c0 + c];
+            roff += n[c0 + c]; q += m[c0 + c];
+            t.q0[c + 1] = (int)q;
+        }
+        hipLaunchKernelGGL(knn_sort_ragged_kernel, dim3(t.q0[nc] - t.q0[0]), dim3(KS_T), lds, (hipStream_t)stream, ref, query, t, nc,
+                           K, idx_out, dist_out);
+    }
+    return pf_last_launch_status();
+}
+
+extern "C" int pf_normalize_pc_ragged(const float* x, const int* n, int B, float* out, float* centroid, float* fdist, void* stream) {
+    if (!x || !n || !out || !centroid || !fdist) return PF_ERR_NULL;
+    if (B <= 0) return PF_ERR_SHAPE;
+    long long tot = 0;
+    for (int i = 0; i < B; ++i) {
+        if (n[i] <= 0) return PF_ERR_SHAPE;
+        tot += n[i];
+    }
+    if (tot * 3 > 0x7fffffffll) return PF_ERR_SHAPE;
+    long long off = 0;
+    for (int c0 = 0; c0 < B; c0 += PF_RAGGED_MAXB) {
+        NrmRaggedTab t;
+        const int nc = B - c0 < PF_RAGGED_MAXB ? B - c0 : PF_RAGGED_MAXB;
+        for (int c = 0; c < nc; ++c) { t.off[c] = (int)off; off += n[c0 + c]; }
+        t.off[nc] = (int)off;
+        hipLaunchKernelGGL(normalize_pc_ragged_kernel, dim3(nc), dim3(NRM_T), 0, (hipStream_t)stream, x, t, out, centroid + c0 * 3,
+                           fdist + c0);
+    }
     return pf_last_launch_status();
 }

@@ -6,7 +6,8 @@
 //   * The HOST guarantees that THIS kernel alone fits: it launches a waiting grid only when pf_resident_per_cu (the occupancy API
 //     for the kernel's block size and dynamic LDS) x the CU count covers the grid under the caller's policy.  Kernels of the same
 //     process on other streams, and other processes, are not counted (FPS relies on in-order dispatch instead: the lowest
-//     unfinished cloud always has all of its workgroups resident).
+//     unfinished cloud always has all of its workgroups resident - also in a ragged launch, where clouds have different numbers
+//     of workgroups: ids stay cloud-major and ascending, and a single cloud's <= 32 workgroups always fit the chip).
 //   * Every wait is BOUNDED.  A waiter that runs out of budget stops waiting and its kernel reports it, so the grid drains instead
 //     of hanging: ec_fwdp / ec_bwdp set the sticky word sync[3] (train_ops.check_persist_status raises), the EMD kernels make
 //     their slice of dist NaN and add 1 to the status word (loss.check_emd_status), FPS writes the abort value into the cloud's

@@ -221,3 +221,115 @@ class KNN:
         if not self.transpose_mode:
             return dist.transpose(1, 2).contiguous(), idx.transpose(1, 2).contiguous()
         return dist, idx
+
+
+# ----------------------------------------------------------------------------------------
+# Ragged ("packed") patch operators: B clouds of lengths[i] points stored back to back as one [sum, 3] tensor.
+# Every cloud gets, bit for bit, what the dense operator above gives it alone; the lengths are host integers.
+# ----------------------------------------------------------------------------------------
+def _lengths(lengths, total: int, what: str):
+    lengths = [int(v) for v in lengths]
+    if not lengths or min(lengths) <= 0 or sum(lengths) != total:
+        raise _lib.PuflowHipError(f"{what}: lengths {lengths} do not describe a packed tensor of {total} rows")
+    return lengths
+
+
+def _packed(t: torch.Tensor, what: str) -> torch.Tensor:
+    t = _f32c(t)
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise _lib.PuflowHipError(f"{what}: a packed cloud tensor is [sum of lengths, 3], got {tuple(t.shape)}")
+    return t
+
+
+def normalize_pc_ragged(pc: torch.Tensor, lengths):
+    """normalize_pc per cloud of a packed tensor: pc [sum, 3] -> (normalised [sum, 3], centroid [B,1,3], furthest distance
+    [B,1,1])."""
+    lib = _lib.load()
+    pc = _packed(pc, "normalize_pc_ragged")
+    lengths = _lengths(lengths, pc.shape[0], "normalize_pc_ragged")
+    B = len(lengths)
+    out = torch.empty_like(pc)
+    cen = torch.empty((B, 1, 3), dtype=torch.float32, device=pc.device)
+    fd = torch.empty((B, 1, 1), dtype=torch.float32, device=pc.device)
+    _lib.check(lib.pf_normalize_pc_ragged(pc.data_ptr(), _lib.counts(lengths), B, out.data_ptr(), cen.data_ptr(), fd.data_ptr(),
+                                          _stream()), "pf_normalize_pc_ragged")
+    return out, cen, fd
+
+
+def fps_ragged_layout(lengths, group: int = 0):
+    """pf_fps_ragged_layout (host only): dict with the scratch size in floats, every cloud's scratch offset (floats), its
+    workgroups in the cooperative launch (0: single-workgroup kernel), the points per thread of that launch and the positions of
+    the clouds' status words (64-bit words of the scratch)."""
+    import ctypes
+    lib = _lib.load()
+    lengths = [int(v) for v in lengths]
+    B = len(lengths)
+    off, wgs = (ctypes.c_longlong * B)(), (ctypes.c_int * B)()
+    total, word, stride = ctypes.c_longlong(0), ctypes.c_longlong(0), ctypes.c_longlong(0)
+    ppt = lib.pf_fps_ragged_layout(_lib.counts(lengths), B, int(group), off, wgs, ctypes.byref(total), ctypes.byref(word),
+                                   ctypes.byref(stride))
+    if ppt < 0:
+        _lib.check(int(ppt), "pf_fps_ragged_layout")
+    return {"total_floats": total.value, "scratch_off": list(off), "workgroups": list(wgs), "ppt": int(ppt),
+            "status_words": [word.value + i * stride.value for i in range(B)]}
+
+
+def furthest_point_sample_ragged(xyz: torch.Tensor, lengths, npoints, group: int = 0) -> torch.Tensor:
+    """furthest_point_sample per cloud of a packed tensor: xyz [sum, 3], npoints[i] samples of cloud i -> int32 [sum npoints],
+    indices inside each cloud (every cloud starts at its index 0).  `group`: the layout hint of furthest_point_sample."""
+    lib = _lib.load()
+    xyz = _packed(xyz, "furthest_point_sample_ragged")
+    lengths = _lengths(lengths, xyz.shape[0], "furthest_point_sample_ragged")
+    npoints = [int(v) for v in npoints]
+    if len(npoints) != len(lengths):
+        raise _lib.PuflowHipError("furthest_point_sample_ragged: one sample count per cloud")
+    lay = fps_ragged_layout(lengths, group)
+    idx = torch.zeros((max(sum(npoints), 0),), dtype=torch.int32, device=xyz.device)
+    scratch = torch.empty((lay["total_floats"],), dtype=torch.float32, device=xyz.device)
+    _lib.check(lib.pf_fps_ragged(xyz.data_ptr(), _lib.counts(lengths), _lib.counts(npoints), len(lengths), int(group),
+                                 scratch.data_ptr(), idx.data_ptr(), _stream()), "pf_fps_ragged")
+    _check_fps_abort_ragged(scratch, lay["status_words"])
+    return idx
+
+
+def _check_fps_abort_ragged(scratch: torch.Tensor, status_words) -> None:
+    """_check_fps_abort for a ragged pass: one status word per cloud (whichever kernel ran it), all read in ONE device -> host
+    read; anything but 0 means that cloud's index row is invalid."""
+    words = scratch.view(-1)[: scratch.numel() // 2 * 2].view(torch.int64)
+    pos = torch.tensor(list(status_words), dtype=torch.int64).to(scratch.device, non_blocking=True)
+    bad = (words[pos] != 0).cpu()
+    if bool(bad.any()):
+        which = [i for i, b in enumerate(bad.tolist()) if b]
+        raise _lib.PuflowHipError(f"pf_fps_ragged: clouds {which} of the pass did not complete (the cooperative kernel's workgroups "
+                                  "timed out waiting for each other or were never co-resident); the sampled indices are invalid")
+
+
+def knn_ragged(ref: torch.Tensor, ref_lengths, query: torch.Tensor, query_lengths, k: int):
+    """KNN(k) per cloud of packed tensors: the query_lengths[i] queries of cloud i against its own ref_lengths[i] references
+    -> (dist [sum queries, k] squared L2, idx [sum queries, k] int64 inside the cloud), ordered by (distance, index)."""
+    lib = _lib.load()
+    ref, query = _packed(ref, "knn_ragged"), _packed(query, "knn_ragged")
+    rl = _lengths(ref_lengths, ref.shape[0], "knn_ragged")
+    ql = _lengths(query_lengths, query.shape[0], "knn_ragged")
+    if len(rl) != len(ql):
+        raise _lib.PuflowHipError("knn_ragged: one query count per cloud")
+    idx = torch.empty((query.shape[0], k), dtype=torch.int32, device=ref.device)
+    dist = torch.empty((query.shape[0], k), dtype=torch.float32, device=ref.device)
+    _lib.check(lib.pf_knn_large_ragged(ref.data_ptr(), query.data_ptr(), _lib.counts(rl), _lib.counts(ql), len(rl), int(k),
+                                       idx.data_ptr(), dist.data_ptr(), _stream()), "pf_knn_large_ragged")
+    return dist, idx.long()
+
+
+def nearest_distance_ragged(x: torch.Tensor, x_lengths, y: torch.Tensor, y_lengths) -> torch.Tensor:
+    """nearest_distance per cloud of packed tensors: squared distance of every point of x's cloud i to the nearest point of y's
+    cloud i -> [sum x_lengths]."""
+    lib = _lib.load()
+    x, y = _packed(x, "nearest_distance_ragged"), _packed(y, "nearest_distance_ragged")
+    xl = _lengths(x_lengths, x.shape[0], "nearest_distance_ragged")
+    yl = _lengths(y_lengths, y.shape[0], "nearest_distance_ragged")
+    if len(xl) != len(yl):
+        raise _lib.PuflowHipError("nearest_distance_ragged: the two packed tensors hold different numbers of clouds")
+    d1 = torch.empty((x.shape[0],), dtype=torch.float32, device=x.device)
+    _lib.check(lib.pf_nn1_ragged(x.data_ptr(), y.data_ptr(), _lib.counts(xl), _lib.counts(yl), len(xl), d1.data_ptr(), None,
+                                 _stream()), "pf_nn1_ragged")
+    return d1

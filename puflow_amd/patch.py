@@ -124,3 +124,70 @@ class PatchHelper(object):
         keep[idxb, idx_outliers] = 0
         idx_inverse = torch.nonzero(keep, as_tuple=False)[:, 1].view(B, N - num_outliers)
         return sr[idxb, idx_inverse]
+
+    # ---- ragged pass: clouds of different sizes through the pipeline together (no reference counterpart) ----
+    @staticmethod
+    def _rows(lengths, device):
+        """For a packed tensor of these lengths: (first row of every cloud [B], cloud of every row [sum], row inside the cloud
+        [sum]), built from the host lengths without a device -> host read."""
+        cnt = torch.tensor(lengths, dtype=torch.int64)
+        first = torch.cumsum(cnt, 0) - cnt
+        total = int(cnt.sum())
+        cnt, first = cnt.to(device), first.to(device)
+        cloud = torch.repeat_interleave(torch.arange(len(lengths), device=device), cnt, output_size=total)
+        return first, cloud, torch.arange(total, device=device) - first[cloud]
+
+    def upsample_ragged(self, upsampler, clouds, npoints, upratio=None, names=None, **kwargs):
+        """`upsample` for clouds of different sizes in ONE pass: clouds = list of [N_i, 3] GPU tensors, npoints = output size
+        per cloud (a list, or one int for all) -> list of [npoint_i, 3].  Every cloud gets, bit for bit, what
+        `upsample(upsampler, cloud[None], npoint_i, upratio)` gives it alone: the patches of all clouds go through the network
+        as one batch, FPS / kNN / normalisation run as ragged launches (ops.*_ragged).  names: what to call the clouds in an
+        error message (the CLI passes its file names)."""
+        B, k = len(clouds), self._npoint_patch
+        lengths = [int(c.shape[0]) for c in clouds]
+        npoints = [int(npoints)] * B if isinstance(npoints, int) else [int(v) for v in npoints]
+        for i, n in enumerate(lengths):
+            if n < k:       # the dense path fails in its kNN (K > N): the same exception, before anything is launched
+                raise ops._lib.PuflowHipError(f"{names[i] if names else 'cloud %d' % i}: {n} points, fewer than one patch ({k})")
+        n_patch = [int(n / k * self._patch_expand_ratio) for n in lengths]
+        dev = clouds[0].device
+        # every index helper depends on the sizes alone: built (and uploaded) before the first kernel of the pass is queued
+        c_first, _, _ = PatchHelper._rows(lengths, dev)
+        _, p_cloud, _ = PatchHelper._rows(n_patch, dev)
+        per_patch = k * ((upratio or 4) + 1)                                                   # sampled points + the patch itself
+        cand_lengths = [p * per_patch for p in n_patch]
+        m_first, _, _ = PatchHelper._rows(cand_lengths, dev)
+        _, o_cloud, _ = PatchHelper._rows(npoints, dev)
+        pc = torch.cat([c.reshape(-1, 3) for c in clouds], dim=0)
+        pc, g_centroid, g_furthest_distance = ops.normalize_pc_ragged(pc, lengths)
+        seeds = ops.furthest_point_sample_ragged(pc, lengths, n_patch).long() + c_first[p_cloud]
+        _, idx_patches = ops.knn_ragged(pc, lengths, pc[seeds], n_patch, k)                    # [sum n_patch, k] inside the cloud
+        patches = pc[idx_patches + c_first[p_cloud].view(-1, 1)]                               # [sum n_patch, k, 3]
+        patches, centroids, furthest_distance = PatchHelper.normalize_pc(patches)
+        predict = upsampler.sample(patches.contiguous(), upratio=(upratio or 4), **kwargs)
+        predict = torch.cat([predict, patches], dim=1)
+        predict = predict * furthest_distance + centroids                                      # [sum n_patch, per_patch, 3]
+        if predict.shape[1] != per_patch:
+            raise ValueError(f"the upsampler returned {predict.shape[1] - k} points per patch, expected {per_patch - k}")
+        cand = predict.reshape(-1, 3).contiguous()
+        idx = ops.furthest_point_sample_ragged(cand, cand_lengths, npoints, group=per_patch).long() + m_first[o_cloud]
+        out = cand[idx] * g_furthest_distance.view(B, 1)[o_cloud] + g_centroid.view(B, 3)[o_cloud]
+        return list(torch.split(out, npoints))
+
+    @staticmethod
+    def remove_outliers_ragged(srs, lrs, num_outliers: int):
+        """`remove_outliers` for lists of clouds of different sizes: srs[i] [n_i, 3] against lrs[i] [m_i, 3] -> list of
+        [n_i - num_outliers, 3]; the same stable descending order per cloud, one nearest-neighbour pass for all."""
+        B, dev = len(srs), srs[0].device
+        ns, ms = [int(s.shape[0]) for s in srs], [int(l.shape[0]) for l in lrs]
+        if min(ns) < num_outliers:
+            raise ValueError(f"cannot remove {num_outliers} outliers from a cloud of {min(ns)} points")
+        sr = torch.cat([s.reshape(-1, 3) for s in srs], dim=0)
+        _, row_cloud, row_col = PatchHelper._rows(ns, dev)
+        dist1 = ops.nearest_distance_ragged(sr, ns, torch.cat([l.reshape(-1, 3) for l in lrs], dim=0), ms)
+        padded = torch.full((B, max(ns)), float("-inf"), dtype=torch.float32, device=dev)     # padding sorts behind every distance
+        padded[row_cloud, row_col] = dist1
+        idx_outliers = torch.argsort(padded, dim=-1, descending=True, stable=True)[:, :num_outliers]
+        keep = torch.ones((B, max(ns)), dtype=torch.bool, device=dev)
+        keep[torch.arange(B, device=dev).view(-1, 1), idx_outliers] = False
+        return list(torch.split(sr[keep[row_cloud, row_col]], [n - num_outliers for n in ns]))

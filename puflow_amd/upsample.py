@@ -22,6 +22,28 @@ def shard_paths(paths: List[str], rank: int, world: int) -> List[str]:
     return sorted(paths)[rank::world] if world > 1 else list(paths)
 
 
+def pass_is_full(count: int, points: int, next_points: int, cloud_batch: int, pass_points=None) -> bool:
+    """Must a pass that holds `count` files / `points` input points be flushed before a file of `next_points` joins it?"""
+    if count == 0:
+        return False                                     # a file larger than pass_points is a pass of its own
+    return count >= max(int(cloud_batch), 1) or (pass_points is not None and points + next_points > int(pass_points))
+
+
+def plan_passes(sizes, cloud_batch: int, pass_points=None):
+    """How the CLI groups consecutive files into passes: [(first, last + 1), ...] over the files in order.  A pass takes up to
+    `cloud_batch` files whatever their point counts and, with `pass_points`, at most that many input points (a single larger
+    file is a pass of its own).  The CLI's loop applies the same rule (pass_is_full) file by file."""
+    passes, first, points = [], 0, 0
+    for i, n in enumerate(sizes):
+        if pass_is_full(i - first, points, int(n), cloud_batch, pass_points):
+            passes.append((first, i))
+            first, points = i, 0
+        points += int(n)
+    if len(sizes) > first:
+        passes.append((first, len(sizes)))
+    return passes
+
+
 def save_xyz(path, points: np.ndarray) -> None:
     """`np.savetxt(path, points, fmt="%.6f")` (upsample.py:57) - the same bytes - formatted by the library's host-side
     `pf_format_xyz` (~1 ms for a 20 000-point cloud instead of 36 ms; the call releases the GIL, so the writer thread really
@@ -69,7 +91,7 @@ def load_xyz(path) -> np.ndarray:
 @torch.no_grad()
 def upsampling(data_paths: List[str], target_path: str, checkpoint_path: str, up_ratio: int, num_outlier: int,
                num_patch: int, num_upsampling: int = None, seed=None, state_dict=None, network_cls=PointInterpFlow,
-               cloud_batch: int = None):
+               cloud_batch: int = None, pass_points: int = None):
     # The continuous model integrates all patches of a pass with ONE adaptive step sequence (the error norm is taken over the
     # whole batch, cnf.py:97-113), so a cloud's result depends on what shares its pass: it keeps the reference's one file at a
     # time unless asked otherwise.  The discrete model's patches never interact.
@@ -84,13 +106,13 @@ def upsampling(data_paths: List[str], target_path: str, checkpoint_path: str, up
     torch.set_num_threads(1)
     try:
         return _upsampling(data_paths, target_path, checkpoint_path, up_ratio, num_outlier, num_patch, num_upsampling, seed,
-                           state_dict, network_cls, cloud_batch)
+                           state_dict, network_cls, cloud_batch, pass_points)
     finally:
         torch.set_num_threads(host_threads)
 
 
 def _upsampling(data_paths, target_path, checkpoint_path, up_ratio, num_outlier, num_patch, num_upsampling, seed, state_dict,
-                network_cls, cloud_batch):
+                network_cls, cloud_batch, pass_points=None):
     if seed is not None:
         np.random.seed(seed)
         torch.random.manual_seed(seed)
@@ -111,27 +133,36 @@ def _upsampling(data_paths, target_path, checkpoint_path, up_ratio, num_outlier,
     network.set_to_initialized_state()
     network = network.to(device).eval()
     patch_helper = PatchHelper(num_patch, patch_expand_ratio=4)
-    # The reference takes one file at a time (upsample.py:42-57).  Here up to `cloud_batch` consecutive files of the same
-    # point count go through the pipeline together: the FPS merge, which is sequential in its 4N output points and 95 % of a
-    # cloud's GPU time, then runs for all of them at once (16 clouds take the time of 1.35).  Every cloud's result is the one it
-    # gets alone (clouds never interact; the per-file shuffles are drawn in file order as before), and finished clouds are
-    # written by a worker thread while the GPU works on the next batch.
+    # The reference takes one file at a time (upsample.py:42-57).  Here up to `cloud_batch` consecutive files go through the
+    # pipeline together, whatever their point counts: the FPS merge, which is sequential in its 4N output points and 95 % of a
+    # cloud's GPU time, then runs for all of them at once (16 clouds take the time of 1.35).  Files of one size (or a single file)
+    # take the dense [B, N, 3] path, mixed sizes the ragged one (PatchHelper.upsample_ragged: the clouds stored back to back).
+    # Either way every cloud's result is the one it gets alone (clouds never interact; the per-file shuffles are drawn in file
+    # order as before), and finished clouds are written by a worker thread while the GPU works on the next pass.
     from concurrent.futures import ThreadPoolExecutor
     writes = []
     pending = []                                                   # (file name, shuffled cloud [1,N,3] on the host)
 
+    def npoint_of(n):
+        return (n * up_ratio if num_upsampling is None else num_upsampling) + (num_outlier or 0)
+
     def flush(pool):
         if not pending:
             return
-        pt_input = torch.cat([c for _, c in pending], dim=0).to(device)
-        if num_upsampling is None:
-            npoint = pt_input.shape[1] * up_ratio + (num_outlier or 0)
+        sizes = [c.shape[1] for _, c in pending]
+        if len(set(sizes)) == 1:
+            pt_input = torch.cat([c for _, c in pending], dim=0).to(device)
+            pred = patch_helper.upsample(network, pt_input, npoint=npoint_of(sizes[0]), upratio=up_ratio, jitter=False)
+            if num_outlier is not None and num_outlier > 0:
+                pred = PatchHelper.remove_outliers(pred, pt_input, num_outlier)
+            pred = list(pred.cpu().numpy())
         else:
-            npoint = num_upsampling + (num_outlier or 0)
-        pred = patch_helper.upsample(network, pt_input, npoint=npoint, upratio=up_ratio, jitter=False)
-        if num_outlier is not None and num_outlier > 0:
-            pred = PatchHelper.remove_outliers(pred, pt_input, num_outlier)
-        pred = pred.cpu().numpy()
+            clouds = list(torch.split(torch.cat([c[0] for _, c in pending], dim=0).to(device), sizes))
+            pred = patch_helper.upsample_ragged(network, clouds, [npoint_of(n) for n in sizes], upratio=up_ratio,
+                                                names=[name for name, _ in pending])
+            if num_outlier is not None and num_outlier > 0:
+                pred = PatchHelper.remove_outliers_ragged(pred, clouds, num_outlier)
+            pred = [p.numpy() for p in torch.split(torch.cat(pred, dim=0).cpu(), [p.shape[0] for p in pred])]
         for (file_name, _), cloud in zip(pending, pred):
             writes.append(pool.submit(save_xyz, Path(target_path) / file_name, cloud))
         pending.clear()
@@ -144,7 +175,7 @@ def _upsampling(data_paths, target_path, checkpoint_path, up_ratio, num_outlier,
             if path not in mine:
                 continue                                            # another rank's file: only the RNG draw is replayed
             pt_input = pt_input[:, perm].contiguous()
-            if pending and (pending[0][1].shape[1] != pt_input.shape[1] or len(pending) >= max(int(cloud_batch), 1)):
+            if pass_is_full(len(pending), sum(c.shape[1] for _, c in pending), pt_input.shape[1], cloud_batch, pass_points):
                 flush(pool)
             pending.append((file_name, pt_input))
         flush(pool)
@@ -162,15 +193,19 @@ def main(argv=None, network_cls=PointInterpFlow):
     parser.add_argument("--num_patch", type=int, help="number of point in each patch", default=256)
     parser.add_argument("--num_out", type=int, default=None, help="number of point of output point cloud")
     parser.add_argument("--cloud_batch", type=int, default=None,
-                        help="(not in the reference) files of equal point count that share one pass; 1 = one file at a time "
-                             "(default: 16 for the discrete model, 1 for the continuous one)")
+                        help="(not in the reference) consecutive files, of any point counts, that share one pass; 1 = one file at a "
+                             "time (default: 16 for the discrete model, 1 for the continuous one)")
+    parser.add_argument("--pass_points", type=int, default=None,
+                        help="(not in the reference) a pass is also closed before its input points would exceed this "
+                             "(default: no limit); a larger file is a pass of its own")
     args = parser.parse_args(argv)
     os.makedirs(args.target, exist_ok=True)            # exist_ok: several ranks may race to create it
     data_paths = []
     for root, _dirs, files in os.walk(args.source):
         data_paths.extend([os.path.join(root, f) for f in files if ".xyz" in f])
     upsampling(data_paths, args.target, args.checkpoint, up_ratio=args.up_ratio, num_outlier=24, num_patch=args.num_patch,
-               num_upsampling=args.num_out, seed=args.seed, network_cls=network_cls, cloud_batch=args.cloud_batch)
+               num_upsampling=args.num_out, seed=args.seed, network_cls=network_cls, cloud_batch=args.cloud_batch,
+               pass_points=args.pass_points)
 
 
 if __name__ == "__main__":
