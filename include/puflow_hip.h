@@ -266,7 +266,7 @@ int pf_batch_sum_bwd(const float* x, const float* g, int B, long long M, int mod
 /* DistanceEncoder.distance_vec (interpflow.py:100-115): out [B*N*K,10] = [x_i, x_j, x_i - x_j, |x_i - x_j|] */
 int pf_dist_feature(const float* xyz, const int* idx, int B, int N, int K, float* out, void* stream);
 
-/* ---- one FeatureExtractUnit (EdgeConv dense block) of the training step, fused (csrc/train_fused.hip) ----
+/* ---- one FeatureExtractUnit (EdgeConv dense block) of the training step, fused (csrc/pf_ec_train.h: train_ec_fwd.hip, train_fused.hip) ----
  * Replaces FeatureExtractUnit.forward in train() mode and its autograd backward (modules/discrete/interpflow.py:190-248):
  * edge feature -> [Conv2d 1x1 + BatchNorm2d(batch statistics) + LeakyReLU, dense concatenation] x nconv -> conv_out ->
  * max over the K neighbours (pooling = 1) or the per-edge output (pooling = 0, the interpolation's feat_conv).
@@ -364,7 +364,7 @@ int pf_ec_train_fwd(const PfEcTrain* p, void* stream);
 int pf_ec_train_fold_batch(const PfEcTrain* descs, int n, void* stream);
 int pf_ec_train_bwd(const PfEcTrain* p, void* stream);
 
-/* ---- BatchNorm MLP of the interpolation module in the training step, fused (csrc/train_fused.hip) ----
+/* ---- BatchNorm MLP of the interpolation module in the training step, fused (csrc/train_bnmlp.hip) ----
  * Replaces DistanceEncoder.mlp / WeightEstimationUnit.mlp (modules/discrete/interpflow.py:85-151: [Conv2d 1x1 +
  * BatchNorm2d(batch statistics) + LeakyReLU(slope)] x (nl - 1), then Conv2d 1x1) in train() mode with their autograd
  * backward.  Input = cat[xa [rows, kin0a], xb [rows, kin0b]] (never built; kin0b = 0: one input); widths multiples of 16

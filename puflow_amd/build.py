@@ -8,7 +8,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpuflow_hip.so")
-SOURCES = ["api.hip", "knn.hip", "edgeconv.hip", "pointwise.hip", "flow.hip", "interp.hip", "chamfer.hip", "emd.hip", "train_ops.hip", "train_fused.hip", "train_mlp.hip", "train_flow.hip", "train_flowchain.hip", "train_glue.hip", "optim.hip", "patch_ops.hip", "cnf.hip", "xyz_io.hip", "eval_metrics.hip"]
+SOURCES = ["api.hip", "knn.hip", "edgeconv.hip", "pointwise.hip", "flow.hip", "interp.hip", "chamfer.hip", "emd.hip", "train_ops.hip", "train_fused.hip", "train_ec_fwd.hip", "train_csr.hip", "train_bnmlp.hip", "train_mlp.hip", "train_flow.hip", "train_flowchain.hip", "train_glue.hip", "optim.hip", "patch_ops.hip", "cnf.hip", "xyz_io.hip", "eval_metrics.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=on", "-Wno-unused-result"]
 # The fused MFMA kernels never see NaNs; without the flag every fmaxf() is preceded by a canonicalising v_max x,x and
 # the DPP row-max steps stay as v_mov_dpp + v_max instead of one v_max_f32_dpp (3x the instructions of a max-pool).
@@ -115,8 +115,9 @@ def build_gradf32(force: bool = False, verbose: bool = True) -> str:
     build(force=False, verbose=verbose)
     # the same with the FORWARD left as in the default build: isolates the backward arithmetic (a forward that differs by 1e-6
     # already moves ill-conditioned gradients by 1e-3 through max-pool routes and the flow's conditioning)
+    # only the sources that read these macros: the backward ones in train_fused.hip, PF_EC_FWD_F32 in train_ec_fwd.hip
     build(force=force, verbose=verbose, defines=BWDF32_DEFINES, tag="bwdf32", only=("train_fused.hip",))
-    return build(force=force, verbose=verbose, defines=GRADF32_DEFINES, tag="gradf32", only=("train_fused.hip",))
+    return build(force=force, verbose=verbose, defines=GRADF32_DEFINES, tag="gradf32", only=("train_fused.hip", "train_ec_fwd.hip"))
 
 
 if __name__ == "__main__":

@@ -225,7 +225,7 @@ __global__ __launch_bounds__(NW * 64) void flow_kernel(FlowArgs a) {
         // ---- log-likelihood: the workgroup that arrives last reduces the wave-tile sums per batch item (probs.py:73-75,
         // interpflow.py:339-345), a fixed order whichever workgroup that is.  No release fence (it would write the whole L2
         // back, tens of microseconds): the partials are agent-scope stores, waiting for their acknowledgement orders them
-        // before the arrival count (the same protocol as train_fused.hip stat_flush).
+        // before the arrival count (the same protocol as pf_train_stat.h stat_flush).
         __shared__ float sa[NW * 64];
         __shared__ int is_last;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

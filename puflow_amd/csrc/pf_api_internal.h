@@ -4,6 +4,9 @@
 #include "../../include/puflow_hip.h"
 #include "pf_grid.h"
 
+// host helpers that cross source files without being part of the C ABI: kept out of the library's dynamic symbol table
+#define PF_INTERNAL __attribute__((visibility("hidden")))
+
 static inline int pf_last_launch_status() {
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? PF_OK : PF_ERR_LAUNCH;

@@ -1,6 +1,6 @@
 // Inter-workgroup synchronisation of the persistent kernels, and the host queries that make it safe.
 //
-// Kernels whose workgroups wait for each other: ec_fwdp_kernel / ec_bwdp_kernel (train_fused.hip: pf_grid_barrier),
+// Kernels whose workgroups wait for each other: ec_fwdp_kernel / ec_bwdp_kernel (train_ec_fwd.hip / train_fused.hip: pf_grid_barrier),
 // emd_repl_kernel / emd_coop_kernel (emd.hip: pf_sum_barrier) and fps_coopm_kernel / fps_exchange_probe_kernel (patch_ops.hip:
 // pf_ring_poll).  What holds them together:
 //   * The HOST guarantees that THIS kernel alone fits: it launches a waiting grid only when pf_resident_per_cu (the occupancy API

@@ -16,7 +16,7 @@
 //
 // Reductions: per-workgroup partial sums written with device-scope atomic stores, the workgroup that arrives last (atomic
 // counter) adds them up in a fixed order - deterministic, no second launch and no device-wide fence (a release fence
-// writes the whole L2 back on this multi-die part: tens of microseconds per launch, see csrc/train_fused.hip).
+// writes the whole L2 back on this multi-die part: tens of microseconds per launch, see csrc/pf_train_stat.h stat_flush).
 #include <hip/hip_runtime.h>
 #include "pf_api_internal.h"
 

@@ -81,7 +81,7 @@ def _stat(dev) -> Tensor:
 
 
 _SYNCW = {}
-# persistent (grid-barrier) kernels of the training step (csrc/train_fused.hip: ec_fwdp_kernel): "1" = the main chain's EdgeConv
+# persistent (grid-barrier) kernels of the training step (csrc/train_ec_fwd.hip: ec_fwdp_kernel, csrc/train_fused.hip: ec_bwdp_kernel): "1" = the main chain's EdgeConv
 # units may use them (the default; the network attribute `train_persistent` and a device shared between processes switch them
 # off per module), "0" = the per-layer kernels everywhere (the A/B reference).  Read once at import.
 _PERSIST = os.environ.get("PF_TRAIN_PERSIST", "1") != "0"
@@ -319,7 +319,7 @@ def sync_bn(on: bool):
 # Bit-reproducible training steps (debugging switch; VERDICT / ADVICE r4): `net.deterministic = True` (TrainerModule:
 # `cfg.deterministic`).  forward_train copies it here at the start of every train-mode forward and the autograd functions read it
 # when they run (the backward of that forward included): BatchNorm statistics as exact 64-bit fixed-point sums
-# (PF_TRAIN_DETERMINISTIC: csrc/train_fused.hip stat_add; the persistent kernels are not used), the latent's gradient as a gather
+# (PF_TRAIN_DETERMINISTIC: csrc/pf_train_stat.h stat_add; the persistent kernels are not used), the latent's gradient as a gather
 # over the sorted transposed neighbour lists, the Chamfer gradient by pf_chamfer_bwd_det.  Everything else in the fused step is
 # already order-fixed (split-K partials reduced in index order, the dQ gather over the now sorted lists, the auction).
 _DET = False
@@ -833,7 +833,7 @@ def edgeconv_train(p, x: Tensor, idx: Tensor, pooling: bool = True, csr=None, pe
 
 
 class EdgeConvUnitFn(Function):
-    """One FeatureExtractUnit in train mode as ~11 launches forward / ~20 backward (csrc/train_fused.hip: the folded edge
+    """One FeatureExtractUnit in train mode as ~11 launches forward / ~20 backward (csrc/train_ec_fwd.hip, csrc/train_fused.hip: the folded edge
     feature, BatchNorm applied on load by the consumer of each layer, statistics in the GEMM epilogues, max-pool in the
     accumulator layout).  Same function and gradients as `edgeconv_train` (interpflow.py:190-248), which stays as the
     A/B reference (PF_TRAIN_FUSED=0) and as the SyncBN path."""
@@ -1508,7 +1508,7 @@ class FoldWuFn(Function):
 
 class BnMlpFn(Function):
     """[Conv2d 1x1 + BatchNorm2d(train) + LeakyReLU] x 2 + Conv2d 1x1 on rows (DistanceEncoder / WeightEstimationUnit,
-    interpflow.py:85-151) on cat[xa, xb] without building it: 3-4 launches forward, ~10 backward (csrc/train_fused.hip).
+    interpflow.py:85-151) on cat[xa, xb] without building it: 3-4 launches forward, ~10 backward (csrc/train_bnmlp.hip).
     apply(xa, xb | None, cfg, W0, b0, W1, b1, W2, b2, gamma0, beta0, gamma1, beta1)"""
 
     @staticmethod
@@ -1848,7 +1848,7 @@ def knn_csr_pair(idx: Tensor, K2: int):
 
 
 def _ec_fused_supported(p, x: Tensor, idx: Tensor, pooling: bool) -> bool:
-    """Shapes the fused unit kernels are built for (csrc/train_fused.hip: ec_dims); anything else takes the per-op path."""
+    """Shapes the fused unit kernels are built for (csrc/train_fused.hip: pf_ec_dims); anything else takes the per-op path."""
     g, nconv, odim = p.convs[0][0].weight.shape[0], len(p.convs), p.conv_out.weight.shape[0]
     B, N, _ = x.shape
     K = idx.shape[-1]

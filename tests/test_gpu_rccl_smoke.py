@@ -79,7 +79,7 @@ def test_inference_bench_over_rccl_one_rank():
 @pytest.mark.parametrize("graph", ["1", "0"])
 def test_syncbn_training_step_over_rccl_one_rank(graph):
     """cfg.sync_batchnorm on the fused kernels with RCCL: every BatchNorm layer's 257-double all-reduce (csrc/train_fused.hip
-    stat_sync -> train_ops._sync_cb_impl -> dist.all_reduce) between two launches - eager, and CAPTURED into the step's hipGraph
+    pf_stat_sync -> train_ops._sync_cb_impl -> dist.all_reduce) between two launches - eager, and CAPTURED into the step's hipGraph
     (graph = 1: graphed_train_step no longer refuses SyncBN when the backend is nccl).  One rank, multi-rank path forced."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--mode", "train", "--steps", "3", "--warmup", "1",
                           "--no-cpu-baseline", "--no-grad-parity"], cwd=ROOT, env=dict(_env(), PF_BENCH_GRAPH=graph, PF_BENCH_SYNCBN="1"),

@@ -75,7 +75,7 @@ def test_syncbn_two_ranks_equal_full_batch():
         assert (torch.from_numpy(r[5]) - rm).abs().max() < 1e-6 and (torch.from_numpy(r[6]) - rv).abs().max() < 1e-5
 
 
-# ---- SyncBN on the FUSED training kernels (csrc/train_fused.hip: a layer's local column sums are all-reduced between its launch
+# ---- SyncBN on the FUSED training kernels (csrc/pf_train_stat.h, train_fused.hip pf_stat_sync: a layer's local column sums are all-reduced between its launch
 # and a one-block finalisation; train_ops._attach_sync) -------------------------------------------------------------------
 def _unit_and_data():
     from puflow_amd.interpflow import _EdgeConvParams

@@ -1,4 +1,4 @@
-"""GPU: the fused training kernels of one EdgeConv unit (csrc/train_fused.hip) against the un-fused composition
+"""GPU: the fused training kernels of one EdgeConv unit (csrc/train_ec_fwd.hip, csrc/train_fused.hip) against the un-fused composition
 (train_ops.edgeconv_train with PF_TRAIN_FUSED semantics off), which is itself pinned to the oracle's train step in
 tests/test_gpu_train.py.  Output, input gradient and every parameter gradient, all unit shapes of the network
 (interpflow.py:190-248: growth 8/16/32, pooled K = 16 and the interpolation's un-pooled K = 8 unit with 8 layers)."""
@@ -179,7 +179,7 @@ def test_mlp_fused_matches_unfused(kind, cc, td, cdiv, rows):
 
 @pytest.mark.parametrize("two_inputs,rows", [(False, 4096), (True, 4096), (True, 65536)])
 def test_bnmlp_fused_matches_unfused(two_inputs, rows):
-    """The interpolation module's BatchNorm MLPs (csrc/train_fused.hip, pf_bnmlp_train_*) against the un-fused layer kernels:
+    """The interpolation module's BatchNorm MLPs (csrc/train_bnmlp.hip, pf_bnmlp_train_*) against the un-fused layer kernels:
     DistanceEncoder (10 -> 64 -> 64 -> 128, input without gradient) and WeightEstimationUnit (cat[128, 128] -> 128 -> 64 -> 32)."""
     from puflow_amd import train_ops
     from puflow_amd.interpflow import _InterpParams
@@ -487,7 +487,7 @@ def test_edgeconv_unit_persistent_forward_matches_the_per_layer_kernels(cin, odi
 
 
 # ---- round 5: pf_gemm on conflict-free LDS images (gemm2_kernel) = the round-1 kernel bit for bit ---------------------------
-# operand orientations of the three point GEMMs of an EdgeConv unit (train_fused.hip: PQ = x Wpq^T + b, dx = dPQ Wpq,
+# operand orientations of the three point GEMMs of an EdgeConv unit (train_ec_fwd.hip / train_fused.hip: PQ = x Wpq^T + b, dx = dPQ Wpq,
 # dWpq = dPQ^T x with split-K) plus ragged shapes, every tile shape of gemm_shape()
 @pytest.mark.parametrize("M,N,K,a_kfast,b_nfast,bias", [
     (8192, 512, 128, True, False, True),        # PQ forward, 128-channel unit

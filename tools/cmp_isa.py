@@ -1,0 +1,121 @@
+#!/usr/bin/env python3
+"""Check A: compare kernels of two source trees (resources + instruction streams) for the default, bwdf32 and gradf32 builds.
+python tools/cmp_isa.py PARENT_ROOT BRANCH_ROOT [--dump DIR]   (two checkouts; build container, no GPU)"""
+import concurrent.futures, filecmp, hashlib, importlib.util, os, re, subprocess, sys, tempfile
+
+VARIANTS = {"default": [], "bwdf32": ["PF_EC_BWDG_F32", "PF_EC_DW_F32"], "gradf32": ["PF_EC_BWDG_F32", "PF_EC_DW_F32", "PF_EC_FWD_F32"]}
+
+
+def load_build(root):
+    spec = importlib.util.spec_from_file_location("b_" + hashlib.md5(root.encode()).hexdigest(), os.path.join(root, "puflow_amd", "build.py"))
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)
+    return m
+
+
+def compile_s(B, path, defines, out):
+    subprocess.check_call(["/opt/rocm/bin/hipcc"] + B.FLAGS + B.EXTRA_FLAGS.get(os.path.basename(path), []) + [f"-D{d}" for d in defines] +
+                          ["-S", "--cuda-device-only", "-o", out, path], stderr=subprocess.DEVNULL)
+    return out
+
+
+def demangle(names):
+    out = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.split("\n")
+    return dict(zip(names, out))
+
+
+RES_KEYS = ("NumSgprs", "NumVgprs", "NumAgprs", "TotalNumVgprs", "ScratchSize", "Occupancy", "LDSByteSize")
+
+
+def parse(asm_path):
+    text = open(asm_path).read()
+    kernels = re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", text, re.M)
+    dm = demangle(kernels)
+    res = {}
+    for k in kernels:
+        m = re.search(r"^" + re.escape(k) + r":[^\n]*\n(.*?)^\.Lfunc_end\d+:\n(.*?)(?=^\s*\.(?:section|text|protected|globl)\b)", text, re.S | re.M)
+        assert m, k
+        body, tail = m.group(1), m.group(2)
+        body = body[:body.rindex("s_endpgm") + len("s_endpgm")]
+        lines = []
+        for line in body.splitlines():
+            line = line.split(";")[0].strip()
+            if not line:
+                continue
+            line = re.sub(r"\.LBB\d+_", ".LBB_", line)
+            line = re.sub(r"\s+", " ", line)
+            lines.append(line)
+        r = {}
+        for key in RES_KEYS:
+            mm = re.search(r";\s*" + key + r":\s*(\d+)", tail)
+            r[key] = int(mm.group(1)) if mm else None
+        res.setdefault(dm[k].replace("(anonymous namespace)::", ""), []).append((os.path.basename(asm_path), r, lines))
+    return res
+
+
+def main():
+    parent, branch = sys.argv[1], sys.argv[2]
+    dump = sys.argv[sys.argv.index("--dump") + 1] if "--dump" in sys.argv else None
+    trees = {"parent": parent, "branch": branch}
+    Bs = {k: load_build(v) for k, v in trees.items()}
+    files = {}
+    for k, root in trees.items():
+        other = trees["branch" if k == "parent" else "parent"]
+        fs = []
+        for s in Bs[k].SOURCES:
+            a, b = os.path.join(root, "puflow_amd/csrc", s), os.path.join(other, "puflow_amd/csrc", s)
+            if not os.path.exists(b) or not filecmp.cmp(a, b, shallow=False):
+                fs.append(s)
+        files[k] = fs
+    print("sources that differ:", files)
+    tmp = tempfile.mkdtemp(prefix="cmpisa_")
+    jobs = {}
+    with concurrent.futures.ThreadPoolExecutor(8) as ex:
+        for k, root in trees.items():
+            for v, defs in VARIANTS.items():
+                for s in files[k]:
+                    out = os.path.join(tmp, f"{k}_{v}_{s}.s")
+                    jobs[(k, v, s)] = ex.submit(compile_s, Bs[k], os.path.join(root, "puflow_amd/csrc", s), defs, out)
+        for j in jobs.values():
+            j.result()
+    ok = True
+    for v in VARIANTS:
+        side = {}
+        for k in trees:
+            allk = {}
+            for s in files[k]:
+                for name, lst in parse(jobs[(k, v, s)].result()).items():
+                    allk.setdefault(name, []).extend([(s,) + x[1:] for x in lst])
+            side[k] = allk
+        P, Bk = side["parent"], side["branch"]
+        print(f"\n== {v}: parent {sum(map(len, P.values()))} kernels ({len(P)} names), branch {sum(map(len, Bk.values()))} kernels ({len(Bk)} names)")
+        only_p, only_b = sorted(set(P) - set(Bk)), sorted(set(Bk) - set(P))
+        print("   only in parent:", only_p or "none")
+        print("   only in branch:", only_b or "none")
+        if only_b or [n for n in only_p if not re.search(r"::(ec_dw4_kernel|ec_dw5_kernel|ec_bwd_kernel<)", n)]:
+            ok = False
+        nsame = 0
+        for name in sorted(set(P) & set(Bk)):
+            ps, pr, pl = P[name][0]
+            for bs, br, bl in Bk[name]:
+                if br["ScratchSize"]:
+                    print("   SCRATCH", name, br); ok = False
+                if pr != br:
+                    print(f"   RESOURCES DIFFER {name}\n      parent {ps}: {pr}\n      branch {bs}: {br}"); ok = False
+                if pl != bl:
+                    print(f"   ISA DIFFERS {name} ({ps}: {len(pl)} instr, {bs}: {len(bl)} instr)"); ok = False
+                    if dump:
+                        os.makedirs(dump, exist_ok=True)
+                        h = hashlib.md5(name.encode()).hexdigest()[:8]
+                        open(os.path.join(dump, f"{v}_{h}_parent.s"), "w").write(name + "\n" + "\n".join(pl) + "\n")
+                        open(os.path.join(dump, f"{v}_{h}_branch.s"), "w").write(name + "\n" + "\n".join(bl) + "\n")
+                if pr == br and pl == bl:
+                    nsame += 1
+        print(f"   identical (registers, scratch, LDS, occupancy, instruction stream): {nsame} kernel copies; "
+              f"total instructions compared {sum(len(x[2]) for l in Bk.values() for x in l)}")
+    print("\nRESULT:", "ALL IDENTICAL" if ok else "DIFFERENCES")
+    return 0 if ok else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Build container: timing-only variants of the persistent EdgeConv forward kernel (-DPF_ECP_DBG=mask, csrc/train_fused.hip);
+"""Build container: timing-only variants of the persistent EdgeConv forward kernel (-DPF_ECP_DBG=mask, csrc/train_ec_fwd.hip);
 GPU box: time the 128-channel unit's forward with each (the kernel's own duration from rocprofv3 would be better still; the
 HIP-event time of the whole call is enough to rank the pieces).
   python tools/ecp_ablate.py build            (here)
@@ -11,7 +11,7 @@ MASKS = (0, 1, 2, 4, 8, 16, 1 | 2, 1 | 2 | 4 | 8 | 16)
 if sys.argv[1] == "build":
     from puflow_amd import build as B
     for m in MASKS[1:]:
-        print(B.build(verbose=False, defines=[f"PF_ECP_DBG={m}"], tag=f"ecp{m}", only=("train_fused.hip",)))
+        print(B.build(verbose=False, defines=[f"PF_ECP_DBG={m}"], tag=f"ecp{m}", only=("train_ec_fwd.hip",)))
 else:
     from puflow_amd.build import LIB
     for m in MASKS:

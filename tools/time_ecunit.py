@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """GPU box: one EdgeConv unit of the training step, forward (and backward) as the per-layer launches vs the persistent
-grid-barrier launch (csrc/train_fused.hip ec_fwdp_kernel), HIP-event times at the training shape 32 x 256 points, K = 16.
+grid-barrier launch (csrc/train_ec_fwd.hip ec_fwdp_kernel), HIP-event times at the training shape 32 x 256 points, K = 16.
   python tools/time_ecunit.py [B] [N]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
