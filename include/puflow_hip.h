@@ -752,6 +752,59 @@ long long pf_point_mesh_ws_floats(int P, int F);
 int pf_point_mesh_dist(const float* pts, int P, const float* tris, int F, const int* seed, int brute, float* dist, int* face,
                        float* ws, long long ws_floats, void* stream);
 
+/* ---- training batches on the device (csrc/data_aug.hip; the reference's dataset/pu1k/fetcher.py:69-101) ---------------------
+ * One launch assembles and augments rows [0, b) of a batch from a device-resident dataset: one workgroup per patch, no grid
+ * barrier, no float atomics, no host synchronisation, no global state.
+ *   inp [M, n_in, 3], gt [M, n_out, 3], radius [M] fp32; order [M] int32, a permutation of 0..M-1 (the epoch's shuffle).
+ *   Row r takes patch order[(pos + r) mod M]; its random numbers belong to the GLOBAL PATCH SLOT slot0 + r (the caller passes
+ *   step * batch_size + first row, so a rank that produces rows [lo, hi) of a batch gets exactly those rows of the whole batch).
+ * Stages, in the reference's order, each behind its flag:
+ *   PF_PATCH_SUBSAMPLE  n_in > n only: nonuniform_sampling - loc ~ U(0.1, 0.9), candidates int((loc + 0.3 z_j) n_in) (truncation),
+ *                       out-of-range ones dropped, the first n DISTINCT ones in stream order kept (what the reference's
+ *                       sequential rejection loop yields).  Candidates come in rounds of 1024, at most PF_PATCH_MAX_ROUNDS;
+ *                       a patch still short then sets PF_PATCH_ST_SHORT and repeats its last index.  Needs
+ *                       n_in <= PF_PATCH_MAX_NIN and n <= PF_PATCH_MAX_N (LDS tables), else PF_ERR_UNSUPPORTED.
+ *                       n_in > n without this flag: PF_ERR_SHAPE.
+ *   PF_PATCH_JITTER     input only: x += clip(sigma z, -clip, clip), three normals per point.
+ *   PF_PATCH_ROTATE     input and gt: row vector times R = Rz Ry Rx, angles 2 pi u each; with PF_PATCH_Z_ROTATED R = Rz.
+ *   PF_PATCH_SCALE      input, gt and radius times s ~ U(scale_low, scale_high).
+ *   PF_PATCH_SHIFT      input and gt plus t ~ U(-shift_range, shift_range)^3; off when shift_range == 0.
+ *   With no flag the outputs are copies of the selected patches (the validation setting).
+ * Random numbers: Philox-4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter
+ *   (element, stream, slot & 0xffffffff, slot >> 32), giving four 32-bit words x0..x3 per counter:
+ *   stream 0 (parameters): element 0 -> x0: loc, x1 x2 x3: the angles about x, y, z; element 1 -> x0: scale, x1 x2 x3: shifts;
+ *   stream 1 (candidates): stream position p reads element p / 4, words (x0, x1) for p mod 4 < 2, else (x2, x3);
+ *                          z = r cos(2 pi u1) for even p, r sin(2 pi u1) for odd p, r = sqrt(-2 ln u0)   (Box-Muller);
+ *   stream 2 (jitter):     point i of the OUTPUT reads element i: (x0, x1) -> the x and y noise (cos, sin), (x2, x3) -> z (cos).
+ *   Word to uniform: u = (x >> 8) 2^-24 + 2^-25 in fp32, never 0; the one value that fp32 rounds to 1 is kept at 1 - 2^-24.
+ *   U(lo, hi) = lo + (hi - lo) u; the shifts use 2u - 1 of the unrounded u (exact in fp32) times shift_range.
+ *   logf, sinf, cosf are the precise ones; every operation is a separate fp32 rounding except the rotation, which is
+ *   fma(z, R2j, fma(y, R1j, x R0j)) for output coordinate j - the same order for every row wherever it is produced.
+ * Outputs: out_inp [b, n, 3], out_gt [b, n_out, 3], out_radius [b];
+ *   params [b, 16], always written: R row-major (9; identity when off), scale (1 when off), shifts (3; 0 when off), loc (0 when
+ *   no subsample), the number of candidate rounds drawn, 0;
+ *   idx [b, n] (nullable): the index of inp's point behind every output point; cand [b, T] (nullable, tests): the candidate
+ *   stream as drawn, out-of-range values included, positions < min(T, 1024 x rounds drawn) - the rest is left untouched;
+ *   status: one int32 the kernel only ever ORs bits into (PF_PATCH_ST_*); the caller zeroes it once and reads it when it
+ *   synchronises anyway. */
+#define PF_PATCH_SUBSAMPLE 1
+#define PF_PATCH_JITTER 2
+#define PF_PATCH_ROTATE 4
+#define PF_PATCH_Z_ROTATED 8
+#define PF_PATCH_SCALE 16
+#define PF_PATCH_SHIFT 32
+#define PF_PATCH_ALL 63
+#define PF_PATCH_MAX_NIN 8192
+#define PF_PATCH_MAX_N 4096
+#define PF_PATCH_MAX_ROUNDS 64
+#define PF_PATCH_ST_SHORT 1     /* a patch had fewer than n distinct candidates after PF_PATCH_MAX_ROUNDS rounds */
+#define PF_PATCH_ST_ORDER 2     /* order held a value outside [0, M): patch 0 was used instead                    */
+int pf_patch_batch(const float* inp, const float* gt, const float* radius, const int* order, int M, int n_in, int n_out,
+                   long long pos, int b, int n, unsigned long long slot0, unsigned long long seed, int flags,
+                   float jitter_sigma, float jitter_clip, float scale_low, float scale_high, float shift_range,
+                   float* out_inp, float* out_gt, float* out_radius, float* params, int* idx, int* cand, int T, int* status,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,7 @@
 
 One process per GPU under `torchrun` (batches are sharded by the data object, gradients averaged by one all-reduce);
 rank 0 saves.  CLI:  python -m puflow_amd.train --dataset pu1k --data data/pu1k_...h5 [--synthetic] [--max_epochs 100]
+                     [--graph] [--device_data] [--random_input]
 """
 from __future__ import annotations
 
@@ -44,6 +45,10 @@ def model_specific_args() -> argparse.ArgumentParser:
     p.add_argument("--begin_checkpoint", default=None)
     p.add_argument("--sync_batchnorm", action="store_true")
     p.add_argument("--graph", action="store_true", help="replay the training step from a hipGraph per batch shape")
+    p.add_argument("--device_data", action="store_true", help="keep the training set on the GPU and assemble + augment every batch "
+                   "there in one launch (data.DevicePatchData) instead of on the host")
+    p.add_argument("--random_input", action="store_true", help="train on non-uniform subsamples of the 4x input (the reference's "
+                   "use_random_input); validation keeps the plain input")
     return p
 
 
@@ -70,36 +75,47 @@ def fit(module: TrainerModule, train_data: Iterable, val_data: Optional[Iterable
     rank, _ = _dist()
     graphs = {}
     use_graph = graph and next(module.parameters()).is_cuda
-    for epoch in range(max_epochs):
-        module.train()
-        last = None
-        for bi, batch in enumerate(train_data):
-            if use_graph:
-                key = _batch_key(batch)
-                if key not in graphs:
-                    graphs[key] = module.graphed_train_step(batch, optimizer, clip, warmup=1)
-                    last = graphs[key].warmup_loss
-                else:
-                    last = graphs[key](batch)
-                continue
-            last = module.train_step(batch, optimizer, clip)
-        hist["loss"].append(float(last) if last is not None else float("nan"))
-        if next(module.parameters()).is_cuda:
-            module.check_device_status()          # end of epoch, the host just synchronised: EMD barrier time-outs raise, NaN substitutions are printed
-        if val_data is not None:
-            outs = [module.validation_step(b, i) for i, b in enumerate(val_data)]
-            cd = module.validation_epoch_end(outs)["CD"]
-            if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
-                t = torch.tensor([cd], dtype=torch.float64, device=next(module.parameters()).device)
-                torch.distributed.all_reduce(t)                     # every rank steps the scheduler on the same number
-                cd = float(t.item())
-            scheduler.step(cd)                                      # monitor: 'CD' (configure_optimizers)
-            hist["CD"].append(cd)
-        hist["lr"].append(optimizer.param_groups[0]["lr"])
-        hist["epochs"] = epoch + 1
-        if rank == 0 and log is not None:
-            log(f"epoch {epoch}: loss {hist['loss'][-1]:.6f}" + (f"  CD {hist['CD'][-1]:.6f}" if hist["CD"] else "") +
-                f"  lr {hist['lr'][-1]:.2e}")
+    try:
+        for epoch in range(max_epochs):
+            module.train()
+            last = None
+            for bi, batch in enumerate(train_data):
+                if use_graph:
+                    key = _batch_key(batch)
+                    if key not in graphs:
+                        graphs[key] = module.graphed_train_step(batch, optimizer, clip, warmup=1)
+                        last = graphs[key].warmup_loss
+                        if hasattr(train_data, "bind"):          # device-side data: the next batches land in the captured inputs
+                            train_data.bind(graphs[key].static)
+                    else:
+                        last = graphs[key](batch)
+                    continue
+                last = module.train_step(batch, optimizer, clip)
+            hist["loss"].append(float(last) if last is not None else float("nan"))
+            if next(module.parameters()).is_cuda:
+                module.check_device_status()          # end of epoch, the host just synchronised: EMD barrier time-outs raise, NaN substitutions are printed
+            if hasattr(train_data, "status"):
+                st = train_data.status()
+                if st:
+                    raise RuntimeError(f"the device data pipeline reported status {st} (bit 1: a patch ran out of distinct subsample "
+                                       "candidates, bit 2: corrupt permutation)")
+            if val_data is not None:
+                outs = [module.validation_step(b, i) for i, b in enumerate(val_data)]
+                cd = module.validation_epoch_end(outs)["CD"]
+                if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+                    t = torch.tensor([cd], dtype=torch.float64, device=next(module.parameters()).device)
+                    torch.distributed.all_reduce(t)                     # every rank steps the scheduler on the same number
+                    cd = float(t.item())
+                scheduler.step(cd)                                      # monitor: 'CD' (configure_optimizers)
+                hist["CD"].append(cd)
+            hist["lr"].append(optimizer.param_groups[0]["lr"])
+            hist["epochs"] = epoch + 1
+            if rank == 0 and log is not None:
+                log(f"epoch {epoch}: loss {hist['loss'][-1]:.6f}" + (f"  CD {hist['CD'][-1]:.6f}" if hist["CD"] else "") +
+                    f"  lr {hist['lr'][-1]:.2e}")
+    finally:
+        if use_graph and hasattr(train_data, "bind"):
+            train_data.bind(None)                   # the captured inputs go away with `graphs`: later batches get fresh tensors again
     return hist
 
 
@@ -132,7 +148,7 @@ def train(phase: str = "Train", checkpoint_path: Optional[str] = None, begin_che
 
 
 def main(argv=None) -> None:
-    from .data import SyntheticPatchData, patch_data_from_file
+    from .data import SyntheticDevicePatchData, SyntheticPatchData, patch_data_from_file
     a = model_specific_args().parse_args(argv)
     from ._host import limit_host_threads
     limit_host_threads()                       # torch's OpenMP pool within the container's CPU quota (puflow_amd/_host.py)
@@ -146,11 +162,12 @@ def main(argv=None) -> None:
                       seed=a.seed, sync_batchnorm=a.sync_batchnorm)
     kw = dict(batch_size=a.batch_size, num_point_patch=256, device=dev, seed=a.seed, rank=rank, world=world,
               is_augment=True, jitter_sigma=0.01, jitter_max=0.03)            # train_pu1k.py:132-141
+    tkw = {**kw, "use_random_input": True} if a.random_input else kw          # the validation set: no subsample, no augmentation
     if a.synthetic or a.data is None:
-        tr = SyntheticPatchData(num_patches=8 * a.batch_size, up_ratio=4, **kw)
+        tr = (SyntheticDevicePatchData if a.device_data else SyntheticPatchData)(num_patches=8 * a.batch_size, up_ratio=4, **tkw)
         va = SyntheticPatchData(num_patches=2 * a.batch_size, up_ratio=4, **{**kw, "is_augment": False, "seed": a.seed + 7})
     else:
-        tr = patch_data_from_file(a.data, up_ratio=4, **kw)
+        tr = patch_data_from_file(a.data, up_ratio=4, on_device=a.device_data, **tkw)
         va = patch_data_from_file(a.data, up_ratio=4, num_batches=a.val_batches, **{**kw, "is_augment": False})
     train("Train", a.checkpoint_path or DEFAULT_CKPT[a.dataset], a.begin_checkpoint, cfg, tr, va, a.max_epochs, a.dataset, dev,
           graph=a.graph)

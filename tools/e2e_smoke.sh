@@ -6,6 +6,9 @@ D=${1:-/tmp/e2e}
 rm -rf "$D" && mkdir -p "$D/in" "$D/out"
 timeout -k 10 400 python3 -m puflow_amd.train --synthetic --max_epochs 11 --val_batches 2 --graph --checkpoint_path "$D/model.ckpt" > "$D/train.out" 2> "$D/train.err" || { tail -5 "$D/train.err"; exit 1; }
 grep "epoch 0:\|epoch 10:\|saved" "$D/train.out"
+# the same loop fed from the device: the training set stays on the GPU, one launch per batch subsamples + augments it
+timeout -k 10 300 python3 -m puflow_amd.train --synthetic --max_epochs 3 --val_batches 2 --graph --device_data --random_input > "$D/train_dev.out" 2> "$D/train_dev.err" || { tail -5 "$D/train_dev.err"; exit 1; }
+grep "epoch 0:\|epoch 2:" "$D/train_dev.out"
 python3 - "$D" <<'PY'
 import sys, numpy as np
 sys.path.insert(0, ".")
