@@ -805,6 +805,43 @@ int pf_patch_batch(const float* inp, const float* gt, const float* radius, const
                    float* out_inp, float* out_gt, float* out_radius, float* params, int* idx, int* cand, int T, int* status,
                    void* stream);
 
+/* ---- uniformity of an upsampled cloud on its mesh (csrc/eval_uniform.hip; the reference's evaluate.py:105-165 analyze_uniform
+ * and the disk search evaluation.cpp:79-113 was meant to feed it) --------------------------------------------------------------
+ * Closest points: out[P,3] = the closest point of triangle face[p] of tris [F,9] to pts[p] (Voronoi-region classification in
+ * double, relative to the point).  A face index outside [0, F) gives NaN, never a read outside tris. */
+int pf_tri_closest_points(const float* pts, int P, const float* tris, int F, const int* face, float* out, void* stream);
+
+/* Seeds on the surface: for s in [0, S) the words x0 x1 x2 of Philox-4x32-10 with key (seed & 0xffffffff, seed >> 32) and
+ * counter (s, 0, 0, 0) give u0 u1 u2 (the word-to-uniform mapping above: never 0, never 1).  face[s] = the first f with
+ * cum_area[f] > u0 cum_area[F-1] (cum_area [F] double, the running sum of the triangle areas - a device pointer; F - 1 when
+ * there is none), seeds[s] = (1 - sqrt u1) a + sqrt u1 (1 - u2) b + sqrt u1 u2 c of that triangle, uniforms [S,3] = u0 u1 u2.
+ * A seed depends on (mesh, seed, s) only.  S <= 2^24. */
+int pf_mesh_sample(const float* tris, int F, const double* cum_area, int S, unsigned long long seed, float* seeds, int* face,
+                   float* uniforms, void* stream);
+
+/* Disks: the points of mapped [N,3] within the Euclidean distance radii[j] of seeds[s] (seeds [S,3]; radii [J] HOST doubles,
+ * positive and ascending, J <= PF_DISK_MAX_RADII), |mapped - seed|^2 <= fp32(radii[j]^2) with the seed subtracted first.
+ *   pf_disk_count: counts [S,J] int32.
+ *   pf_disk_fill:  row s of the CSR, member / level [offsets[s], offsets[s+1]) (offsets [S+1] int64 on the device, sized by the
+ *                  caller from counts[:, J-1]): the members of the largest disk in ascending index order and, for each, the
+ *                  smallest j whose disk holds it.  A row shorter than its disk is filled and not overrun.
+ * One workgroup per seed sweeps all N points; order comes from wave ballots and prefix counts, not from atomics. */
+#define PF_DISK_MAX_RADII 8
+int pf_disk_count(const float* mapped, int N, const float* seeds, int S, const double* radii, int J, int* counts, void* stream);
+int pf_disk_fill(const float* mapped, int N, const float* seeds, int S, const double* radii, int J, const long long* offsets,
+                 int* member, int* level, void* stream);
+
+/* The statistic of every disk of a CSR (from pf_disk_fill or from files): member k of row s belongs to disk (s, j) when
+ * level[k] <= j.  out_n [S,J] = the member count, out_dis [S,J] = mean over the members of (d - e)^2 / e, with d the distance
+ * to the nearest OTHER member of the same disk (another entry of the row: duplicated points give 0) and
+ * e = sqrt(2 (pi radii[j]^2 / n) / 1.732); NaN for fewer than two members.  Both double.  Squared distances are fp32 sums of
+ * squared fp32 differences; d, the terms and their sum (a fixed order) are double.  Rows of any length: PF_DISK_TILE members
+ * are staged at a time (pf_disk_tile() returns it).  Member indices are clamped to [0, N), the caller validates them. */
+#define PF_DISK_TILE 1024
+int pf_disk_tile(void);
+int pf_disk_uniformity(const float* mapped, int N, const long long* offsets, const int* member, const int* level, int S,
+                       const double* radii, int J, double* out_n, double* out_dis, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

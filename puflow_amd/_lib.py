@@ -227,6 +227,13 @@ SIGNATURES = {
     "pf_patch_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_longlong, c_int, c_int, c_ulonglong,
                                c_ulonglong, c_int, c_float, c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "pf_tri_closest_points": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "pf_mesh_sample": (c_int, [c_void_p, c_int, c_void_p, c_int, c_ulonglong, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pf_disk_count": (c_int, [c_void_p, c_int, c_void_p, c_int, POINTER(c_double), c_int, c_void_p, c_void_p]),
+    "pf_disk_fill": (c_int, [c_void_p, c_int, c_void_p, c_int, POINTER(c_double), c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pf_disk_tile": (c_int, []),
+    "pf_disk_uniformity": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, POINTER(c_double), c_int, c_void_p,
+                                   c_void_p, c_void_p]),
 }
 
 

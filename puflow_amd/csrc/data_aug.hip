@@ -4,12 +4,13 @@
 // one launch, one 1024-thread workgroup per patch, no grid barrier, no float atomics, no host synchronisation.
 // The work is ~0.5 MB per batch: the launch is latency-bound, what it buys is the host work and the three copies it removes.
 //
-// Randomness is counter-based (Philox-4x32-10, Salmon et al. 2011): every value is a pure function of (seed, global patch slot,
+// Randomness is counter-based (Philox-4x32-10, pf_philox.h): every value is a pure function of (seed, global patch slot,
 // stage, element), so a patch does not depend on the grid shape, on the rows a call produces or on the rank that produced them.
 // Every fp32 operation that reaches an output is written as an explicit __f*_rn / fmaf call: -ffp-contract changes nothing.
 #include <climits>
 #include <hip/hip_runtime.h>
 #include "pf_api_internal.h"
+#include "pf_philox.h"
 
 namespace {
 
@@ -30,26 +31,8 @@ struct PbArgs {
     int* idx; int* cand; int* status;
 };
 
-struct U4 { unsigned x, y, z, w; };
-
-// Philox-4x32-10: counter (c0 c1 c2 c3), key (k0 k1); Random123's constants and round function
-__device__ __forceinline__ U4 philox(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-        const unsigned h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-        const unsigned n0 = h1 ^ c1 ^ k0, n2 = h0 ^ c3 ^ k1;
-        c0 = n0; c1 = l1; c2 = n2; c3 = l0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return U4{c0, c1, c2, c3};
-}
 __device__ __forceinline__ U4 draw(const PbArgs& a, unsigned long long slot, unsigned stream, unsigned elem) {
     return philox(elem, stream, (unsigned)slot, (unsigned)(slot >> 32), (unsigned)a.seed, (unsigned)(a.seed >> 32));
-}
-// u = (x >> 8) 2^-24 + 2^-25 rounded to fp32, kept below 1 (the largest 24-bit value would round to 1.0)
-__device__ __forceinline__ float u01(unsigned x) {
-    return fminf(fmaf((float)(x >> 8), 0x1p-24f, 0x1p-25f), 0x1.fffffep-1f);
 }
 // 2u - 1 of the same u, exact: an odd integer below 2^24 in magnitude times 2^-24 (a symmetric range has no cancellation then)
 __device__ __forceinline__ float usym(unsigned x) {

@@ -2,7 +2,7 @@
 point-to-surface column) on the GPU:
 
   python -m puflow_amd.evaluate --pred DIR --gt DIR --save_path DIR [--mesh DIR] [--write_p2m] [--cloud_batch N]
-                                [--emd_levels_top 7]
+                                [--emd_levels_top 7] [--uniform [--uniform_seeds 1000] [--uniform_seed 0] [--write_disks]]
 
 Every `<name>.xyz` of --pred with a `<name>.xyz` in --gt is scored (evaluate.py:187-195): CD, EMD (approx-match), Hausdorff
 and JSD (puflow_amd.metrics).  P2F, the point-to-surface distance of the predicted points: with --mesh it is computed from
@@ -12,6 +12,14 @@ them); without --mesh an existing `<pred>_point2mesh_distance.xyz` (the binary's
 `<save_path>/evaluation.csv` gets the reference's header, one row per file and one summary row, and the summary line is printed
 as evaluate.py:294-298 prints it.
 
+Uniformity (uniform_0..4, evaluate.py:105-165 analyze_uniform) is filled with --uniform only; without it the columns read `-`.
+With --mesh the disks are made on the GPU: --uniform_seeds seeds on the surface (Philox, --uniform_seed), the predicted points
+mapped to their closest mesh points, and around every seed the mapped points within r_j = sqrt(p_j A / pi), p = 0.4 .. 1.2 % of
+the area A; --write_disks also writes `<pred>_disk_idx.txt`, `<pred>_radius.txt` and `<pred>_point2mesh_distance.txt`, the
+three files the reference reads.  Without --mesh those three files are read, whoever wrote them, as evaluate.py:256-262 does.
+Disks made from a mesh are Euclidean balls (the pre-filter of evaluation.cpp:97-100, without its geodesic refinement): they
+differ from geodesic disks on thin parts, where a ball also takes in points of the opposite side.
+
 The reference's quirks, kept or fixed:
   - kept: a file's JSD appears in its row only when it has a P2F (evaluate.py:255), for CSV compatibility; the summary JSD
     is over all files;
@@ -19,8 +27,8 @@ The reference's quirks, kept or fixed:
   - fixed: `load` is undefined in evaluate.py:94,220,248 - read here as np.loadtxt float32 (upsample.load_xyz for clouds);
   - fixed: the summary print raises KeyError when no file has a P2F - `-` is printed instead;
   - fixed: rows follow `glob`'s order there - sorted by name here;
-  - uniformity (uniform_0..4) stays `-`: it needs the `_disk_idx.txt` files the shipped binary never writes, so the reference
-    never computes it either.
+  - kept: uniformity appears in a row only when the file has a P2F (evaluate.py:255-256); the summary is the mean over the
+    files that have it (evaluate.py:283-287).
 """
 from __future__ import annotations
 
@@ -71,14 +79,16 @@ def _batches(items, key, size):
 
 
 def evaluate(pred_dir: str, gt_dir: str, save_path: str, mesh_dir: str = None, write_p2m: bool = False,
-             cloud_batch: int = 16, emd_levels_top: int = 7, device=None):
+             cloud_batch: int = 16, emd_levels_top: int = 7, device=None, uniform: bool = False, uniform_seeds: int = 1000,
+             uniform_seed: int = 0, write_disks: bool = False):
     """Score the directory; returns (per-file rows, summary row) as written to evaluation.csv."""
+    uni = dict(seeds=int(uniform_seeds), seed=int(uniform_seed), write=bool(write_disks)) if uniform else None
     device = torch.device(device or "cuda:0")
     pairs = pair_paths(pred_dir, gt_dir)
     if not pairs:
         raise FileNotFoundError(f"no <name>.xyz is in both {pred_dir} and {gt_dir}")
     loaded = [(name, gp, pp, np.atleast_2d(load_xyz(pp))[:, :3], np.atleast_2d(load_xyz(gp))[:, :3]) for name, gp, pp in pairs]
-    rows, g_cd, g_emd, g_hd, g_jsd, g_p2f = [], [], [], [], [], []
+    rows, g_cd, g_emd, g_hd, g_jsd, g_p2f, g_uni = [], [], [], [], [], [], []
     for run in _batches(loaded, lambda it: (it[3].shape[0], it[4].shape[0]), max(1, int(cloud_batch))):
         pred = torch.from_numpy(np.stack([it[3] for it in run])).to(device)
         gt = torch.from_numpy(np.stack([it[4] for it in run])).to(device)
@@ -94,12 +104,16 @@ def evaluate(pred_dir: str, gt_dir: str, save_path: str, mesh_dir: str = None, w
             g_hd.append(hd[i])
             g_emd.append(emd[i])
             g_jsd.append(float(jsd[i]))
-            p2f = _p2f(pp, pred, i, name, mesh_dir, write_p2m)
+            p2f, u = _p2f(pp, pred, i, name, mesh_dir, write_p2m, uni)
             if p2f is not None and p2f.size > 0:
                 row["p2f avg"] = np.nanmean(p2f)
                 row["p2f std"] = np.nanstd(p2f)
                 g_p2f.append(p2f)
                 row["JSD"] = float(jsd[i])
+                if u is not None:
+                    g_uni.append(u)
+                    for j in range(PERCENTAGES):
+                        row["uniform_%d" % j] = u[j]
             rows.append(row)
     summary = OrderedDict()
     summary["CD"] = np.nanmean(g_cd)
@@ -110,6 +124,9 @@ def evaluate(pred_dir: str, gt_dir: str, save_path: str, mesh_dir: str = None, w
         summary["p2f avg"] = np.nanmean(allp)
         summary["p2f std"] = np.nanstd(allp)
     summary["JSD"] = np.nanmean(g_jsd)
+    if g_uni:
+        for j, v in enumerate(np.mean(np.array(g_uni), axis=0)):
+            summary["uniform_%d" % j] = v
     os.makedirs(save_path, exist_ok=True)
     with open(os.path.join(save_path, "evaluation.csv"), "w") as f:
         writer = csv.DictWriter(f, fieldnames=FIELDNAMES, restval="-", extrasaction="ignore")
@@ -120,26 +137,47 @@ def evaluate(pred_dir: str, gt_dir: str, save_path: str, mesh_dir: str = None, w
     return rows, summary
 
 
-def _p2f(pred_path, pred_gpu, i, name, mesh_dir, write_p2m):
-    """The file's point-to-surface distances (float32 [N]) or None."""
+def _p2f(pred_path, pred_gpu, i, name, mesh_dir, write_p2m, uni=None):
+    """(the file's point-to-surface distances (float32 [N]) or None, its uniformity [5] or None).  uni: None, or the
+    --uniform settings dict(seeds, seed, write)."""
     out_path = pred_path[:-4] + "_point2mesh_distance.xyz"
+    prefix = pred_path[:-4]
+    dev = pred_gpu.device
     if mesh_dir is None:
         if not os.path.isfile(out_path):
-            return None
+            return None, None
         d = np.atleast_2d(np.loadtxt(out_path, dtype=np.float32))
-        return d[:, 3] if d.size > 0 else d.reshape(-1)
+        u = None
+        if uni is not None and all(os.path.isfile(prefix + t) for t in ("_disk_idx.txt", "_radius.txt", "_point2mesh_distance.txt")):
+            mapped, radii, csr = metrics.read_disk_files(prefix)
+            if len(radii) != PERCENTAGES:
+                raise ValueError(f"{prefix}_radius.txt: {len(radii)} radii, the CSV has {PERCENTAGES} uniformity columns")
+            u = metrics.uniformity(torch.from_numpy(mapped).to(dev), tuple(torch.from_numpy(a).to(dev) for a in csr), radii)
+        return (d[:, 3] if d.size > 0 else d.reshape(-1)), u
     off = os.path.join(mesh_dir, name + ".off")
     if not os.path.isfile(off):
-        return None
+        return None, None
     verts, faces = metrics.read_off(off)
-    dev = pred_gpu.device
-    dist = metrics.point_to_mesh_distance(pred_gpu[i], torch.from_numpy(verts).to(dev), torch.from_numpy(faces).to(dev))
+    vt, ft = torch.from_numpy(verts).to(dev), torch.from_numpy(faces).to(dev)
+    if uni is None:
+        dist, face = metrics.point_to_mesh_distance(pred_gpu[i], vt, ft), None
+    else:
+        dist, face = metrics.point_to_mesh_distance(pred_gpu[i], vt, ft, return_face=True)
     dist = dist.cpu().numpy()
     if write_p2m:
         tokens = np.atleast_2d(np.loadtxt(pred_path, dtype=np.float64))[:, :3]
         with open(out_path, "w") as f:
             f.write(format_p2m(tokens, dist))
-    return dist
+    u = None
+    if uni is not None:
+        radii, _ = metrics.mesh_area_radii(verts, faces)
+        mapped = metrics.mapped_points(pred_gpu[i], vt, ft, face=face)
+        seeds, _, _ = metrics.sample_mesh(vt, ft, uni["seeds"], uni["seed"])
+        _, csr = metrics.disks(mapped, seeds, radii)
+        u = metrics.uniformity(mapped, csr, radii)
+        if uni["write"]:
+            metrics.write_disk_files(prefix, pred_gpu[i], dist, mapped, csr, radii)
+    return dist, u
 
 
 def summary_line(summary) -> str:
@@ -156,9 +194,18 @@ def main(argv=None):
     ap.add_argument("--write_p2m", action="store_true", help="with --mesh: write <pred>_point2mesh_distance.xyz")
     ap.add_argument("--cloud_batch", type=int, default=16)
     ap.add_argument("--emd_levels_top", type=int, default=7)
+    ap.add_argument("--uniform", action="store_true",
+                    help="fill uniform_0..4: with --mesh from disks made on the GPU - Euclidean balls around seeds on the mesh, "
+                         "which differ from geodesic disks on thin parts; without --mesh from <pred>_disk_idx.txt, _radius.txt "
+                         "and _point2mesh_distance.txt")
+    ap.add_argument("--uniform_seeds", type=int, default=1000, help="seeds (disks per radius) per mesh")
+    ap.add_argument("--uniform_seed", type=int, default=0, help="key of the seeds' random numbers")
+    ap.add_argument("--write_disks", action="store_true",
+                    help="with --uniform --mesh: write <pred>_disk_idx.txt, _radius.txt and _point2mesh_distance.txt")
     a = ap.parse_args(argv)
     _, summary = evaluate(os.path.abspath(a.pred), os.path.abspath(a.gt), a.save_path, a.mesh, a.write_p2m, a.cloud_batch,
-                          a.emd_levels_top)
+                          a.emd_levels_top, uniform=a.uniform, uniform_seeds=a.uniform_seeds, uniform_seed=a.uniform_seed,
+                          write_disks=a.write_disks)
     print(f"Evaluation: {a.save_path}")
     print(summary_line(summary))
 

@@ -3,9 +3,15 @@ binary evaluation/evaluation_code/evaluation.cpp) on the GPU.
 
 Every function takes torch tensors on the GPU; a CPU tensor raises PuflowHipError (there is no CPU fallback).  The hot parts are
 HIP (csrc/eval_metrics.hip: approx-match EMD and point-to-mesh distance; csrc/knn.hip pf_nn1: the nearest-neighbour searches
-of CD / Hausdorff and of the JSD occupancy lookup); torch only gathers, sorts and reduces small arrays around them.
+of CD / Hausdorff and of the JSD occupancy lookup; csrc/eval_uniform.hip: the seeds, disks and in-disk statistic of the
+uniformity columns); torch only gathers, sorts and reduces small arrays around them.
+
+Uniformity (evaluate.py:105-165 analyze_uniform): disks made here from a mesh are Euclidean balls around seeds on the surface,
+which differ from the geodesic disks of PU-GAN's definition on thin parts, where a ball also reaches the opposite side.
 """
 from __future__ import annotations
+
+import ctypes
 
 import numpy as np
 import torch
@@ -184,3 +190,184 @@ def read_off(path):
             raise ValueError(f"{path}: a face with {len(idx)} corners")
         tris += [(idx[0], idx[i], idx[i + 1]) for i in range(1, k - 1)]
     return verts, np.array(tris, dtype=np.int64).reshape(-1, 3)
+
+
+# ---- uniformity -----------------------------------------------------------------------------------------------------------
+PERCENTAGES = (0.004, 0.006, 0.008, 0.010, 0.012)          # evaluate.py:105: the disks' share of the surface area
+
+
+def _tris(verts: torch.Tensor, faces: torch.Tensor, what: str) -> torch.Tensor:
+    if not (torch.is_tensor(verts) and torch.is_tensor(faces) and verts.is_cuda and faces.is_cuda):
+        raise _lib.PuflowHipError(f"{what} needs GPU tensors (no CPU fallback)")
+    return ops._f32c(verts)[faces.long()].reshape(-1, 9).contiguous()
+
+
+def _radii(radii):
+    r = np.ascontiguousarray(np.atleast_1d(np.asarray(radii, dtype=np.float64)))
+    return r, (ctypes.c_double * len(r))(*r.tolist())
+
+
+def mesh_area_radii(verts, faces, percentages=PERCENTAGES):
+    """(radii [J], cumulative triangle areas [F]) of a mesh, host float64 (verts / faces: arrays or tensors):
+    r_j = sqrt(p_j A / pi) with A the total area - a disk of radius r_j covers the share p_j of a flat surface of area A."""
+    v = np.asarray(verts.cpu() if torch.is_tensor(verts) else verts, dtype=np.float64)
+    f = np.asarray(faces.cpu() if torch.is_tensor(faces) else faces, dtype=np.int64)
+    t = v[f]
+    cum = np.cumsum(0.5 * np.linalg.norm(np.cross(t[:, 1] - t[:, 0], t[:, 2] - t[:, 0]), axis=1))
+    return np.sqrt(np.asarray(percentages, dtype=np.float64) * cum[-1] / np.pi), cum
+
+
+def sample_mesh(verts: torch.Tensor, faces: torch.Tensor, S: int = 1000, seed: int = 0):
+    """S seeds on the surface (pf_mesh_sample): the face area-weighted, the position uniform inside it, from Philox-4x32-10
+    with key `seed` and counter s - seed s depends on (mesh, seed, s) only.  -> (seeds [S,3] float32, face [S] int64,
+    uniforms [S,3] float32: the three numbers behind every seed)."""
+    lib = _lib.load()
+    tris = _tris(verts, faces, "sample_mesh")
+    _, cum = mesh_area_radii(verts, faces)
+    cum_d = torch.from_numpy(cum).to(tris.device)
+    seeds = torch.empty((S, 3), dtype=torch.float32, device=tris.device)
+    uni = torch.empty((S, 3), dtype=torch.float32, device=tris.device)
+    face = torch.empty(S, dtype=torch.int32, device=tris.device)
+    _lib.check(lib.pf_mesh_sample(tris.data_ptr(), tris.shape[0], cum_d.data_ptr(), int(S), int(seed) & (2 ** 64 - 1),
+                                  seeds.data_ptr(), face.data_ptr(), uni.data_ptr(), ops._stream()), "pf_mesh_sample")
+    return seeds, face.long(), uni
+
+
+def mapped_points(points: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, face: torch.Tensor = None) -> torch.Tensor:
+    """The closest point of the mesh to every point of points [P,3] (evaluation.cpp:225-228): the closest point of the
+    triangle `point_to_mesh_distance(..., return_face=True)` finds (face [P]: that result, when the caller has it)."""
+    lib = _lib.load()
+    tris = _tris(verts, faces, "mapped_points")
+    pts = ops._f32c(points)
+    if face is None:
+        _, face = point_to_mesh_distance(pts, verts, faces, return_face=True)
+    fi = face.to(device=pts.device, dtype=torch.int32).contiguous()
+    out = torch.empty_like(pts)
+    _lib.check(lib.pf_tri_closest_points(pts.data_ptr(), pts.shape[0], tris.data_ptr(), tris.shape[0], fi.data_ptr(),
+                                         out.data_ptr(), ops._stream()), "pf_tri_closest_points")
+    return out
+
+
+def disks(mapped: torch.Tensor, seeds: torch.Tensor, radii):
+    """The points of mapped [N,3] inside the Euclidean balls of radii [J] (ascending) around seeds [S,3].
+    -> (counts [S,J] int32, (offsets [S+1] int64, member [nnz] int32, level [nnz] int32)): row s of the CSR lists the members
+    of the largest ball of seed s in ascending index, each with the smallest j whose ball holds it (pf_disk_count / _fill)."""
+    lib = _lib.load()
+    m, sd = ops._f32c(mapped), ops._f32c(seeds)
+    r, rc = _radii(radii)
+    N, S, J = m.shape[0], sd.shape[0], len(r)
+    counts = torch.empty((S, J), dtype=torch.int32, device=m.device)
+    _lib.check(lib.pf_disk_count(m.data_ptr(), N, sd.data_ptr(), S, rc, J, counts.data_ptr(), ops._stream()), "pf_disk_count")
+    offsets = torch.zeros(S + 1, dtype=torch.int64, device=m.device)
+    offsets[1:] = counts[:, J - 1].long().cumsum(0)
+    nnz = int(offsets[-1])                                       # the host sizes the buffer
+    member = torch.empty(max(nnz, 1), dtype=torch.int32, device=m.device)
+    level = torch.empty(max(nnz, 1), dtype=torch.int32, device=m.device)
+    _lib.check(lib.pf_disk_fill(m.data_ptr(), N, sd.data_ptr(), S, rc, J, offsets.data_ptr(), member.data_ptr(),
+                                level.data_ptr(), ops._stream()), "pf_disk_fill")
+    return counts, (offsets, member[:nnz], level[:nnz])
+
+
+def disk_statistics(mapped: torch.Tensor, csr, radii):
+    """(n [S,J], dis_mean [S,J]) float64 on the device of every disk of the CSR (`disks`, or `read_disk_files`): the member
+    count and the mean of (d - e)^2 / e over the members, d the distance to the nearest other member of the same disk,
+    e = sqrt(2 (pi r_j^2 / n) / 1.732) (evaluate.py:153-158).  A row's values depend on that row alone (pf_disk_uniformity)."""
+    lib = _lib.load()
+    m = ops._f32c(mapped)
+    offsets, member, level = csr
+    if not (offsets.is_cuda and member.is_cuda and level.is_cuda):
+        raise _lib.PuflowHipError("disk_statistics needs GPU tensors (no CPU fallback)")
+    r, rc = _radii(radii)
+    N, S, J = m.shape[0], offsets.shape[0] - 1, len(r)
+    offsets = offsets.long().contiguous()
+    member, level = member.int().contiguous(), level.int().contiguous()
+    nnz = member.shape[0]
+    if level.shape[0] != nnz or S < 1 or int(offsets[0]) < 0 or int(offsets[-1]) > nnz or bool((offsets[1:] < offsets[:-1]).any()):
+        raise _lib.PuflowHipError("disk_statistics: the CSR's offsets do not describe its member list")
+    if nnz and (int(member.min()) < 0 or int(member.max()) >= N or int(level.min()) < 0):
+        raise _lib.PuflowHipError(f"disk_statistics: a member index outside [0, {N}) or a negative level")
+    if nnz == 0:
+        member, level = member.new_zeros(1), level.new_zeros(1)
+    n = torch.empty((S, J), dtype=torch.float64, device=m.device)
+    dis = torch.empty((S, J), dtype=torch.float64, device=m.device)
+    _lib.check(lib.pf_disk_uniformity(m.data_ptr(), N, offsets.data_ptr(), member.data_ptr(), level.data_ptr(), S, rc, J,
+                                      n.data_ptr(), dis.data_ptr(), ops._stream()), "pf_disk_uniformity")
+    return n, dis
+
+
+def uniformity_from_statistics(n, dis_mean, N: int, percentages=None) -> np.ndarray:
+    """The host finish in float64 (evaluate.py:132-162): coverage = (n - p_j N)^2 / (p_j N); disks with fewer than 5 members
+    are left out; uniform_j = the mean over the kept disks of float32(coverage dis_mean) - nan when none is kept."""
+    n = np.asarray(n.cpu() if torch.is_tensor(n) else n, dtype=np.float64)
+    d = np.asarray(dis_mean.cpu() if torch.is_tensor(dis_mean) else dis_mean, dtype=np.float64)
+    J = n.shape[1]
+    p = np.asarray(PERCENTAGES[:J] if percentages is None else percentages, dtype=np.float64)
+    if len(p) != J:
+        raise ValueError(f"{J} radii and {len(p)} percentages")
+    out = np.full(J, np.nan)
+    for j in range(J):
+        keep = n[:, j] >= 5
+        if keep.any():
+            expect = p[j] * N
+            out[j] = np.mean(((n[keep, j] - expect) ** 2 / expect * d[keep, j]).astype(np.float32))
+    return out
+
+
+def uniformity(mapped: torch.Tensor, csr, radii, percentages=None) -> np.ndarray:
+    """uniform_j [J] (host float64) of the mapped points and their disks: `disk_statistics` and its host finish."""
+    n, dis = disk_statistics(mapped, csr, radii)
+    return uniformity_from_statistics(n, dis, mapped.shape[0], percentages)
+
+
+# the three files of evaluate.py:256-262 (what the reference's CGAL binary was meant to write)
+def write_disk_files(prefix: str, points, dist, mapped, csr, radii) -> None:
+    """`<prefix>_disk_idx.txt`: line s J + j = `count:idx idx ...` (the members of disk (s, j), ascending);
+    `<prefix>_radius.txt`: the J radii; `<prefix>_point2mesh_distance.txt`: `x y z d mx my mz` per point, the mapped point
+    in columns 4-6.  %.9g: float32 values read back exactly."""
+    host = lambda a: np.asarray(a.cpu() if torch.is_tensor(a) else a)      # noqa: E731
+    offsets, member, level = (host(a) for a in csr)
+    r = np.atleast_1d(np.asarray(radii, dtype=np.float64))
+    with open(prefix + "_disk_idx.txt", "w") as f:
+        for s in range(len(offsets) - 1):
+            mem, lev = member[offsets[s]:offsets[s + 1]], level[offsets[s]:offsets[s + 1]]
+            for j in range(len(r)):
+                idx = mem[lev <= j]
+                f.write("%d:%s\n" % (len(idx), " ".join(map(str, idx.tolist()))))
+    with open(prefix + "_radius.txt", "w") as f:
+        f.write("".join("%.17g\n" % x for x in r))
+    rows = np.concatenate([host(points).reshape(-1, 3), host(dist).reshape(-1, 1), host(mapped).reshape(-1, 3)], axis=1)
+    with open(prefix + "_point2mesh_distance.txt", "w") as f:
+        f.write("".join(("%.9g %.9g %.9g %.9g %.9g %.9g %.9g\n" % tuple(row)) for row in rows.tolist()))
+
+
+def read_disk_files(prefix: str):
+    """-> (mapped [N,3] float32, radii [J] float64, (offsets, member, level) as host arrays) of the three files, whoever wrote
+    them.  The disks of a seed need not be nested there: a member's level is the first j that lists it, and the row holds the
+    union of the seed's J lines - a file whose later disks drop members of earlier ones is refused."""
+    mapped = np.atleast_2d(np.loadtxt(prefix + "_point2mesh_distance.txt", dtype=np.float32))[:, 4:7]
+    radii = np.atleast_1d(np.loadtxt(prefix + "_radius.txt", dtype=np.float64))
+    J = len(radii)
+    with open(prefix + "_disk_idx.txt") as f:
+        lines = [ln for ln in f.read().split("\n") if ln.strip()]
+    if len(lines) % J:
+        raise ValueError(f"{prefix}_disk_idx.txt: {len(lines)} lines for {J} radii")
+    offsets, member, level = [0], [], []
+    for s in range(len(lines) // J):
+        seen = np.zeros(0, dtype=np.int64)
+        for j in range(J):
+            idx = np.array(lines[s * J + j].split(":", 1)[1].split(), dtype=np.int64)
+            new = np.setdiff1d(idx, seen)
+            if len(idx) != len(seen) + len(new) or len(np.unique(idx)) != len(idx):
+                raise ValueError(f"{prefix}_disk_idx.txt: the disks of seed {s} are not nested sets")
+            member.append(new)
+            level.append(np.full(len(new), j, dtype=np.int32))
+            seen = idx
+        offsets.append(offsets[-1] + len(seen))
+    member = np.concatenate(member).astype(np.int32) if member else np.zeros(0, np.int32)
+    level = np.concatenate(level) if level else np.zeros(0, np.int32)
+    out_m, out_l = np.empty_like(member), np.empty_like(level)
+    for s in range(len(offsets) - 1):                             # ascending index inside every row, like `disks`
+        a, b = offsets[s], offsets[s + 1]
+        o = np.argsort(member[a:b], kind="stable")
+        out_m[a:b], out_l[a:b] = member[a:b][o], level[a:b][o]
+    return np.ascontiguousarray(mapped), radii, (np.array(offsets, dtype=np.int64), out_m, out_l)
