@@ -842,6 +842,67 @@ int pf_disk_tile(void);
 int pf_disk_uniformity(const float* mapped, int N, const long long* offsets, const int* member, const int* level, int S,
                        const double* radii, int J, double* out_n, double* out_dis, void* stream);
 
+/* ---- Poisson-disk point sets by weighted sample elimination (csrc/poisson.hip; Yuksel 2015 - the reference has no counterpart:
+ * its training patches and test clouds came from PU-GAN's Meshlab preparation) ------------------------------------------------
+ * A pool is s candidate points on a surface of area A, thinned to exactly m.  B pools are stored back to back as one
+ * [sum s, 3] array, like the ragged patch operators, and under their contract: every pool gets, bit for bit, what it gets alone.
+ * Parameters (HOST, double, rounded to fp32 once): with t = m / s,
+ *   r_max = sqrt(A / (2 sqrt(3) m)),  r_min = r_max (1 - t sqrt(t)) 0.65,
+ *   consts = { R2 = fp32((2 r_max)^2), inv = fp32(1 / (2 r_max)), lo = fp32(2 r_min) }.
+ * pf_poisson_params: one pool's values (all outputs nullable); SHAPE unless 1 <= m <= s and 0 < A < 1e30.
+ * pf_poisson_pools:  the table the device entry points read (a HOST array the caller uploads): pool b's first candidate
+ *   (off), first output slot (out_off), constants, and path = 1 when pf_poisson_eliminate_wg takes it (s <= PF_POISSON_WG_MAX and
+ *   flags without PF_POISSON_NO_WG), 0 when pf_poisson_rounds does.  Both paths return the same indices. */
+#define PF_POISSON_WG_MAX 8192
+#define PF_POISSON_MAX_TOTAL (1 << 30)
+#define PF_POISSON_NO_WG 1
+#define PF_POISSON_ST_DEGREE 1  /* a candidate has 65535 neighbours or more (the pool is far denser than its radius assumes) */
+#define PF_POISSON_ST_WEIGHT 2  /* a weight left 32 bits: the kept set is not the sequential one                            */
+typedef struct PfPoissonPool {
+    int off, s, m, out_off;
+    float R2, inv, lo;
+    int path;
+} PfPoissonPool;
+typedef struct PfPoissonState { /* per pool, on the device; zeroed by pf_poisson_begin */
+    unsigned long long tau;     /* the phase's threshold key: (w << 32) | (0xffffffff - index)                              */
+    int k, done, phases, rounds, alive, pad;
+} PfPoissonState;
+int pf_poisson_params(double area, int s, int m, double* r_max, double* r_min, float* consts);
+int pf_poisson_pools(const int* s, const int* m, const double* area, int B, int flags, PfPoissonPool* pools);
+
+/* The neighbour graph.  i ~ j (i != j, same pool) when d2 < R2 with d2 = ((dx dx) + (dy dy)) + (dz dz), unfused fp32 (the kNN
+ * kernels' rule).  Edge weight: d = sqrt(d2) correctly rounded, x = max(1 - max(d, lo) inv, 0), every operation a separate
+ * fp32 rounding, x^8 by three squarings, q_ij = (uint32) rint(x^8 65536); w_i = sum_j q_ij, an integer.
+ *   pf_poisson_degree: deg [sum s] int32, the neighbours of every candidate;
+ *   pf_poisson_graph:  row i of the CSR, nbr / q [offsets[i], offsets[i+1]) (offsets [sum s + 1] int64 on the device, the
+ *                      running sum of deg): the neighbours' indices INSIDE THE POOL, ascending, and their q; w [sum s] uint32.
+ *                      A row shorter than its degree is filled and not overrun.
+ * pools: the DEVICE copy of pf_poisson_pools' table, max_s / total: the largest and the summed s.  One thread per candidate
+ * sweeps its pool through LDS tiles (s^2 pair tests per pool).  status: one int32 the kernels only OR PF_POISSON_ST_* into. */
+int pf_poisson_degree(const float* pts, const PfPoissonPool* pools, int B, int max_s, long long total, int* deg, int* status,
+                      void* stream);
+int pf_poisson_graph(const float* pts, const PfPoissonPool* pools, int B, int max_s, long long total, const long long* offsets,
+                     int* nbr, int* q, unsigned* w, int* status, void* stream);
+
+/* The elimination.  Its result is the alive set of the sequential process "while more than m are alive: remove the alive i
+ * with the largest key (w_i, smaller index first), subtract q_ij from every alive neighbour j" - ascending indices inside the
+ * pool, keep [out_off, out_off + m).  It is computed in phases and rounds instead (csrc/poisson.hip's head):
+ * a phase fixes tau = the (k+1)-th largest alive key, k = alive - m; a round removes at once every alive candidate above tau
+ * and above all its alive neighbours; the phase ends when no alive key exceeds tau.  Integer atomics only, no grid barrier.
+ *   pf_poisson_begin:        state [sum s] int32 = alive, st [B] zeroed.  w is consumed by the elimination.
+ *   pf_poisson_eliminate_wg: the pools of path 1, one workgroup per pool, every round inside one launch.
+ *   pf_poisson_rounds:       rounds round0 .. round0 + n_rounds - 1 of the pools of path 0, three launches a round (the pool's
+ *                            bookkeeping and radix select of tau in one workgroup; pick; apply).  *unfinished (device int32) is
+ *                            set to r + 1 by round r when a pool still had work in it: the caller reads it after a batch and
+ *                            stops when it is not round0 + n_rounds.  Rounds after a pool is done cost it nothing but the launch.
+ * st[b].phases / .rounds count what pool b took. */
+int pf_poisson_begin(const PfPoissonPool* pools, int B, int max_s, long long total, int* state, PfPoissonState* st, void* stream);
+int pf_poisson_eliminate_wg(const PfPoissonPool* pools, int B, const long long* offsets, const int* nbr, const int* q, unsigned* w,
+                            int* state, PfPoissonState* st, int* keep, void* stream);
+int pf_poisson_rounds(const PfPoissonPool* pools, int B, int max_s, long long total, const long long* offsets, const int* nbr,
+                      const int* q, unsigned* w, int* state, PfPoissonState* st, int* keep, int round0, int n_rounds,
+                      int* unfinished, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -63,6 +63,12 @@ class PfFlowChain(ctypes.Structure):
                 ("ws", c_void_p), ("ws_floats", c_longlong), ("dev_descs", c_void_p), ("dz1s", c_void_p), ("img_ready", c_int)]
 
 
+class PfPoissonPool(ctypes.Structure):
+    """include/puflow_hip.h: PfPoissonPool (one pool of the sample elimination, as the kernels read it)."""
+    _fields_ = [("off", c_int), ("s", c_int), ("m", c_int), ("out_off", c_int), ("R2", c_float), ("inv", c_float), ("lo", c_float),
+                ("path", c_int)]
+
+
 # name -> (restype, argtypes); must list every symbol declared in include/puflow_hip.h
 SIGNATURES = {
     "pf_version": (c_int, []),
@@ -234,6 +240,16 @@ SIGNATURES = {
     "pf_disk_tile": (c_int, []),
     "pf_disk_uniformity": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, POINTER(c_double), c_int, c_void_p,
                                    c_void_p, c_void_p]),
+    "pf_poisson_params": (c_int, [c_double, c_int, c_int, POINTER(c_double), POINTER(c_double), POINTER(c_float)]),
+    "pf_poisson_pools": (c_int, [POINTER(c_int), POINTER(c_int), POINTER(c_double), c_int, c_int, c_void_p]),
+    "pf_poisson_degree": (c_int, [c_void_p, c_void_p, c_int, c_int, c_longlong, c_void_p, c_void_p, c_void_p]),
+    "pf_poisson_graph": (c_int, [c_void_p, c_void_p, c_int, c_int, c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p]),
+    "pf_poisson_begin": (c_int, [c_void_p, c_int, c_int, c_longlong, c_void_p, c_void_p, c_void_p]),
+    "pf_poisson_eliminate_wg": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p]),
+    "pf_poisson_rounds": (c_int, [c_void_p, c_int, c_int, c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_int, c_int, c_void_p, c_void_p]),
 }
 
 
