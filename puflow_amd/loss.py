@@ -2,7 +2,6 @@
 metric/emd/emd_module.py:31-79), backed by the HIP library."""
 from __future__ import annotations
 
-import os
 import torch
 import torch.nn as nn
 from torch import Tensor
@@ -118,15 +117,9 @@ class ChamferCUDA(nn.Module):
                                     point_reduction="mean")
 
 
-_GRAD_FUSED = os.environ.get("PF_LOSS_GRAD_FUSED", "1") != "0"   # the loss head's backward in two launches (pf_pugan_grad); "0": four
-
-
 def train_ops_deterministic() -> bool:
     from . import train_ops
     return train_ops.deterministic()
-
-
-_CD_SIDE = os.environ.get("PF_LOSS_CD_SIDE", "1") != "0"      # Chamfer's nearest neighbours beside the EMD auction (side stream)
 
 
 class PuganLossFn(Function):
@@ -160,7 +153,7 @@ class PuganLossFn(Function):
         per = None
         i1 = i2 = torch.empty((0,), dtype=torch.int32, device=dev)
         cd_side = None
-        if w_cd != 0.0 and _CD_SIDE and pred.is_cuda:
+        if w_cd != 0.0 and pred.is_cuda:
             from .train_ops import _side_stream
             cd_side = _side_stream(dev)
             cd_side.wait_stream(torch.cuda.current_stream())
@@ -201,7 +194,7 @@ class PuganLossFn(Function):
         if g is None:                                      # (set_materialize_grads(False): only `terms` was used)
             return (None,) * 8
         g1d = g.contiguous().float().view(1)
-        if _GRAD_FUSED and not ctx.needs_input_grad[1] and not train_ops_deterministic():
+        if not ctx.needs_input_grad[1] and not train_ops_deterministic():
             # the prediction's gradient in two launches: own terms (EMD + first Chamfer direction) stored, the second direction
             # scattered onto them (pf_pugan_grad) - it was four, all on the chain between the auction and the flow's backward
             dlogp = torch.empty((1,), **f32)

@@ -13,12 +13,13 @@ Activations are channels-last [rows, C] fp32 (rows = points or edges).
 """
 from __future__ import annotations
 
+import contextlib
+import contextvars
 import ctypes
+import math
 import os
 import sys
-
-import math
-from typing import List, Tuple
+from typing import List, NamedTuple, Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -45,6 +46,10 @@ def _ws(dev, n: int) -> Tensor:
     return t
 
 
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
 # Matrix-pipe arithmetic of the training GEMMs: "f32" (default) = every GEMM on the f32 MFMA (bit-exact fp32 fma chains);
 # "split" = forward GEMMs as split-fp16 products (3 fp16 MFMAs per 32-deep step), GEMMs with a gradient operand as
 # split-bf16 (6 bf16 MFMAs, fp32 exponent range) - csrc/train_ops.hip gemm_split_kernel.  Measured at 32 x (256 -> 1024):
@@ -52,6 +57,16 @@ def _ws(dev, n: int) -> Tensor:
 # profiles/r2_train), so the exact arithmetic stays the default; the gradient tests pass in both modes.
 _GEMM_MODE = os.environ.get("PF_TRAIN_GEMM", "f32")
 ARITH_FWD, ARITH_BWD = (2, 3) if _GEMM_MODE == "split" else (0, 0)
+
+
+def _per_stream(cache: dict, dev, make) -> Tensor:
+    """cache[(device, current stream)], made by `make()` on first use: the one look-up behind _stat, _sync_words, _sync_sums,
+    _counter and _desc_buf.  Each keeps its own dict - the tests and check_persist_status index them by name."""
+    key = (dev, _stream())
+    t = cache.get(key)
+    if t is None:
+        t = cache[key] = make()
+    return t
 
 
 _STAT = {}
@@ -72,12 +87,7 @@ def _zeros_kept(n: int, dtype, dev) -> Tensor:
 
 def _stat(dev) -> Tensor:
     """4097 doubles (PF_TRAIN_STAT_DOUBLES) per (device, stream): the column-statistics accumulators of the fused training kernels."""
-    key = (dev, _stream())
-    t = _STAT.get(key)
-    if t is None:
-        t = _zeros_kept(4097, torch.float64, dev)
-        _STAT[key] = t
-    return t
+    return _per_stream(_STAT, dev, lambda: _zeros_kept(4097, torch.float64, dev))
 
 
 _SYNCW = {}
@@ -90,12 +100,7 @@ _PERSIST = os.environ.get("PF_TRAIN_PERSIST", "1") != "0"
 def _sync_words(dev) -> Tensor:
     """4 zero-initialised 32-bit words per (device, stream): arrivals / generation / exits of the persistent kernels' grid
     barriers (left zero by every launch) and a sticky status word (check_persist_status)."""
-    key = (dev, _stream())
-    t = _SYNCW.get(key)
-    if t is None:
-        t = _zeros_kept(4, torch.int32, dev)
-        _SYNCW[key] = t
-    return t
+    return _per_stream(_SYNCW, dev, lambda: _zeros_kept(4, torch.int32, dev))
 
 
 def check_persist_status(device=None) -> None:
@@ -123,11 +128,7 @@ _SYNC_CB_T = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ct
 
 
 def _sync_sums(dev) -> Tensor:
-    key = (dev, _stream())
-    t = _SYNC_SUMS.get(key)
-    if t is None:
-        t = _SYNC_SUMS[key] = _zeros_kept(2 * 128 + 1, torch.float64, dev)
-    return t
+    return _per_stream(_SYNC_SUMS, dev, lambda: _zeros_kept(2 * 128 + 1, torch.float64, dev))
 
 
 def _sync_cb_impl(user, sums, n, stream):
@@ -301,9 +302,6 @@ class SyncBnLreluFn(Function):
 # BatchNorm statistics over all ranks: an ARGUMENT of the forward, not process state - `forward_train` takes it from the
 # module (`PointInterpFlow.sync_batchnorm`, set from `cfg.sync_batchnorm`) and holds it in this context variable for the
 # duration of that call; `sync_bn(True)` is the same scope for callers of the single ops (tests)
-import contextlib
-import contextvars
-
 _SYNC_BN: contextvars.ContextVar = contextvars.ContextVar("puflow_sync_bn", default=False)
 
 
@@ -336,8 +334,8 @@ def deterministic() -> bool:
 
 # Weight gradients beside the backward chain (csrc/api.hip pf_train_set_dw_stream) - an opt-in that did NOT pay at the bench
 # shape.  The backward of a unit produces the gradient of its input - which the unit before it waits for - and the gradients of
-# its weights, which nothing reads before the optimizer: with the switch on (`net.train_dw_stream = True` / cfg.dw_stream, or
-# PF_TRAIN_DW_STREAM=1; =0 forces it off) the split-K weight-gradient kernels and their reductions of the EdgeConv units and the
+# its weights, which nothing reads before the optimizer: with the switch on (`net.train_dw_stream = True` / cfg.dw_stream)
+# the split-K weight-gradient kernels and their reductions of the EdgeConv units and the
 # conditioner / merge MLPs go to one more stream (a third parallel branch of the captured step), ~0.9 ms of the main chain's
 # ~3.9 ms of kernels at 32 x (256 -> 1024).  Their workspaces come from that stream's own pool, every buffer they read is kept
 # alive until the join, and the join - the calling stream waits for the weight-gradient stream - is an autograd end-of-pass
@@ -347,7 +345,6 @@ def deterministic() -> bool:
 # by the SUM of its kernels' work (each of them fills the chip), not by the length of the dependent chain, and kernels that share
 # the chip slow each other down by more than the chain gets shorter.  (The flow chains stay on the calling stream in any case:
 # f and g share their parameters, so autograd adds their gradients there before any join.)
-_DW_ENV = os.environ.get("PF_TRAIN_DW_STREAM")
 _DW_NET = False
 _DW_STREAMS = {}
 _DW_PASS = {"pending": False, "keep": [], "streams": []}
@@ -365,7 +362,7 @@ def _dw_join() -> None:
 def _dw_begin(dev, *keep):
     """The weight-gradient stream for one backward call on `dev`, or None (switch off, SyncBN, not inside an autograd pass).
     `keep`: tensors the side kernels read - held until the join so that the allocator cannot hand their memory to the main chain."""
-    if not (_DW_ENV == "1" or (_DW_ENV is None and _DW_NET)) or _sync_bn_active():
+    if not _DW_NET or _sync_bn_active():
         return None
     # one join per autograd pass, keyed by the pass's id: a pass that died with an exception must not leave the next one without
     tid = torch._C._current_graph_task_id() if hasattr(torch._C, "_current_graph_task_id") else 0
@@ -773,25 +770,6 @@ class BatchSumFn(Function):
 # ----------------------------------------------------------------------------------------------------
 # train-mode network forward (differentiable)
 # ----------------------------------------------------------------------------------------------------
-_UNFOLDED = os.environ.get("PF_TRAIN_FOLD", "1") == "0"
-
-
-def edgeconv_train_unfolded(p, x: Tensor, idx: Tensor, pooling: bool = True) -> Tensor:
-    """FeatureExtractUnit in train mode, the reference formulation on the materialised edge feature
-    (interpflow.py:223-248); kept for A/B checks of the folded version below (PF_TRAIN_FOLD=0)."""
-    B, N, _ = x.shape
-    K = idx.shape[-1]
-    f = EdgeFeatureFn.apply(x, idx)
-    for seq in p.convs:
-        conv, bn = seq[0], seq[1]
-        y = linear(f, conv.weight, conv.bias)
-        f = torch.cat([f, bn_lrelu(y, bn, 0.05)], dim=1)
-    y = linear(f, p.conv_out.weight, p.conv_out.bias)
-    if not pooling:
-        return y
-    return MaxPoolKFn.apply(y, K).view(B, N, -1)
-
-
 def edgeconv_train(p, x: Tensor, idx: Tensor, pooling: bool = True, csr=None, persistent: bool = False, prefold=None,
                    tap: bool = False) -> Tensor:
     """FeatureExtractUnit in train mode (interpflow.py:234-248). x [B,N,C]; returns [B,N,odim] or [B*N*K, odim].
@@ -802,8 +780,6 @@ def edgeconv_train(p, x: Tensor, idx: Tensor, pooling: bool = True, csr=None, pe
     repeat / gather / add; only the growth-feature columns run per edge.  5.4x fewer MACs at C = 128 and the
     [B*N*K, 3C] edge tensor is never materialised.  Gradients reach W through the slices, x through the point GEMM
     and the gather's scatter-add - exact algebra, same results up to fp32 rounding."""
-    if _UNFOLDED:
-        return edgeconv_train_unfolded(p, x, idx, pooling)
     if _FUSED and _ec_fused_supported(p, x, idx, pooling):
         return edgeconv_train_fused(p, x, idx, pooling, csr, persistent, prefold=prefold, tap=tap)   # tap: -> (out, x again)
     B, N, C = x.shape
@@ -832,6 +808,25 @@ def edgeconv_train(p, x: Tensor, idx: Tensor, pooling: bool = True, csr=None, pe
     return MaxPoolKFn.apply(y.contiguous(), K).view(B, N, -1)
 
 
+class EcCfg(NamedTuple):                    # what EdgeConvUnitFn takes besides tensors with a gradient (edgeconv_train_fused)
+    K: int
+    growth: int
+    nconv: int
+    odim: int
+    pooling: bool
+    slope: float
+    eps: float
+    momentum: float
+    run_means: list
+    run_vars: list
+    csr: Optional[tuple] = None       # (off, edge) of knn_csr(idx): dQ as a gather, no float atomics
+    persistent: bool = False          # the forward / the dense block's backward as one persistent launch where the library can
+    sync_bn: bool = False             # statistics over all ranks (fixed at forward time: the backward runs after the sync_bn() scope)
+    dw_inline: bool = False           # conv_out's gradient is consumed INSIDE the pass (FoldWuFn): no weight-gradient stream
+    prefold: Optional[tuple] = None   # (Wpq, bpq) folded by ec_prefold for this forward
+    tap: bool = False                 # also return x, for x's other consumer (see forward)
+
+
 class EdgeConvUnitFn(Function):
     """One FeatureExtractUnit in train mode as ~11 launches forward / ~20 backward (csrc/train_ec_fwd.hip, csrc/train_fused.hip: the folded edge
     feature, BatchNorm applied on load by the consumer of each layer, statistics in the GEMM epilogues, max-pool in the
@@ -840,24 +835,22 @@ class EdgeConvUnitFn(Function):
 
     @staticmethod
     def _desc(x, idx, cfg, Ws, bs, gammas, betas):
-        K, g, nconv, odim, pooling, slope, eps, momentum, rmeans, rvars = cfg[:10]
         B, N, C = x.shape
         d = _lib.PfEcTrain()
-        d.B, d.N, d.K, d.C, d.growth, d.nconv, d.odim, d.pooling = B, N, K, C, g, nconv, odim, int(pooling)
-        d.slope, d.eps, d.momentum = slope, eps, momentum
+        d.B, d.N, d.K, d.C, d.growth, d.nconv, d.odim, d.pooling = B, N, cfg.K, C, cfg.growth, cfg.nconv, cfg.odim, int(cfg.pooling)
+        d.slope, d.eps, d.momentum = cfg.slope, cfg.eps, cfg.momentum
         d.x, d.idx = x.data_ptr(), idx.data_ptr()
-        for t in range(nconv + 1):
+        for t in range(cfg.nconv + 1):
             d.W[t], d.bias[t] = Ws[t].data_ptr(), bs[t].data_ptr()
-        for t in range(nconv):
+        for t in range(cfg.nconv):
             d.gamma[t], d.beta[t] = gammas[t].data_ptr(), betas[t].data_ptr()
-            d.run_mean[t] = rmeans[t].data_ptr() if rmeans[t] is not None else None
-            d.run_var[t] = rvars[t].data_ptr() if rvars[t] is not None else None
+            d.run_mean[t], d.run_var[t] = _ptr(cfg.run_means[t]), _ptr(cfg.run_vars[t])
         return d
 
     @staticmethod
     def forward(ctx, x, idx, cfg, *params):
         lib = _lib.load()
-        K, g, nconv, odim, pooling = cfg[:5]
+        K, g, nconv, odim, pooling = cfg.K, cfg.growth, cfg.nconv, cfg.odim, cfg.pooling
         nc1 = nconv + 1
         Ws = [w.contiguous() for w in params[:nc1]]
         bs = [b.contiguous() for b in params[nc1:2 * nc1]]
@@ -870,7 +863,7 @@ class EdgeConvUnitFn(Function):
         S = GT + odim
         dev = x.device
         f32 = dict(dtype=torch.float32, device=dev)
-        pre = cfg[14] if len(cfg) > 14 else None              # (Wpq, bpq) folded by ec_prefold for this forward
+        pre = cfg.prefold
         if pre is not None and tuple(pre[0].shape) != (2 * S, C):
             raise ValueError("EdgeConvUnitFn: prefolded weights of another unit")
         Wpq, bpq = pre if pre is not None else (torch.empty((2 * S, C), **f32), torch.empty((2 * S,), **f32))
@@ -887,20 +880,20 @@ class EdgeConvUnitFn(Function):
         ws = _ws(dev, need)
         d.ws, d.ws_floats = ws.data_ptr(), ws.numel()
         d.stat = _stat(dev).data_ptr()
-        if len(cfg) > 11 and cfg[11] and not _DET:            # the whole forward as one persistent launch where the library can
+        if cfg.persistent and not _DET:                       # the whole forward as one persistent launch where the library can
             d.flags, d.sync = 1, _sync_words(dev).data_ptr()
         if _DET:
             d.flags |= 2                                      # PF_TRAIN_DETERMINISTIC
         if pre is not None:
             d.flags |= 4                                      # PF_EC_PREFOLDED
-        if len(cfg) > 12 and cfg[12]:                         # SyncBN: statistics over all ranks (fixed at forward time: the
-            _attach_sync(d, dev)                              # backward runs after the sync_bn() scope has ended)
+        if cfg.sync_bn:
+            _attach_sync(d, dev)
         _lib.check(lib.pf_ec_train_fwd(ctypes.byref(d), _stream()), "pf_ec_train_fwd")
         ctx.cfg = cfg
         ctx.has_arg = pooling
         ctx.save_for_backward(x, idx, Wpq, PQ, Y, aff, *(() if arg is None else (arg,)), *Ws, *gammas)
         res = out.view(B, N, odim) if pooling else out
-        if len(cfg) > 15 and cfg[15]:
+        if cfg.tap:
             # tap: x again, as a second output for x's OTHER consumer - that consumer's gradient then arrives HERE (dtap) and is
             # added in the epilogue of the dx GEMM (PfEcTrain.dx_add) instead of by a launch of autograd's own
             return res, x_in.view_as(x_in)
@@ -910,7 +903,7 @@ class EdgeConvUnitFn(Function):
     def backward(ctx, dout, dtap=None):
         lib = _lib.load()
         cfg = ctx.cfg
-        K, g, nconv, odim, pooling = cfg[:5]
+        K, g, nconv, odim = cfg.K, cfg.growth, cfg.nconv, cfg.odim
         nc1 = nconv + 1
         sv = list(ctx.saved_tensors)
         x, idx, Wpq, PQ, Y, aff = sv[:6]
@@ -949,16 +942,15 @@ class EdgeConvUnitFn(Function):
         ws = _ws(dev, need)
         d.ws, d.ws_floats = ws.data_ptr(), ws.numel()
         d.stat = _stat(dev).data_ptr()
-        csr = cfg[10] if len(cfg) > 10 else None
-        if csr is not None:                                   # transposed neighbour lists: dQ as a gather, no float atomics
-            d.csr_off, d.csr_edge = csr[0].data_ptr(), csr[1].data_ptr()
-        if len(cfg) > 11 and cfg[11] and not _DET:            # the dense block's backward as one persistent launch (see forward)
+        if cfg.csr is not None:                               # transposed neighbour lists: dQ as a gather, no float atomics
+            d.csr_off, d.csr_edge = cfg.csr[0].data_ptr(), cfg.csr[1].data_ptr()
+        if cfg.persistent and not _DET:                       # the dense block's backward as one persistent launch (see forward)
             d.flags, d.sync = 1, _sync_words(dev).data_ptr()
         if _DET:
             d.flags |= 2
-        if len(cfg) > 12 and cfg[12]:
+        if cfg.sync_bn:
             _attach_sync(d, dev)
-        dwst = None if (len(cfg) > 13 and cfg[13]) else _dw_begin(dev, sv, dout, dA, dPQ, coef, dWpq, ws)
+        dwst = None if cfg.dw_inline else _dw_begin(dev, sv, dout, dA, dPQ, coef, dWpq, ws)
         if dwst is not None:                                  # weight gradients on their own stream, with their own workspace
             ws2 = _dw_ws(dwst, dev, need)
             d.ws_dw, d.ws_dw_floats = ws2.data_ptr(), ws2.numel()
@@ -973,16 +965,7 @@ _COUNTER = {}
 def _counter(dev) -> Tensor:
     """One zero-initialised 32-bit word per (device, stream): the arrival counter of the in-kernel grid reductions (reset by
     the workgroup that uses it last)."""
-    key = (dev, _stream())
-    t = _COUNTER.get(key)
-    if t is None:
-        t = torch.zeros(1, dtype=torch.int32, device=dev)
-        _COUNTER[key] = t
-    return t
-
-
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
+    return _per_stream(_COUNTER, dev, lambda: torch.zeros(1, dtype=torch.int32, device=dev))
 
 
 class FlowParamsFn(Function):
@@ -1117,7 +1100,6 @@ class InjectInv2Fn(Function):
 
 _FC_IMG = {}                     # device -> (key, image) of the last flow-chain forward (FlowChainFn.forward)
 _FC_SCOPE = [0, 0]               # [id of the forward_train call in progress (0: none), calls so far]
-_IMG_SHARE = os.environ.get("PF_TRAIN_IMG_SHARE", "1") != "0"
 
 
 class FlowChainFn(Function):
@@ -1181,7 +1163,7 @@ class FlowChainFn(Function):
         # packed weights (the conditioner nets' LDS images), kept for the backward.  They do not depend on the direction: the g chain
         # of a forward takes the image the f chain packed from the same parameters on the same stream (one pack launch fewer)
         key = (_FC_SCOPE[0], tuple(int(c) for c in ccs), _stream(), tuple((t.data_ptr(), t._version) for t in prm))
-        cached = _FC_IMG.get(dev) if (_IMG_SHARE and _FC_SCOPE[0]) else None      # only inside one forward_train call
+        cached = _FC_IMG.get(dev) if _FC_SCOPE[0] else None      # only inside one forward_train call
         if cached is not None and cached[0] == key:
             img = cached[1]
             d.img_ready = 1
@@ -1231,7 +1213,7 @@ class FlowChainFn(Function):
         dob = torch.empty((nb, rows, 2), **f32)
         d.dz1, d.dz2, d.dob = dz[0].data_ptr(), dz[1].data_ptr(), dob.data_ptr()
         dzs = None
-        if R > 1 and _DZSUM:
+        if R > 1:
             # the first hidden layer's gradient summed over the R rows that share a conditioning row: the weight-gradient launch
             # then runs that layer's conditioning columns (cc of cc + td) over rows / R summed rows (PF_MLP_DW_DZSUM)
             dzs = torch.empty((nb, T, 64), **f32)
@@ -1264,10 +1246,6 @@ class FlowChainFn(Function):
         _lib.check(lib.pf_flowchain_bwd(ctypes.byref(d), _stream()), "pf_flowchain_bwd")
         grads = [g.view(shp) for g, shp in zip(gp, pshapes)]
         return (None, None, None, None, dx, dcflat, dst, None, *grads)
-
-
-_DZSUM = os.environ.get("PF_TRAIN_DZSUM", "1") != "0"         # g chain: conditioner weight gradients from replica-summed dz (FlowChainFn.backward)
-_FANOUT = os.environ.get("PF_TRAIN_FANOUT", "1") != "0"       # gradients of the flattened conditioning features summed in one launch
 
 
 class FanoutFn(Function):
@@ -1506,6 +1484,16 @@ class FoldWuFn(Function):
         return dW0, db0, dW6, db6, dWout, dbout
 
 
+class BnMlpCfg(NamedTuple):                 # what BnMlpFn takes besides tensors with a gradient (built by bnmlp_fused)
+    slope: float
+    eps: float
+    momentum: float
+    run_means: list
+    run_vars: list
+    sync_bn: bool = False
+    sum_inputs: bool = False          # PF_BNMLP_SUM_INPUTS: y[0] = xa + xb
+
+
 class BnMlpFn(Function):
     """[Conv2d 1x1 + BatchNorm2d(train) + LeakyReLU] x 2 + Conv2d 1x1 on rows (DistanceEncoder / WeightEstimationUnit,
     interpflow.py:85-151) on cat[xa, xb] without building it: 3-4 launches forward, ~10 backward (csrc/train_bnmlp.hip).
@@ -1513,21 +1501,19 @@ class BnMlpFn(Function):
 
     @staticmethod
     def _desc(xa, xb, cfg, Ws):
-        slope, eps, momentum, rmeans, rvars = cfg[:5]
         d = _lib.PfBnMlpTrain()
         d.rows, d.nl = xa.shape[0], len(Ws)
         d.kin0a, d.kin0b = xa.shape[1], (xb.shape[1] if xb is not None else 0)
         for l, w in enumerate(Ws):
             d.width[l] = w.shape[0]
             d.W[l] = w.data_ptr()
-        d.slope, d.eps, d.momentum = slope, eps, momentum
+        d.slope, d.eps, d.momentum = cfg.slope, cfg.eps, cfg.momentum
         d.xa, d.xb = xa.data_ptr(), _ptr(xb)
         return d
 
     @staticmethod
     def forward(ctx, xa, xb, cfg, *prm):
         lib = _lib.load()
-        slope, eps, momentum, rmeans, rvars = cfg[:5]
         xa = xa.contiguous()
         xb = xb.contiguous() if xb is not None else None
         Ws = [w.contiguous() for w in prm[0:6:2]]
@@ -1542,10 +1528,10 @@ class BnMlpFn(Function):
             d.b[l], d.y[l] = bs[l].data_ptr(), ys[l].data_ptr()
         for l in range(2):
             d.gamma[l], d.beta[l], d.aff[l] = gb[2 * l].data_ptr(), gb[2 * l + 1].data_ptr(), affs[l].data_ptr()
-            d.run_mean[l], d.run_var[l] = _ptr(rmeans[l]), _ptr(rvars[l])
+            d.run_mean[l], d.run_var[l] = _ptr(cfg.run_means[l]), _ptr(cfg.run_vars[l])
         d.stat = _stat(dev).data_ptr()
-        d.flags = (2 if _DET else 0) | (4 if (len(cfg) > 6 and cfg[6]) else 0)      # 4 = PF_BNMLP_SUM_INPUTS: y[0] = xa + xb
-        if len(cfg) > 5 and cfg[5]:
+        d.flags = (2 if _DET else 0) | (4 if cfg.sum_inputs else 0)
+        if cfg.sync_bn:
             _attach_sync(d, dev)
         _lib.check(lib.pf_bnmlp_train_fwd(ctypes.byref(d), _stream()), "pf_bnmlp_train_fwd")
         ctx.cfg, ctx.has_b = cfg, xb is not None
@@ -1583,9 +1569,9 @@ class BnMlpFn(Function):
         ws = _ws(dev, need)
         d.ws, d.ws_floats = ws.data_ptr(), ws.numel()
         d.stat = _stat(dev).data_ptr()
-        sum_in = len(ctx.cfg) > 6 and ctx.cfg[6]
+        sum_in = ctx.cfg.sum_inputs
         d.flags = (2 if _DET else 0) | (4 if sum_in else 0)
-        if len(ctx.cfg) > 5 and ctx.cfg[5]:
+        if ctx.cfg.sync_bn:
             _attach_sync(d, dev)
         _lib.check(lib.pf_bnmlp_train_bwd(ctypes.byref(d), _stream()), "pf_bnmlp_train_bwd")
         if sum_in:                                           # y[0] = xa + xb: both inputs take d[0]; layer 0 has no weights of its own
@@ -1610,8 +1596,8 @@ def bnmlp_fused(mlp, xa: Tensor, xb=None, last=None, sum_inputs: bool = False) -
     """last = (W, b): other tensors for the last (linear) layer - the next module's first layer folded in (interp_weights);
     sum_inputs: layer 0 = xa + xb (its weights live folded in the two producers' last layers)."""
     convs, bns = [mlp[0], mlp[3], mlp[6]], [mlp[1], mlp[4]]
-    cfg = (0.01, float(bns[0].eps), float(bns[0].momentum), [bn.running_mean for bn in bns], [bn.running_var for bn in bns],
-           _sync_bn_active(), bool(sum_inputs))
+    cfg = BnMlpCfg(slope=0.01, eps=float(bns[0].eps), momentum=float(bns[0].momentum), run_means=[bn.running_mean for bn in bns],
+                   run_vars=[bn.running_var for bn in bns], sync_bn=_sync_bn_active(), sum_inputs=bool(sum_inputs))
     prm = []
     for i, c in enumerate(convs):
         if i == 2 and last is not None:
@@ -1642,12 +1628,7 @@ _DESC_BUF = {}
 
 
 def _desc_buf(dev) -> Tensor:
-    key = (dev, _stream())
-    t = _DESC_BUF.get(key)
-    if t is None:
-        t = torch.empty(16 * ctypes.sizeof(_lib.PfMlpTrain), dtype=torch.uint8, device=dev)
-        _DESC_BUF[key] = t
-    return t
+    return _per_stream(_DESC_BUF, dev, lambda: torch.empty(16 * ctypes.sizeof(_lib.PfMlpTrain), dtype=torch.uint8, device=dev))
 
 
 class CondNetBatchFn(Function):
@@ -1808,7 +1789,6 @@ def mlp_fused(y, c: Tensor, td: int, cdiv: int, slopes, layers) -> Tensor:
 
 
 _FUSED = os.environ.get("PF_TRAIN_FUSED", "1") != "0"
-_MERGE_BATCH = os.environ.get("PF_TRAIN_MERGE_BATCH", "1") != "0"   # the FeatMergeUnits of all units in one batched launch; "0" = one per unit
 _FOLD_WU = os.environ.get("PF_TRAIN_FOLD_WU", "1") != "0"    # the weight unit's first conv folded into its producers (interp_weights); "0" = A/B reference
 
 
@@ -1856,20 +1836,18 @@ def _ec_fused_supported(p, x: Tensor, idx: Tensor, pooling: bool) -> bool:
             and (B * N * K) % 16 == 0 and (K == 16 or not pooling))
 
 
-# The interpolation branch runs on the side stream either way; this is only WHEN the host issues it: before the feature units
-# (default) or after them - autograd replays nodes in reverse creation order, so issued late it is the FIRST thing the backward
-# enqueues after the flow stage instead of the last
-_SIDE_LATE = os.environ.get("PF_TRAIN_SIDE_LATE", "0") == "1"
-_SIDE_STREAM = os.environ.get("PF_TRAIN_STREAMS", "1") != "0"      # "0": the interpolation branch on the calling stream (timing reference)
-_TAP = os.environ.get("PF_TRAIN_TAP", "1") != "0"     # a unit's output gradient from its merge unit added inside the next unit's dx GEMM
-_PREFOLD = os.environ.get("PF_TRAIN_PREFOLD", "1") != "0"     # the feature units' folded weights in one launch at the top of the forward
+# References of three bit-for-bit / rounding-level comparisons in tests/test_gpu_train.py, which assigns False to them: not
+# environment switches, and nothing else sets them
+_PREFOLD = True      # the feature units' folded weights in one launch at the top of the forward (ec_prefold); False: one per unit
+_TAP = True          # a unit's output gradient from its merge unit added inside the next unit's dx GEMM; False: autograd's add launch
+_FANOUT = True       # the four gradients of the flattened conditioning features summed in one launch (FanoutFn); False: autograd's adds
 
 
 def ec_prefold(units, x0: Tensor, K: int):
     """Folded edge-feature weights (Wpq, bpq) of a CHAIN of pooled units (unit i + 1 reads unit i's output) in one launch
     (pf_ec_train_fold_batch) -> one pair per unit for `edgeconv_train_fused(..., prefold=)`, or None where the fused path
     does not apply.  Parameters only: valid until the next optimizer update."""
-    if not (_FUSED and _PREFOLD) or _UNFOLDED or not 1 <= len(units) <= 8:
+    if not (_FUSED and _PREFOLD) or not 1 <= len(units) <= 8:
         return None
     B, N, C = x0.shape
     if (B * N * K) % 16:
@@ -1909,24 +1887,19 @@ def edgeconv_train_fused(p, x: Tensor, idx: Tensor, pooling: bool = True, csr=No
     convs = [seq[0] for seq in p.convs] + [p.conv_out]
     bns = [seq[1] for seq in p.convs]
     g, nconv, odim = convs[0].weight.shape[0], len(bns), p.conv_out.weight.shape[0]
+    ws, bs = [c.weight for c in convs], [c.bias for c in convs]
+    sync = _sync_bn_active()
+    cfg = EcCfg(K=idx.shape[-1], growth=g, nconv=nconv, odim=odim, pooling=bool(pooling), slope=0.05, eps=float(bns[0].eps),
+                momentum=float(bns[0].momentum), run_means=[bn.running_mean for bn in bns], run_vars=[bn.running_var for bn in bns],
+                csr=csr, persistent=bool(persistent) and _PERSIST and not sync, sync_bn=sync)
     if out is not None:
-        ws = [c.weight for c in convs[:-1]] + [out[0]]
-        bs = [c.bias for c in convs[:-1]] + [out[1]]
-        cfg = (idx.shape[-1], g, nconv, odim, bool(pooling), 0.05, float(bns[0].eps), float(bns[0].momentum),
-               [bn.running_mean for bn in bns], [bn.running_var for bn in bns], csr,
-               bool(persistent) and _PERSIST and not _sync_bn_active(), _sync_bn_active(),
-               True)         # [13]: conv_out's gradient is consumed INSIDE the pass (FoldWuFn): no weight-gradient stream for this unit
-        res = EdgeConvUnitFn.apply(x, idx, cfg, *ws, *bs, *[bn.weight for bn in bns], *[bn.bias for bn in bns])
-        _count_batches(bns)
-        return res
-    cfg = (idx.shape[-1], g, nconv, odim, bool(pooling), 0.05, float(bns[0].eps), float(bns[0].momentum),
-           [bn.running_mean for bn in bns], [bn.running_var for bn in bns], csr,
-           bool(persistent) and _PERSIST and not _sync_bn_active(), _sync_bn_active(), False, prefold,
-           bool(tap) and x.requires_grad)
-    out = EdgeConvUnitFn.apply(x, idx, cfg, *[c.weight for c in convs], *[c.bias for c in convs],
-                               *[bn.weight for bn in bns], *[bn.bias for bn in bns])
+        ws[-1], bs[-1] = out
+        cfg = cfg._replace(dw_inline=True)
+    else:
+        cfg = cfg._replace(prefold=prefold, tap=bool(tap) and x.requires_grad)
+    res = EdgeConvUnitFn.apply(x, idx, cfg, *ws, *bs, *[bn.weight for bn in bns], *[bn.bias for bn in bns])
     _count_batches(bns)
-    return out
+    return res
 
 
 def cond_net(net, h: Tensor) -> Tensor:
@@ -2001,13 +1974,11 @@ class _Lin:
         self.weight, self.bias = weight, bias
 
 
-_FAN = os.environ.get("PF_TRAIN_FAN", "1") != "0"
 # all flow blocks of a direction as one autograd node (FlowChainFn); "0" = one node per block piece (the A/B reference)
 _CHAIN = os.environ.get("PF_TRAIN_CHAIN", "1") != "0"
 # chains of one-element torch launches as fused kernels (csrc/train_glue.hip: interpolation of the latent, the log-likelihood
 # inside the f chain, the loss head of loss.PuganLossFn); "0" = the torch expressions (the A/B reference)
 _GLUE = os.environ.get("PF_TRAIN_GLUE", "1") != "0"
-_CSR_SIDE = os.environ.get("PF_TRAIN_CSR_SIDE", "1") != "0"      # A/B switch, read once at import like its neighbours (README "Switches")
 
 
 def _flow_param_aliases(net):
@@ -2017,10 +1988,7 @@ def _flow_param_aliases(net):
         L = blk.coupling1.bias_net.layers
         plist += [(blk.actnorm.logs, 3), (blk.actnorm.bias, 2), (blk.permutate1.permutater.W, 2), (L[0].weight, 2),
                   (L[2].weight, 2), (L[2].bias, 2), (L[4].weight, 2), (L[4].bias, 2)]
-    if _FAN:
-        flat = list(ParamFanFn.apply(tuple(u for _, u in plist), *[p for p, _ in plist]))
-    else:
-        flat = [p for p, u in plist for _ in range(u)]
+    flat = list(ParamFanFn.apply(tuple(u for _, u in plist), *[p for p, _ in plist]))
     out, k = [], 0
     for _ in net.flow_blocks:
         a = {}
@@ -2039,10 +2007,8 @@ def _flow_chain_params(net):
         L = blk.coupling1.bias_net.layers
         plist += [blk.actnorm.logs, blk.actnorm.bias, blk.permutate1.permutater.W, L[0].weight, L[2].weight, L[2].bias,
                   L[4].weight, L[4].bias]
-    if _FAN:
-        flat = list(ParamFanFn.apply(tuple(2 for _ in plist), *plist))
-        return flat[0::2], flat[1::2]
-    return plist, plist
+    flat = list(ParamFanFn.apply(tuple(2 for _ in plist), *plist))
+    return flat[0::2], flat[1::2]
 
 
 def forward_train(net, xyz: Tensor, upratio: int) -> Tuple[Tensor, Tensor]:
@@ -2069,151 +2035,177 @@ def forward_train(net, xyz: Tensor, upratio: int) -> Tuple[Tensor, Tensor]:
 def _forward_train(net, xyz: Tensor, upratio: int) -> Tuple[Tensor, Tensor]:
     from . import ops
     xyz = xyz.detach().contiguous().float()
-    B, N, _ = xyz.shape
-    R = upratio
     idx16, _ = ops.knn_idx32(xyz, xyz, 16)
-    fused_ec = _FUSED                                     # also under SyncBN: the fused kernels defer a layer's statistics to an all-reduce
-    use_side = getattr(net, "train_streams", True) and not _sync_bn_active() and _SIDE_STREAM
-    # the 8 nearest of the 16: only the interpolation branch (and, after the join, the latent's interpolation) reads them - with a
-    # side stream the copy is made there, off the chain knn -> fold -> first unit
-    idx8 = None if use_side else idx16[..., :8].contiguous()
-    # transposed neighbour lists: only the BACKWARD of the EdgeConv units reads them - with a side stream they are built there,
-    # off the main chain (8 small launches, ~55 us), and joined with the interpolation weights
-    csr16 = csr8 = None
-    csr_side = use_side and _CSR_SIDE
-    if fused_ec and not csr_side:
-        csr16, csr8 = knn_csr_pair(idx16, 8)
-
     # ---- interpolation weights (interpflow.py:85-151): a function of xyz and the neighbour lists only, independent of the
     # feature extractor / flow f chain that follows.  At 32 x 256 points no kernel of the step fills the chip, so this branch
     # (two BatchNorm MLPs + one EdgeConv unit, forward and - autograd keeps the stream - backward) runs on a side stream
     # beside the main chain; inside a captured step it becomes a parallel branch of the graph.  Scratch buffers are per
     # (device, stream) (_ws / _stat), results are identical to the one-stream order (net.train_streams = False).
-    def interp_weights():
-        ip = net.interp
-        fd = torch.empty((B * N * 8, 10), dtype=torch.float32, device=xyz.device)        # inputs only: no gradient
-        _lib.check(_lib.load().pf_dist_feature(xyz.data_ptr(), idx8.data_ptr(), B, N, 8, fd.data_ptr(), _stream()), "pf_dist_feature")
-        fused_bn = _FUSED
-        de, wu, fc = ip.knn_context.distance_encoder.mlp, ip.weight_unit.mlp, ip.knn_context.feat_conv
-        if (fused_bn and _FOLD_WU and _ec_fused_supported(fc, xyz, idx8, False)
-                and wu[0].weight.shape[0] == de[6].weight.shape[0] == fc.conv_out.weight.shape[0] == wu[0].weight.shape[1] // 2):
-            # The weight unit's first conv sees cat[d, feat] with NO nonlinearity after the producers' last (linear) layers
-            # (interpflow.py:134,144-146), so W0 [d; feat] + b0 = (W0a W6) a2 + (W0b Wout) e + (W0a b6 + W0b bout + b0): the
-            # producers' last layers run with the PRODUCT weights and emit the two halves of the pre-BatchNorm output directly;
-            # the first layer of the weight unit is their sum (PF_BNMLP_SUM_INPUTS) - two [E8, 128] x [128, 128] products per
-            # direction less, same function.  The products and their chain rule back to W0, W6, Wout and the three biases are one
-            # small launch each (FoldWuFn; the same algebra as the eval path's packing.fold_state_dict).
-            W6f, b6f, Wof, bof = FoldWuFn.apply(wu[0].weight, wu[0].bias, de[6].weight, de[6].bias, fc.conv_out.weight,
-                                                fc.conv_out.bias)
-            d = bnmlp_fused(de, fd, last=(W6f, b6f))
-            feat = edgeconv_train_fused(fc, xyz, idx8, False, csr8, False, out=(Wof, bof))
-            return bnmlp_fused(wu, d, feat, sum_inputs=True)
-        d = bnmlp_fused(de, fd) if fused_bn else _mlp_bn(de, fd)
-        feat = edgeconv_train(fc, xyz, idx8, pooling=False, csr=csr8)                            # d, feat: [E8,128]
-        if fused_bn:
-            return bnmlp_fused(wu, d, feat)                       # on cat[d, feat] (interpflow.py:146) without building it
-        return _mlp_bn(ip.weight_unit.mlp, torch.cat([d, feat], dim=1))  # [E8,32]
-
+    # With a side stream the neighbour lists are made there too, off the chain knn -> fold -> first unit
+    side = _side_stream(xyz.device) if getattr(net, "train_streams", True) and not _sync_bn_active() else None
+    if side is None:
+        idx8, csr16, csr8 = _neighbour_lists(idx16)
     # folded edge-feature weights of the six feature units: parameters only - one launch here instead of one per unit
-    pre = ec_prefold(list(net.feat_convs), xyz, 16) if (fused_ec and not _sync_bn_active()) else None
-
-    side = None
-    if use_side:
-        side = _side_stream(xyz.device)
+    # (the fused kernels also run under SyncBN - they defer a layer's statistics to an all-reduce - but without the prefold)
+    pre = ec_prefold(list(net.feat_convs), xyz, 16) if (_FUSED and not _sync_bn_active()) else None
+    if side is not None:
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
-            idx8 = idx16[..., :8].contiguous()
-            if fused_ec and csr_side:
-                csr16, csr8 = knn_csr_pair(idx16, 8)
-            if not _SIDE_LATE:
-                w = interp_weights()
+            idx8, csr16, csr8 = _neighbour_lists(idx16)
+            w = _interp_weights(net, xyz, idx8, csr8)
     else:
-        w = interp_weights()
+        w = _interp_weights(net, xyz, idx8, csr8)
+    branch = (side, w, csr16, csr8, idx8)                       # the arguments of _join_side
 
-    # ---- feature extractor  (the merge units on a second side stream beside EdgeConv unit i + 1 were tried: 7.65 -> 8.35 ms per
-    # captured step - six fork / join pairs of tiny kernels cost more in graph dependencies than their overlap returns)
+    cs, cflat_m = _features(net, xyz, idx16, csr16, pre)
+    R, nb = upratio, net.num_blocks
+    chain = (_CHAIN and _FUSED and nb <= 8 and R in (1, 2, 4, 8, 16)
+             and all(b.actnorm.is_inited for b in net.flow_blocks) and all(c.shape[-1] in (32, 64, 128) for c in cs)
+             and all(b.coupling1.bias_net.layers[2].weight.shape == (64, 64) for b in net.flow_blocks))
+    # ActNorm's data-dependent init needs each block's input on the host side of the chain: the first step takes the per-block path
+    if chain:
+        return _flow_chain(net, xyz, R, cs, cflat_m, branch)
+    return _flow_blocks(net, xyz, R, cs, branch)
+
+
+def _neighbour_lists(idx16: Tensor):
+    """-> (idx8, csr16, csr8) on the current stream.  idx8: the 8 nearest of the 16 - only the interpolation branch (and, after the
+    join, the latent's interpolation) reads them.  csr*: the transposed neighbour lists (8 small launches, ~55 us) - only the
+    BACKWARD of the fused EdgeConv units reads them."""
+    idx8 = idx16[..., :8].contiguous()
+    csr16, csr8 = knn_csr_pair(idx16, 8) if _FUSED else (None, None)
+    return idx8, csr16, csr8
+
+
+def _join_side(side, w, csr16, csr8, idx8) -> None:
+    """The calling stream waits for the interpolation branch and takes over what was allocated on the side stream."""
+    if side is None:
+        return
+    cur = torch.cuda.current_stream()
+    cur.wait_stream(side)
+    w.record_stream(cur)
+    for t in (csr16 or ()) + (csr8 or ()) + (idx8,):
+        t.record_stream(cur)
+
+
+def _interp_weights(net, xyz: Tensor, idx8: Tensor, csr8) -> Tensor:
+    """The interpolation logits [E8, 32] of net.interp (interpflow.py:85-151) on the current stream."""
+    B, N, _ = xyz.shape
+    ip = net.interp
+    fd = torch.empty((B * N * 8, 10), dtype=torch.float32, device=xyz.device)        # inputs only: no gradient
+    _lib.check(_lib.load().pf_dist_feature(xyz.data_ptr(), idx8.data_ptr(), B, N, 8, fd.data_ptr(), _stream()), "pf_dist_feature")
+    de, wu, fc = ip.knn_context.distance_encoder.mlp, ip.weight_unit.mlp, ip.knn_context.feat_conv
+    if (_FUSED and _FOLD_WU and _ec_fused_supported(fc, xyz, idx8, False)
+            and wu[0].weight.shape[0] == de[6].weight.shape[0] == fc.conv_out.weight.shape[0] == wu[0].weight.shape[1] // 2):
+        # The weight unit's first conv sees cat[d, feat] with NO nonlinearity after the producers' last (linear) layers
+        # (interpflow.py:134,144-146), so W0 [d; feat] + b0 = (W0a W6) a2 + (W0b Wout) e + (W0a b6 + W0b bout + b0): the
+        # producers' last layers run with the PRODUCT weights and emit the two halves of the pre-BatchNorm output directly;
+        # the first layer of the weight unit is their sum (PF_BNMLP_SUM_INPUTS) - two [E8, 128] x [128, 128] products per
+        # direction less, same function.  The products and their chain rule back to W0, W6, Wout and the three biases are one
+        # small launch each (FoldWuFn; the same algebra as the eval path's packing.fold_state_dict).
+        W6f, b6f, Wof, bof = FoldWuFn.apply(wu[0].weight, wu[0].bias, de[6].weight, de[6].bias, fc.conv_out.weight,
+                                            fc.conv_out.bias)
+        d = bnmlp_fused(de, fd, last=(W6f, b6f))
+        feat = edgeconv_train_fused(fc, xyz, idx8, False, csr8, False, out=(Wof, bof))
+        return bnmlp_fused(wu, d, feat, sum_inputs=True)
+    d = bnmlp_fused(de, fd) if _FUSED else _mlp_bn(de, fd)
+    feat = edgeconv_train(fc, xyz, idx8, pooling=False, csr=csr8)                            # d, feat: [E8,128]
+    if _FUSED:
+        return bnmlp_fused(wu, d, feat)                       # on cat[d, feat] (interpflow.py:146) without building it
+    return _mlp_bn(wu, torch.cat([d, feat], dim=1))           # [E8,32]
+
+
+def _features(net, xyz: Tensor, idx16: Tensor, csr16, pre):
+    """The feature extractor: EdgeConv unit i on unit i - 1's output, a FeatMergeUnit on each unit's output.
+    -> (cs: the conditioning features [B, N, cd_i] per block, cflat_m: the flat tensor they are views of | None)
+    (the merge units on a second side stream beside EdgeConv unit i + 1 were tried: 7.65 -> 8.35 ms per captured step - six
+    fork / join pairs of tiny kernels cost more in graph dependencies than their overlap returns)"""
+    B, N, _ = xyz.shape
+    # all merge units in one batched launch (MergeBatchFn) after the last unit; one launch per unit for more than 16 blocks
+    batch_merge = _FUSED and net.num_blocks <= 16
+    # the main chain's units may run as persistent grid-barrier launches: nothing else with a grid barrier runs beside them
+    # (the side stream's interpolation unit keeps the per-layer kernels; the EMD auction starts after the forward)
+    # An explicit opt-in (ADVICE r4): TrainerModule sets `network.train_persistent` from its configuration (on, unless the
+    # device is shared: cfg.emd_workgroups == 1 / cfg.persistent_kernels = False); a bare PointInterpFlow.train() forward on a
+    # GPU it may share with another process keeps the per-layer kernels - a grid barrier whose workgroups are not all resident
+    # spins for seconds before its bounded time-out makes the output NaN.
+    persistent = getattr(net, "train_persistent", False)
     cs: List[Tensor] = []
     hs_all: List[Tensor] = []
     h = xyz
     for i in range(net.num_blocks):
-        # the main chain's units may run as persistent grid-barrier launches: nothing else with a grid barrier runs beside them
-        # (the side stream's interpolation unit keeps the per-layer kernels; the EMD auction starts after the forward)
-        # An explicit opt-in: TrainerModule sets `network.train_persistent` from its configuration (on, unless the
-        # device is shared: cfg.emd_workgroups == 1 / cfg.persistent_kernels = False); a bare PointInterpFlow.train() forward on a
-        # GPU it may share with another process keeps the per-layer kernels - a grid barrier whose workgroups are not all resident
-        # spins for seconds before its bounded time-out makes the output NaN.
-        batch_merge = _FUSED and _MERGE_BATCH and net.num_blocks <= 16
-        h = edgeconv_train(net.feat_convs[i], h, idx16, csr=csr16, persistent=getattr(net, "train_persistent", False),
+        h = edgeconv_train(net.feat_convs[i], h, idx16, csr=csr16, persistent=persistent,
                            prefold=pre[i] if pre is not None else None, tap=_TAP and batch_merge and i > 0)
         if isinstance(h, tuple):                                  # (output, the input again): the merge unit reads the alias, so
             h, hs_all[i - 1] = h                                  # its gradient reaches the previous unit through THIS unit's dx GEMM
         m = net.merge_convs[i]
-        if _FUSED and _MERGE_BATCH and net.num_blocks <= 16:
-            hs_all.append(h)                                      # all merge units in one batched launch below
+        if batch_merge:
+            hs_all.append(h)
         elif _FUSED:
             cs.append(mlp_fused(None, h, 0, 1, (0.0,), [m.conv1, m.conv2]).view(B, N, -1))
         else:
             cs.append(linear(ActFn.apply(linear(h, m.conv1.weight, m.conv1.bias), 0.0), m.conv2.weight))
-    if side is not None and _SIDE_LATE:
-        with torch.cuda.stream(side):
-            w = interp_weights()
-    if hs_all:
-        mp = []
-        for m in net.merge_convs:
-            mp += [m.conv1.weight, m.conv1.bias, m.conv2.weight]
-        cflat_m = MergeBatchFn.apply(len(hs_all), *hs_all, *mp)
-        off = 0
-        for m in net.merge_convs:
-            cd = m.conv2.weight.shape[0]
-            cs.append(cflat_m[off:off + B * N * cd].view(B, N, cd))
-            off += B * N * cd
+    if not hs_all:
+        return cs, None
+    mp = []
+    for m in net.merge_convs:
+        mp += [m.conv1.weight, m.conv1.bias, m.conv2.weight]
+    cflat_m = MergeBatchFn.apply(len(hs_all), *hs_all, *mp)
+    off = 0
+    for m in net.merge_convs:
+        cd = m.conv2.weight.shape[0]
+        cs.append(cflat_m[off:off + B * N * cd].view(B, N, cd))
+        off += B * N * cd
+    return cs, cflat_m
 
-    # ---- injector nets (s, t) of every block: functions of cs[i] only - one batched launch (and shared by f and g)
-    st_all = None
+
+def _injector_params(net) -> List[Tensor]:
+    """The injector nets (s, t) of every block: functions of cs[i] only - one batched launch (and shared by f and g)."""
     st_prm = []
-    nb = net.num_blocks
-    chain = (_CHAIN and _FUSED and nb <= 8 and R in (1, 2, 4, 8, 16)
-             and all(b.actnorm.is_inited for b in net.flow_blocks) and all(c.shape[-1] in (32, 64, 128) for c in cs)
-             and all(b.coupling1.bias_net.layers[2].weight.shape == (64, 64) for b in net.flow_blocks))
-    if _FUSED:
-        for blk in net.flow_blocks:
-            for cn in (blk.coupling2.scale_net, blk.coupling2.bias_net):
-                L = cn.layers
-                st_prm += [L[0].weight, L[2].weight, L[2].bias, L[4].weight, L[4].bias]
-        if not chain:
-            cidx = tuple(i for i in range(net.num_blocks) for _ in range(2))
-            st_all = CondNetBatchFn.apply(cidx, *cs, *st_prm)
+    for blk in net.flow_blocks:
+        for cn in (blk.coupling2.scale_net, blk.coupling2.bias_net):
+            L = cn.layers
+            st_prm += [L[0].weight, L[2].weight, L[2].bias, L[4].weight, L[4].bias]
+    return st_prm
 
-    # ---- f, interpolation, g with every flow block of a direction in one autograd node (csrc/train_flowchain.hip).  ActNorm's
-    # data-dependent init needs each block's input on the host side of the chain: the first step takes the per-block path below
-    if chain:
-        pf, pg = _flow_chain_params(net)
-        ccs = tuple(int(c.shape[-1]) for c in cs)
-        cflat = cflat_m if hs_all else torch.cat([c.reshape(-1) for c in cs])       # one tensor for its consumers
-        cflat_t = None
-        cflat_f = cflat_g = cflat
-        if _FANOUT:                                                   # their four gradients: one launch (FanoutFn)
-            cflat, cflat_t, cflat_f, cflat_g = FanoutFn.apply(4, cflat)
-        st = CondNetStackFn.apply(ccs, B * N, cflat, cflat_t, *st_prm)
-        if _GLUE and nb < 8:
-            z, logp1 = FlowChainFn.apply(0, 1, float(N), ccs, xyz, cflat_f, st, B, *pf)     # log-likelihood from the kernel's epilogue
-            logp = logp1.view(())
-        else:
-            z, ssum, ld = FlowChainFn.apply(0, 1, float(N), ccs, xyz, cflat_f, st, 0, *pf)
-            logp = -(BatchSumFn.apply(z, 1).mean() + ld.sum() - ssum.sum() / B)
-        if side is not None:
-            torch.cuda.current_stream().wait_stream(side)
-            w.record_stream(torch.cuda.current_stream())
-            for t in (csr16 or ()) + (csr8 or ()) + (idx8,):
-                t.record_stream(torch.cuda.current_stream())
-        if _GLUE and R <= 8:
-            u = InterpWsumFn.apply(w.view(B * N, 8, -1), z, idx8, R, csr8 if _DET else None)
-        else:
-            zj = GatherRowsFn.apply(z, idx8)
-            fz = SoftmaxWsumFn.apply(w.view(B * N, 8, -1), zj.view(B * N, 8, 3), R)
-            u = fz.transpose(1, 2).reshape(B, N * R, 3)
-        x = FlowChainFn.apply(1, R, float(N), ccs, u, cflat_g, st, 0, *pg)
-        return x, logp
+
+def _flow_chain(net, xyz: Tensor, R: int, cs, cflat_m, branch) -> Tuple[Tensor, Tensor]:
+    """f, interpolation, g with every flow block of a direction in one autograd node (csrc/train_flowchain.hip): the default."""
+    B, N, _ = xyz.shape
+    _, w, _, csr8, idx8 = branch
+    st_prm = _injector_params(net)
+    pf, pg = _flow_chain_params(net)
+    ccs = tuple(int(c.shape[-1]) for c in cs)
+    cflat = cflat_m if cflat_m is not None else torch.cat([c.reshape(-1) for c in cs])       # one tensor for its consumers
+    cflat_t = None
+    cflat_f = cflat_g = cflat
+    if _FANOUT:                                                   # their four gradients: one launch (FanoutFn)
+        cflat, cflat_t, cflat_f, cflat_g = FanoutFn.apply(4, cflat)
+    st = CondNetStackFn.apply(ccs, B * N, cflat, cflat_t, *st_prm)
+    if _GLUE and net.num_blocks < 8:
+        z, logp1 = FlowChainFn.apply(0, 1, float(N), ccs, xyz, cflat_f, st, B, *pf)     # log-likelihood from the kernel's epilogue
+        logp = logp1.view(())
+    else:
+        z, ssum, ld = FlowChainFn.apply(0, 1, float(N), ccs, xyz, cflat_f, st, 0, *pf)
+        logp = -(BatchSumFn.apply(z, 1).mean() + ld.sum() - ssum.sum() / B)
+    _join_side(*branch)
+    if _GLUE and R <= 8:
+        u = InterpWsumFn.apply(w.view(B * N, 8, -1), z, idx8, R, csr8 if _DET else None)
+    else:
+        zj = GatherRowsFn.apply(z, idx8)
+        fz = SoftmaxWsumFn.apply(w.view(B * N, 8, -1), zj.view(B * N, 8, 3), R)
+        u = fz.transpose(1, 2).reshape(B, N * R, 3)
+    x = FlowChainFn.apply(1, R, float(N), ccs, u, cflat_g, st, 0, *pg)
+    return x, logp
+
+
+def _flow_blocks(net, xyz: Tensor, R: int, cs, branch) -> Tuple[Tensor, Tensor]:
+    """f, interpolation, g block by block: the first step (ActNorm's init), shapes the chain kernels do not take, _CHAIN off (one
+    fused node per block piece) and _FUSED off (the per-op reference)."""
+    B, N, _ = xyz.shape
+    _, w, _, _, idx8 = branch
+    if _FUSED:
+        st_all = CondNetBatchFn.apply(tuple(i for i in range(net.num_blocks) for _ in range(2)), *cs, *_injector_params(net))
 
     # ---- f + log-likelihood
     p = xyz
@@ -2264,11 +2256,7 @@ def _forward_train(net, xyz: Tensor, upratio: int) -> Tuple[Tensor, Tensor]:
         logp = -torch.mean(BatchSumFn.apply(z, 1) + ldj)
 
     # ---- interpolation: the weights w were started on the side stream before the feature extractor
-    if side is not None:
-        torch.cuda.current_stream().wait_stream(side)
-        w.record_stream(torch.cuda.current_stream())
-        for t in (csr16 or ()) + (csr8 or ()) + (idx8,):
-            t.record_stream(torch.cuda.current_stream())
+    _join_side(*branch)
     zj = GatherRowsFn.apply(z, idx8)                              # [E8,3]
     fz = SoftmaxWsumFn.apply(w.view(B * N, 8, -1), zj.view(B * N, 8, 3), R)      # [T,3,R]
     u = fz.transpose(1, 2).reshape(B, N * R, 3)
