@@ -842,6 +842,55 @@ int pf_disk_tile(void);
 int pf_disk_uniformity(const float* mapped, int N, const long long* offsets, const int* member, const int* level, int S,
                        const double* radii, int J, double* out_n, double* out_dis, void* stream);
 
+/* ---- Surface-connected neighbourhoods (csrc/surface_reach.hip; the reference has no runnable counterpart: its disks were
+ * meant to come from CGAL's geodesic distance, evaluation.cpp:88-107) ----------------------------------------------------------
+ * For a source point src[s] on face src_face[s] of tris [F,9]: d2(f) = the squared distance from the source to the closest
+ * point of triangle f (Voronoi-region classification in double relative to the source, rounded once to fp32; the distance to
+ * the plane of a face the source all but lies in - its own - is summed without cancellation, pf_surface.h plane_d2), and the
+ * bottleneck field b2(f) = min over face paths src_face = g0 .. gk = f of max_i d2(g_i), faces adjacent as the caller's CSR
+ * face_adj_offsets [F+1] int64 / face_adj says (metrics.face_adjacency: a shared welded vertex).
+ *   pf_reach_count: counts [S] int32 = the faces with d2 <= r2_stop[s], the candidates - a superset of the faces reachable
+ *                   inside that ball.  A source whose own face is no candidate (or outside [0, F): never read) counts 0 and
+ *                   sets PF_REACH_ST_START.
+ *   pf_reach_fill:  row s of the CSR, rface / rd2 [offsets[s], offsets[s+1]) (offsets [S+1] int64 on the device, sized by the
+ *                   caller from counts): the candidates in ascending face index with their d2.  Order comes from wave ballots
+ *                   and prefix counts, not from atomics.  A row shorter than its candidates is filled and not overrun.
+ *   pf_reach_relax: rb2 [nnz] = b2 of every candidate, +inf for one not reached through candidates.  One workgroup per source
+ *                   sweeps b2(f) <- min(b2(f), max(d2(f), b2(g))) over the adjacent candidates g (found by binary search in
+ *                   the sorted row; unsigned atomicMin on the fp32 bits) until a sweep lowers nothing.  Values only fall, each
+ *                   is the bottleneck of a real path, and the end state is the least fixed point - b2 itself - whatever the
+ *                   sweep order, the wave scheduling, S or the grid; a repeat gives the same bits.  Every finite value is exact:
+ *                   a path of bottleneck <= r2_stop uses only faces with d2 <= r2_stop, all candidates.  Rows of at most
+ *                   PF_REACH_LDS_FACES entries (pf_reach_lds_faces() returns it) are worked on in LDS, longer ones in rb2
+ *                   itself, by the same device code.  At most row length + 1 sweeps, then PF_REACH_ST_ITER; no grid barrier,
+ *                   no co-residency requirement.  sweeps [S] int32 (nullable): the sweeps each source took.  A row that does
+ *                   not hold its source's face sets PF_REACH_ST_START, one that lists a face outside [0, F) (never a row of
+ *                   pf_reach_fill) PF_REACH_ST_ROW; neither is relaxed, and the adjacency is not read for it: all +inf.
+ *   pf_reach_point_d2: out [S,N] = max(|pts[i] - src[s]|^2, b2(pts_face[i])), the squared surface distance of every point
+ *                   (fp32, the source subtracted first, as pf_disk_count); +inf for a point on a face the row does not hold.
+ * status: one int32 the kernels only OR PF_REACH_ST_* into. */
+#define PF_REACH_LDS_FACES 4096
+#define PF_REACH_ST_START 1     /* a source's own face is not among its candidates: its row is empty            */
+#define PF_REACH_ST_ITER 2      /* a row did not settle within its length + 1 sweeps (never seen: a defect)      */
+#define PF_REACH_ST_ROW 4       /* pf_reach_relax was given a row that lists a face outside [0, F): left +inf    */
+int pf_reach_lds_faces(void);
+int pf_reach_count(const float* tris, int F, const float* src, const int* src_face, const float* r2_stop, int S, int* counts,
+                   int* status, void* stream);
+int pf_reach_fill(const float* tris, int F, const float* src, const int* src_face, const float* r2_stop, int S,
+                  const long long* offsets, int* rface, float* rd2, int* status, void* stream);
+int pf_reach_relax(const long long* offsets, const int* rface, const float* rd2, int F, const long long* face_adj_offsets,
+                   const int* face_adj, const int* src_face, int S, float* rb2, int* sweeps, int* status, void* stream);
+int pf_reach_point_d2(const float* pts, int N, const int* pts_face, const float* src, int S, const long long* offsets,
+                      const int* rface, const float* rb2, float* out, void* stream);
+/* pf_disk_count / pf_disk_fill with the surface distance: a point is in disk (s, j) when
+ * max(|mapped - seed|^2, b2(mapped_face)) <= fp32(radii[j]^2), b2 from row s of the reach CSR (reach_offsets, rface, rb2) made
+ * with seeds as sources and r2_stop >= fp32(radii[J-1]^2).  The same kernels and the same CSR format as the Euclidean pair. */
+int pf_disk_count_reach(const float* mapped, int N, const float* seeds, int S, const double* radii, int J, const int* mapped_face,
+                        const long long* reach_offsets, const int* rface, const float* rb2, int* counts, void* stream);
+int pf_disk_fill_reach(const float* mapped, int N, const float* seeds, int S, const double* radii, int J, const int* mapped_face,
+                       const long long* reach_offsets, const int* rface, const float* rb2, const long long* offsets, int* member,
+                       int* level, void* stream);
+
 /* ---- Poisson-disk point sets by weighted sample elimination (csrc/poisson.hip; Yuksel 2015 - the reference has no counterpart:
  * its training patches and test clouds came from PU-GAN's Meshlab preparation) ------------------------------------------------
  * A pool is s candidate points on a surface of area A, thinned to exactly m.  B pools are stored back to back as one

@@ -240,6 +240,17 @@ SIGNATURES = {
     "pf_disk_tile": (c_int, []),
     "pf_disk_uniformity": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, POINTER(c_double), c_int, c_void_p,
                                    c_void_p, c_void_p]),
+    "pf_reach_lds_faces": (c_int, []),
+    "pf_reach_count": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "pf_reach_fill": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                              c_void_p]),
+    "pf_reach_relax": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                               c_void_p, c_void_p]),
+    "pf_reach_point_d2": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pf_disk_count_reach": (c_int, [c_void_p, c_int, c_void_p, c_int, POINTER(c_double), c_int, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_void_p]),
+    "pf_disk_fill_reach": (c_int, [c_void_p, c_int, c_void_p, c_int, POINTER(c_double), c_int, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pf_poisson_params": (c_int, [c_double, c_int, c_int, POINTER(c_double), POINTER(c_double), POINTER(c_float)]),
     "pf_poisson_pools": (c_int, [POINTER(c_int), POINTER(c_int), POINTER(c_double), c_int, c_int, c_void_p]),
     "pf_poisson_degree": (c_int, [c_void_p, c_void_p, c_int, c_int, c_longlong, c_void_p, c_void_p, c_void_p]),

@@ -4,6 +4,8 @@
 //   pf_mesh_sample        - S seed points on the surface, area-weighted, from Philox-4x32-10 (key = seed, counter = s);
 //   pf_disk_count / _fill - the mapped points inside the Euclidean balls of J nested radii around every seed: counts, then a
 //                           CSR of the largest ball's members in ascending index order with each member's level;
+//   pf_disk_count_reach / _fill_reach - the same kernels with the surface distance max(|q - s|^2, b2(face(q))) in place of
+//                           |q - s|^2, b2 from the seed's row of a reach CSR (surface_reach.hip);
 //   pf_disk_uniformity    - per (seed, radius): member count and the mean of (d - d^)^2 / d^ over the members, d the distance
 //                           to the nearest other member of the same disk.
 // One workgroup per seed everywhere a seed is swept; ordered compaction by wave ballots and prefix counts, sums in double in
@@ -11,6 +13,7 @@
 #include <hip/hip_runtime.h>
 #include "pf_api_internal.h"
 #include "pf_philox.h"
+#include "pf_surface.h"
 
 namespace {
 
@@ -18,65 +21,6 @@ constexpr int DU_T = 256;                       // threads per seed
 constexpr int DU_W = DU_T / 64;
 constexpr int DU_J = PF_DISK_MAX_RADII;
 constexpr int DU_TILE = PF_DISK_TILE;           // members staged in LDS at a time
-
-// ---- closest point of a triangle ------------------------------------------------------------------------------------------
-// The triangle (a, b, c) is given relative to the query point; the result is the closest point, relative to it too.  The same
-// Voronoi-region classification as eval_metrics.hip's tri_d2 (Ericson 5.1.5), which returns only the distance.
-__device__ __forceinline__ void seg_closest(double ax, double ay, double az, double bx, double by, double bz, double* q) {
-    const double ex = bx - ax, ey = by - ay, ez = bz - az;
-    const double ee = ex * ex + ey * ey + ez * ez;
-    double t = ee > 0.0 ? -(ax * ex + ay * ey + az * ez) / ee : 0.0;
-    t = t < 0.0 ? 0.0 : (t > 1.0 ? 1.0 : t);
-    q[0] = ax + t * ex; q[1] = ay + t * ey; q[2] = az + t * ez;
-}
-
-__device__ __forceinline__ void tri_closest(double ax, double ay, double az, double bx, double by, double bz, double cx,
-                                            double cy, double cz, double* q) {
-    const double abx = bx - ax, aby = by - ay, abz = bz - az;
-    const double acx = cx - ax, acy = cy - ay, acz = cz - az;
-    const double d1 = -(abx * ax + aby * ay + abz * az), d2 = -(acx * ax + acy * ay + acz * az);
-    if (d1 <= 0.0 && d2 <= 0.0) { q[0] = ax; q[1] = ay; q[2] = az; return; }                        // vertex a
-    const double d3 = -(abx * bx + aby * by + abz * bz), d4 = -(acx * bx + acy * by + acz * bz);
-    if (d3 >= 0.0 && d4 <= d3) { q[0] = bx; q[1] = by; q[2] = bz; return; }                          // vertex b
-    const double vc = d1 * d4 - d3 * d2;
-    if (vc <= 0.0 && d1 >= 0.0 && d3 <= 0.0) {                                                       // edge ab
-        const double den = d1 - d3, t = den > 0.0 ? d1 / den : 0.0;
-        q[0] = ax + t * abx; q[1] = ay + t * aby; q[2] = az + t * abz;
-        return;
-    }
-    const double d5 = -(abx * cx + aby * cy + abz * cz), d6 = -(acx * cx + acy * cy + acz * cz);
-    if (d6 >= 0.0 && d5 <= d6) { q[0] = cx; q[1] = cy; q[2] = cz; return; }                          // vertex c
-    const double vb = d5 * d2 - d1 * d6;
-    if (vb <= 0.0 && d2 >= 0.0 && d6 <= 0.0) {                                                       // edge ac
-        const double den = d2 - d6, t = den > 0.0 ? d2 / den : 0.0;
-        q[0] = ax + t * acx; q[1] = ay + t * acy; q[2] = az + t * acz;
-        return;
-    }
-    const double va = d3 * d6 - d5 * d4;
-    if (va <= 0.0 && d4 - d3 >= 0.0 && d5 - d6 >= 0.0) {                                             // edge bc
-        const double den = (d4 - d3) + (d5 - d6), t = den > 0.0 ? (d4 - d3) / den : 0.0;
-        q[0] = bx + t * (cx - bx); q[1] = by + t * (cy - by); q[2] = bz + t * (cz - bz);
-        return;
-    }
-    const double nx = aby * acz - abz * acy, ny = abz * acx - abx * acz, nz = abx * acy - aby * acx;
-    const double nn = nx * nx + ny * ny + nz * nz;
-    if (!(va + vb + vc > 0.0) || !(nn > 0.0)) {                                                       // degenerate: its edges
-        double e[3][3];
-        seg_closest(ax, ay, az, bx, by, bz, e[0]);
-        seg_closest(bx, by, bz, cx, cy, cz, e[1]);
-        seg_closest(cx, cy, cz, ax, ay, az, e[2]);
-        int k = 0;
-        double best = e[0][0] * e[0][0] + e[0][1] * e[0][1] + e[0][2] * e[0][2];
-        for (int i = 1; i < 3; ++i) {
-            const double d = e[i][0] * e[i][0] + e[i][1] * e[i][1] + e[i][2] * e[i][2];
-            if (d < best) { best = d; k = i; }
-        }
-        q[0] = e[k][0]; q[1] = e[k][1]; q[2] = e[k][2];
-        return;
-    }
-    const double h = (nx * ax + ny * ay + nz * az) / nn;                                              // face: the foot of the normal
-    q[0] = h * nx; q[1] = h * ny; q[2] = h * nz;
-}
 
 __global__ void closest_points_kernel(const float* __restrict__ pts, int P, const float* __restrict__ tris, int F,
                                       const int* __restrict__ face, float* __restrict__ out) {
@@ -119,11 +63,13 @@ __global__ void mesh_sample_kernel(const float* __restrict__ tris, int F, const 
 struct R2 { float v[DU_J]; };                   // squared radii, ascending; unused slots hold the largest
 struct RD { double v[DU_J]; };                  // the radii themselves
 
-// the smallest j with |q - seed|^2 <= r_j^2, J when the point is outside every ball; the seed is subtracted first, so the
-// squares are of O(r) numbers
-__device__ __forceinline__ int disk_level(const float* __restrict__ q, float sx, float sy, float sz, const R2& r2, int J) {
-    const float dx = q[0] - sx, dy = q[1] - sy, dz = q[2] - sz;
-    const float d2 = dx * dx + dy * dy + dz * dz;
+// the smallest j with D2 <= r_j^2, J when the point is outside every disk.  D2 = |q - seed|^2 (pf_surface.h seed_d2); REACH:
+// the larger of that and the bottleneck value of the point's face in the seed's reach row (+inf for a face not in it)
+template <bool REACH>
+__device__ __forceinline__ int disk_level(const float* __restrict__ mapped, int i, int s, float sx, float sy, float sz,
+                                          const R2& r2, int J, const PfReach& R) {
+    float d2 = seed_d2(mapped + (size_t)i * 3, sx, sy, sz);
+    if (REACH) d2 = fmaxf(d2, reach_b2(R, s, R.face[i]));
     int lev = J;
 #pragma unroll
     for (int j = DU_J - 1; j >= 0; --j)
@@ -131,8 +77,9 @@ __device__ __forceinline__ int disk_level(const float* __restrict__ q, float sx,
     return lev;
 }
 
+template <bool REACH>
 __global__ __launch_bounds__(DU_T) void disk_count_kernel(const float* __restrict__ mapped, int N, const float* __restrict__ seeds,
-                                                          R2 r2, int J, int* __restrict__ counts) {
+                                                          R2 r2, int J, int* __restrict__ counts, PfReach R) {
     __shared__ int wcnt[DU_W][DU_J];
     const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float sx = seeds[(size_t)s * 3], sy = seeds[(size_t)s * 3 + 1], sz = seeds[(size_t)s * 3 + 2];
@@ -141,7 +88,7 @@ __global__ __launch_bounds__(DU_T) void disk_count_kernel(const float* __restric
     for (int j = 0; j < DU_J; ++j) cnt[j] = 0;
     for (int i0 = 0; i0 < N; i0 += DU_T) {       // uniform trip count: the ballots see whole waves
         const int i = i0 + tid;
-        const int lev = i < N ? disk_level(mapped + (size_t)i * 3, sx, sy, sz, r2, J) : J;
+        const int lev = i < N ? disk_level<REACH>(mapped, i, s, sx, sy, sz, r2, J, R) : J;
 #pragma unroll
         for (int j = 0; j < DU_J; ++j) cnt[j] += __popcll(__ballot(lev <= j));
     }
@@ -156,9 +103,10 @@ __global__ __launch_bounds__(DU_T) void disk_count_kernel(const float* __restric
     }
 }
 
+template <bool REACH>
 __global__ __launch_bounds__(DU_T) void disk_fill_kernel(const float* __restrict__ mapped, int N, const float* __restrict__ seeds,
                                                          R2 r2, int J, const long long* __restrict__ offsets,
-                                                         int* __restrict__ member, int* __restrict__ level) {
+                                                         int* __restrict__ member, int* __restrict__ level, PfReach R) {
     __shared__ int wsum[DU_W];
     const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float sx = seeds[(size_t)s * 3], sy = seeds[(size_t)s * 3 + 1], sz = seeds[(size_t)s * 3 + 2];
@@ -166,7 +114,7 @@ __global__ __launch_bounds__(DU_T) void disk_fill_kernel(const float* __restrict
     long long base = 0;
     for (int i0 = 0; i0 < N; i0 += DU_T) {
         const int i = i0 + tid;
-        const int lev = i < N ? disk_level(mapped + (size_t)i * 3, sx, sy, sz, r2, J) : J;
+        const int lev = i < N ? disk_level<REACH>(mapped, i, s, sx, sy, sz, r2, J, R) : J;
         const bool in = lev < J;
         const unsigned long long m = __ballot(in);
         if (lane == 0) wsum[wave] = __popcll(m);
@@ -332,7 +280,19 @@ extern "C" int pf_disk_count(const float* mapped, int N, const float* seeds, int
     if (!mapped || !seeds || !radii || !counts) return PF_ERR_NULL;
     R2 r2;
     if (N <= 0 || S <= 0 || N > (1 << 26) || S > (1 << 24) || !radii_ok(radii, J, &r2)) return PF_ERR_SHAPE;
-    hipLaunchKernelGGL(disk_count_kernel, dim3(S), dim3(DU_T), 0, (hipStream_t)stream, mapped, N, seeds, r2, J, counts);
+    hipLaunchKernelGGL(disk_count_kernel<false>, dim3(S), dim3(DU_T), 0, (hipStream_t)stream, mapped, N, seeds, r2, J, counts,
+                       PfReach{});
+    return pf_last_launch_status();
+}
+
+extern "C" int pf_disk_count_reach(const float* mapped, int N, const float* seeds, int S, const double* radii, int J,
+                                   const int* mapped_face, const long long* reach_offsets, const int* rface, const float* rb2,
+                                   int* counts, void* stream) {
+    if (!mapped || !seeds || !radii || !counts || !mapped_face || !reach_offsets || !rface || !rb2) return PF_ERR_NULL;
+    R2 r2;
+    if (N <= 0 || S <= 0 || N > (1 << 26) || S > (1 << 24) || !radii_ok(radii, J, &r2)) return PF_ERR_SHAPE;
+    hipLaunchKernelGGL(disk_count_kernel<true>, dim3(S), dim3(DU_T), 0, (hipStream_t)stream, mapped, N, seeds, r2, J, counts,
+                       PfReach{mapped_face, reach_offsets, rface, rb2});
     return pf_last_launch_status();
 }
 
@@ -341,8 +301,20 @@ extern "C" int pf_disk_fill(const float* mapped, int N, const float* seeds, int 
     if (!mapped || !seeds || !radii || !offsets || !member || !level) return PF_ERR_NULL;
     R2 r2;
     if (N <= 0 || S <= 0 || N > (1 << 26) || S > (1 << 24) || !radii_ok(radii, J, &r2)) return PF_ERR_SHAPE;
-    hipLaunchKernelGGL(disk_fill_kernel, dim3(S), dim3(DU_T), 0, (hipStream_t)stream, mapped, N, seeds, r2, J, offsets, member,
-                       level);
+    hipLaunchKernelGGL(disk_fill_kernel<false>, dim3(S), dim3(DU_T), 0, (hipStream_t)stream, mapped, N, seeds, r2, J, offsets,
+                       member, level, PfReach{});
+    return pf_last_launch_status();
+}
+
+extern "C" int pf_disk_fill_reach(const float* mapped, int N, const float* seeds, int S, const double* radii, int J,
+                                  const int* mapped_face, const long long* reach_offsets, const int* rface, const float* rb2,
+                                  const long long* offsets, int* member, int* level, void* stream) {
+    if (!mapped || !seeds || !radii || !offsets || !member || !level || !mapped_face || !reach_offsets || !rface || !rb2)
+        return PF_ERR_NULL;
+    R2 r2;
+    if (N <= 0 || S <= 0 || N > (1 << 26) || S > (1 << 24) || !radii_ok(radii, J, &r2)) return PF_ERR_SHAPE;
+    hipLaunchKernelGGL(disk_fill_kernel<true>, dim3(S), dim3(DU_T), 0, (hipStream_t)stream, mapped, N, seeds, r2, J, offsets,
+                       member, level, PfReach{mapped_face, reach_offsets, rface, rb2});
     return pf_last_launch_status();
 }
 

@@ -2,7 +2,8 @@
 point-to-surface column) on the GPU:
 
   python -m puflow_amd.evaluate --pred DIR --gt DIR --save_path DIR [--mesh DIR] [--write_p2m] [--cloud_batch N]
-                                [--emd_levels_top 7] [--uniform [--uniform_seeds 1000] [--uniform_seed 0] [--write_disks]]
+                                [--emd_levels_top 7] [--uniform [--uniform_seeds 1000] [--uniform_seed 0] [--write_disks]
+                                                       [--uniform_disks ball|surface]]
 
 Every `<name>.xyz` of --pred with a `<name>.xyz` in --gt is scored (evaluate.py:187-195): CD, EMD (approx-match), Hausdorff
 and JSD (puflow_amd.metrics).  P2F, the point-to-surface distance of the predicted points: with --mesh it is computed from
@@ -17,8 +18,13 @@ With --mesh the disks are made on the GPU: --uniform_seeds seeds on the surface 
 mapped to their closest mesh points, and around every seed the mapped points within r_j = sqrt(p_j A / pi), p = 0.4 .. 1.2 % of
 the area A; --write_disks also writes `<pred>_disk_idx.txt`, `<pred>_radius.txt` and `<pred>_point2mesh_distance.txt`, the
 three files the reference reads.  Without --mesh those three files are read, whoever wrote them, as evaluate.py:256-262 does.
-Disks made from a mesh are Euclidean balls (the pre-filter of evaluation.cpp:97-100, without its geodesic refinement): they
-differ from geodesic disks on thin parts, where a ball also takes in points of the opposite side.
+--uniform_disks ball (the default): disks made from a mesh are Euclidean balls (the pre-filter of evaluation.cpp:97-100,
+without its geodesic refinement); on parts thinner than the radius a ball also takes in points of the opposite side.
+--uniform_disks surface: a ball's member stays only when its face is connected to the seed's face along the surface inside a
+ball no larger than the disk's (metrics.surface_reach, r_stop = the largest radius; the seeds' faces from the sampler, the
+points' faces from the P2F search).  This restriction is the project's own: it is not a geodesic length, and its parity with
+the reference's CGAL geodesic disks is unpinned - the reference's binary never writes them.  --write_disks writes whichever
+disks were made.
 
 The reference's quirks, kept or fixed:
   - kept: a file's JSD appears in its row only when it has a P2F (evaluate.py:255), for CSV compatibility; the summary JSD
@@ -80,9 +86,12 @@ def _batches(items, key, size):
 
 def evaluate(pred_dir: str, gt_dir: str, save_path: str, mesh_dir: str = None, write_p2m: bool = False,
              cloud_batch: int = 16, emd_levels_top: int = 7, device=None, uniform: bool = False, uniform_seeds: int = 1000,
-             uniform_seed: int = 0, write_disks: bool = False):
+             uniform_seed: int = 0, write_disks: bool = False, uniform_disks: str = "ball"):
     """Score the directory; returns (per-file rows, summary row) as written to evaluation.csv."""
-    uni = dict(seeds=int(uniform_seeds), seed=int(uniform_seed), write=bool(write_disks)) if uniform else None
+    if uniform_disks not in ("ball", "surface"):
+        raise ValueError(f"uniform_disks is 'ball' or 'surface', got {uniform_disks!r}")
+    uni = dict(seeds=int(uniform_seeds), seed=int(uniform_seed), write=bool(write_disks),
+               surface=uniform_disks == "surface") if uniform else None
     device = torch.device(device or "cuda:0")
     pairs = pair_paths(pred_dir, gt_dir)
     if not pairs:
@@ -139,7 +148,7 @@ def evaluate(pred_dir: str, gt_dir: str, save_path: str, mesh_dir: str = None, w
 
 def _p2f(pred_path, pred_gpu, i, name, mesh_dir, write_p2m, uni=None):
     """(the file's point-to-surface distances (float32 [N]) or None, its uniformity [5] or None).  uni: None, or the
-    --uniform settings dict(seeds, seed, write)."""
+    --uniform settings dict(seeds, seed, write, surface)."""
     out_path = pred_path[:-4] + "_point2mesh_distance.xyz"
     prefix = pred_path[:-4]
     dev = pred_gpu.device
@@ -172,8 +181,12 @@ def _p2f(pred_path, pred_gpu, i, name, mesh_dir, write_p2m, uni=None):
     if uni is not None:
         radii, _ = metrics.mesh_area_radii(verts, faces)
         mapped = metrics.mapped_points(pred_gpu[i], vt, ft, face=face)
-        seeds, _, _ = metrics.sample_mesh(vt, ft, uni["seeds"], uni["seed"])
-        _, csr = metrics.disks(mapped, seeds, radii)
+        seeds, seed_face, _ = metrics.sample_mesh(vt, ft, uni["seeds"], uni["seed"])
+        if uni.get("surface"):
+            reach = metrics.surface_reach(seeds, seed_face, vt, ft, float(radii[-1]))
+            _, csr = metrics.disks(mapped, seeds, radii, reach=reach, mapped_face=face)
+        else:
+            _, csr = metrics.disks(mapped, seeds, radii)
         u = metrics.uniformity(mapped, csr, radii)
         if uni["write"]:
             metrics.write_disk_files(prefix, pred_gpu[i], dist, mapped, csr, radii)
@@ -195,9 +208,12 @@ def main(argv=None):
     ap.add_argument("--cloud_batch", type=int, default=16)
     ap.add_argument("--emd_levels_top", type=int, default=7)
     ap.add_argument("--uniform", action="store_true",
-                    help="fill uniform_0..4: with --mesh from disks made on the GPU - Euclidean balls around seeds on the mesh, "
-                         "which differ from geodesic disks on thin parts; without --mesh from <pred>_disk_idx.txt, _radius.txt "
-                         "and _point2mesh_distance.txt")
+                    help="fill uniform_0..4: with --mesh from disks made on the GPU around seeds on the mesh (--uniform_disks); "
+                         "without --mesh from <pred>_disk_idx.txt, _radius.txt and _point2mesh_distance.txt")
+    ap.add_argument("--uniform_disks", choices=("ball", "surface"), default="ball",
+                    help="ball: Euclidean balls, which on thin parts also take in the opposite side; surface: only the ball's "
+                         "points connected to the seed along the surface inside it (not a geodesic length; parity with CGAL's "
+                         "geodesic disks unpinned)")
     ap.add_argument("--uniform_seeds", type=int, default=1000, help="seeds (disks per radius) per mesh")
     ap.add_argument("--uniform_seed", type=int, default=0, help="key of the seeds' random numbers")
     ap.add_argument("--write_disks", action="store_true",
@@ -205,7 +221,7 @@ def main(argv=None):
     a = ap.parse_args(argv)
     _, summary = evaluate(os.path.abspath(a.pred), os.path.abspath(a.gt), a.save_path, a.mesh, a.write_p2m, a.cloud_batch,
                           a.emd_levels_top, uniform=a.uniform, uniform_seeds=a.uniform_seeds, uniform_seed=a.uniform_seed,
-                          write_disks=a.write_disks)
+                          write_disks=a.write_disks, uniform_disks=a.uniform_disks)
     print(f"Evaluation: {a.save_path}")
     print(summary_line(summary))
 

@@ -4,10 +4,15 @@ binary evaluation/evaluation_code/evaluation.cpp) on the GPU.
 Every function takes torch tensors on the GPU; a CPU tensor raises PuflowHipError (there is no CPU fallback).  The hot parts are
 HIP (csrc/eval_metrics.hip: approx-match EMD and point-to-mesh distance; csrc/knn.hip pf_nn1: the nearest-neighbour searches
 of CD / Hausdorff and of the JSD occupancy lookup; csrc/eval_uniform.hip: the seeds, disks and in-disk statistic of the
-uniformity columns); torch only gathers, sorts and reduces small arrays around them.
+uniformity columns; csrc/surface_reach.hip: the bottleneck field behind surface disks); torch only gathers, sorts and reduces
+small arrays around them.
 
-Uniformity (evaluate.py:105-165 analyze_uniform): disks made here from a mesh are Euclidean balls around seeds on the surface,
-which differ from the geodesic disks of PU-GAN's definition on thin parts, where a ball also reaches the opposite side.
+Uniformity (evaluate.py:105-165 analyze_uniform): `disks` makes either Euclidean balls around seeds on the surface - which on
+parts thinner than the radius also take in the opposite side - or, given `surface_reach`, surface disks: a point belongs when
+it is inside the ball AND its face is connected to the seed's face along the surface inside a ball no larger than the radius
+(the bottleneck field).  That restriction is this project's own definition.  It is not a geodesic
+length, and its parity with the CGAL geodesic disks of PU-GAN's definition (evaluation.cpp:88-107) is unpinned: the
+reference's binary never writes its disks.
 """
 from __future__ import annotations
 
@@ -248,15 +253,145 @@ def mapped_points(points: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor
     return out
 
 
-def disks(mapped: torch.Tensor, seeds: torch.Tensor, radii):
+REACH_ST_START, REACH_ST_ITER, REACH_ST_ROW = 1, 2, 4          # include/puflow_hip.h: PF_REACH_ST_*
+
+
+def face_adjacency(verts: torch.Tensor, faces: torch.Tensor):
+    """(offsets [F+1] int64, adj [nnz] int32): row f lists, ascending, the other faces that share a vertex with face f, after
+    welding vertices of equal coordinates (torch.unique(dim=0) on the device; +0 and -0 weld) - a triangle soup in which every
+    face has its own three vertices gets the adjacency of its indexed mesh.  torch ops only: sorts of [3F] and [sum deg^2]."""
+    if not (torch.is_tensor(verts) and torch.is_tensor(faces) and verts.is_cuda and faces.is_cuda):
+        raise _lib.PuflowHipError("face_adjacency needs GPU tensors (no CPU fallback)")
+    return _vertex_sharing_faces(ops._f32c(verts), faces.long())
+
+
+def _vertex_sharing_faces(v: torch.Tensor, f: torch.Tensor):
+    F = f.shape[0]
+    _, weld = torch.unique(v, dim=0, return_inverse=True)
+    vid = weld[f].reshape(-1)                                                    # [3F] welded vertex of every corner
+    fid = torch.arange(F, device=f.device).repeat_interleave(3)
+    vs, order = torch.sort(vid, stable=True)
+    fs = fid[order]                                                              # faces grouped by vertex
+    deg = torch.bincount(vs, minlength=int(weld.max()) + 1)
+    start = torch.cumsum(deg, 0) - deg
+    d = deg[vs]                                                                  # every corner pairs with its vertex's whole group
+    a = fs.repeat_interleave(d)
+    first = start[vs].repeat_interleave(d)
+    within = torch.arange(a.shape[0], device=f.device) - (torch.cumsum(d, 0) - d).repeat_interleave(d)
+    b = fs[first + within]
+    key = torch.unique(a[a != b] * F + b[a != b])                                # sorted: by face, then by neighbour
+    offsets = torch.zeros(F + 1, dtype=torch.int64, device=f.device)
+    offsets[1:] = torch.bincount(key // F, minlength=F).cumsum(0)
+    return offsets, (key % F).int()
+
+
+def surface_reach(src: torch.Tensor, src_face: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, r_stop,
+                  adjacency=None, return_info: bool = False):
+    """The bottleneck field around the sources src [S,3], each on face src_face [S] of the mesh, inside the balls of radius
+    r_stop (a number, or [S]): the CSR (offsets [S+1] int64, rface [nnz] int32, rb2 [nnz] float32).  Row s lists, ascending,
+    the faces whose closest point is within r_stop[s] of the source, with b2 = the smallest squared radius of a ball around the
+    source inside which the face is connected to the source's face over vertex-sharing faces (`face_adjacency`, or
+    `adjacency` when the caller has it) - +inf when no such path stays inside r_stop.  Finite values are exact, whatever
+    r_stop.  The surface distance of a point q on face f is D2 = max(|q - s|^2, b2(f)) (`disks(..., reach=)`,
+    `surface_distances`).  return_info: also {"rd2" [nnz], "sweeps" [S], "status"}.  (pf_reach_count / _fill / _relax)"""
+    lib = _lib.load()
+    tris = _tris(verts, faces, "surface_reach")
+    sd = ops._f32c(src)
+    dev, S, F = sd.device, sd.shape[0], tris.shape[0]
+    sf = src_face.to(device=dev, dtype=torch.int32).contiguous()
+    rs = torch.from_numpy(np.asarray(r_stop.cpu() if torch.is_tensor(r_stop) else r_stop, dtype=np.float64).reshape(-1))
+    if rs.numel() == 1:
+        rs = rs.expand(S)
+    if sd.dim() != 2 or sd.shape[1] != 3 or sf.shape[0] != S or rs.shape[0] != S:
+        raise _lib.PuflowHipError(f"surface_reach: src {tuple(sd.shape)}, src_face {tuple(sf.shape)}, r_stop {tuple(rs.shape)}")
+    r2 = (rs * rs).float().to(dev).contiguous()                                  # fp32(r^2), as the disks round their radii
+    adj_off, adj = face_adjacency(verts, faces) if adjacency is None else adjacency
+    adj_off, adj = adj_off.long().contiguous(), adj.int().contiguous()
+    if adj_off.shape[0] != F + 1 or int(adj_off[-1]) != adj.shape[0]:
+        raise _lib.PuflowHipError("surface_reach: the adjacency is not a CSR over the mesh's faces")
+    if adj.numel() == 0:
+        adj = adj.new_zeros(1)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    counts = torch.empty(S, dtype=torch.int32, device=dev)
+    _lib.check(lib.pf_reach_count(tris.data_ptr(), F, sd.data_ptr(), sf.data_ptr(), r2.data_ptr(), S, counts.data_ptr(),
+                                  status.data_ptr(), ops._stream()), "pf_reach_count")
+    offsets = torch.zeros(S + 1, dtype=torch.int64, device=dev)
+    offsets[1:] = counts.long().cumsum(0)
+    nnz = int(offsets[-1])                                                       # the host sizes the buffers
+    rface = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)
+    rd2 = torch.empty(max(nnz, 1), dtype=torch.float32, device=dev)
+    rb2 = torch.full((max(nnz, 1),), float("inf"), dtype=torch.float32, device=dev)
+    sweeps = torch.zeros(S, dtype=torch.int32, device=dev)
+    _lib.check(lib.pf_reach_fill(tris.data_ptr(), F, sd.data_ptr(), sf.data_ptr(), r2.data_ptr(), S, offsets.data_ptr(),
+                                 rface.data_ptr(), rd2.data_ptr(), status.data_ptr(), ops._stream()), "pf_reach_fill")
+    _lib.check(lib.pf_reach_relax(offsets.data_ptr(), rface.data_ptr(), rd2.data_ptr(), F, adj_off.data_ptr(), adj.data_ptr(),
+                                  sf.data_ptr(), S, rb2.data_ptr(), sweeps.data_ptr(), status.data_ptr(), ops._stream()),
+               "pf_reach_relax")
+    st = int(status)
+    if st & (REACH_ST_ITER | REACH_ST_ROW):
+        raise _lib.PuflowHipError("surface_reach: a row did not settle within its length + 1 sweeps, or lists a face outside the mesh")
+    csr = (offsets, rface[:nnz], rb2[:nnz])
+    if return_info:
+        return csr, {"rd2": rd2[:nnz], "sweeps": sweeps, "status": st}
+    return csr
+
+
+def _reach_args(reach, face, S: int, N: int, dev, what: str):
+    if reach is None or face is None:
+        raise _lib.PuflowHipError(f"{what}: reach and the points' faces go together")
+    off, rface, rb2 = reach
+    if not (off.is_cuda and rface.is_cuda and rb2.is_cuda and face.is_cuda):
+        raise _lib.PuflowHipError(f"{what} needs GPU tensors (no CPU fallback)")
+    off, rface, rb2 = off.long().contiguous(), rface.int().contiguous(), rb2.float().contiguous()
+    fi = face.to(device=dev, dtype=torch.int32).contiguous()
+    nnz = rface.shape[0]
+    if off.shape[0] != S + 1 or fi.shape[0] != N or rb2.shape[0] != nnz or int(off[0]) < 0 or int(off[-1]) > nnz or \
+            bool((off[1:] < off[:-1]).any()):
+        raise _lib.PuflowHipError(f"{what}: the reach CSR does not describe {S} sources, or the faces not {N} points")
+    if nnz == 0:
+        rface, rb2 = rface.new_zeros(1), rb2.new_zeros(1)
+    return fi, off, rface, rb2
+
+
+def surface_distances(points: torch.Tensor, points_face: torch.Tensor, src: torch.Tensor, reach) -> torch.Tensor:
+    """D2 [S,N] float32: max(|q - s|^2, b2(face(q))) of every point of points [N,3] (on faces points_face [N]) from every
+    source - +inf for a point whose face the source's reach row does not hold (pf_reach_point_d2)."""
+    lib = _lib.load()
+    p, sd = ops._f32c(points), ops._f32c(src)
+    N, S = p.shape[0], sd.shape[0]
+    fi, off, rface, rb2 = _reach_args(reach, points_face, S, N, p.device, "surface_distances")
+    out = torch.empty((S, N), dtype=torch.float32, device=p.device)
+    _lib.check(lib.pf_reach_point_d2(p.data_ptr(), N, fi.data_ptr(), sd.data_ptr(), S, off.data_ptr(), rface.data_ptr(),
+                                     rb2.data_ptr(), out.data_ptr(), ops._stream()), "pf_reach_point_d2")
+    return out
+
+
+def disks(mapped: torch.Tensor, seeds: torch.Tensor, radii, reach=None, mapped_face: torch.Tensor = None):
     """The points of mapped [N,3] inside the Euclidean balls of radii [J] (ascending) around seeds [S,3].
     -> (counts [S,J] int32, (offsets [S+1] int64, member [nnz] int32, level [nnz] int32)): row s of the CSR lists the members
-    of the largest ball of seed s in ascending index, each with the smallest j whose ball holds it (pf_disk_count / _fill)."""
+    of the largest ball of seed s in ascending index, each with the smallest j whose ball holds it (pf_disk_count / _fill).
+    reach (`surface_reach` of the seeds with r_stop >= the largest radius) and mapped_face [N] (the face every mapped point
+    lies on): surface disks instead - a point is in disk j when max(|q - s|^2, b2(face(q))) <= fp32(r_j^2), so a ball's
+    members on a part of the surface not connected to the seed inside that ball are left out (pf_disk_count_reach /
+    _fill_reach: the same kernels, the same CSR)."""
     lib = _lib.load()
     m, sd = ops._f32c(mapped), ops._f32c(seeds)
     r, rc = _radii(radii)
     N, S, J = m.shape[0], sd.shape[0], len(r)
     counts = torch.empty((S, J), dtype=torch.int32, device=m.device)
+    if reach is not None or mapped_face is not None:
+        fi, roff, rface, rb2 = _reach_args(reach, mapped_face, S, N, m.device, "disks")
+        extra = (fi.data_ptr(), roff.data_ptr(), rface.data_ptr(), rb2.data_ptr())
+        _lib.check(lib.pf_disk_count_reach(m.data_ptr(), N, sd.data_ptr(), S, rc, J, *extra, counts.data_ptr(), ops._stream()),
+                   "pf_disk_count_reach")
+        offsets = torch.zeros(S + 1, dtype=torch.int64, device=m.device)
+        offsets[1:] = counts[:, J - 1].long().cumsum(0)
+        nnz = int(offsets[-1])
+        member = torch.empty(max(nnz, 1), dtype=torch.int32, device=m.device)
+        level = torch.empty(max(nnz, 1), dtype=torch.int32, device=m.device)
+        _lib.check(lib.pf_disk_fill_reach(m.data_ptr(), N, sd.data_ptr(), S, rc, J, *extra, offsets.data_ptr(), member.data_ptr(),
+                                          level.data_ptr(), ops._stream()), "pf_disk_fill_reach")
+        return counts, (offsets, member[:nnz], level[:nnz])
     _lib.check(lib.pf_disk_count(m.data_ptr(), N, sd.data_ptr(), S, rc, J, counts.data_ptr(), ops._stream()), "pf_disk_count")
     offsets = torch.zeros(S + 1, dtype=torch.int64, device=m.device)
     offsets[1:] = counts[:, J - 1].long().cumsum(0)

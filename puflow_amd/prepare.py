@@ -1,7 +1,7 @@
 """Data preparation CLI - from meshes to what the other entry points read, on the GPU (puflow_amd.sampling):
 
   python -m puflow_amd.prepare --mesh DIR --out DIR [--seed 0] [--ratio 5]
-                               [--patches P [--num_point 256] [--up_ratio 4] [--cloud_points 2500]]
+                               [--patches P [--num_point 256] [--up_ratio 4] [--cloud_points 2500] [--patch_metric ball|surface]]
                                [--clouds 2048,8192]
 
 --patches P writes `<out>/patches.npz`: P patches of every `<mesh>/<name>.off` (sorted by name), arrays `poisson_<num_point>`
@@ -12,7 +12,10 @@ writer.  Each count has its own Philox seed (--seed + 3 + its position; the patc
 no subset of the ground truth.  The reference has no counterpart: its files came from PU-GAN's Meshlab preparation.
 
 The same arguments give the same bytes: the samples depend on (mesh, seed, counts) only, and the .npz is written with a fixed
-time stamp.  Distances are Euclidean (sampling.py's head).
+time stamp.  The elimination's distances are Euclidean; a patch is cropped around its seed by Euclidean distance
+(--patch_metric ball, the default) or by the surface distance of metrics.surface_reach (--patch_metric surface: on a thin part
+a piece of one side instead of a two-sided slab; the project's own surface restriction, not a geodesic length - sampling.py's
+head).
 """
 from __future__ import annotations
 
@@ -47,7 +50,7 @@ def mesh_paths(mesh_dir: str):
 
 
 def prepare(mesh_dir: str, out_dir: str, seed: int = 0, ratio: int = 5, patches: int = 0, num_point: int = 256,
-            up_ratio: int = 4, cloud_points: int = 2500, clouds=(), device=None):
+            up_ratio: int = 4, cloud_points: int = 2500, clouds=(), device=None, patch_metric: str = "ball"):
     """Returns the paths written."""
     device = torch.device(device or "cuda:0")
     os.makedirs(out_dir, exist_ok=True)
@@ -60,7 +63,8 @@ def prepare(mesh_dir: str, out_dir: str, seed: int = 0, ratio: int = 5, patches:
         vt, ft = torch.from_numpy(verts).to(device), torch.from_numpy(faces).to(device)
         if patches > 0:
             per_mesh.append({k: v.cpu().numpy() for k, v in
-                             sampling.make_patches(vt, ft, patches, num_point, up_ratio, cloud_points, seed, ratio).items()})
+                             sampling.make_patches(vt, ft, patches, num_point, up_ratio, cloud_points, seed, ratio,
+                                                   metric=patch_metric).items()})
         for i, n in enumerate(clouds):
             pts, _ = sampling.poisson_disk(vt, ft, n, seed + 3 + i, ratio)
             written.append(os.path.join(out_dir, ("input_%d" if i == 0 else "gt_%d") % n, name + ".xyz"))
@@ -82,12 +86,15 @@ def main(argv=None):
     ap.add_argument("--num_point", type=int, default=256)
     ap.add_argument("--up_ratio", type=int, default=4)
     ap.add_argument("--cloud_points", type=int, default=2500, help="points of the cloud the patch seeds are taken from")
+    ap.add_argument("--patch_metric", choices=("ball", "surface"), default="ball",
+                    help="how a patch is cropped around its seed: Euclidean ball, or surface-connected (metrics.surface_reach)")
     ap.add_argument("--clouds", type=str, default="", help="point counts, e.g. 2048,8192: input_<first> and gt_<others>")
     a = ap.parse_args(argv)
     clouds = [int(t) for t in a.clouds.split(",") if t.strip()]
     if a.patches <= 0 and not clouds:
         ap.error("nothing to do: give --patches and / or --clouds")
-    for p in prepare(a.mesh, a.out, a.seed, a.ratio, a.patches, a.num_point, a.up_ratio, a.cloud_points, clouds):
+    for p in prepare(a.mesh, a.out, a.seed, a.ratio, a.patches, a.num_point, a.up_ratio, a.cloud_points, clouds,
+                     patch_metric=a.patch_metric):
         print(p)
 
 

@@ -3,9 +3,13 @@ ready-made - training patches (`poisson_256` / `poisson_1024`) and the 2048- / 8
 counterpart; the method is weighted sample elimination (Yuksel 2015, "Sample Elimination for Generating Poisson Disk Sample
 Sets") over area-weighted surface samples (metrics.sample_mesh), in HIP (csrc/poisson.hip).
 
-Every function takes torch tensors on the GPU; a CPU tensor raises PuflowHipError (there is no CPU fallback).  Distances are
-Euclidean, not geodesic: on parts thinner than 2 r_max candidates of the opposite side count as neighbours, so such parts get
-about the density of one side shared between both ("Poisson-disk sampling").
+Every function takes torch tensors on the GPU; a CPU tensor raises PuflowHipError (there is no CPU fallback).  The
+elimination's neighbour graph is Euclidean, not geodesic: on parts thinner than 2 r_max candidates of the opposite side count
+as neighbours, so such parts get about the density of one side shared between both ("Poisson-disk sampling").  A
+patch's pool is cropped either by Euclidean distance from its seed (`metric="ball"`: on a thin part a two-sided slab) or by
+the surface distance of metrics.surface_reach (`metric="surface"`: only samples connected to the seed along the surface inside
+the ball that holds them) - this project's own surface restriction, not a geodesic length; its parity with PU-GAN's
+geodesic crop is unpinned.
 """
 from __future__ import annotations
 
@@ -148,8 +152,52 @@ def poisson_disk(verts: torch.Tensor, faces: torch.Tensor, m: int, seed: int = 0
     return pool[keep], face[keep]
 
 
+POOL_GROWTHS = 8                       # surface_pool: times r_stop is multiplied by 1.5 before a seed's component is called too small
+
+
+def surface_pool(samples: torch.Tensor, sample_face: torch.Tensor, seeds: torch.Tensor, seed_face: torch.Tensor,
+                 verts: torch.Tensor, faces: torch.Tensor, k: int, adjacency=None) -> torch.Tensor:
+    """idx [P,k] int64: per seed the k samples with the smallest (D2, index), D2 = max(|q - seed|^2, b2(face(q))) the surface
+    distance (metrics.surface_reach / surface_distances), nearest first.  The field is computed inside the ball of r_stop = the
+    Euclidean distance of the min(2k, n)-th nearest sample (pf_knn_large; at most its 8192-th on sets beyond 16384, the
+    largest that search takes there).  A value at or below fp32(r_stop^2) is exact and a true value above it shows as itself or
+    as +inf, so a seed is finished once its k-th smallest value is at or below fp32(r_stop^2): those k are then the k smallest
+    over the whole mesh, wherever r_stop started.  Until then its r_stop grows by 1.5, at most POOL_GROWTHS times; a seed still
+    short after that lies on a component of the mesh too small for its pool, and raises."""
+    k = int(k)
+    n, P = samples.shape[0], seeds.shape[0]
+    if k > n:
+        raise ValueError(f"surface_pool: {k} samples wanted of {n}")
+    if adjacency is None:
+        adjacency = metrics.face_adjacency(verts, faces)
+    kk = min(2 * k, n) if n <= 16384 else min(2 * k, 8192)
+    dist, _ = ops.KNN(kk, transpose_mode=True)(samples[None], seeds[None])
+    r_stop = dist[0, :, -1].double().sqrt().cpu().numpy()                   # KNN's distances are squared, ascending
+    idx = torch.empty((P, k), dtype=torch.int64, device=samples.device)
+    todo = np.arange(P)
+    for growth in range(POOL_GROWTHS + 1):
+        sel = torch.from_numpy(todo).to(samples.device)
+        reach = metrics.surface_reach(seeds[sel], seed_face[sel], verts, faces, r_stop[todo], adjacency)
+        d2 = metrics.surface_distances(samples, sample_face, seeds[sel], reach)
+        val, order = torch.sort(d2, dim=1, stable=True)                     # (D2, index)
+        r2 = torch.from_numpy(r_stop[todo] * r_stop[todo]).float().to(val.device)      # fp32(r^2), as surface_reach rounds it
+        ok_t = val[:, k - 1] <= r2
+        idx[sel[ok_t]] = order[:, :k][ok_t]
+        ok = ok_t.cpu().numpy()
+        if ok.all():
+            return idx
+        if growth == POOL_GROWTHS:
+            b = int(np.flatnonzero(~ok)[0])                                 # the first seed still short
+            faces_reached = int(torch.isfinite(reach[2][int(reach[0][b]):int(reach[0][b + 1])]).sum())
+            raise _lib.PuflowHipError(f"surface_pool: seed {int(todo[b])} lies on a component of the mesh too small for its pool: "
+                                      f"after {POOL_GROWTHS} growths of r_stop {faces_reached} faces are connected to it, holding "
+                                      f"{int(torch.isfinite(val[b]).sum())} of the {k} samples wanted")
+        todo = todo[~ok]
+        r_stop[todo] *= 1.5
+
+
 def make_patches(verts: torch.Tensor, faces: torch.Tensor, n_patches: int, num_point: int = 256, up_ratio: int = 4,
-                 cloud_points: int = 2500, seed: int = 0, ratio: int = 5, return_pools: bool = False):
+                 cloud_points: int = 2500, seed: int = 0, ratio: int = 5, return_pools: bool = False, metric: str = "ball"):
     """Training patches of one mesh, un-normalised (data.load_patch_arrays normalises):
     {"poisson_<num_point>": [P, num_point, 3], "poisson_<num_point * up_ratio>": [P, num_point * up_ratio, 3]} on the GPU.
     The patch seeds are a farthest-point sample of poisson_disk(cloud_points, seed).  A patch's ground truth is the
@@ -157,18 +205,29 @@ def make_patches(verts: torch.Tensor, faces: torch.Tensor, n_patches: int, num_p
     eliminated to num_point * up_ratio; its input the same with ratio * num_point out of ratio * cloud_points samples
     (seed + 2), eliminated to num_point - drawn independently of the ground truth, as in PU-GAN's files.  A pool's area is the
     mesh's times its share of the sample set.  All 2 P pools go through one elimination call.
-    return_pools: also {"seeds" [P,3], "input_pool" [P, ratio * num_point, 3], "gt_pool" [P, ratio * num_point * up_ratio, 3]}."""
+    return_pools: also {"seeds" [P,3], "input_pool" [P, ratio * num_point, 3], "gt_pool" [P, ratio * num_point * up_ratio, 3],
+    "seed_face" [P], "input_idx" / "gt_idx": the pools' indices into their sample sets}.
+    metric: "ball" - nearest by Euclidean distance (pf_knn_large); "surface" - the ratio * n_out samples with the smallest
+    (D2, index), D2 = max(|q - seed|^2, b2(face(q))) the surface distance of metrics.surface_reach (`surface_pool`)."""
+    if metric not in ("ball", "surface"):
+        raise ValueError(f"make_patches: metric is 'ball' or 'surface', got {metric!r}")
     n_patches, num_point, up_ratio, cloud_points, ratio = (int(v) for v in (n_patches, num_point, up_ratio, cloud_points, ratio))
     if min(n_patches, num_point, up_ratio, ratio) < 1 or cloud_points < max(n_patches, num_point):
         raise ValueError("make_patches: need positive counts and cloud_points >= max(n_patches, num_point)")
     area = _area(verts, faces)
-    cloud, _ = poisson_disk(verts, faces, cloud_points, seed, ratio)
-    seeds = cloud[ops.furthest_point_sample(cloud[None], n_patches)[0].long()]
-    pools, sizes, targets, areas = [], [], [], []
+    cloud, cloud_face = poisson_disk(verts, faces, cloud_points, seed, ratio)
+    pick = ops.furthest_point_sample(cloud[None], n_patches)[0].long()
+    seeds, seed_face = cloud[pick], cloud_face[pick]
+    adjacency = metrics.face_adjacency(verts, faces) if metric == "surface" else None
+    pools, sizes, targets, areas, idxs = [], [], [], [], []
     for n_out, n_set, sd in ((num_point, ratio * cloud_points, seed + 2), (num_point * up_ratio, ratio * cloud_points * up_ratio, seed + 1)):
-        samples, _, _ = metrics.sample_mesh(verts, faces, n_set, sd)
-        _, idx = ops.KNN(ratio * n_out, transpose_mode=True)(samples[None], seeds[None])
-        pools.append(samples[idx[0]])                                       # [P, ratio * n_out, 3], nearest first
+        samples, sface, _ = metrics.sample_mesh(verts, faces, n_set, sd)
+        if metric == "surface":
+            idx = surface_pool(samples, sface, seeds, seed_face, verts, faces, ratio * n_out, adjacency)[None]
+        else:
+            _, idx = ops.KNN(ratio * n_out, transpose_mode=True)(samples[None], seeds[None])
+        idxs.append(idx[0].long())
+        pools.append(samples[idx[0].long()])                                # [P, ratio * n_out, 3], nearest first
         sizes += [ratio * n_out] * n_patches
         targets += [n_out] * n_patches
         areas += [area * (ratio * n_out) / n_set] * n_patches
@@ -178,5 +237,6 @@ def make_patches(verts: torch.Tensor, faces: torch.Tensor, n_patches: int, num_p
     out = {f"poisson_{num_point}": torch.gather(pools[0], 1, k_in[..., None].expand(-1, -1, 3)),
            f"poisson_{num_point * up_ratio}": torch.gather(pools[1], 1, k_gt[..., None].expand(-1, -1, 3))}
     if return_pools:
-        return out, {"seeds": seeds, "input_pool": pools[0], "gt_pool": pools[1]}
+        return out, {"seeds": seeds, "input_pool": pools[0], "gt_pool": pools[1], "seed_face": seed_face, "input_idx": idxs[0],
+                     "gt_idx": idxs[1]}
     return out
