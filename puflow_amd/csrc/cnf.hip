@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include "pf_api_internal.h"
 #include "pf_mfma.h"
+#include "pf_wave.h"
 
 namespace {
 
@@ -185,6 +186,7 @@ __device__ __forceinline__ f4 cnf_eval(const CnfW& w, int q, f4 y, float t, floa
             }
     }
     // sum over the 4 q groups of the column (lanes col, col+16, col+32, col+48)
+    // (the three sums interleaved, written out: one after the other they cost the step kernels their instruction streams)
     r0 += __shfl_xor(r0, 16); r1 += __shfl_xor(r1, 16); r2 += __shfl_xor(r2, 16);
     r0 += __shfl_xor(r0, 32); r1 += __shfl_xor(r1, 32); r2 += __shfl_xor(r2, 32);
     // (the W1 rows of the record carry the forward's 2 log2e: taken out of the three sums here)
@@ -308,7 +310,7 @@ __global__ __launch_bounds__(CNF_NW * 64) void cnf_step_kernel(CnfStepArgs a) {
             }
         }
     }
-    // workgroup sum (fixed order): lanes -> wave -> workgroup
+    // workgroup sum (fixed order): lanes -> wave -> workgroup (the loop kept: no test launches this host-stepped kernel)
 #pragma unroll
     for (int m = 1; m < 64; m <<= 1) acc += __shfl_xor(acc, m);
     if (lane == 0) red[wave] = acc;
@@ -339,12 +341,11 @@ __device__ __forceinline__ double cnf_partial_total(const double* partial, int n
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int i = threadIdx.x + j * CNF_NW * 64;
-        v[j] = i < nblocks ? __hip_atomic_load(partial + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
+        v[j] = i < nblocks ? PF_LD(partial + i) : 0.0;
     }
     static_assert(CNF_NW * 64 * 4 >= 1024, "a workgroup covers the largest grid in four loads per thread");
     double sum = ((v[0] + v[1]) + v[2]) + v[3];
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) sum += __shfl_xor(sum, m);
+    sum = pf_wave_sum(sum);
     __syncthreads();                                                         // red4 may still be read from an earlier total
     if ((threadIdx.x & 63) == 0) red4[threadIdx.x >> 6] = sum;
     __syncthreads();
@@ -545,8 +546,7 @@ __global__ __launch_bounds__(CNF_NW * 64, PF_CNF_WPE) void cnf_step_dev_kernel(C
             }
         }
     }
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) acc += __shfl_xor(acc, m);
+    acc = pf_wave_sum(acc);
     if (lane == 0) red[wave] = acc;
     __syncthreads();
     // ---- this workgroup's share of the error sum; the workgroup that finishes LAST takes the controller's decision (it was a
@@ -556,7 +556,7 @@ __global__ __launch_bounds__(CNF_NW * 64, PF_CNF_WPE) void cnf_step_dev_kernel(C
     if (threadIdx.x == 0) {
         double tt = 0.0;
         for (int i = 0; i < CNF_NW; ++i) tt += red[i];
-        __hip_atomic_store(a.partial + blockIdx.x, tt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        PF_ST(a.partial + blockIdx.x, tt);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         unsigned* counter = reinterpret_cast<unsigned*>(a.ctl + CTL_ARRIVE);
         last = atomicAdd(counter, 1u) == gridDim.x - 1 ? 1 : 0;
@@ -636,15 +636,14 @@ __global__ __launch_bounds__(CNF_NW * 64) void cnf_init_kernel(CnfInitArgs a) {
             }
         }
     }
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) { acc0 += __shfl_xor(acc0, m); acc1 += __shfl_xor(acc1, m); }
+    acc0 = pf_wave_sum(acc0); acc1 = pf_wave_sum(acc1);
     if (lane == 0) { red[0][wave] = acc0; red[1][wave] = acc1; }
     __syncthreads();
     if (threadIdx.x == 0) {
         double s0 = 0.0, s1 = 0.0;
         for (int i = 0; i < CNF_NW; ++i) { s0 += red[0][i]; s1 += red[1][i]; }
-        __hip_atomic_store(a.partial + (PROBE ? 2048 : 0) + blockIdx.x, s0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (!PROBE) __hip_atomic_store(a.partial + 1024 + blockIdx.x, s1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        PF_ST(a.partial + (PROBE ? 2048 : 0) + blockIdx.x, s0);
+        if (!PROBE) PF_ST(a.partial + 1024 + blockIdx.x, s1);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         unsigned* counter = reinterpret_cast<unsigned*>(a.ctl + CTL_ARRIVE);
         last = atomicAdd(counter, 1u) == gridDim.x - 1 ? 1 : 0;

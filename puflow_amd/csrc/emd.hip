@@ -19,6 +19,7 @@
 // (the literal 3.0 in cu:146 is a double), d2 unfused fp32.
 #include <hip/hip_runtime.h>
 #include "pf_api_internal.h"
+#include "pf_wave.h"
 
 namespace {
 
@@ -49,25 +50,8 @@ struct EmdArgs {
 // over the lanes (a total order: value descending, index ascending; lanes hold distinct indices), done
 // with DPP row rotates + 4 readlanes per reduction instead of 18 dependent ds_bpermute shuffles.  (No measurable change of the 0.87 ms a
 // far-off 32 x 1024 prediction takes, tools/time_emd.py: a bid is bound by its 16 objects per lane x ~26 operations.)
-template <int CTRL>
-__device__ __forceinline__ float emd_dpp_f(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float emd_wave_max(float v) {              // values are never NaN here
-    v = fmaxf(v, emd_dpp_f<0x128>(v)); v = fmaxf(v, emd_dpp_f<0x124>(v));
-    v = fmaxf(v, emd_dpp_f<0x122>(v)); v = fmaxf(v, emd_dpp_f<0x121>(v));
-    const int b = __builtin_bit_cast(int, v);
-    return fmaxf(fmaxf(__builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 0)), __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 16))),
-                 fmaxf(__builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 32)), __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 48))));
-}
-__device__ __forceinline__ unsigned emd_wave_min_u(unsigned v) {
-    v = min(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xf, 0xf, false));
-    v = min(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x124, 0xf, 0xf, false));
-    v = min(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x122, 0xf, 0xf, false));
-    v = min(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x121, 0xf, 0xf, false));
-    return min(min((unsigned)__builtin_amdgcn_readlane((int)v, 0), (unsigned)__builtin_amdgcn_readlane((int)v, 16)),
-               min((unsigned)__builtin_amdgcn_readlane((int)v, 32), (unsigned)__builtin_amdgcn_readlane((int)v, 48)));
-}
+__device__ __forceinline__ float emd_wave_max(float v) { return pf_wave_reduce(v, PfMax{}); }              // values are never NaN here
+__device__ __forceinline__ unsigned emd_wave_min_u(unsigned v) { return pf_wave_reduce(v, PfMin{}); }
 __device__ __forceinline__ void tri_wave(float& best, float& better, int& idx) {
     const float vmax = emd_wave_max(best);
     const unsigned widx = emd_wave_min_u(best == vmax ? (unsigned)idx : 0xffffffffu);
@@ -224,10 +208,11 @@ struct EmdCoopArgs {
     int n, iters, G;
     float eps;
 };
+
 template <typename T>
-__device__ __forceinline__ T ald(const T* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ T ald(const T* p) { return PF_LD(p); }
 template <typename T>
-__device__ __forceinline__ void ast(T* p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void ast(T* p, T v) { PF_ST(p, v); }
 
 // ---- a wave's bid for one point with a cheap FILTER in front of the exact values (round 5) -----------------------------------
 // A bid needs the exact largest and second largest value over all n objects (and the smallest index holding the largest).  The

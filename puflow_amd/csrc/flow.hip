@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 #include "pf_api_internal.h"
 #include "pf_mfma.h"
+#include "pf_wave.h"
 
 // waves per workgroup: both directions fit 128 VGPRs -> 16 waves (4 per SIMD) since the coupling nets run on the f16n
 // helpers (no cross accumulator)
@@ -208,14 +209,14 @@ __global__ __launch_bounds__(NW * 64) void flow_kernel(FlowArgs a) {
                 // on another XCD: its L2 is not coherent with ours)
                 float sl = ld;
                 float sz = -0.5f * (v[0] * v[0] + LOG2PI_F) + -0.5f * (v[1] * v[1] + LOG2PI_F) + -0.5f * (v[2] * v[2] + LOG2PI_F);
-                sl += __shfl_xor(sl, 1); sz += __shfl_xor(sz, 1);
-                sl += __shfl_xor(sl, 2); sz += __shfl_xor(sz, 2);
+                sl += __shfl_xor(sl, 1); sz += __shfl_xor(sz, 1);           // the two sums interleaved, written out: one after the
+                sl += __shfl_xor(sl, 2); sz += __shfl_xor(sz, 2);           // other (pf_xor_sum) costs flow_kernel its instruction stream
                 sl += __shfl_xor(sl, 4); sz += __shfl_xor(sz, 4);
                 sl += __shfl_xor(sl, 8); sz += __shfl_xor(sz, 8);
                 if (ok && lane == 0) {
                     const int wt = g >> 4;
-                    __hip_atomic_store(a.part + wt, sl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(a.part + (a.rows >> 4) + wt, sz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    PF_ST(a.part + wt, sl);
+                    PF_ST(a.part + (a.rows >> 4) + wt, sz);
                 }
             }
         }
@@ -240,11 +241,10 @@ __global__ __launch_bounds__(NW * 64) void flow_kernel(FlowArgs a) {
         for (int b = wave; b < a.B; b += NW) {
             float accl = 0.f, accz = 0.f;
             for (int i = lane; i < per; i += 64) {
-                accl += __hip_atomic_load(a.part + b * per + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                accz += __hip_atomic_load(a.part + half + b * per + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                accl += PF_LD(a.part + b * per + i);
+                accz += PF_LD(a.part + half + b * per + i);
             }
-#pragma unroll
-            for (int m = 32; m > 0; m >>= 1) { accl += __shfl_xor(accl, m); accz += __shfl_xor(accz, m); }
+            accl = pf_xor_sum<32, 1>(accl); accz = pf_xor_sum<32, 1>(accz);          // masks 32, 16, .. 1
             if (lane == 0) {
                 const float l = accl + a.ld_const * (float)a.N;
                 a.ldj[b] = l;
@@ -258,7 +258,7 @@ __global__ __launch_bounds__(NW * 64) void flow_kernel(FlowArgs a) {
             for (int b = 0; b < a.B; ++b) tot += b < NW * 64 ? sa[b] : a.lps[b];       // batch order, whatever wave produced the term
         if (tid == 0) {
             *a.logp = -tot / (float)a.B;
-            __hip_atomic_store(a.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // ready for the next launch
+            PF_ST(a.counter, 0u);          // ready for the next launch
         }
     }
 }

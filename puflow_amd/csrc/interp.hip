@@ -24,6 +24,7 @@
 #include <hip/hip_runtime.h>
 #include "pf_api_internal.h"
 #include "pf_mfma.h"
+#include "pf_wave.h"
 
 // tuned on MI355X with tools/tune_variants.py (P = column tiles per wave, NW = waves per workgroup)
 #ifndef PF_INTERP_P
@@ -228,15 +229,15 @@ __global__ __launch_bounds__(NW * 64) void interp_kernel(InterpArgs a) {
                         const int row = 16 * ob + 4 * q + r;
                         const float x = w3[p][ob][r];
                         float m = x;
-                        m = fmaxf(m, __shfl_xor(m, 1)); m = fmaxf(m, __shfl_xor(m, 2)); m = fmaxf(m, __shfl_xor(m, 4));
+                        m = pf_xor_max<1, 4>(m);
                         const float ex = expf(x - m);
                         float sm = ex;
-                        sm += __shfl_xor(sm, 1); sm += __shfl_xor(sm, 2); sm += __shfl_xor(sm, 4);
+                        sm = pf_xor_sum<1, 4>(sm);
                         const float av = ex / sm;
 #pragma unroll
                         for (int c = 0; c < 3; ++c) {
                             float s = av * zj[c];
-                            s += __shfl_xor(s, 1); s += __shfl_xor(s, 2); s += __shfl_xor(s, 4);
+                            s = pf_xor_sum<1, 4>(s);
                             if (ok[p] && k == 0 && row < a.R) a.u[((size_t)gi[p] * a.R + row) * 3 + c] = s;
                         }
                     }
@@ -246,10 +247,10 @@ __global__ __launch_bounds__(NW * 64) void interp_kernel(InterpArgs a) {
                 for (int r = 0; r < R; ++r) {
                     const float x = w3[p][0][r];
                     float m = x;
-                    m = fmaxf(m, __shfl_xor(m, 1)); m = fmaxf(m, __shfl_xor(m, 2)); m = fmaxf(m, __shfl_xor(m, 4));
+                    m = pf_xor_max<1, 4>(m);
                     const float ex = expf(x - m);
                     float s = ex;
-                    s += __shfl_xor(s, 1); s += __shfl_xor(s, 2); s += __shfl_xor(s, 4);
+                    s = pf_xor_sum<1, 4>(s);
                     av[r] = ex / s;
                 }
                 if (a.aw) {                                                      // weights only (uniform branch)
@@ -263,7 +264,7 @@ __global__ __launch_bounds__(NW * 64) void interp_kernel(InterpArgs a) {
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
                     float s = av[r] * zj;
-                    s += __shfl_xor(s, 1); s += __shfl_xor(s, 2); s += __shfl_xor(s, 4);
+                    s = pf_xor_sum<1, 4>(s);
                     if (ok[p] && k == 0 && q < 3 && r < a.R) a.u[((size_t)gi[p] * a.R + r) * 3 + q] = s;
                 }
             }

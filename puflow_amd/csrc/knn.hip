@@ -26,6 +26,7 @@
 // distances in index order.
 #include <hip/hip_runtime.h>
 #include "pf_api_internal.h"
+#include "pf_wave.h"
 #include <type_traits>
 
 #ifndef PF_KNN5
@@ -553,8 +554,7 @@ __global__ __launch_bounds__(NW * 64) void knn5_kernel(const float* __restrict__
         }
         tab[j] = e;
     }
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) rm = fmaxf(rm, __shfl_xor(rm, m));
+    rm = pf_xor_max<1, 32>(rm);
     if (lane == 0) rmx[wave] = rm;
     __syncthreads();
     float Rmax = rmx[0];
@@ -727,12 +727,7 @@ __global__ __launch_bounds__(NW * 64) void knn5_kernel(const float* __restrict__
     for (int i = 0; i < K; ++i) { sd[i][lane] = bd[i]; si[i][lane] = (unsigned short)bi[i]; }
     __builtin_amdgcn_wave_barrier();
     // survivors of the query = the four lanes of its column
-    int ctot = cnt;
-    ctot += __shfl_xor(ctot, 16);
-    ctot += __shfl_xor(ctot, 32);
-    int cmax = cnt;
-    cmax = max(cmax, __shfl_xor(cmax, 16));
-    cmax = max(cmax, __shfl_xor(cmax, 32));
+    const int ctot = pf_xor_sum<16, 32>(cnt), cmax = pf_xor_max<16, 32>(cnt);
 #if defined(PF_KNN_ABL) && PF_KNN_ABL == 4          // timing-only: never the exact path
     if (false) {
 #else

@@ -13,6 +13,7 @@
 // buffers).
 #include <hip/hip_runtime.h>
 #include "pf_api_internal.h"
+#include "pf_wave.h"
 
 namespace {
 
@@ -35,12 +36,11 @@ __global__ __launch_bounds__(256) void adam_norm_kernel(AdamArgs a) {
     const float* gp = a.gtab ? a.gtab[a.chunks[c * 4 + 0]] + a.chunks[c * 4 + 1] : a.g + fo;
     double s = 0.0;
     for (int i = threadIdx.x; i < len; i += 256) { const float x = gp[i]; s += (double)x * (double)x; }
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) s += __shfl_xor(s, m);
+    s = pf_wave_sum(s);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0)
-        __hip_atomic_store(a.partial + c, (red[0] + red[1]) + (red[2] + red[3]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        PF_ST(a.partial + c, (red[0] + red[1]) + (red[2] + red[3]));
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (threadIdx.x == 0) last = atomicAdd(a.counter, 1u) == gridDim.x - 1 ? 1 : 0;
@@ -48,9 +48,8 @@ __global__ __launch_bounds__(256) void adam_norm_kernel(AdamArgs a) {
     if (!last) return;
     double t = 0.0;
     for (int k = threadIdx.x; k < a.nchunks; k += 256)
-        t += __hip_atomic_load(a.partial + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) t += __shfl_xor(t, m);
+        t += PF_LD(a.partial + k);
+    t = pf_wave_sum(t);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = t;
     __syncthreads();

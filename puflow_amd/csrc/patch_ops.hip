@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <hip/hip_runtime.h>
 #include "pf_api_internal.h"
+#include "pf_wave.h"
 
 namespace {
 
@@ -41,12 +42,7 @@ __device__ __forceinline__ void fps_body(const float* __restrict__ p, int N, int
             md[k] = d;
             if (d > best) { best = d; besti = k; }          // increasing k: first maximum kept
         }
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) {
-            const float ov = __shfl_xor(best, m);
-            const int oi = __shfl_xor(besti, m);
-            if (ov > best || (ov == best && oi < besti)) { best = ov; besti = oi; }
-        }
+        pf_xor_argmax<1, 32>(best, besti);
         if (lane == 0) { sv[wave] = best; si[wave] = besti; }
         __syncthreads();
         if (tid == 0) {
@@ -91,25 +87,9 @@ constexpr int FPSC_SLOTS = FPSC_GMAX * (FPSC_T / 64);    // one slot per wave of
 static_assert(FPSC_SLOTS <= 128, "a lane of wave 0 polls two words per word a wave publishes");
 // status word of a cloud (after its ring): 2 = not finished (set by fps_init_kernel), 1 = aborted, 0 = complete
 constexpr unsigned long long FPSC_ST_DONE = 0ull, FPSC_ST_ABORT = PF_RING_ABORT, FPSC_ST_INIT = 2ull;
-__device__ __forceinline__ void fps_st(unsigned long long* p, unsigned long long v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// wave-wide reductions without LDS traffic: rotate-reduce inside the 16-lane rows (DPP row_ror), then the four row results
-// through SGPRs.  The result is wave-uniform.
-template <int CTRL>
-__device__ __forceinline__ int dpp_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, false); }
-__device__ __forceinline__ int wave_max_i32(int v) {
-    v = max(v, dpp_i<0x128>(v)); v = max(v, dpp_i<0x124>(v)); v = max(v, dpp_i<0x122>(v)); v = max(v, dpp_i<0x121>(v));
-    return max(max(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
-               max(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
-}
-__device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
-    v = max(v, (unsigned)dpp_i<0x128>((int)v)); v = max(v, (unsigned)dpp_i<0x124>((int)v));
-    v = max(v, (unsigned)dpp_i<0x122>((int)v)); v = max(v, (unsigned)dpp_i<0x121>((int)v));
-    return max(max((unsigned)__builtin_amdgcn_readlane((int)v, 0), (unsigned)__builtin_amdgcn_readlane((int)v, 16)),
-               max((unsigned)__builtin_amdgcn_readlane((int)v, 32), (unsigned)__builtin_amdgcn_readlane((int)v, 48)));
-}
+// wave-wide reductions without LDS traffic (pf_wave_reduce: DPP rotates inside the 16-lane rows, the four row results through SGPRs)
+__device__ __forceinline__ int wave_max_i32(int v) { return pf_wave_reduce(v, PfMax{}); }
+__device__ __forceinline__ unsigned wave_max_u32(unsigned v) { return pf_wave_reduce(v, PfMax{}); }
 
 // The exchange: every WAVE reduces its own points in registers (DPP) and publishes 64-bit words (distance bits << 32 | tag |
 // ~index: an integer max is "farthest, then smallest index") into its slots of a 4-deep ring; wave 0 of every workgroup reads
@@ -306,14 +286,14 @@ __device__ __forceinline__ void fps_coopm_body(const float* __restrict__ p, int 
         }
         if (lane == 0) {
 #pragma unroll
-            for (int e = 0; e < KW; ++e) fps_st(slot + KW * (g * NW + wave) + e, fps_key(pv[e], pidx[e], tag));
+            for (int e = 0; e < KW; ++e) PF_ST(slot + KW * (g * NW + wave) + e, fps_key(pv[e], pidx[e], tag));
         }
         if (wave == 0) {
             unsigned long long kk[NT];
             const bool dead = !pf_ring_poll<NT>(slot, SW, tag, abort_w, kk);
             float* sl = s_l[r & 1];
             if (dead) {                                                     // uniform over the wave
-                if (lane == 0) { fps_st(abort_w, FPSC_ST_ABORT); sl[3 * MS + 1] = -1.f; }
+                if (lane == 0) { PF_ST(abort_w, FPSC_ST_ABORT); sl[3 * MS + 1] = -1.f; }
             } else {
                 // B: the largest LAST key of a wave (word w = KW * wave + e is a last key iff w mod KW == KW - 1)
                 unsigned long long lastk = 0ull, f0 = 0ull;
@@ -428,7 +408,7 @@ __device__ __forceinline__ void fps_coopm_body(const float* __restrict__ p, int 
     }
     // the word after the status word: exchange rounds this cloud took (measurement only: bench.py --mode pugan reports
     // samples per round and the time per round next to the exchange floor of pf_fps_exchange_probe)
-    if (g == 0 && tid == 0) { fps_st(abort_w + 1, (unsigned long long)rounds); fps_st(abort_w, FPSC_ST_DONE); }
+    if (g == 0 && tid == 0) { PF_ST(abort_w + 1, (unsigned long long)rounds); PF_ST(abort_w, FPSC_ST_DONE); }
 }
 
 template <int PPT>
@@ -476,7 +456,7 @@ __global__ __launch_bounds__(FPS_T) void fps_ragged_kernel(const float* __restri
                                                            int* __restrict__ out) {
     const int c = blockIdx.x;
     fps_body(xyz + (size_t)t.off[c] * 3, t.n[c], t.npoint[c], scratch + t.soff[c], out + t.ooff[c]);
-    if (threadIdx.x == 0) fps_st(status + 2 * t.cloud[c], FPSC_ST_DONE);
+    if (threadIdx.x == 0) PF_ST(status + 2 * t.cloud[c], FPSC_ST_DONE);
 }
 
 // ---- the exchange alone: what a round of the two-sample kernel costs with NO points to update ------------------------------
@@ -497,14 +477,14 @@ __global__ __launch_bounds__(FPSC_T) void fps_exchange_probe_kernel(int G, int r
         unsigned long long* slot = ring + (r & 3) * FPSC_SLOTS2;
         const unsigned tag = ((unsigned)(((r >> 2) & 3) << 1) | 1u) << 29;
         if (lane == 0) {
-            fps_st(slot + 2 * (g * NW + wave), ((unsigned long long)acc << 32) | tag | 1u);
-            fps_st(slot + 2 * (g * NW + wave) + 1, ((unsigned long long)(acc >> 1) << 32) | tag);
+            PF_ST(slot + 2 * (g * NW + wave), ((unsigned long long)acc << 32) | tag | 1u);
+            PF_ST(slot + 2 * (g * NW + wave) + 1, ((unsigned long long)(acc >> 1) << 32) | tag);
         }
         if (wave == 0) {
             unsigned long long k[4];
             const bool dead = !pf_ring_poll<4>(slot, S2, tag, abort_w, k);
             if (dead) {
-                if (lane == 0) { fps_st(abort_w, FPSC_ST_ABORT); s_l[r & 1][1] = -1.f; }
+                if (lane == 0) { PF_ST(abort_w, FPSC_ST_ABORT); s_l[r & 1][1] = -1.f; }
             } else {
                 const unsigned long long K1 = wave_max_u64(u64max(u64max(k[0], k[1]), u64max(k[2], k[3])));
                 if (lane == 0) { s_l[r & 1][0] = __uint_as_float((unsigned)(K1 >> 32) & 0xffffu); s_l[r & 1][1] = 1.f; }
@@ -515,7 +495,7 @@ __global__ __launch_bounds__(FPSC_T) void fps_exchange_probe_kernel(int G, int r
         acc = acc * 1664525u + (unsigned)__float_as_uint(s_l[r & 1][0]) + 1013904223u;      // the next word depends on this round's result
         acc &= 0x7fffffffu;
     }
-    if (g == 0 && tid == 0) fps_st(abort_w, FPSC_ST_DONE);
+    if (g == 0 && tid == 0) PF_ST(abort_w, FPSC_ST_DONE);
 }
 
 // ---- large-K kNN: one workgroup per query; keys (dist bits << 32 | index) bitonic-sorted in LDS.

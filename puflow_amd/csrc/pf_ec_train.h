@@ -79,30 +79,71 @@ constexpr int ECP_SPIN = 1 << 22;
 #define PF_ECP_DBG 0
 #endif
 
-__device__ __forceinline__ float ecp_ald(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void ecp_ast(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-template <int CTRL>
-__device__ __forceinline__ float ecp_dppf(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float ecp_rowsum16(float v) {           // sum over the 16 lanes of a DPP row, in every lane
-    v += ecp_dppf<0x128>(v); v += ecp_dppf<0x124>(v); v += ecp_dppf<0x122>(v); v += ecp_dppf<0x121>(v);
-    return v;
-}
-__device__ __forceinline__ float ecp_rowmax16(float v) {
-    v = fmaxf(v, ecp_dppf<0x128>(v)); v = fmaxf(v, ecp_dppf<0x124>(v)); v = fmaxf(v, ecp_dppf<0x122>(v)); v = fmaxf(v, ecp_dppf<0x121>(v));
-    return v;
-}
-__device__ __forceinline__ int ecp_rowmin16(int v) {
-    v = min(v, __builtin_amdgcn_update_dpp(0, v, 0x128, 0xf, 0xf, false)); v = min(v, __builtin_amdgcn_update_dpp(0, v, 0x124, 0xf, 0xf, false));
-    v = min(v, __builtin_amdgcn_update_dpp(0, v, 0x122, 0xf, 0xf, false)); v = min(v, __builtin_amdgcn_update_dpp(0, v, 0x121, 0xf, 0xf, false));
-    return v;
-}
+// sum over the 16 lanes of a DPP row, in every lane
+__device__ __forceinline__ float ecp_rowsum16(float v) { return pf_row_reduce(v, PfSum{}); }
 
 // grid barrier number `gen` (1, 2, ...) of this launch (pf_grid.h); false when the spin gave up (uniform over the workgroup)
 __device__ __forceinline__ bool ecp_barrier(unsigned* sync, unsigned gen, int* flag) {
     if (PF_ECP_DBG & 2) { __syncthreads(); return true; }
     return pf_grid_barrier<ECP_SPIN>(sync, gen, flag);
+}
+
+// ---- the grid-wide column-statistic exchange of one BatchNorm layer, the same in both persistent kernels.  A layer has its own 32
+// statistics columns 32 slot .. of the spread double accumulators `acc`, so nothing has to be cleared between two barriers of a
+// launch.  The grid barrier between the two halves stays in the kernels (what a kernel does before it differs).
+// Publish: lane (col, q) holds sums s0 / s1 over its edges for the channels 16 (b0 + nt) + 4 q + r, of which col0 .. col0 + G - 1
+// are the layer's: DPP row sum -> LDS over the waves (red: ECP_WAVES x 64 floats) -> ONE double atomic per column and statistic.
+template <int G, int NTG>
+__device__ __forceinline__ void ecp_stat_publish(const f4 (&s0)[NTG], const f4 (&s1)[NTG], int b0, int col0, int slot, double* acc,
+                                                 float* red, bool atomics) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = lane & 15, q = lane >> 4;
+#pragma unroll
+    for (int nt = 0; nt < NTG; ++nt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float a0 = ecp_rowsum16(s0[nt][r]), a1 = ecp_rowsum16(s1[nt][r]);
+            const int c = 16 * (b0 + nt) + 4 * q + r - col0;
+            if (col == 0 && c >= 0 && c < G) { red[wave * 64 + c] = a0; red[wave * 64 + 32 + c] = a1; }
+        }
+    __syncthreads();
+    if (atomics && threadIdx.x < 64 && (threadIdx.x & 31) < G) {
+        float v = 0.f;
+#pragma unroll
+        for (int w = 0; w < ECP_WAVES; ++w) v += red[w * 64 + threadIdx.x];
+        unsafeAtomicAdd(acc + (blockIdx.x % STAT_COPIES) * 2 * STAT_W + (threadIdx.x >> 5) * STAT_W + 32 * slot + (threadIdx.x & 31), (double)v);
+    }
+}
+// Fetch (after the barrier): thread (pt = tid & 3, stat = (tid >> 2) & 1, column = tid >> 3) of the first 256 reads 4 of the 16
+// copies of one sum (all loads of the workgroup in flight at once), the 4 parts meet through lane shuffles.  `part`: the sum over
+// all 16 copies of the thread's statistic of its column, `other`: the other statistic of the same column - the threads with
+// (tid & 7) == 0 hold (sum 0, sum 1) of column tid >> 3.
+struct EcpSums { double part, other; };
+__device__ __forceinline__ EcpSums ecp_stat_fetch(const double* acc, int slot) {
+    double part = 0.0;
+    if (threadIdx.x < 256) {
+        const int pt = threadIdx.x & 3, stt = (threadIdx.x >> 2) & 1, c = threadIdx.x >> 3;
+        double v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = PF_LD(acc + (4 * pt + k) * 2 * STAT_W + stt * STAT_W + 32 * slot + c);
+        part = pf_xor_sum<1, 2>((v[0] + v[1]) + (v[2] + v[3]));
+    }
+    return {part, __shfl_xor(part, 4)};
+}
+// End of the launch: the workgroup that leaves last clears the accumulator columns the `nlayers` layers used and puts the barrier
+// words back to zero (every workgroup is past every barrier and has read every sum by then).  `flag`: one int of LDS.
+__device__ __forceinline__ void ecp_exit_reset(double* acc, unsigned* sync, int nlayers, int* flag) {
+    __syncthreads();
+    if (threadIdx.x == 0) *flag = atomicAdd(sync + 2, 1u) == gridDim.x - 1 ? 1 : 0;
+    __syncthreads();
+    if (*flag == 1) {
+        for (int i = threadIdx.x; i < STAT_COPIES * 2 * STAT_W; i += ECP_T)
+            if ((i % STAT_W) < 32 * nlayers) PF_ST(acc + i, 0.0);
+        if (threadIdx.x == 0) {
+            PF_ST(sync + 0, 0u);
+            PF_ST(sync + 1, 0u);
+            PF_ST(sync + 2, 0u);
+        }
+    }
 }
 
 }  // namespace

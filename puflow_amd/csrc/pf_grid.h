@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 #include <mutex>
 #include <vector>
+#include "pf_wave.h"
 
 // ---- arrival barrier with a generation word -----------------------------------------------------------------------------------
 // Grid barrier number `gen` (1, 2, ...) of this launch: sync[0] counts arrivals, the workgroup that arrives last publishes the
@@ -34,11 +35,11 @@ __device__ __forceinline__ bool pf_grid_barrier(unsigned* sync, unsigned gen, in
     if (threadIdx.x == 0) {
         int fl = 0;
         if (atomicAdd(sync, 1u) == gen * gridDim.x - 1)
-            __hip_atomic_store(sync + 1, gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            PF_ST(sync + 1, gen);
         else {
             int budget = SPIN;
-            while (__hip_atomic_load(sync + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < gen && --budget > 0) __builtin_amdgcn_s_sleep(1);
-            if (budget <= 0) { fl = 2; __hip_atomic_store(sync + 3, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+            while (PF_LD(sync + 1) < gen && --budget > 0) __builtin_amdgcn_s_sleep(1);
+            if (budget <= 0) { fl = 2; PF_ST(sync + 3, 1u); }
         }
         *flag = fl;
     }
@@ -66,10 +67,10 @@ __device__ __forceinline__ unsigned pf_sum_barrier(unsigned long long* words, un
         atomicAdd(word, ((unsigned long long)value << 32) | 1ull);
         const unsigned target = ((nb + 1) >> 1) * G;             // arrivals at the barriers of this parity so far
         int budget = SPIN;
-        unsigned long long v = __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        unsigned long long v = PF_LD(word);
         while ((unsigned)v < target && --budget > 0) {
             __builtin_amdgcn_s_sleep(SLEEP);
-            v = __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            v = PF_LD(word);
         }
         if (budget <= 0) st.dead = 1;
         const unsigned sum = (unsigned)(v >> 32);
@@ -96,13 +97,12 @@ __device__ __forceinline__ bool pf_ring_poll(const unsigned long long* slot, int
         bool ok = true;
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
-            kk[t] = lane + 64 * t < nw ? __hip_atomic_load(slot + lane + 64 * t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                                       : (unsigned long long)tag;
+            kk[t] = lane + 64 * t < nw ? PF_LD(slot + lane + 64 * t) : (unsigned long long)tag;
             ok = ok && ((unsigned)kk[t] & (7u << 29)) == tag;
         }
         if (!__any(!ok)) break;
         if (++spins > PF_RING_SPIN ||
-            (spins % 1024 == 0 && __hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == PF_RING_ABORT)) {
+            (spins % 1024 == 0 && PF_LD(status) == PF_RING_ABORT)) {
             dead = true;
             break;
         }

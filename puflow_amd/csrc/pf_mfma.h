@@ -15,6 +15,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <type_traits>
+#include "pf_wave.h"
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 
@@ -380,14 +381,7 @@ __device__ __forceinline__ f4 pf_bias(const float* __restrict__ b, int ob, int q
 }
 
 // max over the 16 lanes of a DPP row (= the 16 columns of one MFMA tile); every lane gets the max.
-__device__ __forceinline__ float pf_rowmax16(float v) {
-    // row_ror:n = 0x120 + n
-    v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x128, 0xf, 0xf, false)));
-    v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x124, 0xf, 0xf, false)));
-    v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x122, 0xf, 0xf, false)));
-    v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x121, 0xf, 0xf, false)));
-    return v;
-}
+__device__ __forceinline__ float pf_rowmax16(float v) { return pf_row_reduce(v, PfMax{}); }
 
 // XCD-aware tile order (guide T1): virtual id v -> logical tile so that the workgroups that
 // share an XCD (equal blockIdx % 8 under round-robin dispatch) walk one contiguous chunk of

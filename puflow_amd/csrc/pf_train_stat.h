@@ -80,11 +80,9 @@ __device__ __forceinline__ void stat_add(double* acc, float v, int det) {
     } else
         unsafeAtomicAdd(acc, (double)v);
 }
-__device__ __forceinline__ double stat_load(const double* acc) {
-    return __hip_atomic_load(acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
+__device__ __forceinline__ double stat_load(const double* acc) { return PF_LD(acc); }
 __device__ __forceinline__ long long stat_load_fix(const double* acc) {
-    return (long long)__hip_atomic_load(reinterpret_cast<const unsigned long long*>(acc), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return (long long)PF_LD(reinterpret_cast<const unsigned long long*>(acc));
 }
 // det: one column's sum from its hi / lo words - integer sums first (exact, any order), then one fixed conversion
 __device__ __forceinline__ double stat_load_det(const double* acc) {
@@ -131,8 +129,8 @@ __device__ __forceinline__ void stat_flush(float (&s0)[NT], float (&s1)[NT], int
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
-        s0[nt] += __shfl_xor(s0[nt], 16); s0[nt] += __shfl_xor(s0[nt], 32);
-        s1[nt] += __shfl_xor(s1[nt], 16); s1[nt] += __shfl_xor(s1[nt], 32);
+        s0[nt] += __shfl_xor(s0[nt], 16); s0[nt] += __shfl_xor(s0[nt], 32);       // written out: through pf_xor_sum the 25 kernels that
+        s1[nt] += __shfl_xor(s1[nt], 16); s1[nt] += __shfl_xor(s1[nt], 32);       // end in stat_flush compile to other instruction streams
     }
     if (lane < 16) {                                                  // red[wave][2][STAT_W]
 #pragma unroll

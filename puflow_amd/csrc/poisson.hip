@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include "pf_api_internal.h"
+#include "pf_wave.h"
 
 namespace {
 
@@ -35,10 +36,8 @@ struct PoolScratch {                            // LDS of the per-pool workgroup
     u64 prefix;
 };
 
-// loads / stores of the elimination's state that other waves change between barriers: never served from a stale line
-__device__ __forceinline__ unsigned ld_u(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ int ld_i(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_i(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// the elimination's state (w, state) changes under other waves between barriers: it is read and written with PF_LD / PF_ST,
+// never served from a stale line
 
 // larger key = removed earlier: the weight, then the smaller index
 __device__ __forceinline__ u64 make_key(unsigned w, int i) { return ((u64)w << 32) | (u64)(0xFFFFFFFFu - (unsigned)i); }
@@ -118,7 +117,7 @@ __device__ bool round_begin(const PfPoissonPool& P, const unsigned* w, const int
     const int phases = st->phases;
     int alive = 0, above = 0;
     for (int i = tid; i < P.s; i += PE_T)
-        if (ld_i(state + i) & 1) { ++alive; above += make_key(ld_u(w + i), i) > tau; }
+        if (PF_LD(state + i) & 1) { ++alive; above += make_key(PF_LD(w + i), i) > tau; }
     for (int o = 32; o > 0; o >>= 1) { alive += __shfl_down(alive, o); above += __shfl_down(above, o); }
     if (lane == 0) { atomicAdd(&sm.cnt[0], alive); atomicAdd(&sm.cnt[1], above); }
     __syncthreads();
@@ -133,7 +132,7 @@ __device__ bool round_begin(const PfPoissonPool& P, const unsigned* w, const int
         int base = 0;
         for (int i0 = 0; i0 < P.s; i0 += PE_T) {
             const int i = i0 + tid;
-            const bool in = i < P.s && (ld_i(state + i) & 1);
+            const bool in = i < P.s && (PF_LD(state + i) & 1);
             const u64 b = __ballot(in);
             if (lane == 0) sm.wsum[wave] = __popcll(b);
             __syncthreads();
@@ -155,8 +154,8 @@ __device__ bool round_begin(const PfPoissonPool& P, const unsigned* w, const int
         __syncthreads();
         const u64 prefix = sm.prefix;
         for (int i = tid; i < P.s; i += PE_T)
-            if (ld_i(state + i) & 1) {
-                const u64 key = make_key(ld_u(w + i), i);
+            if (PF_LD(state + i) & 1) {
+                const u64 key = make_key(PF_LD(w + i), i);
                 if (b == 7 || (key >> (8 * (b + 1))) == (prefix >> (8 * (b + 1)))) atomicAdd(&sm.hist[(int)((key >> (8 * b)) & 255)], 1);
             }
         __syncthreads();
@@ -179,29 +178,29 @@ __device__ bool round_begin(const PfPoissonPool& P, const unsigned* w, const int
 // Step 2, candidate i: picked when alive, above tau and above every alive neighbour.  Reads keys, writes its own state only.
 __device__ __forceinline__ void round_select(const PfPoissonPool& P, u64 tau, const long long* __restrict__ offsets,
                                              const int* __restrict__ nbr, const unsigned* w, int* state, int i) {
-    if (!(ld_i(state + P.off + i) & 1)) return;
-    const u64 key = make_key(ld_u(w + P.off + i), i);
+    if (!(PF_LD(state + P.off + i) & 1)) return;
+    const u64 key = make_key(PF_LD(w + P.off + i), i);
     if (key <= tau) return;
     const long long e1 = offsets[P.off + i + 1];
     for (long long e = offsets[P.off + i]; e < e1; ++e) {
         const int j = nbr[e];
         if ((unsigned)j >= (unsigned)P.s) continue;                       // a foreign graph: never outside the pool
-        if ((ld_i(state + P.off + j) & 1) && make_key(ld_u(w + P.off + j), j) > key) return;
+        if ((PF_LD(state + P.off + j) & 1) && make_key(PF_LD(w + P.off + j), j) > key) return;
     }
-    st_i(state + P.off + i, 3);
+    PF_ST(state + P.off + i, 3);
 }
 
 // Step 3, candidate i if picked: dies, and its alive neighbours lose q_ij.  No two neighbours are picked in one round.
 __device__ __forceinline__ void round_apply(const PfPoissonPool& P, const long long* __restrict__ offsets,
                                             const int* __restrict__ nbr, const int* __restrict__ q, unsigned* w, int* state,
                                             int i) {
-    if (ld_i(state + P.off + i) != 3) return;
-    st_i(state + P.off + i, 0);
+    if (PF_LD(state + P.off + i) != 3) return;
+    PF_ST(state + P.off + i, 0);
     const long long e1 = offsets[P.off + i + 1];
     for (long long e = offsets[P.off + i]; e < e1; ++e) {
         const int j = nbr[e];
         if ((unsigned)j >= (unsigned)P.s) continue;
-        if (ld_i(state + P.off + j) & 1) atomicSub(w + P.off + j, (unsigned)q[e]);
+        if (PF_LD(state + P.off + j) & 1) atomicSub(w + P.off + j, (unsigned)q[e]);
     }
 }
 
@@ -210,7 +209,7 @@ __global__ __launch_bounds__(PE_T) void begin_kernel(const PfPoissonPool* __rest
     __shared__ PoolScratch sm;
     const PfPoissonPool P = pools[blockIdx.x];
     if (P.path == PATH_WG) return;
-    if (round_begin(P, w, state, st + blockIdx.x, keep, sm) && threadIdx.x == 0) st_i(unfinished, round_id + 1);
+    if (round_begin(P, w, state, st + blockIdx.x, keep, sm) && threadIdx.x == 0) PF_ST(unfinished, round_id + 1);
 }
 
 __global__ __launch_bounds__(PG_T) void select_kernel(const PfPoissonPool* __restrict__ pools, const PfPoissonState* __restrict__ st,

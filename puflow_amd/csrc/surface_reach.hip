@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include "pf_api_internal.h"
 #include "pf_surface.h"
+#include "pf_wave.h"
 
 namespace {
 
@@ -89,7 +90,7 @@ __global__ __launch_bounds__(SR_T) void reach_sweep_kernel(const float* __restri
 // on in global memory is not served from a stale cache line; in LDS the scope changes nothing).
 __device__ __forceinline__ void init_row(unsigned* w, const unsigned* __restrict__ d2b, int n, int k0) {
     for (int k = threadIdx.x; k < n; k += SR_T)
-        __hip_atomic_store(w + k, k == k0 ? d2b[k] : SR_INF, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        PF_ST(w + k, k == k0 ? d2b[k] : SR_INF);
 }
 
 // The sweeps over one row; w holds the bit patterns of the row's values (LDS or global: the same code).  Returns the sweeps
@@ -104,14 +105,14 @@ __device__ __forceinline__ int relax_row(unsigned* w, const int* __restrict__ rf
         bool any = false;
         for (int k = tid; k < n; k += SR_T) {
             const unsigned mine = d2b[k];
-            unsigned cur = __hip_atomic_load(w + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            unsigned cur = PF_LD(w + k);
             if (cur <= mine) continue;                                // already its own d2: nothing lower exists
             const int f = rf[k];
             unsigned best = cur;
             for (long long e = adj_off[f]; e < adj_off[f + 1]; ++e) {
                 const int kg = reach_find(rf, n, adj[e]);
                 if (kg < 0) continue;
-                const unsigned g = __hip_atomic_load(w + kg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                const unsigned g = PF_LD(w + kg);
                 const unsigned v = g > mine ? g : mine;
                 best = v < best ? v : best;
             }

@@ -1,6 +1,7 @@
 // Forward of one FeatureExtractUnit of the training step (pf_ec_train.h describes the whole unit): weight fold, the per-layer
 // kernels and the persistent one-launch form.
 #include "pf_ec_train.h"
+#include "pf_wave.h"
 
 namespace {
 
@@ -467,23 +468,7 @@ __global__ __launch_bounds__(ECP_T) void ec_fwdp_kernel(EcFwdPArgs a) {
                     s1[nt] = s1[nt] + vc * vc;
                 }
             }
-        // ---- column sums: DPP row -> LDS over the waves -> spread double accumulators (columns 32 t ..: a layer has its own,
-        // nothing has to be cleared between two barriers of a launch)
-#pragma unroll
-        for (int nt = 0; nt < NTG; ++nt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float a0 = ecp_rowsum16(s0[nt][r]), a1 = ecp_rowsum16(s1[nt][r]);
-                const int c = 16 * (b0 + nt) + 4 * q + r - col0;
-                if (col == 0 && c >= 0 && c < G) { red[wave * 64 + c] = a0; red[wave * 64 + 32 + c] = a1; }
-            }
-        __syncthreads();
-        if (!(PF_ECP_DBG & 16) && threadIdx.x < 64 && (threadIdx.x & 31) < G) {
-            float v = 0.f;
-#pragma unroll
-            for (int w = 0; w < ECP_WAVES; ++w) v += red[w * 64 + threadIdx.x];
-            unsafeAtomicAdd(a.acc + (blockIdx.x % STAT_COPIES) * 2 * STAT_W + (threadIdx.x >> 5) * STAT_W + 32 * t + (threadIdx.x & 31), (double)v);
-        }
+        ecp_stat_publish<G>(s0, s1, b0, col0, t, a.acc, red, !(PF_ECP_DBG & 16));
         if constexpr (OWN && t + 1 < NC) addends(std::integral_constant<int, t + 1>{});      // next layer's gathers fly during the barrier
         // the pivot of the column this thread finalises below, read BEFORE the barrier: workgroup 0 updates the running mean right
         // after it (every workgroup has arrived, i.e. has read its pivots, by then)
@@ -493,23 +478,10 @@ __global__ __launch_bounds__(ECP_T) void ec_fwdp_kernel(EcFwdPArgs a) {
         if (!alive) return;
         // ---- every workgroup turns the sums into the layer's constants for itself (the StatFin mode-1 arithmetic); workgroup 0
         // also leaves them in `aff` for the backward and updates the running statistics
-        // 256 threads: thread (part = tid & 3, stat = (tid >> 2) & 1, column = tid >> 3) fetches 4 of the 16 copies of one sum
-        // (all loads of the workgroup in flight at once, 8 registers each), the 4 parts meet through lane shuffles
-        double part = 0.0;
-        if (threadIdx.x < 256) {
-            const int pt = threadIdx.x & 3, stt = (threadIdx.x >> 2) & 1, c = threadIdx.x >> 3;
-            double v[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                v[k] = __hip_atomic_load(a.acc + (4 * pt + k) * 2 * STAT_W + stt * STAT_W + 32 * t + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            part = (v[0] + v[1]) + (v[2] + v[3]);
-            part += __shfl_xor(part, 1);
-            part += __shfl_xor(part, 2);                       // lanes pt = 0..3 now hold the sum over all 16 copies
-        }
-        const double other = __shfl_xor(part, 4);              // the other statistic of the same column
+        const EcpSums sums = ecp_stat_fetch(a.acc, t);
         if (threadIdx.x < 256 && (threadIdx.x & 7) == 0 && (threadIdx.x >> 3) < G) {
             const int c = threadIdx.x >> 3;
-            const double a0 = part, a1 = other;
+            const double a0 = sums.part, a1 = sums.other;
             const double pv = (double)fpv;
             const double dm = a0 / a.R;
             const double mean = pv + dm;
@@ -612,12 +584,7 @@ __global__ __launch_bounds__(ECP_T) void ec_fwdp_kernel(EcFwdPArgs a) {
 #pragma unroll
                     for (int r = 1; r < 4; ++r)
                         if (v[r] > best) { best = v[r]; bk = 4 * q + r; }
-#pragma unroll
-                    for (int m = 16; m < 64; m <<= 1) {
-                        const float ov = __shfl_xor(best, m);
-                        const int okk = __shfl_xor(bk, m);
-                        if (ov > best || (ov == best && okk < bk)) { best = ov; bk = okk; }
-                    }
+                    pf_xor_argmax<16, 32>(best, bk);
                     if (q == 0 && ok[s]) {
                         const size_t o0 = (size_t)tl[s] * ODIM + 16 * (oc + o) + col;
                         a.out[o0] = best;
@@ -632,20 +599,7 @@ __global__ __launch_bounds__(ECP_T) void ec_fwdp_kernel(EcFwdPArgs a) {
                 for (int c = 4 * q; c < ODIM; c += 16)
                     *reinterpret_cast<f4*>(a.out + (size_t)tl[s] * ODIM + c) = pf_splat(__builtin_nanf(""));
     }
-    // ---- the workgroup that leaves last clears the accumulator columns the layers used and puts the barrier words back to zero
-    // (every workgroup is past every barrier and has read every sum by then)
-    __syncthreads();
-    if (threadIdx.x == 0) flag = atomicAdd(a.sync + 2, 1u) == gridDim.x - 1 ? 1 : 0;
-    __syncthreads();
-    if (flag == 1) {
-        for (int i = threadIdx.x; i < STAT_COPIES * 2 * STAT_W; i += ECP_T)
-            if ((i % STAT_W) < 32 * NC) __hip_atomic_store(a.acc + i, 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (threadIdx.x == 0) {
-            __hip_atomic_store(a.sync + 0, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(a.sync + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(a.sync + 2, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
+    ecp_exit_reset(a.acc, a.sync, NC, &flag);
 }
 
 // ------------------------------------------------------------------------------------------------ weight folding / un-folding

@@ -19,6 +19,7 @@
 // writes the whole L2 back on this multi-die part: tens of microseconds per launch, see csrc/pf_train_stat.h stat_flush).
 #include <hip/hip_runtime.h>
 #include "pf_api_internal.h"
+#include "pf_wave.h"
 
 namespace {
 
@@ -33,14 +34,13 @@ __device__ __forceinline__ void grid_sums(float (&v)[NV], float* partial, unsign
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
         float s = v[i];
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) s += __shfl_xor(s, m);
+        s = pf_wave_sum(s);
         if (lane == 0) red[wave][i] = s;
     }
     __syncthreads();
     if (threadIdx.x < NV) {
         const float s = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
-        __hip_atomic_store(partial + (size_t)blockIdx.x * NV + threadIdx.x, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        PF_ST(partial + (size_t)blockIdx.x * NV + threadIdx.x, s);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -54,7 +54,7 @@ __device__ __forceinline__ void grid_sums(float (&v)[NV], float* partial, unsign
         float s = 0.f;
         if (vi < NV)
             for (unsigned w = sub; w < gridDim.x; w += 16)
-                s += __hip_atomic_load(partial + (size_t)w * NV + vi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                s += PF_LD(partial + (size_t)w * NV + vi);
         fs[sub][vi] = s;
     }
     __syncthreads();

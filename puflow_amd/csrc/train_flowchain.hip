@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 #include "pf_api_internal.h"
 #include "pf_mfma.h"
+#include "pf_wave.h"
 
 namespace {
 
@@ -241,9 +242,7 @@ __device__ __forceinline__ void fc_mlp_bwd(const float* lds, float do0, float do
             const f4 wx = *reinterpret_cast<const f4*>(lds + FB_WX + (cb * 16 + 4 * q + r) * 4);
             s0 = fmaf(g1[cb][r], wx.x, s0); s1 = fmaf(g1[cb][r], wx.y, s1); s2 = fmaf(g1[cb][r], wx.z, s2);
         }
-    s0 += __shfl_xor(s0, 16); s0 += __shfl_xor(s0, 32);
-    s1 += __shfl_xor(s1, 16); s1 += __shfl_xor(s1, 32);
-    s2 += __shfl_xor(s2, 16); s2 += __shfl_xor(s2, 32);
+    s0 = pf_xor_sum<16, 32>(s0); s1 = pf_xor_sum<16, 32>(s1); s2 = pf_xor_sum<16, 32>(s2);
     sj[0] = s0; sj[1] = s1; sj[2] = s2;
 #pragma unroll
     for (int ub = 0; ub < 8; ++ub) {
@@ -327,10 +326,9 @@ __global__ __launch_bounds__(64 * FC_NW) void flowchain_fwd_kernel(PfFlowChain a
 #pragma unroll
             for (int c = 0; c < 3; ++c) p[c] = (h[2 - c] - t[c]) * expf(-s[c]);
             float sv = (valid && q == 0) ? (s[0] + s[1]) + s[2] : 0.f;
-#pragma unroll
-            for (int w = 1; w < 64; w <<= 1) sv += __shfl_xor(sv, w);
+            sv = pf_wave_sum(sv);
             if (lane == 0 && tile < ntiles)
-                __hip_atomic_store(a.part + (size_t)i * ntiles + tile, sv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                PF_ST(a.part + (size_t)i * ntiles + tile, sv);
         } else {
             if (valid && q == 0) { a.o[slab * 2] = o0; a.o[slab * 2 + 1] = o1; }
             float mi[3];
@@ -346,10 +344,9 @@ __global__ __launch_bounds__(64 * FC_NW) void flowchain_fwd_kernel(PfFlowChain a
     if (a.inv) return;
     if (a.logp) {                                       // standard-normal log-density of z (probs.py:73-75), per wave tile
         float gv = (valid && q == 0) ? -0.5f * ((p[0] * p[0] + p[1] * p[1]) + p[2] * p[2] + 3.f * 1.8378770664093453f) : 0.f;
-#pragma unroll
-        for (int w = 1; w < 64; w <<= 1) gv += __shfl_xor(gv, w);
+        gv = pf_wave_sum(gv);
         if (lane == 0 && tile < ntiles)
-            __hip_atomic_store(a.part + (size_t)a.nb * ntiles + tile, gv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            PF_ST(a.part + (size_t)a.nb * ntiles + tile, gv);
     }
     // sum(s) of every block: the workgroup that arrives last adds the per-tile sums in a fixed order
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -364,9 +361,8 @@ __global__ __launch_bounds__(64 * FC_NW) void flowchain_fwd_kernel(PfFlowChain a
         float sv = 0.f;
         if (i < nrow)
             for (int w = sub; w < ntiles; w += 32)
-                sv += __hip_atomic_load(a.part + (size_t)i * ntiles + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-        for (int w = 1; w < 32; w <<= 1) sv += __shfl_xor(sv, w);
+                sv += PF_LD(a.part + (size_t)i * ntiles + w);
+        sv = pf_xor_sum<1, 16>(sv);
         if (i < a.nb && sub == 0) a.ssum[i] = sv;
         if (i < nrow && sub == 0) tot[i] = sv;
         __syncthreads();
@@ -518,6 +514,7 @@ __global__ __launch_bounds__(64 * FC_NW) void flowchain_bwd_kernel(PfFlowChain a
 #pragma unroll
         for (int n = 0; n < 15; ++n) {
             float sv = (valid && q == 0) ? acc[n] : 0.f;
+            // written out: through pf_xor_sum<1, 8> flowchain_bwd_kernel compiles to another instruction stream
             sv += __shfl_xor(sv, 1); sv += __shfl_xor(sv, 2); sv += __shfl_xor(sv, 4); sv += __shfl_xor(sv, 8);
             acc[n] = sv;
         }

@@ -614,35 +614,11 @@ __global__ __launch_bounds__(ECP_T) void ec_bwdp_kernel(EcBwdPArgs a) {
                 }
             }
         }
-#pragma unroll
-        for (int nt = 0; nt < NTG; ++nt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float a0 = ecp_rowsum16(s0[nt][r]), a1 = ecp_rowsum16(s1[nt][r]);
-                const int c = 16 * (b0 + nt) + 4 * q + r - col0;
-                if (col == 0 && c >= 0 && c < G) { red[wave * 64 + c] = a0; red[wave * 64 + 32 + c] = a1; }
-            }
-        __syncthreads();
-        if (threadIdx.x < 64 && (threadIdx.x & 31) < G) {
-            float v = 0.f;
-#pragma unroll
-            for (int w = 0; w < ECP_WAVES; ++w) v += red[w * 64 + threadIdx.x];
-            unsafeAtomicAdd(a.acc + (blockIdx.x % STAT_COPIES) * 2 * STAT_W + (threadIdx.x >> 5) * STAT_W + 32 * s + (threadIdx.x & 31), (double)v);
-        }
+        ecp_stat_publish<G>(s0, s1, b0, col0, s, a.acc, red, true);
         alive = ecp_barrier(a.sync, (unsigned)(NC - s), &flag);
         if (!alive) return;
-        double part = 0.0;
-        if (threadIdx.x < 256) {
-            const int pt = threadIdx.x & 3, stt = (threadIdx.x >> 2) & 1, c = threadIdx.x >> 3;
-            double v[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                v[k] = __hip_atomic_load(a.acc + (4 * pt + k) * 2 * STAT_W + stt * STAT_W + 32 * s + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            part = (v[0] + v[1]) + (v[2] + v[3]);
-            part += __shfl_xor(part, 1);
-            part += __shfl_xor(part, 2);
-        }
-        const double other = __shfl_xor(part, 4);
+        const EcpSums sums = ecp_stat_fetch(a.acc, s);
+        const double part = sums.part, other = sums.other;
         if (threadIdx.x < 256 && (threadIdx.x & 7) == 0 && (threadIdx.x >> 3) < G) {
             const int c = threadIdx.x >> 3;
             m12[c] = (float)(part / a.R);
@@ -684,18 +660,7 @@ __global__ __launch_bounds__(ECP_T) void ec_bwdp_kernel(EcBwdPArgs a) {
                 for (int c = 4 * q; c < GT; c += 16)
                     *reinterpret_cast<f4*>(a.dA + ((size_t)tl[t] * 16 + col) * a.ld + c) = pf_splat(__builtin_nanf(""));
     }
-    __syncthreads();
-    if (threadIdx.x == 0) flag = atomicAdd(a.sync + 2, 1u) == gridDim.x - 1 ? 1 : 0;
-    __syncthreads();
-    if (flag == 1) {
-        for (int i = threadIdx.x; i < STAT_COPIES * 2 * STAT_W; i += ECP_T)
-            if ((i % STAT_W) < 32 * NC) __hip_atomic_store(a.acc + i, 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (threadIdx.x == 0) {
-            __hip_atomic_store(a.sync + 0, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(a.sync + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(a.sync + 2, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
+    ecp_exit_reset(a.acc, a.sync, NC, &flag);
 }
 
 // growth layer 0 has no growth input: only dA[:, 0:g] -> dy in place

@@ -14,6 +14,7 @@
 //                               the zero-filled gradient buffers they accumulate into, and d logp
 #include <hip/hip_runtime.h>
 #include "pf_api_internal.h"
+#include "pf_wave.h"
 
 namespace {
 
@@ -71,7 +72,7 @@ __global__ __launch_bounds__(256) void interp_wsum_bwd_kernel(const float* __res
         const float ak = a[tk * R + r];
         const float da = g0 * z0 + g1 * z1 + g2 * z2;
         float dot = ak * da;
-        dot += __shfl_xor(dot, 1); dot += __shfl_xor(dot, 2); dot += __shfl_xor(dot, 4);
+        dot = pf_xor_sum<1, 4>(dot);
         dw[tk * ldw + r] = ak * (da - dot);
         g0s += ak * g0; g1s += ak * g1; g2s += ak * g2;
     }
@@ -127,8 +128,7 @@ __global__ __launch_bounds__(1024) void pugan_loss_fwd_kernel(const float* __res
         for (; i + 192 < n; i += 256) { s0 += dp[i]; s1 += dp[i + 64]; s2 += dp[i + 128]; s3 += dp[i + 192]; }
         for (; i < n; i += 64) s0 += dp[i];
         float sv = (s0 + s1) + (s2 + s3);
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) sv += __shfl_xor(sv, m);
+        sv = pf_wave_sum(sv);
         acc += sv / (radius ? radius[b] : 1.f);
     }
     if (lane == 0) part[wave] = acc;

@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include "pf_api_internal.h"
 #include "pf_mfma.h"
+#include "pf_wave.h"
 
 namespace {
 
@@ -308,9 +309,7 @@ __global__ __launch_bounds__(256) void mlp_bwd_kernel(MlpBatch bb) {
                             const f4 wx = *reinterpret_cast<const f4*>(Wx + (cb * 16 + 4 * q + r) * 4);
                             s0 = fmaf(g[cb][r], wx.x, s0); s1 = fmaf(g[cb][r], wx.y, s1); s2 = fmaf(g[cb][r], wx.z, s2);
                         }
-                s0 += __shfl_xor(s0, 16); s0 += __shfl_xor(s0, 32);
-                s1 += __shfl_xor(s1, 16); s1 += __shfl_xor(s1, 32);
-                s2 += __shfl_xor(s2, 16); s2 += __shfl_xor(s2, 32);
+                s0 = pf_xor_sum<16, 32>(s0); s1 = pf_xor_sum<16, 32>(s1); s2 = pf_xor_sum<16, 32>(s2);
                 if (q == 0 && valid && G.dy) {
                     const float sv[3] = {s0, s1, s2};
                     for (int j = 0; j < p.ldy; ++j) G.dy[(size_t)p0 * p.ldy + j] = (j < p.td && j < 3) ? sv[j < 3 ? j : 0] : 0.f;

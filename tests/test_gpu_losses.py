@@ -18,7 +18,8 @@ def _unit_cube(B, n, seed):
     return torch.rand(B, n, 3, generator=g)
 
 
-@pytest.mark.parametrize("B,N,M", [(2, 256, 1024), (3, 1000, 777), (1, 8192, 8192), (32, 1024, 1024), (40, 300, 500)])
+@pytest.mark.parametrize("B,N,M", [(2, 256, 1024), (3, 1000, 777), (1, 8192, 8192), (32, 1024, 1024), (40, 300, 500),
+                                   (64, 1000, 1100)])          # 256 strips of 256 queries: knn5_kernel<1> with 16 waves
 def test_chamfer_forward(B, N, M):
     from puflow_amd import ops
     x = synth_patches(B, N, seed=N, surface=False)

@@ -1,9 +1,22 @@
 #!/usr/bin/env python3
-"""Check A: compare kernels of two source trees (resources + instruction streams) for the default, bwdf32 and gradf32 builds.
-python tools/cmp_isa.py PARENT_ROOT BRANCH_ROOT [--dump DIR]   (two checkouts; build container, no GPU)"""
-import concurrent.futures, filecmp, hashlib, importlib.util, os, re, subprocess, sys, tempfile
+"""Check A: compare kernels of two source trees (resources + instruction streams) for the default, bwdf32, gradf32 and f16 builds.
+python tools/cmp_isa.py PARENT_ROOT BRANCH_ROOT [--dump DIR]   (two checkouts; build container, no GPU)
 
-VARIANTS = {"default": [], "bwdf32": ["PF_EC_BWDG_F32", "PF_EC_DW_F32"], "gradf32": ["PF_EC_BWDG_F32", "PF_EC_DW_F32", "PF_EC_FWD_F32"]}
+A source is compiled when its own text differs between the trees or ANY header under csrc/ or include/ does (a header edit
+changes every kernel that includes it).  Verdict per kernel copy:
+  identical   same resource record, same instruction stream
+  reordered   same resource record, same instruction count, same multiset of (mnemonic, operand count): the streams differ by
+              register names and the order of independent instructions only
+  ISA DIFFERS anything else
+Exit status 0 only when every kernel is identical or reordered, none appeared or disappeared and none uses scratch that did
+not at the parent."""
+import collections, concurrent.futures, filecmp, hashlib, importlib.util, os, re, subprocess, sys, tempfile
+
+# variant -> (defines, the sources build.py recompiles for it: None = all, a str = that attribute of build.py)
+VARIANTS = {"default": ([], None),
+            "bwdf32": (["PF_EC_BWDG_F32", "PF_EC_DW_F32"], ("train_fused.hip",)),
+            "gradf32": (["PF_EC_BWDG_F32", "PF_EC_DW_F32", "PF_EC_FWD_F32"], ("train_fused.hip", "train_ec_fwd.hip")),
+            "f16": (["PF_MMN_TERMS=1"], "F16_SOURCES")}
 
 
 def load_build(root):
@@ -53,37 +66,64 @@ def parse(asm_path):
     return res
 
 
+def headers(root):
+    hs = {}
+    for d in ("puflow_amd/csrc", "include"):
+        for f in sorted(os.listdir(os.path.join(root, d))):
+            if f.endswith(".h"):
+                hs[d + "/" + f] = open(os.path.join(root, d, f), "rb").read()
+    return hs
+
+
+def histogram(lines):
+    """multiset of (mnemonic, operand count); labels count as themselves"""
+    c = collections.Counter()
+    for line in lines:
+        op, _, rest = line.partition(" ")
+        c[(op, len(rest.split(",")) if rest else 0)] += 1
+    return c
+
+
 def main():
     parent, branch = sys.argv[1], sys.argv[2]
     dump = sys.argv[sys.argv.index("--dump") + 1] if "--dump" in sys.argv else None
     trees = {"parent": parent, "branch": branch}
     Bs = {k: load_build(v) for k, v in trees.items()}
+    hp, hb = headers(parent), headers(branch)
+    hdr_diff = sorted(h for h in set(hp) | set(hb) if hp.get(h) != hb.get(h))
+    print("headers that differ:", hdr_diff or "none")
     files = {}
     for k, root in trees.items():
         other = trees["branch" if k == "parent" else "parent"]
         fs = []
         for s in Bs[k].SOURCES:
             a, b = os.path.join(root, "puflow_amd/csrc", s), os.path.join(other, "puflow_amd/csrc", s)
-            if not os.path.exists(b) or not filecmp.cmp(a, b, shallow=False):
+            if hdr_diff or not os.path.exists(b) or not filecmp.cmp(a, b, shallow=False):
                 fs.append(s)
         files[k] = fs
     print("sources that differ:", files)
     tmp = tempfile.mkdtemp(prefix="cmpisa_")
     jobs = {}
+
+    def vfiles(k, v):
+        only = VARIANTS[v][1]
+        only = getattr(Bs[k], only) if isinstance(only, str) else only
+        return [s for s in files[k] if only is None or s in only]
+
     with concurrent.futures.ThreadPoolExecutor(8) as ex:
         for k, root in trees.items():
-            for v, defs in VARIANTS.items():
-                for s in files[k]:
+            for v, (defs, _) in VARIANTS.items():
+                for s in vfiles(k, v):
                     out = os.path.join(tmp, f"{k}_{v}_{s}.s")
                     jobs[(k, v, s)] = ex.submit(compile_s, Bs[k], os.path.join(root, "puflow_amd/csrc", s), defs, out)
         for j in jobs.values():
             j.result()
-    ok = True
+    ok, totals = True, [0, 0, 0]
     for v in VARIANTS:
         side = {}
         for k in trees:
             allk = {}
-            for s in files[k]:
+            for s in vfiles(k, v):
                 for name, lst in parse(jobs[(k, v, s)].result()).items():
                     allk.setdefault(name, []).extend([(s,) + x[1:] for x in lst])
             side[k] = allk
@@ -94,26 +134,39 @@ def main():
         print("   only in branch:", only_b or "none")
         if only_b or [n for n in only_p if not re.search(r"::(ec_dw4_kernel|ec_dw5_kernel|ec_bwd_kernel<)", n)]:
             ok = False
-        nsame = 0
+        nsame, reordered, differs = 0, [], []
         for name in sorted(set(P) & set(Bk)):
             ps, pr, pl = P[name][0]
             for bs, br, bl in Bk[name]:
-                if br["ScratchSize"]:
-                    print("   SCRATCH", name, br); ok = False
+                if br["ScratchSize"] and not pr["ScratchSize"]:
+                    print("   NEW SCRATCH", name, br); ok = False
                 if pr != br:
-                    print(f"   RESOURCES DIFFER {name}\n      parent {ps}: {pr}\n      branch {bs}: {br}"); ok = False
-                if pl != bl:
-                    print(f"   ISA DIFFERS {name} ({ps}: {len(pl)} instr, {bs}: {len(bl)} instr)"); ok = False
-                    if dump:
-                        os.makedirs(dump, exist_ok=True)
-                        h = hashlib.md5(name.encode()).hexdigest()[:8]
-                        open(os.path.join(dump, f"{v}_{h}_parent.s"), "w").write(name + "\n" + "\n".join(pl) + "\n")
-                        open(os.path.join(dump, f"{v}_{h}_branch.s"), "w").write(name + "\n" + "\n".join(bl) + "\n")
+                    print(f"   RESOURCES DIFFER {name}\n      parent {ps}: {pr}\n      branch {bs}: {br}")
                 if pr == br and pl == bl:
                     nsame += 1
+                    continue
+                nline = sum(x != y for x, y in zip(pl, bl)) + abs(len(pl) - len(bl))
+                what = f"{name} ({ps}: {len(pl)} instr, {bs}: {len(bl)} instr, {nline} lines differ)"
+                if pr == br and len(pl) == len(bl) and histogram(pl) == histogram(bl):
+                    reordered.append(what)
+                else:
+                    differs.append(what); ok = False
+                if dump:
+                    os.makedirs(dump, exist_ok=True)
+                    h = hashlib.md5(name.encode()).hexdigest()[:8]
+                    open(os.path.join(dump, f"{v}_{h}_parent.s"), "w").write(name + "\n" + "\n".join(pl) + "\n")
+                    open(os.path.join(dump, f"{v}_{h}_branch.s"), "w").write(name + "\n" + "\n".join(bl) + "\n")
         print(f"   identical (registers, scratch, LDS, occupancy, instruction stream): {nsame} kernel copies; "
               f"total instructions compared {sum(len(x[2]) for l in Bk.values() for x in l)}")
-    print("\nRESULT:", "ALL IDENTICAL" if ok else "DIFFERENCES")
+        print(f"   reordered (same resources, instruction count and (mnemonic, operand count) multiset): {len(reordered)} kernel copies")
+        for w in reordered:
+            print("      REORDERED", w)
+        print(f"   ISA DIFFERS: {len(differs)} kernel copies")
+        for w in differs:
+            print("      ISA DIFFERS", w)
+        totals[0] += nsame; totals[1] += len(reordered); totals[2] += len(differs)
+    print(f"\nTOTAL: identical {totals[0]}, reordered {totals[1]}, ISA differs {totals[2]}")
+    print("RESULT:", "DIFFERENCES" if not ok else "ALL IDENTICAL" if not totals[1] else "IDENTICAL OR REORDERED")
     return 0 if ok else 1
 
 
