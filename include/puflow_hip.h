@@ -685,6 +685,27 @@ int pf_cnf_rhs(const float* y0, const float* k, const float* coef, int ncoef, fl
                const float* ctx, const float* e, const float* rec, float* kout, float* yout, int rows, int R,
                void* stream);
 
+/* Vector-Jacobian product of that right-hand side (csrc/cnf_bwd.hip), the kernel a differentiable flow block is built on.
+ * With k = sgn * ( f(t, y), -e^T (df/dy) e ) - pf_cnf_rhs's kout for the state y [rows,4] - and S = sum_rows kbar . k:
+ *   ybar   [rows,4]  OVERWRITTEN  dS/dy, column 3 zero (log p never enters f)
+ *   ctxbar [T,288]   +=           dS/d(hyper-network outputs) per original point, summed over the point's R rows, in the ctx
+ *                                 layout gate1[64] bias1[64] gate2[64] bias2[64] gate3 bias3.  In the units of the model's own
+ *                                 pre-activations (the -log2e / 2 log2e the forward folds into ctx are NOT in it), and layer 3
+ *                                 uses the first of its four replicated slots only: columns 256..258 and 272..274; the
+ *                                 columns 259..271 and 275..287 are never touched.
+ *   grad   [4900]    +=           [0,4096) dW2 [64][64]   [4096,4288) dW1 [64][3]   [4288,4352) db1   [4352,4416) db2
+ *                                 [4416,4608) dW3 [3][64]   [4608,4611) db3   [4611] unused
+ *                                 [4612,4900) gradients of the 288 time coefficients, ctx layout as for ctxbar: t x the column
+ *                                 sums of THIS evaluation's ctxbar contributions (not recoverable from ctxbar later, which
+ *                                 sums evaluations taken at different t).  All in the parameters' own units.
+ * rows must be a multiple of R and R <= 16: a 16-row MFMA tile holds floor(16 / R) whole points, so a point never straddles
+ * tiles and its rows are summed inside the wave.  No float atomics: workgroups sum their tiles on chip, write one partial slab
+ * each into ws, and a second small launch adds the slabs in a fixed order - results are the same bits from run to run.
+ * ws: pf_cnf_rhs_vjp_workspace_bytes(rows, R) bytes (negative: bad shape), never more than 256 * 4900 floats. */
+long long pf_cnf_rhs_vjp_workspace_bytes(int rows, int R);
+int pf_cnf_rhs_vjp(const float* y, const float* kbar, float t, float sgn, const float* ctx, const float* e, const float* rec,
+                   float* ybar, float* ctxbar, float* grad, int rows, int R, void* ws, void* stream);
+
 /* One whole Dormand-Prince 5(4) step attempt per launch (the six stage evaluations fused, stage derivatives in
  * registers): y1 = y0 + h sum b_j k_j with k_1 = f0 (FSAL), f1 = k_7, ymid (nullable) = dense-output mid-point,
  * out[0] (double, device) = sum_i (err_i / (atol + rtol max(|y0_i|, |y1_i|)))^2 of the embedded error estimate.

@@ -1,7 +1,8 @@
 """Continuous (CNF) PU-Flow: `modules/continuous/interpflow.py` on the HIP library.
 
 Same constructor, methods and the 390 state-dict keys of the reference's continuous `PointInterpFlow`
-(`pretrain/puflow-x4-cnf-pu1k.pt` loads with `load_state_dict`).  Eval / inference only.
+(`pretrain/puflow-x4-cnf-pu1k.pt` loads with `load_state_dict`).  The whole model is eval / inference only; ONE flow block is
+differentiable (`PointInterpFlow.flow_block`: taped Dormand-Prince steps, backward by `pf_cnf_rhs_vjp`, csrc/cnf_bwd.hip).
 
 What runs where:
   * kNN, the six EdgeConv units, the merge units and the interpolation module are the discrete model's kernels
@@ -30,7 +31,8 @@ from torch import Tensor
 from . import _lib
 from .interpflow import (COND_CHANNELS, FEAT_CHANNELS, GROWTH, NUM_BLOCKS, _EdgeConvParams, _Engine, _InterpParams,
                          _MergeParams)
-from .packing import CNF_CTX, cnf_split_ok, pack_cnf_block, pack_cnf_context
+from .packing import (CNF_CTX, CNF_GRAD, cnf_hyper_matrix, cnf_split_ok, pack_cnf_block, pack_cnf_context,
+                      unpack_cnf_grads)
 from .train_ops import _gemm
 from .weights import state_dict_spec
 
@@ -108,43 +110,30 @@ def _discrete_shell(sd) -> dict:
     return out
 
 
-class _CnfEngine:
-    """Device-side plan of the continuous model + the dopri5 driver."""
+class _CnfKernels:
+    """Launch wrappers of csrc/cnf.hip shared by the inference engine and the taped single-block engine.  What they read of
+    `self` is set by `_init_kernels` (lib, device, the norm kernels' scratch `ws` / `ws1k` / `red`, the counter `nfe`) and by
+    `_add_block`: per block index i the record `rec[i]`, the context GEMM's `Hc[i]`, `Hci[i]`, `hb[i]` and `T_end[i]`."""
 
-    def __init__(self, sd, device: torch.device, upratio: int):
+    def _init_kernels(self, device: torch.device) -> None:
         self.lib = _lib.load()
         self.device = device
-        self.R = upratio
-        self.base = _Engine(_discrete_shell(sd), device)
-        self.rec, self.Hc, self.Hci, self.hb, self.T_end, self.split = [], [], [], [], [], []
-        for i in range(NUM_BLOCKS):
-            rec, Hc, hb, T_end = pack_cnf_block(sd, i)
-            self.rec.append(torch.from_numpy(rec).to(device))
-            self.Hc.append(torch.from_numpy(Hc).to(device))
-            img, inv = pack_cnf_context(Hc)
-            self.Hci.append((torch.from_numpy(img).to(device), float(inv)))
-            self.hb.append(torch.from_numpy(hb).to(device))
-            self.T_end.append(T_end)
-            # PF_CNF_SPLIT_GATES (include/puflow_hip.h): only where the factored 2^x cannot overflow; PF_CNF_SPLIT=0 keeps the plain kernel
-            self.split.append(int(cnf_split_ok(rec, T_end) and os.environ.get("PF_CNF_SPLIT", "1") != "0"))
+        self.rec, self.Hc, self.Hci, self.hb, self.T_end = {}, {}, {}, {}, {}
         self.ws = torch.empty(256, dtype=torch.float64, device=device)
         self.ws1k = torch.empty(1024, dtype=torch.float64, device=device)
-        self.ws3k = torch.empty(3072, dtype=torch.float64, device=device)
         self.red = torch.empty(1, dtype=torch.float64, device=device)
-        self.red3 = torch.empty(3, dtype=torch.float64, device=device)
-        self.ctl = torch.zeros(16, dtype=torch.float64, device=device)       # dopri5 controller state (csrc/cnf.hip; zero before its first use)
-        self.first_batch = int(os.environ.get("PF_CNF_FIRST_BATCH", "8"))    # step attempts enqueued before the first look
-        self.next_batch = int(os.environ.get("PF_CNF_NEXT_BATCH", "4"))
-        # attempts enqueued per integration when the whole forward runs WITHOUT reading the controller in between (attempts past
-        # the end are ~4 us no-ops; an integration that needs more makes the forward fall back to the look-per-batch loop); 0 = off
-        self.async_attempts = int(os.environ.get("PF_CNF_ASYNC_ATTEMPTS", "1"))             # 0 = never run blind
-        self.logs = torch.zeros((2 * NUM_BLOCKS, 16), dtype=torch.float64, device=device)   # controller state after each integration
-        # step attempts each of the twelve integrations took the last time (accepted + rejected): the blind run enqueues that
-        # many + a margin (the trained model's blocks differ by 10x: 3 attempts for the short ones, 25 for the T = 36 block)
-        self.hint: Optional[List[int]] = None
         self.nfe = 0
-        self.accepted = 0
-        self.rejected = 0
+
+    def _add_block(self, sd, i: int):
+        """Pack block i of the state dict `sd` onto the device -> the host record (for `cnf_split_ok`)."""
+        rec, Hc, hb, T_end = pack_cnf_block(sd, i)
+        img, inv = pack_cnf_context(Hc)
+        self.rec[i] = torch.from_numpy(rec).to(self.device)
+        self.Hc[i] = torch.from_numpy(Hc).to(self.device)
+        self.Hci[i] = (torch.from_numpy(img).to(self.device), float(inv))
+        self.hb[i] = torch.from_numpy(hb).to(self.device)
+        self.T_end[i] = T_end
+        return rec
 
     @staticmethod
     def _stream() -> int:
@@ -187,12 +176,40 @@ class _CnfEngine:
                    "pf_scaled_sumsq")
         return float(self.red.item())                       # the one device->host read per norm
 
-    # ---- dopri5 (control flow of torchdiffeq's adaptive solver, restated: oracle/cnf_ref.py::dopri5) ------
     def context_norm(self, c: Tensor, out: Tensor) -> None:
         """out[0] (device double) = sum (c / (atol + rtol |c|))^2: the context's share of the solver's initial-step norm."""
         _lib.check(self.lib.pf_scaled_sumsq(c.data_ptr(), None, c.data_ptr(), None, None, (ctypes.c_float * 1)(0.0), 0, 0.0,
                                             RTOL, ATOL, c.numel(), self.ws.data_ptr(), out.data_ptr(), self._stream()),
                    "pf_scaled_sumsq")
+
+
+class _CnfEngine(_CnfKernels):
+    """Device-side plan of the continuous model + the dopri5 driver."""
+
+    def __init__(self, sd, device: torch.device, upratio: int):
+        self._init_kernels(device)
+        self.R = upratio
+        self.base = _Engine(_discrete_shell(sd), device)
+        self.split = []
+        for i in range(NUM_BLOCKS):
+            rec = self._add_block(sd, i)
+            # PF_CNF_SPLIT_GATES (include/puflow_hip.h): only where the factored 2^x cannot overflow; PF_CNF_SPLIT=0 keeps the plain kernel
+            self.split.append(int(cnf_split_ok(rec, self.T_end[i]) and os.environ.get("PF_CNF_SPLIT", "1") != "0"))
+        self.ws3k = torch.empty(3072, dtype=torch.float64, device=device)
+        self.red = torch.empty(1, dtype=torch.float64, device=device)
+        self.red3 = torch.empty(3, dtype=torch.float64, device=device)
+        self.ctl = torch.zeros(16, dtype=torch.float64, device=device)       # dopri5 controller state (csrc/cnf.hip; zero before its first use)
+        self.first_batch = int(os.environ.get("PF_CNF_FIRST_BATCH", "8"))    # step attempts enqueued before the first look
+        self.next_batch = int(os.environ.get("PF_CNF_NEXT_BATCH", "4"))
+        # attempts enqueued per integration when the whole forward runs WITHOUT reading the controller in between (attempts past
+        # the end are ~4 us no-ops; an integration that needs more makes the forward fall back to the look-per-batch loop); 0 = off
+        self.async_attempts = int(os.environ.get("PF_CNF_ASYNC_ATTEMPTS", "1"))             # 0 = never run blind
+        self.logs = torch.zeros((2 * NUM_BLOCKS, 16), dtype=torch.float64, device=device)   # controller state after each integration
+        # step attempts each of the twelve integrations took the last time (accepted + rejected): the blind run enqueues that
+        # many + a margin (the trained model's blocks differ by 10x: 3 attempts for the short ones, 25 for the T = 36 block)
+        self.hint: Optional[List[int]] = None
+        self.accepted = 0
+        self.rejected = 0
 
     def integrate(self, i: int, x: Tensor, ctx: Tensor, e: Tensor, R: int, reverse: bool, extra_n: int,
                   extra_d0, log: Optional[Tensor] = None, blind: int = 0, extra_scale: float = 1.0) -> Tensor:
@@ -303,6 +320,167 @@ class _CnfEngine:
         self.rejected += int(L[:k, 7].sum())
         self.nfe += int(L[:k, 8].sum())
         return k
+
+
+class _BlockTapeEngine(_CnfKernels):
+    """The kernels of ONE block around weights packed from the live parameters: the taped integration of
+    `PointInterpFlow.flow_block` and its backward."""
+
+    def __init__(self, sd_block, i: int, device: torch.device):
+        self._init_kernels(device)
+        self._add_block(sd_block, i)
+        self.Hplain = torch.from_numpy(cnf_hyper_matrix(sd_block, i)[:, 1:].copy()).to(device)      # [288, cd], no folded constants
+
+    def step(self, i, y, f0, t, h, reverse, ctx, e, y1, f1, rows, R) -> float:
+        """One Dormand-Prince attempt (pf_cnf_step) -> the scaled error sum, read back (one host read per attempt)."""
+        _lib.check(self.lib.pf_cnf_step(y.data_ptr(), f0.data_ptr(), float(t), float(h), 1 if reverse else 0, ctx.data_ptr(),
+                                        e.data_ptr(), self.rec[i].data_ptr(), y1.data_ptr(), f1.data_ptr(), None, RTOL, ATOL,
+                                        rows, R, self.ws1k.data_ptr(), self.red.data_ptr(), self._stream()), "pf_cnf_step")
+        self.nfe += 6
+        return float(self.red.item())
+
+    def tape_forward(self, i: int, x: Tensor, c: Tensor, e: Tensor, R: int, reverse: bool):
+        """dopri5 on block i with ONE attempt per launch and the control on the host (oracle/cnf_ref.py::dopri5 restated), except
+        that the step which would cover the end time is cut to END there: the result is the last accepted step's solution, not
+        a dense-output value inside it, so the forward is exactly the recorded steps.
+        -> (state [rows,4], tape): tape holds (s, h) per accepted step as host floats (the fp32 values the kernels were given),
+        the state at the start of each step on the device, the context rows and the derivatives at both ends."""
+        rows = x.shape[0]
+        dev = x.device
+        T = self.T_end[i]
+        t0, t1 = (0.0, T) if not reverse else (-T, 0.0)
+        sgn = 1.0 if not reverse else -1.0
+        f32 = lambda v: float(torch.tensor(v, dtype=torch.float32))
+        ctx = self.context(i, c)
+        n_tot = float(rows * 4 + c.numel() * R)                 # the context is a state of the reference's ODE: it enters the norms
+        self.context_norm(c, self.red)
+        d0c = float(self.red.item()) * R
+        y = torch.zeros((rows, 4), dtype=torch.float32, device=dev)
+        y[:, :3] = x
+        f0, f1 = torch.empty_like(y), torch.empty_like(y)
+        self._rhs(i, y, y, [], 0.0, sgn * t0, sgn, ctx, e, f0, None, rows, R)
+        f_start = f0
+        d0 = math.sqrt((self._sumsq(y, None, y, None) + d0c) / n_tot)
+        d1 = math.sqrt(self._sumsq(f0, None, y, None) / n_tot)
+        h0 = 1e-6 if (d0 < 1e-5 or d1 < 1e-5) else 0.01 * d0 / d1
+        self._rhs(i, y, f0, [1.0], h0, sgn * (t0 + h0), sgn, ctx, e, f1, None, rows, R)
+        d2 = math.sqrt(self._sumsq(f1, f0, y, None) / n_tot) / h0
+        h1 = max(1e-6, h0 * 1e-3) if (d1 <= 1e-15 and d2 <= 1e-15) else (0.01 / max(d1, d2)) ** (1.0 / ORDER)
+        dt = min(100 * h0, h1)
+        t = t0
+        steps, states = [], []
+        for _ in range(MAX_NUM_STEPS):
+            cover = t + dt >= t1
+            ts, h = f32(t), f32(t1 - t if cover else dt)
+            y1 = torch.empty_like(y)
+            ratio = math.sqrt(self.step(i, y, f0, ts, h, reverse, ctx, e, y1, f1, rows, R) / n_tot)
+            if not math.isfinite(ratio):
+                raise _lib.PuflowHipError(f"dopri5: non-finite error norm in block {i} at t = {t:g}")
+            if not (t + h > t):
+                raise _lib.PuflowHipError(f"dopri5: underflow in dt ({h:g}) at t = {t:g}, block {i}")
+            if ratio <= 1.0:
+                steps.append((ts, h)); states.append(y)
+                y, f0, f1 = y1, f1, torch.empty_like(y)
+                t = t + h
+                if cover:
+                    break
+            dt = h * IFACTOR if ratio == 0 else h * min(IFACTOR, max(SAFETY / ratio ** (1.0 / ORDER), 1.0 if ratio < 1 else DFACTOR))
+        else:
+            raise _lib.PuflowHipError(f"dopri5: more than {MAX_NUM_STEPS} step attempts in block {i}")
+        return y, dict(steps=steps, states=states, ctx=ctx, f_start=f_start, f_end=f0)
+
+    def vjp(self, i, y, kbar, t, sgn, ctx, e, ybar, ctxbar, grad, rows, R) -> None:
+        if getattr(self, "_vjp_shape", None) != (rows, R):
+            need = self.lib.pf_cnf_rhs_vjp_workspace_bytes(rows, R)
+            if need < 0:
+                raise _lib.PuflowHipError(f"pf_cnf_rhs_vjp: rows = {rows} must be a multiple of R = {R} <= 16")
+            self._vjp_ws = torch.empty(need // 4, dtype=torch.float32, device=y.device)
+            self._vjp_shape = (rows, R)
+        _lib.check(self.lib.pf_cnf_rhs_vjp(y.data_ptr(), kbar.data_ptr(), float(t), float(sgn), ctx.data_ptr(), e.data_ptr(),
+                                           self.rec[i].data_ptr(), ybar.data_ptr(), ctxbar.data_ptr(), grad.data_ptr(), rows, R,
+                                           self._vjp_ws.data_ptr(), self._stream()), "pf_cnf_rhs_vjp")
+
+    def tape_backward(self, i: int, tape: dict, ybar: Tensor, c: Tensor, e: Tensor, R: int, reverse: bool):
+        """The recorded steps in reverse, step sizes as constants.  Per step the stage states are recomputed
+        (pf_cnf_rhs), then for j = 6 .. 1:  kbar_j = h b_j y1bar + h sum_{m > j} a_mj Ybar_m  (pf_lincomb),
+        Ybar_j = VJP_F(Y_j, t_j; kbar_j)  (pf_cnf_rhs_vjp, which also adds the evaluation's weight / context gradients), and
+        y0bar = y1bar + sum_j Ybar_j.  -> (y0bar [rows,4], grad record [4900], ctxbar [T,288])."""
+        rows = ybar.shape[0]
+        dev = ybar.device
+        sgn = 1.0 if not reverse else -1.0
+        ctx = tape["ctx"]
+        grad = torch.zeros(CNF_GRAD, dtype=torch.float32, device=dev)
+        ctxbar = torch.zeros((c.shape[0], CNF_CTX), dtype=torch.float32, device=dev)
+        K = torch.empty((5, rows, 4), dtype=torch.float32, device=dev)             # k_1 .. k_5 of the step being swept
+        Y = torch.empty((6, rows, 4), dtype=torch.float32, device=dev)
+        Yb = torch.empty((6, rows, 4), dtype=torch.float32, device=dev)
+        kb = torch.empty((rows, 4), dtype=torch.float32, device=dev)
+        b = DP_BETA[5]
+        alpha = [0.0] + DP_ALPHA[:5]
+        for (s, h), y0 in zip(reversed(tape["steps"]), reversed(tape["states"])):
+            self._rhs(i, y0, y0, [], 0.0, sgn * s, sgn, ctx, e, K[0], None, rows, R)
+            for j in range(1, 5):
+                self._rhs(i, y0, K, DP_BETA[j - 1], h, sgn * (s + alpha[j] * h), sgn, ctx, e, K[j], Y[j], rows, R)
+            # the last stage's STATE only (its derivative k_6 is not needed: the sweep differentiates it, it does not use it)
+            self._lincomb([y0] + [K[m] for m in range(5)], [1.0] + [h * a for a in DP_BETA[4]], Y[5])
+            for j in reversed(range(6)):
+                terms, w = [ybar], [h * b[j]]
+                for m in range(j + 1, 6):
+                    if DP_BETA[m - 1][j] != 0:
+                        terms.append(Yb[m]); w.append(h * DP_BETA[m - 1][j])
+                self._lincomb(terms, w, kb)
+                self.vjp(i, y0 if j == 0 else Y[j], kb, sgn * (s + alpha[j] * h), sgn, ctx, e, Yb[j], ctxbar, grad, rows, R)
+            nxt = torch.empty_like(ybar)
+            self._lincomb([ybar] + [Yb[j] for j in range(6)], [1.0] * 7, nxt)
+            ybar = nxt
+        return ybar, grad, ctxbar
+
+
+class _FlowBlockFn(torch.autograd.Function):
+    """(x, c, parameters of block i) -> (x', delta logp): `PointInterpFlow.flow_block`."""
+
+    @staticmethod
+    def forward(fctx, x, c, e, i, R, reverse, keys, record, *params):
+        sd = {k: p.detach().cpu() for k, p in zip(keys, params)}
+        eng = _BlockTapeEngine(sd, i, x.device)
+        x32, c32, e32 = x.detach().float().contiguous(), c.detach().float().contiguous(), e.detach().float().contiguous()
+        y, tape = eng.tape_forward(i, x32, c32, e32, R, reverse)
+        fctx.eng, fctx.tape, fctx.args = eng, tape, (i, R, reverse, keys, x.dtype, c.dtype)
+        fctx.save_for_backward(c32, e32, *params)
+        record.extend(tape["steps"])
+        return y[:, :3].contiguous(), y[:, 3].contiguous()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(fctx, gx, gl):
+        i, R, reverse, keys, xdt, cdt = fctx.args
+        c, e, *params = fctx.saved_tensors
+        eng, tape = fctx.eng, fctx.tape
+        rows = tape["states"][0].shape[0]
+        ybar = torch.zeros((rows, 4), dtype=torch.float32, device=c.device)
+        if gx is not None:
+            ybar[:, :3] = gx
+        if gl is not None:
+            ybar[:, 3] = gl
+        y0bar, grad, ctxbar = eng.tape_backward(i, tape, ybar, c, e, R, reverse)
+        # ctx = [1 | c] [hb | Hc]^T:  one GEMM for d(hb | Hc) = ctxbar^T [1 | c] (column 0: the column sums), one for dc
+        T, cd = c.shape
+        c1 = torch.cat([torch.ones((T, 1), dtype=torch.float32, device=c.device), c], dim=1).contiguous()
+        dH1 = torch.empty((CNF_CTX, cd + 1), dtype=torch.float32, device=c.device)
+        _gemm(ctxbar, 1, CNF_CTX, c1, cd + 1, 1, dH1, cd + 1, None, CNF_CTX, cd + 1, T)
+        dc = torch.empty((T, cd), dtype=torch.float32, device=c.device)
+        _gemm(ctxbar, CNF_CTX, 1, eng.Hplain, cd, 1, dc, cd, None, T, cd, CNF_CTX)
+        grads = unpack_cnf_grads(i, grad, dH1[:, 1:], dH1[:, 0])
+        # end time T = sqrt_end_time^2 by the CONTINUOUS formula (not the derivative of the discrete scheme): the solution moves
+        # along the solver's derivative at the end whose time is T - the final state going forward, the start going backward
+        dT = (ybar * tape["f_end"]).sum() if not reverse else (y0bar * tape["f_start"]).sum()
+        out = []
+        for k, p in zip(keys, params):
+            if k.endswith("sqrt_end_time"):
+                out.append((dT * 2.0 * p.detach()).reshape(p.shape).to(p.dtype))
+            else:
+                out.append(grads[k].reshape(p.shape).to(p.dtype))
+        return (y0bar[:, :3].contiguous().to(xdt), dc.to(cdt), None, None, None, None, None, None, *out)
 
 
 class PointInterpFlow(nn.Module):
@@ -437,6 +615,30 @@ class PointInterpFlow(nn.Module):
         if stages:
             return dict(idx16=idx16, cs=cs, z=z, ldj=ldj, logp=logp, x=x, **self.last_stats)
         return x, logp
+
+    def flow_block(self, i: int, x: Tensor, c: Tensor, e: Tensor, R: int = 1, reverse: bool = False):
+        """One CNF flow block, differentiable: x [rows,3] (rows = T R, the R rows of a point adjacent), c [T,cd] context,
+        e [T,3] Hutchinson vector -> (x' [rows,3], delta logp [rows]).  An autograd function over x, c and the parameters of
+        `self.flow_blocks[i]` (e gets no gradient), whatever `self.training` says; the weight record is packed from the live
+        parameters on every call, so an optimizer step needs no `invalidate_plan`.
+        Forward: adaptive Dormand-Prince steps, one attempt per launch, the last step cut to end at the end time.  Backward: the
+        recorded steps in reverse, differentiating exactly what the forward computed with the step sizes as constants
+        (pf_cnf_rhs_vjp).  `sqrt_end_time` gets the CONTINUOUS formula dL/dT = sum(ybar(T) . k(T)) (reversed: -sum(xbar_in . k(T))
+        at the start) x 2 sqrt_end_time - NOT the derivative of the discrete scheme, whose step sizes do not depend on T here.
+        `self.last_block_steps`: the (s, h) of the accepted steps in solver time (s = -t when reversed)."""
+        if not (x.is_cuda and c.is_cuda and e.is_cuda):
+            raise _lib.PuflowHipError("inputs must be GPU tensors (no CPU fallback)")
+        if x.dim() != 2 or x.shape[1] != 3 or c.dim() != 2 or e.shape != (c.shape[0], 3) or x.shape[0] != c.shape[0] * R:
+            raise ValueError("flow_block: x [T R,3], c [T,cd], e [T,3]")
+        if not 1 <= R <= 16:
+            raise ValueError("flow_block: 1 <= R <= 16 (pf_cnf_rhs_vjp keeps a point's R rows inside one 16-row MFMA tile)")
+        pfx = f"flow_blocks.{i}."
+        named = list(self.flow_blocks[i].named_parameters())
+        keys = tuple(pfx + n for n, _ in named)
+        steps: list = []
+        out = _FlowBlockFn.apply(x, c, e, int(i), int(R), bool(reverse), keys, steps, *[p for _, p in named])
+        self.last_block_steps = steps
+        return out
 
     def sample(self, sparse: Tensor, upratio: int = 4) -> Tensor:
         dense, _ = self(sparse, upratio)

@@ -1,0 +1,442 @@
+// Vector-Jacobian product of the continuous blocks' ODE right-hand side (csrc/cnf.hip: cnf_eval), the kernel a
+// differentiable flow block is built on (puflow_amd/cnf.py: flow_block).  The forward of one evaluation is
+//     k = sgn * ( f(t, y), -e^T (df/dy) e )                                      (pf_cnf_rhs's kout)
+// and for a cotangent kbar [rows,4] this file computes the gradient of S = sum_rows kbar . k with respect to y, to the
+// per-point context terms and to the block's weights - oracle/cnf_ref.py::rhs_vjp with a_y = sgn kbar[:, :3] and
+// a_l = sgn kbar[:, 3], which is the checker it is held to (tests/test_gpu_cnf_grad.py).
+//
+// One launch, per 64-row workgroup tile (four waves, 16 rows = one MFMA column tile each, channels on the MFMA rows):
+//   forward   value AND tangent along e through the three ConcatSquash layers (cnf_eval's images: W2 and W3 once more each);
+//   reverse   the two adjoint streams (pbar, pdbar of DESIGN 9a) through W3^T (f32 MFMA), W2^T (the split-fp16 image the
+//             Hutchinson term already uses; each row's adjoints are scaled to O(1) by a power of two first, because a
+//             cotangent has no natural magnitude and the fp16 split has a range) and W1^T;
+//   weights   sums of outer products over rows: the factors of a layer are written to LDS row by row and read back as the
+//             operands of v_mfma_f32_16x16x4_f32 with the ROWS on the reduction index, D += A^T B.  Every wave owns a
+//             16-channel block of each product and keeps its accumulators in registers over ALL tiles of the workgroup
+//             (grid-stride loop); the workgroup writes ONE partial slab at its end and a small second kernel adds the slabs
+//             in a fixed order into the caller's gradient record (and multiplies the time-coefficient part by t).
+// No float atomics anywhere: results are bit-reproducible from run to run.
+//
+// Rows of a point: rows pt R .. pt R + R - 1 are adjacent.  A wave tile holds floor(16 / R) WHOLE points ((16 / R) R of its
+// 16 columns are used - 15 for R = 3), so a point never straddles tiles: its R rows are summed inside the 16-lane row by
+// shuffles and the first lane of the point adds into ctxbar as the only writer of that row.  R <= 16.
+// Clamped lanes (a partial tile re-reads row rows - 1) get a ZERO cotangent: every adjoint quantity is linear in it, so they
+// add nothing to ctxbar, to the weight gradients or anywhere else.
+//
+// Units: the forward record carries folded constants (2 log2e in W1 | b1, W2, b2 and the tanh layers' bias rows, -log2e in
+// the gate rows); everything this file OUTPUTS is in the units of the model's own parameters and pre-activations.
+//   ctxbar [T,288]  += the gradients with respect to the hyper networks' outputs (gate pre-activation, bias), in the ctx
+//                      layout: gate1[64] bias1[64] gate2[64] bias2[64] gate3 bias3; layer 3 uses the FIRST of its four
+//                      replicated slots only (256..258, 272..274), the other twelve + twelve columns are left alone.
+//   grad [4900]     += [0,4096) dW2 [64][64]   [4096,4288) dW1 [64][3]   [4288,4352) db1   [4352,4416) db2
+//                      [4416,4608) dW3 [3][64]  [4608,4611) db3 (4611 unused)
+//                      [4612,4900) gradients of the 288 time coefficients (ctx layout as above): t x this evaluation's
+//                      column sums of the ctxbar contributions.
+#include <hip/hip_runtime.h>
+#include "pf_api_internal.h"
+#include "pf_mfma.h"
+#include "pf_wave.h"
+
+namespace {
+
+constexpr int CNF_REC = 10160;            // csrc/cnf.hip's record and context layouts, restated
+constexpr int CNF_CTX = 288;
+constexpr int BW_NW = 4;                  // waves per workgroup
+constexpr int BW_GRAD = 4900;
+constexpr int BW_TV = 4612;               // time-coefficient part of the gradient record
+constexpr int BW_MAX_GRID = 256;          // one workgroup per CU (LDS-bound); also the number of partial slabs
+// Row strides of the staged matrices (floats).  bw_atb reads row 4 kk + q, column c0 + col per lane: with strides of 16 mod 64 the
+// four q groups of a wave sit 16 banks apart and the 64 lanes of a read hit the 64 LDS banks once each.
+constexpr int BW_ST = 80;                 // a staged 64-column stream
+constexpr int BW_SS = 16;                 // the two 16-column side matrices
+constexpr float BW_IC2 = 0.34657359027997264f;     // 1 / (2 log2e): takes the forward's fold out of W1, W2, b2 products
+
+struct BwArgs {
+    const float* y;         // [rows,4]
+    const float* kbar;      // [rows,4]
+    const float* ctx;       // [T,288]
+    const float* e;         // [T,3]
+    const float* rec;       // CNF_REC floats
+    float* ybar;            // [rows,4]
+    float* ctxbar;          // [T,288]
+    float* slabs;           // [gridDim.x][BW_GRAD]
+    float t, sgn;
+    int rows, R, rpt, ntiles;        // rpt: rows of a wave tile = (16 / R) R
+};
+
+// the hardware-exp sigmoid / tanh of cnf.hip (arguments prescaled by the host: -log2e x, 2 log2e x)
+__device__ __forceinline__ float bw_sigm(float xs) { return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(xs)); }
+__device__ __forceinline__ float bw_tanh(float xs) { return fmaf(-2.f, __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(xs) + 1.f), 1.f); }
+
+// acc += A^T B over the workgroup's 64 staged rows: A [64][sa] columns a0 .. a0 + 15 -> D rows, B [64][sb] columns
+// b0 .. b0 + 15 -> D columns.  Lane (col, q): acc[r] = D[4 q + r][col].
+__device__ __forceinline__ f4 bw_atb(const float* __restrict__ A, int sa, int a0, const float* __restrict__ B, int sb, int b0,
+                                     f4 acc, int col, int q) {
+#pragma unroll
+    for (int kk = 0; kk < 16; ++kk) {
+        const int row = 4 * kk + q;
+        acc = pf_mfma(A[row * sa + a0 + col], B[row * sb + b0 + col], acc);
+    }
+    return acc;
+}
+
+// this lane's 16 channels (4 blocks of 16 cb + 4 q .. + 3) of its row into a staged stream
+__device__ __forceinline__ void bw_stage(float* __restrict__ S, int lrow, int q, const f4 (&v)[4]) {
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb) *reinterpret_cast<f4*>(S + lrow * BW_ST + cb * 16 + 4 * q) = v[cb];
+}
+
+// sum over the R adjacent lanes of a point inside the 16-lane row; complete in the point's first lane (pos == 0)
+__device__ __forceinline__ f4 bw_point_sum(f4 v, int pos, int R) {
+    f4 s = v;
+    for (int d = 1; d < R; ++d) {
+        f4 o;
+        o.x = __shfl_down(v.x, d, 16); o.y = __shfl_down(v.y, d, 16); o.z = __shfl_down(v.z, d, 16); o.w = __shfl_down(v.w, d, 16);
+        if (pos + d < R) s += o;
+    }
+    return s;
+}
+
+// power-of-two scale that brings the largest magnitude of a row's adjoints to [1, 2): the split-fp16 product has fp16's range
+__device__ __forceinline__ void bw_row_scale(const f4 (&a)[4], const f4 (&b)[4], float& sc, float& inv) {
+    float m = 0.f;
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) m = fmaxf(m, fmaxf(fabsf(a[cb][r]), fabsf(b[cb][r])));
+    m = fmaxf(m, __shfl_xor(m, 16));
+    m = fmaxf(m, __shfl_xor(m, 32));
+    int ex = (int)((__builtin_bit_cast(unsigned, m) >> 23) & 0xffu);
+    ex = ex < 1 ? 1 : (ex > 253 ? 253 : ex);
+    sc = __builtin_bit_cast(float, (unsigned)(254 - ex) << 23);
+    inv = __builtin_bit_cast(float, (unsigned)ex << 23);
+}
+
+__global__ __launch_bounds__(BW_NW * 64) void cnf_rhs_vjp_kernel(BwArgs a) {
+    __shared__ f4 wl[CNF_REC / 4];
+    __shared__ f4 stg4[4 * 64 * BW_ST / 4];          // four staged 64-column streams of the workgroup's 64 rows
+    __shared__ f4 side4[2 * 64 * BW_SS / 4];         // Bs = [y 1 | e 0 | 0 ..] and P3 = [gl3 | gld3 | gate_pre3 | bias_pre3]
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int col = lane & 15, q = lane >> 4;
+    for (int i = threadIdx.x; i < CNF_REC / 4; i += BW_NW * 64) wl[i] = reinterpret_cast<const f4*>(a.rec)[i];
+    __syncthreads();
+    const float* rec = reinterpret_cast<const float*>(wl);
+    const PfW2Lds w2{reinterpret_cast<const u4*>(rec), lane}, w2t{reinterpret_cast<const u4*>(rec + 4096), lane},
+                  w3{reinterpret_cast<const u4*>(rec + 8192), lane};
+    const float* tv = rec + 9872;
+    float* stg = reinterpret_cast<float*>(stg4);
+    float* S0 = stg; float* S1 = stg + 64 * BW_ST; float* S2 = stg + 2 * 64 * BW_ST; float* S3 = stg + 3 * 64 * BW_ST;
+    float* Bs = reinterpret_cast<float*>(side4);
+    float* P3 = Bs + 64 * BW_SS;
+    const int lrow = wave * 16 + col;                // this lane's row of the staged matrices
+    const float t = a.t;
+
+    // accumulators over all tiles of this workgroup; wave w owns output block w of every product
+    f4 aW2[4], aB2 = pf_splat(0.f), aG2 = pf_splat(0.f), aH2 = pf_splat(0.f);       // dW2 rows 16 w .., db2, sum gate_pre2, sum bias_pre2
+    f4 aW1a = pf_splat(0.f), aW1b = pf_splat(0.f), aG1 = pf_splat(0.f), aH1 = pf_splat(0.f);
+    f4 aW3a = pf_splat(0.f), aW3b = pf_splat(0.f), aS3 = pf_splat(0.f);
+#pragma unroll
+    for (int nb = 0; nb < 4; ++nb) aW2[nb] = pf_splat(0.f);
+
+    for (int tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
+        const long long g = (long long)(tile * BW_NW + wave) * a.rpt + col;
+        const bool ok = col < a.rpt && g < a.rows;
+        const int row = ok ? (int)g : a.rows - 1;
+        const int pt = row / a.R;
+        const int pos = col % a.R;                                   // position of the row inside its point (ok lanes)
+        const f4 y = *reinterpret_cast<const f4*>(a.y + (size_t)row * 4);
+        f4 kb = *reinterpret_cast<const f4*>(a.kbar + (size_t)row * 4);
+        if (!ok) kb = pf_splat(0.f);
+        const float* cx = a.ctx + (size_t)pt * CNF_CTX;
+        const float e0 = a.e[(size_t)pt * 3 + 0], e1 = a.e[(size_t)pt * 3 + 1], e2 = a.e[(size_t)pt * 3 + 2];
+        const float yb = q == 0 ? y.x : (q == 1 ? y.y : (q == 2 ? y.z : 1.f));
+        const float eb = q == 0 ? e0 : (q == 1 ? e1 : (q == 2 ? e2 : 0.f));
+
+        // ---- forward, layer 1 (3 -> 64): value and tangent.  [W1 | b1] carries 2 log2e.
+        f4 h1[4], h1d[4], g1[4];
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb) {
+            const int ch = cb * 16 + 4 * q;
+            const f4 gc = *reinterpret_cast<const f4*>(cx + ch), bc = *reinterpret_cast<const f4*>(cx + 64 + ch);
+            const f4 gt = *reinterpret_cast<const f4*>(tv + ch), bt = *reinterpret_cast<const f4*>(tv + 64 + ch);
+            const float wa = rec[9216 + (cb * 16 + col) * 4 + q];
+            const f4 lin = pf_mfma(wa, yb, pf_splat(0.f)), lind = pf_mfma(wa, eb, pf_splat(0.f));
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float gate = bw_sigm(fmaf(gt[r], t, gc[r]));
+                const float h = bw_tanh(fmaf(lin[r], gate, fmaf(bt[r], t, bc[r])));
+                g1[cb][r] = gate;
+                h1[cb][r] = h;
+                h1d[cb][r] = (1.f - h * h) * (lind[r] * BW_IC2) * gate;
+            }
+        }
+        // ---- layer 2 (64 -> 64)
+        f4 h2[4], h2d[4], g2[4], lin2[4], lind2[4];
+        {
+            PfPair2 hp[1][2], hpd[1][2];
+            hp[0][0] = pf_pair2(h1[0], h1[1]); hp[0][1] = pf_pair2(h1[2], h1[3]);
+            hpd[0][0] = pf_pair2(h1d[0], h1d[1]); hpd[0][1] = pf_pair2(h1d[2], h1d[3]);
+            f4 a2[1][4], a2d[1][4];
+#pragma unroll
+            for (int ob = 0; ob < 4; ++ob) { a2[0][ob] = pf_bias(rec + 9792, ob, q); a2d[0][ob] = pf_splat(0.f); }
+            pf_mm2f<4, 2, 2>(w2, 0, hp, 0, a2, 0);
+            pf_mm2f<4, 2, 2>(w2, 0, hpd, 0, a2d, 0);
+#pragma unroll
+            for (int cb = 0; cb < 4; ++cb) {
+                const int ch = cb * 16 + 4 * q;
+                const f4 gc = *reinterpret_cast<const f4*>(cx + 128 + ch), bc = *reinterpret_cast<const f4*>(cx + 192 + ch);
+                const f4 gt = *reinterpret_cast<const f4*>(tv + 128 + ch), bt = *reinterpret_cast<const f4*>(tv + 192 + ch);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float gate = bw_sigm(fmaf(gt[r], t, gc[r]));
+                    const float h = bw_tanh(fmaf(a2[0][cb][r], gate, fmaf(bt[r], t, bc[r])));
+                    g2[cb][r] = gate;
+                    h2[cb][r] = h;
+                    lin2[cb][r] = a2[0][cb][r] * BW_IC2;
+                    lind2[cb][r] = a2d[0][cb][r] * BW_IC2;
+                    h2d[cb][r] = (1.f - h * h) * lind2[cb][r] * gate;
+                }
+            }
+        }
+        // ---- layer 3 (64 -> 3; every q group holds channels 0..2 in .x .y .z, .w is a zero row)
+        f4 g3, lin3, lind3;
+        {
+            PfPair2 hp[1][2], hpd[1][2];
+            hp[0][0] = pf_pair2(h2[0], h2[1]); hp[0][1] = pf_pair2(h2[2], h2[3]);
+            hpd[0][0] = pf_pair2(h2d[0], h2d[1]); hpd[0][1] = pf_pair2(h2d[2], h2d[3]);
+            f4 a3[1][1], a3d[1][1];
+            a3[0][0] = *reinterpret_cast<const f4*>(rec + 9856 + 4 * q);
+            a3d[0][0] = pf_splat(0.f);
+            pf_mm2f<1, 2, 2>(w3, 0, hp, 0, a3, 0);
+            pf_mm2f<1, 2, 2>(w3, 0, hpd, 0, a3d, 0);
+            lin3 = a3[0][0]; lind3 = a3d[0][0];
+            const f4 gc = *reinterpret_cast<const f4*>(cx + 256 + 4 * q), gt = *reinterpret_cast<const f4*>(tv + 256 + 4 * q);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) g3[r] = bw_sigm(fmaf(gt[r], t, gc[r]));
+        }
+
+        // ---- reverse, layer 3: seeds fbar = sgn kbar[:3], fdotbar = -sgn kbar[3] e
+        const float al = -a.sgn * kb.w;
+        const f4 pb3 = {a.sgn * kb.x, a.sgn * kb.y, a.sgn * kb.z, 0.f};
+        const f4 pdb3 = {al * e0, al * e1, al * e2, 0.f};
+        const f4 gl3 = pb3 * g3, gld3 = pdb3 * g3;
+        const f4 gp3 = (pb3 * lin3 + pdb3 * lind3) * g3 * (pf_splat(1.f) - g3);
+        f4 xb[4], xdb[4];                                             // adjoints of h2 / its tangent
+        {
+            const float vb = q == 0 ? gl3.x : (q == 1 ? gl3.y : (q == 2 ? gl3.z : 0.f));
+            const float vdb = q == 0 ? gld3.x : (q == 1 ? gld3.y : (q == 2 ? gld3.z : 0.f));
+#pragma unroll
+            for (int cb = 0; cb < 4; ++cb) {
+                const float wa = rec[9472 + (cb * 16 + col) * 4 + q];                 // W3[:, ch] (4th column zero)
+                xb[cb] = pf_mfma(wa, vb, pf_splat(0.f));
+                xdb[cb] = pf_mfma(wa, vdb, pf_splat(0.f));
+            }
+        }
+        // ---- reverse, layer 2
+        f4 gl2[4], gld2[4], gp2[4], bp2[4];
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float h = h2[cb][r], om = 1.f - h * h, gate = g2[cb][r];
+                const float pdb = om * xdb[cb][r];
+                const float pb = om * (xb[cb][r] - 2.f * h * (lind2[cb][r] * gate) * xdb[cb][r]);
+                bp2[cb][r] = pb;
+                gl2[cb][r] = pb * gate;
+                gld2[cb][r] = pdb * gate;
+                gp2[cb][r] = (pb * lin2[cb][r] + pdb * lind2[cb][r]) * gate * (1.f - gate);
+            }
+
+        // ---- weights, first part: dW3 and the layer-3 / layer-2 context sums.  S0 = h2, S1 = h2d, S2 = gate_pre2, S3 = bias_pre2
+        __syncthreads();                                             // the previous tile's products are done with the staging
+        bw_stage(S0, lrow, q, h2); bw_stage(S1, lrow, q, h2d); bw_stage(S2, lrow, q, gp2); bw_stage(S3, lrow, q, bp2);
+        {
+            const f4 bs = q == 0 ? (f4){y.x, y.y, y.z, 1.f} : (q == 1 ? (f4){e0, e1, e2, 0.f} : pf_splat(0.f));
+            const f4 p3 = q == 0 ? gl3 : (q == 1 ? gld3 : (q == 2 ? gp3 : pb3));
+            *reinterpret_cast<f4*>(Bs + lrow * BW_SS + 4 * q) = bs;
+            *reinterpret_cast<f4*>(P3 + lrow * BW_SS + 4 * q) = p3;
+        }
+        __syncthreads();
+        aW3a = bw_atb(P3, BW_SS, 0, S0, BW_ST, 16 * wave, aW3a, col, q);
+        aW3b = bw_atb(P3, BW_SS, 0, S1, BW_ST, 16 * wave, aW3b, col, q);
+        if (wave == 0) aS3 = bw_atb(P3, BW_SS, 0, Bs, BW_SS, 0, aS3, col, q);      // one copy is enough: it covers all 64 rows
+        aG2 = bw_atb(S2, BW_ST, 16 * wave, Bs, BW_SS, 0, aG2, col, q);
+        aH2 = bw_atb(S3, BW_ST, 16 * wave, Bs, BW_SS, 0, aH2, col, q);
+
+        // ---- ctxbar of layers 2 and 3: sum over the point's rows, its first lane is the only writer
+        {
+            float* cb_ = a.ctxbar + (size_t)pt * CNF_CTX;
+#pragma unroll
+            for (int cb = 0; cb < 4; ++cb) {
+                const f4 sg = bw_point_sum(gp2[cb], pos, a.R), sb = bw_point_sum(bp2[cb], pos, a.R);
+                if (ok && pos == 0) {
+                    f4* pg = reinterpret_cast<f4*>(cb_ + 128 + cb * 16 + 4 * q);
+                    f4* pbias = reinterpret_cast<f4*>(cb_ + 192 + cb * 16 + 4 * q);
+                    *pg += sg; *pbias += sb;
+                }
+            }
+            const f4 sg3 = bw_point_sum(gp3, pos, a.R), sb3 = bw_point_sum(pb3, pos, a.R);
+            if (ok && pos == 0 && q == 0) {
+                cb_[256] += sg3.x; cb_[257] += sg3.y; cb_[258] += sg3.z;
+                cb_[272] += sb3.x; cb_[273] += sb3.y; cb_[274] += sb3.z;
+            }
+        }
+
+        // ---- W2^T on both adjoint streams (rows scaled to O(1) for the fp16 split)
+        f4 x1b[4], x1db[4];
+        {
+            float sc, inv;
+            bw_row_scale(gl2, gld2, sc, inv);
+            f4 s0[4], s1[4];
+#pragma unroll
+            for (int cb = 0; cb < 4; ++cb) { s0[cb] = gl2[cb] * sc; s1[cb] = gld2[cb] * sc; }
+            PfPair2 wp[1][2], wpd[1][2];
+            wp[0][0] = pf_pair2(s0[0], s0[1]); wp[0][1] = pf_pair2(s0[2], s0[3]);
+            wpd[0][0] = pf_pair2(s1[0], s1[1]); wpd[0][1] = pf_pair2(s1[2], s1[3]);
+            f4 u1[1][4], u1d[1][4];
+#pragma unroll
+            for (int ob = 0; ob < 4; ++ob) { u1[0][ob] = pf_splat(0.f); u1d[0][ob] = pf_splat(0.f); }
+            pf_mm2f<4, 2, 2>(w2t, 0, wp, 0, u1, 0);
+            pf_mm2f<4, 2, 2>(w2t, 0, wpd, 0, u1d, 0);
+#pragma unroll
+            for (int cb = 0; cb < 4; ++cb) { x1b[cb] = u1[0][cb] * inv; x1db[cb] = u1d[0][cb] * inv; }
+        }
+
+        // ---- weights, second part: dW2, db2.  S0 = gl2, S1 = gld2, S2 = h1, S3 = h1d
+        __syncthreads();
+        bw_stage(S0, lrow, q, gl2); bw_stage(S1, lrow, q, gld2); bw_stage(S2, lrow, q, h1); bw_stage(S3, lrow, q, h1d);
+        __syncthreads();
+#pragma unroll
+        for (int nb = 0; nb < 4; ++nb) {
+            aW2[nb] = bw_atb(S0, BW_ST, 16 * wave, S2, BW_ST, 16 * nb, aW2[nb], col, q);
+            aW2[nb] = bw_atb(S1, BW_ST, 16 * wave, S3, BW_ST, 16 * nb, aW2[nb], col, q);
+        }
+        aB2 = bw_atb(S0, BW_ST, 16 * wave, Bs, BW_SS, 0, aB2, col, q);
+
+        // ---- reverse, layer 1 (its linear parts recomputed: one f32 MFMA each)
+        f4 gl1[4], gld1[4], gp1[4], bp1[4];
+        float r0 = 0.f, r1 = 0.f, r2 = 0.f;
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb) {
+            const float wa = rec[9216 + (cb * 16 + col) * 4 + q];
+            const f4 lin = pf_mfma(wa, yb, pf_splat(0.f)) * BW_IC2, lind = pf_mfma(wa, eb, pf_splat(0.f)) * BW_IC2;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float h = h1[cb][r], om = 1.f - h * h, gate = g1[cb][r];
+                const float pdb = om * x1db[cb][r];
+                const float pb = om * (x1b[cb][r] - 2.f * h * (lind[r] * gate) * x1db[cb][r]);
+                bp1[cb][r] = pb;
+                gl1[cb][r] = pb * gate;
+                gld1[cb][r] = pdb * gate;
+                gp1[cb][r] = (pb * lin[r] + pdb * lind[r]) * gate * (1.f - gate);
+                const f4 wr = *reinterpret_cast<const f4*>(rec + 9216 + (cb * 16 + 4 * q + r) * 4);      // 2 log2e W1[ch, :]
+                r0 = fmaf(wr.x, gl1[cb][r], r0); r1 = fmaf(wr.y, gl1[cb][r], r1); r2 = fmaf(wr.z, gl1[cb][r], r2);
+            }
+        }
+        r0 += __shfl_xor(r0, 16); r1 += __shfl_xor(r1, 16); r2 += __shfl_xor(r2, 16);
+        r0 += __shfl_xor(r0, 32); r1 += __shfl_xor(r1, 32); r2 += __shfl_xor(r2, 32);
+        if (ok && q == 0) *reinterpret_cast<f4*>(a.ybar + (size_t)row * 4) = (f4){r0 * BW_IC2, r1 * BW_IC2, r2 * BW_IC2, 0.f};
+
+        // ---- weights, third part: dW1 | db1 and the layer-1 context sums.  S0 = gl1, S1 = gld1, S2 = gate_pre1, S3 = bias_pre1
+        __syncthreads();
+        bw_stage(S0, lrow, q, gl1); bw_stage(S1, lrow, q, gld1); bw_stage(S2, lrow, q, gp1); bw_stage(S3, lrow, q, bp1);
+        __syncthreads();
+        aW1a = bw_atb(S0, BW_ST, 16 * wave, Bs, BW_SS, 0, aW1a, col, q);
+        aW1b = bw_atb(S1, BW_ST, 16 * wave, Bs, BW_SS, 0, aW1b, col, q);
+        aG1 = bw_atb(S2, BW_ST, 16 * wave, Bs, BW_SS, 0, aG1, col, q);
+        aH1 = bw_atb(S3, BW_ST, 16 * wave, Bs, BW_SS, 0, aH1, col, q);
+        {
+            float* cb_ = a.ctxbar + (size_t)pt * CNF_CTX;
+#pragma unroll
+            for (int cb = 0; cb < 4; ++cb) {
+                const f4 sg = bw_point_sum(gp1[cb], pos, a.R), sb = bw_point_sum(bp1[cb], pos, a.R);
+                if (ok && pos == 0) {
+                    f4* pg = reinterpret_cast<f4*>(cb_ + cb * 16 + 4 * q);
+                    f4* pbias = reinterpret_cast<f4*>(cb_ + 64 + cb * 16 + 4 * q);
+                    *pg += sg; *pbias += sb;
+                }
+            }
+        }
+    }
+
+    // ---- this workgroup's slab, in the gradient record's layout.  Lane (col, q) holds D[4 q + r][col] of its wave's blocks.
+    float* sl = a.slabs + (size_t)blockIdx.x * BW_GRAD;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int o = 16 * wave + 4 * q + r;                         // output channel of the layer-1 / layer-2 blocks
+#pragma unroll
+        for (int nb = 0; nb < 4; ++nb) sl[o * 64 + 16 * nb + col] = aW2[nb][r];
+        // dW1[o][j] = (gl1^T y)[o][j] + (gld1^T e)[o][j]: columns j and 4 + j of the two products against Bs; column 3 of a
+        // product against Bs is the plain column sum
+        const float we = __shfl_down(aW1b[r], 4, 16);
+        if (col < 3) sl[4096 + o * 3 + col] = aW1a[r] + we;
+        if (col == 3) {
+            sl[4288 + o] = aW1a[r];
+            sl[4352 + o] = aB2[r];
+            sl[BW_TV + o] = aG1[r]; sl[BW_TV + 64 + o] = aH1[r];
+            sl[BW_TV + 128 + o] = aG2[r]; sl[BW_TV + 192 + o] = aH2[r];
+        }
+        // dW3[j][i] = (gl3^T h2)[j][i] + (gld3^T h2d)[j][i]: D rows j (q = 0) and 4 + j (q = 1) of the two products
+        const float w3d = __shfl(aW3b[r], lane + 16);
+        if (q == 0 && r < 3) sl[4416 + r * 64 + 16 * wave + col] = aW3a[r] + w3d;
+        if (wave == 0 && col == 3 && r < 3) {
+            if (q == 0) sl[4608 + r] = aS3[r];
+            if (q == 2) sl[BW_TV + 256 + r] = aS3[r];
+            if (q == 3) sl[BW_TV + 272 + r] = aS3[r];
+        }
+    }
+    if (threadIdx.x < 27) {                  // the words nothing above writes: 4611 and the replicated layer-3 slots (13 + 13)
+        const int i = threadIdx.x;
+        sl[i == 0 ? 4611 : (i < 14 ? BW_TV + 258 + i : BW_TV + 261 + i)] = 0.f;
+    }
+}
+
+// grad[i] += (i in the time-coefficient part ? t : 1) x sum of the slabs.  32 outputs per workgroup, eight threads per output take
+// every eighth slab each (eight loads in flight per output instead of one thread walking all slabs), then the eight partial
+// sums are added in a fixed order: the same bits from run to run.
+__global__ __launch_bounds__(256) void cnf_rhs_vjp_reduce_kernel(const float* __restrict__ slabs, int n, float t, float* __restrict__ grad) {
+    __shared__ float part[8][32];
+    const int o = threadIdx.x & 31, g = threadIdx.x >> 5;
+    const int i = blockIdx.x * 32 + o;
+    float s = 0.f;
+    if (i < BW_GRAD)
+        for (int j = g; j < n; j += 8) s += slabs[(size_t)j * BW_GRAD + i];
+    part[g][o] = s;
+    __syncthreads();
+    if (g == 0 && i < BW_GRAD) {
+        float tot = part[0][o];
+#pragma unroll
+        for (int k = 1; k < 8; ++k) tot += part[k][o];
+        grad[i] += i >= BW_TV ? t * tot : tot;
+    }
+}
+
+inline int bw_grid(int rows, int R, int* rpt, int* ntiles) {
+    *rpt = (16 / R) * R;
+    const long long wt = ((long long)rows + *rpt - 1) / *rpt;        // wave tiles
+    *ntiles = (int)((wt + BW_NW - 1) / BW_NW);
+    return *ntiles < BW_MAX_GRID ? *ntiles : BW_MAX_GRID;
+}
+
+}  // namespace
+
+extern "C" long long pf_cnf_rhs_vjp_workspace_bytes(int rows, int R) {
+    if (rows <= 0 || R <= 0 || R > 16 || rows % R != 0) return PF_ERR_SHAPE;
+    int rpt, ntiles;
+    return (long long)bw_grid(rows, R, &rpt, &ntiles) * BW_GRAD * (long long)sizeof(float);
+}
+
+extern "C" int pf_cnf_rhs_vjp(const float* y, const float* kbar, float t, float sgn, const float* ctx, const float* e,
+                              const float* rec, float* ybar, float* ctxbar, float* grad, int rows, int R, void* ws,
+                              void* stream) {
+    if (!y || !kbar || !ctx || !e || !rec || !ybar || !ctxbar || !grad || !ws) return PF_ERR_NULL;
+    if (rows <= 0 || R <= 0 || R > 16 || rows % R != 0) return PF_ERR_SHAPE;
+    BwArgs a{};
+    a.y = y; a.kbar = kbar; a.ctx = ctx; a.e = e; a.rec = rec; a.ybar = ybar; a.ctxbar = ctxbar; a.slabs = (float*)ws;
+    a.t = t; a.sgn = sgn; a.rows = rows; a.R = R;
+    const int grid = bw_grid(rows, R, &a.rpt, &a.ntiles);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(cnf_rhs_vjp_kernel, dim3(grid), dim3(BW_NW * 64), 0, s, a);
+    hipLaunchKernelGGL(cnf_rhs_vjp_reduce_kernel, dim3((BW_GRAD + 31) / 32), dim3(256), 0, s, (const float*)ws, grid, t, grad);
+    return pf_last_launch_status();
+}

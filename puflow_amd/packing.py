@@ -550,6 +550,48 @@ def cnf_split_ok(rec, T_end: float) -> bool:
     return bool(np.abs(g).max() * abs(T_end) <= 100.0)
 
 
+CNF_GRAD = 4900                  # gradient record of pf_cnf_rhs_vjp (include/puflow_hip.h), time-coefficient part from CNF_GRAD_TV on
+CNF_GRAD_TV = 4612
+# (first ctx column, rows) of the hyper networks' outputs: gate and bias of the three layers; layer 3 = the first of its four slots
+CNF_CTX_SLOTS = ((0, 64), (64, 64), (128, 64), (192, 64), (256, 3), (272, 3))
+
+
+def cnf_hyper_matrix(sd, i: int) -> np.ndarray:
+    """[288, 1 + cdim]: the hyper networks' weights [t | c] in the ctx layout WITHOUT the constants pack_cnf_block folds in
+    (layer 3 replicated into its four slots like there).  The backward of the context GEMM multiplies by its c-columns:
+    pf_cnf_rhs_vjp's ctxbar is in the units of the model's own pre-activations."""
+    p = f"flow_blocks.{i}.cnf.odefunc.diffeq.layers"
+    first = _np32(sd[f"{p}.0._hyper_gate.weight"])
+    H = np.zeros((CNF_CTX, first.shape[1]), np.float32)
+    for l in range(3):
+        for kind, base in (("_hyper_gate", 128 * l), ("_hyper_bias", 128 * l + (64 if l < 2 else 16))):
+            W = _np32(sd[f"{p}.{l}.{kind}.weight"])
+            for r0 in ([base] if l < 2 else [base + 4 * qq for qq in range(4)]):
+                H[r0:r0 + W.shape[0]] = W
+    return H
+
+
+def unpack_cnf_grads(i: int, grad, dH, dhb):
+    """The outputs of a block's backward -> tensors keyed and shaped like the state dict.
+    grad [4900]: pf_cnf_rhs_vjp's gradient record (already in the parameters' units: the kernel takes the forward image's
+    2 log2e / -log2e out itself), dH [288, cdim]: ctxbar^T c, dhb [288]: the column sums of ctxbar.  The time coefficients'
+    gradients (grad[4612:]) are column 0 of the hyper weights, as in the reference's cat([t, c])."""
+    import torch
+    p = f"flow_blocks.{i}.cnf.odefunc.diffeq.layers"
+    out = {
+        f"{p}.1._layer.weight": grad[0:4096].reshape(64, 64), f"{p}.0._layer.weight": grad[4096:4288].reshape(64, 3),
+        f"{p}.0._layer.bias": grad[4288:4352], f"{p}.1._layer.bias": grad[4352:4416],
+        f"{p}.2._layer.weight": grad[4416:4608].reshape(3, 64), f"{p}.2._layer.bias": grad[4608:4611],
+    }
+    tv = grad[CNF_GRAD_TV:CNF_GRAD]
+    for l in range(3):
+        (g0, n), (b0, _) = CNF_CTX_SLOTS[2 * l], CNF_CTX_SLOTS[2 * l + 1]
+        out[f"{p}.{l}._hyper_gate.weight"] = torch.cat([tv[g0:g0 + n, None], dH[g0:g0 + n]], dim=1)
+        out[f"{p}.{l}._hyper_gate.bias"] = dhb[g0:g0 + n]
+        out[f"{p}.{l}._hyper_bias.weight"] = torch.cat([tv[b0:b0 + n, None], dH[b0:b0 + n]], dim=1)
+    return {k: v.contiguous() for k, v in out.items()}
+
+
 def pack_cnf_block(sd, i: int):
     """-> (rec [CNF_REC] fp32, Hc [288, cdim], hb [288], T_end).  A ConcatSquash layer (diffeq_layers.py:72-86) is
     (W x + b) * sigmoid(Wg [t; c] + bg) + Wb [t; c]: the c-columns of Wg / Wb form the context GEMM `Hc` (with bg
