@@ -78,6 +78,11 @@ int pf_cond(int unit, const float* h, const float* w, const long long* off, floa
             void* stream);
 int pf_post(int unit, const float* h, const float* w, const long long* off, float* c, float* st, float* cp,
             float* pq_next, int T, void* stream);
+/* Test entry for the layer epilogue of the fused inference kernels (csrc/pf_mfma.h pf_act_pairn): x [n] (n % 8 == 0), every
+ * 8 values one pair of 16-channel-block registers.  Writes n / 2 words each of the packed-fp16 hi and lo operand images of
+ * the sequence the helper replaces (old_*) and of the helper (new_*); inv == 1 takes the helper's form without rescale. */
+int pf_test_act_pairn(const float* x, int n, float inv, float slope, unsigned* old_h, unsigned* old_l, unsigned* new_h,
+                      unsigned* new_l, void* stream);
 /* pf_cond of all six units in ONE launch (the stages only feed the flow kernels, so they run after the EdgeConv chain):
  * h[6] device pointers to the units' EdgeConv outputs (HOST array of device pointers), c[6] likewise (or NULL),
  * st [6][T][8], cp [6][T][64], off[6*13].  st = cp = NULL with c given: the stage stops at the conditioning features (the

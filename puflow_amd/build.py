@@ -22,6 +22,17 @@ EXTRA_FLAGS = {s: ["-fno-honor-nans", "-mllvm", "-amdgpu-mfma-vgpr-form=" + os.e
 # edgeconv.hip: three LDS weight fragments in flight instead of two (pf_mfma.h PfW2Lds::DEPTH; same VGPR count, same bits):
 # +0.3 - 0.7 % on the headline step in two same-box A/Bs (depth 4 the same)
 EXTRA_FLAGS["edgeconv.hip"] = EXTRA_FLAGS["edgeconv.hip"] + ["-DPF_W2LDS_DEPTH=" + os.environ.get("PF_EC_W2LDS_DEPTH", "3")]
+# No packed fp32 (v_pk_mul/add/fma_f32) in the fused inference kernels: beside MFMAs one packed op costs more issue time than
+# the two plain ones it stands for.  Their layer epilogues are written one value at a time (pf_mfma.h
+# pf_act_pairn); this switch does the same for what is left in the tile loops - 4-vector adds of accumulator initialisers, the
+# fmaf groups hipcc's SLP pass packs - by taking the packed instructions away from the code generator.  Same arithmetic, same
+# bits.  The VALU-only kernels (kNN, CNF, training), where packing pays, live in other sources; edgeconv4_kernel, where
+# un-packing measured no gain, takes the feature back through a function attribute (csrc/edgeconv.hip).  It is a cc1 option, so the
+# host pass sees it too and says that it ignores it.  PF_PACKED_FP32=a.hip,b.hip keeps the packed forms there (A/B builds).
+_PACKED = os.environ.get("PF_PACKED_FP32", "").split(",")
+for _s in ("edgeconv.hip", "pointwise.hip", "flow.hip", "interp.hip"):
+    if _s not in _PACKED:
+        EXTRA_FLAGS[_s] = EXTRA_FLAGS[_s] + ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 if os.environ.get("PF_INTERP_TRACKERS", "1") != "0":
     EXTRA_FLAGS["interp.hip"] = EXTRA_FLAGS["interp.hip"] + ["-mllvm", "-amdgpu-use-amdgpu-trackers=1"]
 

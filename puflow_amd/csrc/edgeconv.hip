@@ -11,6 +11,13 @@
 #include "pf_api_internal.h"
 #include "pf_mfma.h"
 
+// per-function override of the file's no-packed-fp32 build switch (device pass only: the host knows no such feature)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define PF_PACKED_FP32_FN __attribute__((target("packed-fp32-ops")))
+#else
+#define PF_PACKED_FP32_FN
+#endif
+
 namespace {
 
 struct EcArgs {
@@ -279,8 +286,10 @@ struct EcWConst {                                             // DBG & 4 (timing
 // P[i] is added once per channel after the max.  VALU per point: ~180 (round 1 split-fp16 kernel: ~450).
 constexpr float EC4_OUT_INV = 1.f / 256.f;       // conv_out accumulators hold 4^4 y (packing.ec4_scales)
 
+// This kernel keeps packed fp32 (the rest of the file is built without it, build.py): un-packed it measured 136.2 us against
+// 135.2 us per launch - its epilogues are short (31 packed ops per point) and sit between gathers, not in a chain.
 template <int P, int NW, int DBG = 0, bool PQF = false>      // DBG bit mask (-DPF_TUNING_VARIANTS timing builds only; wrong results): 1 no gathers, 2 no MFMAs, 4 no LDS weight reads;  PQF: + the next unit's P|Q vectors (pqf_gemm)
-__global__ __launch_bounds__(NW * 64) void edgeconv4_kernel(EcArgs a) {
+__global__ __launch_bounds__(NW * 64) PF_PACKED_FP32_FN void edgeconv4_kernel(EcArgs a) {
     static_assert(!PQF || NW * P == 16, "the fused P|Q GEMM takes a workgroup tile of 16 points as one MFMA column tile");
     constexpr int NCONV = 4, G = 32, S = 256, OBO = 8, OCH = 2, ODIM = 128;
     constexpr int NWF = 2 * (NCONV * (NCONV - 1) / 2) + OBO * NCONV;      // 44 (ob, pair) fragments, 2 KiB each
@@ -455,16 +464,19 @@ int launch4(const EcArgs& a0, hipStream_t s) {
 // Growth layers are 16 channels wide (unit 0: 8, zero-padded): two layers share one 32-channel MFMA step.  conv_out
 // runs with the operands swapped (edges on the MFMA rows) and a reduce-scatter max-pool; feature block t is stored as
 // 4^t x_t, the accumulators of layer t hold 4^t v_t, conv_out's 256 y (packing.ec1n_scales).
-// C3 (unit 0): every pre-activation is one MFMA step against the folded edge table (raw inputs e = (x_i, x_j, 1) in 8 of
-// the 32 k-slots); the same e registers are the B operand of the growth rows and the A operand of the conv_out rows.
+// C3 (unit 0): every pre-activation is ONE MFMA against the folded edge table (raw inputs e = (x_i, x_j, 1); the three terms
+// of the split product share the 32 k-slots: pf_mfma.h pf_edge_operand / pf_mm1); the same e registers are the B operand of
+// the growth rows and the A operand of the conv_out rows.
 // PQ (unit 1): Q[j] gathers as accumulator initialisers, P[i] staged per wave in LDS (one load per point).
-// Fragments in LDS: G1 | G2 | G3 (2 pairs) | Gout (OBO x 2 pairs) | [C3: edge table, S/16 x 1 pair].
+// Fragments in LDS: G1 | G2 | G3 (2 pairs) | Gout (OBO x 2 pairs) | [C3: edge table, S/16 one-MFMA fragments of 1 KiB];
+// C3: one float behind the image = 2^-sw of the table (the table products are multiplied by it before anything else).
 template <int ODIM, bool C3, int P, int NW, bool PQF = false>      // PQF: + the next unit's P|Q vectors (pqf_gemm; ROWS = 256 after unit 0, 512 after unit 1)
 __global__ __launch_bounds__(NW * 64) void edgeconv1n_kernel(EcArgs a) {
     static_assert(!PQF || NW * P == 16, "the fused P|Q GEMM takes a workgroup tile of 16 points as one MFMA column tile");
     constexpr int NCONV = 4, S = 16 * NCONV + ODIM, SB = S / 16, OBO = ODIM / 16;
     constexpr int PQ_ROWS = ODIM == 32 ? 256 : 512;
-    constexpr int FO = 4, FT = FO + OBO * 2, NWF = FT + (C3 ? SB : 0);
+    constexpr int FO = 4, FT = FO + OBO * 2, NWF = FT + (C3 ? SB / 2 : 0);            // C3: SB one-MFMA table fragments of 1 KiB
+    static_assert(!C3 || SB % 2 == 0, "the edge table fills whole 2-KiB slots");
     constexpr int ROWB = 2 * S * 4;                                       // bytes per point of the P|Q table (unit 1)
     static_assert(OBO == 2 || OBO == 4, "reduce-scatter below is written for 2 or 4 output blocks");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -476,6 +488,7 @@ __global__ __launch_bounds__(NW * 64) void edgeconv1n_kernel(EcArgs a) {
     pf_stage_lds(wlds, reinterpret_cast<const u4*>(a.wg), NWF * 128);
     __syncthreads();
     const PfW2Lds ws{wlds, lane};
+    const float inv_tab = C3 ? reinterpret_cast<const float*>(a.wg)[NWF * 512] : 1.f;       // 2^-sw of the edge table, behind the image
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(C3 ? a.xyz : a.pq), 0, 0x7fffffff, 0x00020000);
 
     for (int v = blockIdx.x; v < 8 * a.chunk; v += gridDim.x) {
@@ -483,7 +496,7 @@ __global__ __launch_bounds__(NW * 64) void edgeconv1n_kernel(EcArgs a) {
         if (tile >= a.ntiles) continue;
         const int pt0 = (tile * NW + wave) * P;
         int gi[P], vQ[P], vO[P][4];
-        PfPairN e[P][1];
+        h8 e[P];                         // C3: raw edge inputs (x_i, x_j, 0, 1) as hi | lo | hi | 0 over the lanes q = 0..3
 #pragma unroll
         for (int p = 0; p < P; ++p) {
             int g = pt0 + p;
@@ -499,9 +512,8 @@ __global__ __launch_bounds__(NW * 64) void edgeconv1n_kernel(EcArgs a) {
                     xi[c] = a.xyz[(size_t)g * 3 + c];
                     xj[c] = a.xyz[(size_t)jc * 3 + c];
                 }
-                const f4 z4 = pf_splat(0.f);
                 const f4 e0 = {xi[0], xi[1], xi[2], xj[0]}, e1 = {xj[1], xj[2], 0.f, 1.f};
-                e[p][0] = pf_pairn(q == 0 ? e0 : z4, q == 0 ? e1 : z4);
+                e[p] = pf_edge_operand(e0, e1, q);
             } else {
                 const int4 j4 = *reinterpret_cast<const int4*>(a.idx + (size_t)g * 16 + 4 * q);
                 vQ[p] = jc * ROWB + (S + 4 * q) * 4;
@@ -528,8 +540,17 @@ __global__ __launch_bounds__(NW * 64) void edgeconv1n_kernel(EcArgs a) {
 #pragma unroll
                 for (int b = 0; b < OBO; ++b) outi[p][b] = pf_splat(0.f);
             }
-            pf_mmn<false, NCONV, 1, 1>(ws, FT, e, pre);
-            pf_mmn<true, OBO, 1, 1>(ws, FT + NCONV, e, outi);
+            const PfW1Lds wt{wlds + FT * 128, lane};
+            pf_mm1<false, NCONV>(wt, 0, e, pre);
+            pf_mm1<true, OBO>(wt, NCONV, e, outi);
+            // the table is stored times 2^sw (packing.ec1n_unit0_table: its low halves stay normal fp16 numbers); undo it, exactly
+#pragma unroll
+            for (int p = 0; p < P; ++p) {
+#pragma unroll
+                for (int b = 0; b < NCONV; ++b) pre[p][b] = pre[p][b] * inv_tab;
+#pragma unroll
+                for (int b = 0; b < OBO; ++b) outi[p][b] = outi[p][b] * inv_tab;
+            }
         } else {
 #pragma unroll
             for (int b = 0; b < NCONV; ++b)
@@ -550,11 +571,11 @@ __global__ __launch_bounds__(NW * 64) void edgeconv1n_kernel(EcArgs a) {
         }
 
         PfPairN fp[P][2];
-        f4 last[P];
+        PfHalfN last[P];                 // the split of the latest block: the low half of a pair now, joined with the next block later
 #pragma unroll
         for (int p = 0; p < P; ++p) {
-            last[p] = pf_lrelu(pre[p][0], 0.05f);
-            fp[p][0] = pf_pairn(last[p], pf_splat(0.f));
+            last[p] = pf_act_halfn(pre[p][0], 0.05f);
+            fp[p][0] = pf_join_halfn(last[p], PfHalfN{});
         }
         pf_static_for<1, NCONV>([&](auto tc) {
             constexpr int t = decltype(tc)::value;
@@ -565,9 +586,9 @@ __global__ __launch_bounds__(NW * 64) void edgeconv1n_kernel(EcArgs a) {
             pf_mmn<false, 1, CPT, CPT>(ws, F0, fp, acc);
 #pragma unroll
             for (int p = 0; p < P; ++p) {
-                const f4 f = pf_lrelu(acc[p][0], 0.05f);
-                if constexpr (t % 2 == 1) fp[p][t / 2] = pf_pairn(last[p], f);
-                else fp[p][t / 2] = pf_pairn(f, pf_splat(0.f));
+                const PfHalfN f = pf_act_halfn(acc[p][0], 0.05f);
+                if constexpr (t % 2 == 1) fp[p][t / 2] = pf_join_halfn(last[p], f);
+                else fp[p][t / 2] = pf_join_halfn(f, PfHalfN{});
                 last[p] = f;
             }
         });

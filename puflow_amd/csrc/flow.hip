@@ -99,18 +99,18 @@ __device__ __forceinline__ void coupling_net(const float* rec /*LDS*/, int lane,
                 v.x = fmaf(wa.y, h1[1], v.x); v.y = fmaf(wa.w, h1[1], v.y);
                 v.z = fmaf(wb.y, h1[1], v.z); v.w = fmaf(wb.w, h1[1], v.w);
             }
-            hid[cb] = pf_lrelu(v, 0.01f);
+            hid[cb] = v;
         }
-        hp[0][0] = pf_pairn(hid[0], hid[1]);
-        hp[0][1] = pf_pairn(hid[2], hid[3]);
+        hp[0][0] = pf_act_pairn(hid[0], hid[1], 0.01f);
+        hp[0][1] = pf_act_pairn(hid[2], hid[3], 0.01f);
     }
     const PfW2Lds ws{reinterpret_cast<const u4*>(rec), lane};
     f4 h2[1][4];
 #pragma unroll
     for (int ob = 0; ob < 4; ++ob) h2[0][ob] = pf_bias(rec + 5120, ob, q);
     pf_mmn<false, 4, 2, 2>(ws, 0, hp, h2);
-    hp[0][0] = pf_pairn(pf_lrelu(h2[0][0] * i2, 0.01f), pf_lrelu(h2[0][1] * i2, 0.01f));
-    hp[0][1] = pf_pairn(pf_lrelu(h2[0][2] * i2, 0.01f), pf_lrelu(h2[0][3] * i2, 0.01f));
+    hp[0][0] = pf_act_pairn(h2[0][0], h2[0][1], i2, 0.01f);
+    hp[0][1] = pf_act_pairn(h2[0][2], h2[0][3], i2, 0.01f);
     f4 acc[1][1];
     acc[0][0] = *reinterpret_cast<const f4*>(rec + 5184 + 4 * q);
     pf_mmn<false, 1, 2, 2>(ws, 8, hp, acc);

@@ -9,13 +9,15 @@
 // between (interpflow.py:134,144), so the host composes them (packing.fold_state_dict):
 //     w1 = (W0a W6) d2 + (W0b Gout) feat + [W0b (PA x_i + QB x_j + pb) + b0 + W0a b6]
 // Every term that is affine in the edge's raw inputs e = (x_i, x_j, |x_i - x_j|, 1) - the distance encoder's first
-// layer, the EdgeConv pre-activations, the bracket above - is one MFMA step against an 8-column "edge table"
-// (e occupies 8 of the 32 k-slots).  Only the first R rows of the last weight conv are computed (interpflow.py:180).
+// layer, the EdgeConv pre-activations, the bracket above - is ONE MFMA against an 8-column "edge table": the three terms
+// of the split product share the 32 k-slots (pf_mfma.h pf_edge_operand / pf_mm1, packing._etab_frag1).  Only the first R
+// rows of the last weight conv are computed (interpflow.py:180).
 // Arithmetic: split-fp16 products with a natural-scale low half (pf_mfma.h "f16n": one accumulator, no fold), fp32-class
-// accuracy; 91 fragment pairs = 273 fp16 MFMAs per tile where the unfolded f32 formulation needs 1216.  Matrices that
+// accuracy; 20 table fragments + 71 fragment pairs = 233 fp16 MFMAs per tile where the unfolded f32 formulation needs 1216.  Matrices that
 // share an accumulator share a power-of-two scale (packing.INTERP_SCALES); the kernel multiplies by its inverse.
 //
-// Weight blob (float offsets in `off[]`, see puflow_amd/packing.py::INTERP_SLOTS); matrices are f16x2 fragment images:
+// Weight blob (float offsets in `off[]`, see puflow_amd/packing.py::INTERP_SLOTS); matrices are f16n fragment-pair images,
+// the three edge tables (slots 0, 5, 8) one-MFMA images of 256 floats per 16 rows:
 //   0 dtab [64 x e]        1 d_W3 [64 x 64]     2 d_b3 [64] f32      3 (W0a W6) [128 x 64]    4 scales [6] f32
 //   5 ectab [128 x e]      6 ec G1..G7 (16 pair fragments; layer t starts at fragment floor(t/2) * ceil(t/2))
 //   7 (W0b Gout) [128 x 128]   8 w1tab [128 x e] (bracket above)   9 w_W3 [64 x 128]  10 w_b3 [64] f32
@@ -56,9 +58,10 @@ __global__ __launch_bounds__(NW * 64) void interp_kernel(InterpArgs a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int col = lane & 15, q = lane >> 4;
     const int ps = col >> 3, k = col & 7;
-    // everything but the 64 KiB (W0b Gout) image lives in LDS for the whole persistent workgroup: 76 fragments x 2 KiB
-    // = 152 KiB (edge tables, d_W3, the 7-step growth chain, (W0a W6), w_W3); (W0b Gout) streams from L2, 4 fragments ahead
-    constexpr int L_DT = 0, L_ET = 4, L_WT = 12, L_D3 = 20, L_EC = 28, L_D6 = 44, L_W3 = 60, L_END = 76;
+    // everything but the 64 KiB (W0b Gout) image lives in LDS for the whole persistent workgroup: 66 slots of 2 KiB = 132 KiB
+    // (edge tables: 20 one-MFMA fragments of 1 KiB in 10 slots; d_W3, the 7-step growth chain, (W0a W6), w_W3: 56 fragment
+    // pairs); (W0b Gout) streams from L2, 4 fragments ahead
+    constexpr int L_DT = 0, L_ET = 2, L_WT = 6, L_D3 = 10, L_EC = 18, L_D6 = 34, L_W3 = 50, L_END = 66;
     __shared__ u4 wl[L_END * 128];
     {
         auto stage = [&](int f0, int nf, long long off) {
@@ -67,13 +70,13 @@ __global__ __launch_bounds__(NW * 64) void interp_kernel(InterpArgs a) {
         };
         if (a.contiguous) stage(L_DT, L_END, a.off[0]);
         else {
-            stage(L_DT, 4, a.off[0]); stage(L_ET, 8, a.off[5]); stage(L_WT, 8, a.off[8]); stage(L_D3, 8, a.off[1]);
+            stage(L_DT, 2, a.off[0]); stage(L_ET, 4, a.off[5]); stage(L_WT, 4, a.off[8]); stage(L_D3, 8, a.off[1]);
             stage(L_EC, 16, a.off[6]); stage(L_D6, 16, a.off[3]); stage(L_W3, 16, a.off[9]);
         }
         __syncthreads();
     }
-    const PfW2Lds wsDT{wl + L_DT * 128, lane}, wsET{wl + L_ET * 128, lane}, wsWT{wl + L_WT * 128, lane},
-        wsD3{wl + L_D3 * 128, lane}, wsEC{wl + L_EC * 128, lane}, wsD6{wl + L_D6 * 128, lane}, wsW3{wl + L_W3 * 128, lane};
+    const PfW1Lds wsDT{wl + L_DT * 128, lane}, wsET{wl + L_ET * 128, lane}, wsWT{wl + L_WT * 128, lane};
+    const PfW2Lds wsD3{wl + L_D3 * 128, lane}, wsEC{wl + L_EC * 128, lane}, wsD6{wl + L_D6 * 128, lane}, wsW3{wl + L_W3 * 128, lane};
     const PfW2BufD<4> wsW0(a.w + a.off[7], lane);
     const PfW2BufD<2> wsW6(a.w + a.off[BIG ? 13 : 11], lane);
 
@@ -88,7 +91,7 @@ __global__ __launch_bounds__(NW * 64) void interp_kernel(InterpArgs a) {
         const int pt0 = wt * P * 2;
         int gi[P], gj[P];
         bool ok[P];
-        PfPairN e[P][1];                 // raw edge inputs (x_i, x_j, |x_i - x_j|, 1) in k-slots 0..7 (lanes q = 0)
+        h8 e[P];                         // raw edge inputs (x_i, x_j, |x_i - x_j|, 1): hi | lo | hi | 0 over the lanes q = 0..3
 #pragma unroll
         for (int p = 0; p < P; ++p) {
             const int g = pt0 + p * 2 + ps;
@@ -103,9 +106,8 @@ __global__ __launch_bounds__(NW * 64) void interp_kernel(InterpArgs a) {
             }
             const float v0 = xi[0] - xj[0], v1 = xi[1] - xj[1], v2 = xi[2] - xj[2];
             const float nrm = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(v0, v0), __fmul_rn(v1, v1)), __fmul_rn(v2, v2)));
-            const f4 z4 = pf_splat(0.f);
             const f4 e0 = {xi[0], xi[1], xi[2], xj[0]}, e1 = {xj[1], xj[2], nrm, 1.f};
-            e[p][0] = pf_pairn(q == 0 ? e0 : z4, q == 0 ? e1 : z4);
+            e[p] = pf_edge_operand(e0, e1, q);
         }
 
         // ---- EdgeConv growth features (C=3, g=16, 8 convs) on the same 8 neighbours; conv_out is folded into w1
@@ -113,16 +115,16 @@ __global__ __launch_bounds__(NW * 64) void interp_kernel(InterpArgs a) {
         f4 w1[P][8];
         {
             PfPairN fp[P][4];
-            f4 last[P];
+            PfHalfN last[P];             // the split of the latest 16-channel block, joined with the next one into a pair
             {
                 f4 acc[P][1];
 #pragma unroll
                 for (int p = 0; p < P; ++p) acc[p][0] = pf_splat(0.f);
-                pf_mmn<false, 1, 1, 1>(wsET, 0, e, acc);                 // pre-activation from the raw inputs (edge table)
+                pf_mm1<false, 1>(wsET, 0, e, acc);                       // pre-activation from the raw inputs (edge table)
 #pragma unroll
                 for (int p = 0; p < P; ++p) {
-                    last[p] = pf_lrelu(acc[p][0] * iEC, 0.05f);
-                    fp[p][0] = pf_pairn(last[p], pf_splat(0.f));
+                    last[p] = pf_act_halfn(acc[p][0], iEC, 0.05f);
+                    fp[p][0] = pf_join_halfn(last[p], PfHalfN{});
                 }
             }
             pf_static_for<1, 8>([&](auto tc) {
@@ -132,13 +134,13 @@ __global__ __launch_bounds__(NW * 64) void interp_kernel(InterpArgs a) {
                 f4 acc[P][1];
 #pragma unroll
                 for (int p = 0; p < P; ++p) acc[p][0] = pf_splat(0.f);
-                pf_mmn<false, 1, 1, 1>(wsET, t, e, acc);
+                pf_mm1<false, 1>(wsET, t, e, acc);
                 pf_mmn<false, 1, CPT, CPT>(wsEC, F0, fp, acc);
 #pragma unroll
                 for (int p = 0; p < P; ++p) {
-                    const f4 f = pf_lrelu(acc[p][0] * iEC, 0.05f);
-                    if constexpr (t % 2 == 1) fp[p][t / 2] = pf_pairn(last[p], f);
-                    else fp[p][t / 2] = pf_pairn(f, pf_splat(0.f));
+                    const PfHalfN f = pf_act_halfn(acc[p][0], iEC, 0.05f);
+                    if constexpr (t % 2 == 1) fp[p][t / 2] = pf_join_halfn(last[p], f);
+                    else fp[p][t / 2] = pf_join_halfn(f, PfHalfN{});
                     last[p] = f;
                 }
             });
@@ -147,8 +149,8 @@ __global__ __launch_bounds__(NW * 64) void interp_kernel(InterpArgs a) {
             for (int ob = 0; ob < 8; ++ob)
 #pragma unroll
                 for (int p = 0; p < P; ++p) w1[p][ob] = pf_splat(0.f);
-            pf_mmn<false, 4, 1, 1>(wsWT, 0, e, w1, 0, 0);
-            pf_mmn<false, 4, 1, 1>(wsWT, 4, e, w1, 0, 4);
+            pf_mm1<false, 4>(wsWT, 0, e, w1, 0);
+            pf_mm1<false, 4>(wsWT, 4, e, w1, 4);
             pf_mmn<false, 4, 4, 4>(wsW0, 0, fp, w1, 0, 0);            // two chunks of 4 output blocks
             pf_mmn<false, 4, 4, 4>(wsW0, 16, fp, w1, 0, 4);
         }
@@ -160,12 +162,12 @@ __global__ __launch_bounds__(NW * 64) void interp_kernel(InterpArgs a) {
             for (int cb = 0; cb < 4; ++cb)
 #pragma unroll
                 for (int p = 0; p < P; ++p) d[p][cb] = pf_splat(0.f);
-            pf_mmn<false, 4, 1, 1>(wsDT, 0, e, d);
+            pf_mm1<false, 4>(wsDT, 0, e, d);
             PfPairN dp[P][2];
 #pragma unroll
             for (int p = 0; p < P; ++p) {
-                dp[p][0] = pf_pairn(pf_lrelu(d[p][0] * iDT, 0.01f), pf_lrelu(d[p][1] * iDT, 0.01f));
-                dp[p][1] = pf_pairn(pf_lrelu(d[p][2] * iDT, 0.01f), pf_lrelu(d[p][3] * iDT, 0.01f));
+                dp[p][0] = pf_act_pairn(d[p][0], d[p][1], iDT, 0.01f);
+                dp[p][1] = pf_act_pairn(d[p][2], d[p][3], iDT, 0.01f);
             }
 #pragma unroll
             for (int cb = 0; cb < 4; ++cb)
@@ -174,8 +176,8 @@ __global__ __launch_bounds__(NW * 64) void interp_kernel(InterpArgs a) {
             pf_mmn<false, 4, 2, 2>(wsD3, 0, dp, d);
 #pragma unroll
             for (int p = 0; p < P; ++p) {
-                dp[p][0] = pf_pairn(pf_lrelu(d[p][0] * iD3, 0.01f), pf_lrelu(d[p][1] * iD3, 0.01f));
-                dp[p][1] = pf_pairn(pf_lrelu(d[p][2] * iD3, 0.01f), pf_lrelu(d[p][3] * iD3, 0.01f));
+                dp[p][0] = pf_act_pairn(d[p][0], d[p][1], iD3, 0.01f);
+                dp[p][1] = pf_act_pairn(d[p][2], d[p][3], iD3, 0.01f);
             }
             // w1 += (W0a W6) d2
             pf_mmn<false, 4, 2, 2>(wsD6, 0, dp, w1, 0, 0);
@@ -190,7 +192,7 @@ __global__ __launch_bounds__(NW * 64) void interp_kernel(InterpArgs a) {
             for (int c = 0; c < 4; ++c)
 #pragma unroll
                 for (int p = 0; p < P; ++p)
-                    w1p[p][c] = pf_pairn(pf_lrelu(w1[p][2 * c] * iW1, 0.01f), pf_lrelu(w1[p][2 * c + 1] * iW1, 0.01f));
+                    w1p[p][c] = pf_act_pairn(w1[p][2 * c], w1[p][2 * c + 1], iW1, 0.01f);
             f4 w2[P][4];
 #pragma unroll
             for (int ob = 0; ob < 4; ++ob)
@@ -200,8 +202,8 @@ __global__ __launch_bounds__(NW * 64) void interp_kernel(InterpArgs a) {
             PfPairN w2p[P][2];
 #pragma unroll
             for (int p = 0; p < P; ++p) {
-                w2p[p][0] = pf_pairn(pf_lrelu(w2[p][0] * iW3, 0.01f), pf_lrelu(w2[p][1] * iW3, 0.01f));
-                w2p[p][1] = pf_pairn(pf_lrelu(w2[p][2] * iW3, 0.01f), pf_lrelu(w2[p][3] * iW3, 0.01f));
+                w2p[p][0] = pf_act_pairn(w2[p][0], w2[p][1], iW3, 0.01f);
+                w2p[p][1] = pf_act_pairn(w2[p][2], w2[p][3], iW3, 0.01f);
             }
 #pragma unroll
             for (int p = 0; p < P; ++p)
@@ -282,7 +284,7 @@ static int interp_launch(const float* xyz, const float* z, const int* idx16, con
     InterpArgs a{};
     a.xyz = xyz; a.z = z; a.idx = idx16; a.w = w; a.u = u_out; a.aw = aw_out; a.T = B * N; a.N = N; a.R = R;
     for (int i = 0; i < 15; ++i) a.off[i] = off[i];
-    a.contiguous = off[5] == off[0] + 4 * 512 && off[8] == off[5] + 8 * 512 && off[1] == off[8] + 8 * 512 &&
+    a.contiguous = off[5] == off[0] + 4 * 256 && off[8] == off[5] + 8 * 256 && off[1] == off[8] + 8 * 256 &&       // edge tables: 256 floats per fragment
                    off[6] == off[1] + 8 * 512 && off[3] == off[6] + 16 * 512 && off[9] == off[3] + 16 * 512;
     // launch shape: one column tile per wave x 12 waves.  (2, 8) - two tiles share each weight fragment read, half the LDS / L2
     // weight traffic per tile - measures 169 -> 160 us in a back-to-back loop of this kernel alone (tools/tune_interp.py) and
@@ -316,4 +318,3 @@ extern "C" int pf_interp_weights(const float* xyz, const int* idx16, const float
     if (!xyz || !idx16 || !w || !off || !aw_out) return PF_ERR_NULL;
     return interp_launch(xyz, nullptr, idx16, w, off, nullptr, aw_out, B, N, 4, stream);
 }
-

@@ -266,6 +266,91 @@ __device__ __forceinline__ PfPairN pf_pairn(f4 b0, f4 b1) {
     return p;
 }
 
+// ---- layer epilogues of the fused inference kernels: rescale, LeakyReLU / ReLU and the hi / lo split, single-issue fp32 only ----
+// pf_pairn(pf_lrelu(v * inv, slope), ..) is written with 4-vector expressions, which hipcc turns into v_pk_mul_f32 (and, through
+// SLP, packs neighbouring scalar fp32 math as well).  Beside MFMAs a packed fp32 op is dearer than the two plain ones it
+// replaces, so the epilogues below do the same arithmetic - v * inv, then max(v, v * slope), then the split of pf_pairn, bit for
+// bit - one value at a time.  The multiplies and the max stay C++ on purpose: they are the first readers of MFMA results, and
+// hipcc pads the MFMA -> VALU read hazard only for instructions it issues itself, never for registers read inside an asm
+// statement.  pf_opaque() ends the SLP vectoriser's search at each activated value; the split is asm as in pf_pairn.
+// The rescale stays a multiply of its own: folding `inv` into the conversions (hi = f16(m * inv), lo = f16(m * inv - hi) with
+// m = max(v, slope * v)) saves one instruction per value pair but is not the same bits where v * inv underflows fp32 - the
+// separate multiply rounds to (signed) zero there and the low half of a zero is +0, the fused form keeps the sign.
+__device__ __forceinline__ float pf_opaque(float v) { asm("" : "+v"(v)); return v; }
+
+enum { PF_ACT_LRELU = 0, PF_ACT_RELU = 1 };
+template <bool SCALE, int ACT>
+__device__ __forceinline__ float pf_act1n(float v, float inv, float slope) {
+    if constexpr (SCALE) v = v * inv;
+    if constexpr (ACT == PF_ACT_RELU) return pf_opaque(fmaxf(v, 0.f));
+    else return pf_opaque(fmaxf(v, v * slope));
+}
+
+// hi / lo split of one 16-channel block (half a PfPairN operand): two packed-fp16 registers each
+struct PfHalfN { u2 h, l; };
+__device__ __forceinline__ PfHalfN pf_splitn4(float x0, float x1, float x2, float x3) {
+    const unsigned h0 = pf_pk_f16(x0, x1), h1 = pf_pk_f16(x2, x3);
+    unsigned l0, l1;
+    asm("v_fma_mixlo_f16 %0, %2, -1.0, %4 op_sel_hi:[1,0,0]\n\t"
+        "v_fma_mixlo_f16 %1, %3, -1.0, %6 op_sel_hi:[1,0,0]\n\t"
+        "v_fma_mixhi_f16 %0, %2, -1.0, %5 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
+        "v_fma_mixhi_f16 %1, %3, -1.0, %7 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
+        "s_nop 1"
+        : "=&v"(l0), "=&v"(l1)
+        : "v"(h0), "v"(h1), "v"(x0), "v"(x1), "v"(x2), "v"(x3));
+    return PfHalfN{(u2){h0, h1}, (u2){l0, l1}};
+}
+// the same for two blocks at once (the asm of pf_pairn on scalar operands: no 4-vector is built on the way in)
+__device__ __forceinline__ PfPairN pf_splitn8(float x0, float x1, float x2, float x3, float x4, float x5, float x6, float x7) {
+    const unsigned h0 = pf_pk_f16(x0, x1), h1 = pf_pk_f16(x2, x3), h2_ = pf_pk_f16(x4, x5), h3 = pf_pk_f16(x6, x7);
+    unsigned l0, l1, l2, l3;
+    asm("v_fma_mixlo_f16 %0, %4, -1.0, %8 op_sel_hi:[1,0,0]\n\t"
+        "v_fma_mixlo_f16 %1, %5, -1.0, %10 op_sel_hi:[1,0,0]\n\t"
+        "v_fma_mixlo_f16 %2, %6, -1.0, %12 op_sel_hi:[1,0,0]\n\t"
+        "v_fma_mixlo_f16 %3, %7, -1.0, %14 op_sel_hi:[1,0,0]\n\t"
+        "v_fma_mixhi_f16 %0, %4, -1.0, %9 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
+        "v_fma_mixhi_f16 %1, %5, -1.0, %11 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
+        "v_fma_mixhi_f16 %2, %6, -1.0, %13 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
+        "v_fma_mixhi_f16 %3, %7, -1.0, %15 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
+        "s_nop 1"
+        : "=&v"(l0), "=&v"(l1), "=&v"(l2), "=&v"(l3)
+        : "v"(h0), "v"(h1), "v"(h2_), "v"(h3), "v"(x0), "v"(x1), "v"(x2), "v"(x3), "v"(x4), "v"(x5), "v"(x6), "v"(x7));
+    PfPairN p;
+    p.h = __builtin_bit_cast(h8, (u4){h0, h1, h2_, h3});
+    p.l = __builtin_bit_cast(h8, (u4){l0, l1, l2, l3});
+    return p;
+}
+
+template <bool SCALE, int ACT>
+__device__ __forceinline__ PfPairN pf_act_pairn_t(f4 b0, f4 b1, float inv, float slope) {
+    return pf_splitn8(pf_act1n<SCALE, ACT>(b0.x, inv, slope), pf_act1n<SCALE, ACT>(b0.y, inv, slope),
+                      pf_act1n<SCALE, ACT>(b0.z, inv, slope), pf_act1n<SCALE, ACT>(b0.w, inv, slope),
+                      pf_act1n<SCALE, ACT>(b1.x, inv, slope), pf_act1n<SCALE, ACT>(b1.y, inv, slope),
+                      pf_act1n<SCALE, ACT>(b1.z, inv, slope), pf_act1n<SCALE, ACT>(b1.w, inv, slope));
+}
+template <bool SCALE, int ACT>
+__device__ __forceinline__ PfHalfN pf_act_halfn_t(f4 b, float inv, float slope) {
+    return pf_splitn4(pf_act1n<SCALE, ACT>(b.x, inv, slope), pf_act1n<SCALE, ACT>(b.y, inv, slope),
+                      pf_act1n<SCALE, ACT>(b.z, inv, slope), pf_act1n<SCALE, ACT>(b.w, inv, slope));
+}
+// == pf_pairn(pf_lrelu(b0 * inv, slope), pf_lrelu(b1 * inv, slope));  inv, slope: wave-uniform
+__device__ __forceinline__ PfPairN pf_act_pairn(f4 b0, f4 b1, float inv, float slope) { return pf_act_pairn_t<true, PF_ACT_LRELU>(b0, b1, inv, slope); }
+// inv == 1 (the EdgeConv kernels: the scale plan leaves nothing to undo)
+__device__ __forceinline__ PfPairN pf_act_pairn(f4 b0, f4 b1, float slope) { return pf_act_pairn_t<false, PF_ACT_LRELU>(b0, b1, 1.f, slope); }
+// == pf_pairn(pf_relu(b0 * inv), pf_relu(b1 * inv))
+__device__ __forceinline__ PfPairN pf_relu_pairn(f4 b0, f4 b1, float inv) { return pf_act_pairn_t<true, PF_ACT_RELU>(b0, b1, inv, 0.f); }
+// one block at a time, for the 16-channel layers whose blocks reach a pair one layer apart: the earlier block's half is kept
+// and joined with the next one instead of being split a second time.  A missing block is PfHalfN{} (the split of zeros).
+__device__ __forceinline__ PfHalfN pf_act_halfn(f4 b, float inv, float slope) { return pf_act_halfn_t<true, PF_ACT_LRELU>(b, inv, slope); }
+__device__ __forceinline__ PfHalfN pf_act_halfn(f4 b, float slope) { return pf_act_halfn_t<false, PF_ACT_LRELU>(b, 1.f, slope); }
+__device__ __forceinline__ PfHalfN pf_relu_halfn(f4 b, float inv) { return pf_act_halfn_t<true, PF_ACT_RELU>(b, inv, 0.f); }
+__device__ __forceinline__ PfPairN pf_join_halfn(PfHalfN a, PfHalfN b) {
+    PfPairN p;
+    p.h = __builtin_bit_cast(h8, (u4){a.h.x, a.h.y, b.h.x, b.h.y});
+    p.l = __builtin_bit_cast(h8, (u4){a.l.x, a.l.y, b.l.x, b.l.y});
+    return p;
+}
+
 // reduce-scatter max steps: (a, b) -> lanes 0..31 get max over both halves of a, lanes 32..63 of b;  rows: the same
 // between odd and even 16-lane rows.  Inline asm because the builtin's two results are mis-paired by hipcc 7.2 once they
 // are bit-cast to float; the leading s_nop is the VALU write -> permlane read hazard.
@@ -344,6 +429,40 @@ __device__ __forceinline__ void pf_mmn(const WS& ws, int frag0, const PfPairN (&
 #endif
 }
 
+// ---- edge-table products as ONE MFMA ------------------------------------------------------------------------------------
+// Every affine function of an edge's raw inputs e (8 values: x_i, x_j, a norm or 0, 1) is a product with an 8-column table T.
+// As a split product through pf_mmn it costs three MFMAs whose k-slots are three quarters zeros.  The same three terms fit
+// one: the B operand carries e_hi | e_lo | e_hi | 0 in the k-slots of lanes q = 0..3, the A operand T_hi | T_hi | T_lo | 0
+// (packing._etab_frag1: one 1-KiB fp16 fragment per 16 table rows), and the sum over k is T_hi e_hi + T_hi e_lo + T_lo e_hi.
+// PF_MMN_TERMS == 1 (the reduced-precision build) keeps T_hi e_hi alone: the operand's q = 1, 2 groups are zero then.
+struct PfW1Lds {                                    // weights: [frag][64 lanes] x 16 B in LDS
+    const u4* base;
+    int lane;
+    __device__ __forceinline__ h8 load(int frag) const { return __builtin_bit_cast(h8, base[frag * PF_WAVE + lane]); }
+};
+// e0 | e1: the 8 raw inputs of this lane's edge column, the same in all four q lanes of the column
+__device__ __forceinline__ h8 pf_edge_operand(f4 e0, f4 e1, int q) {
+    const PfPairN s = pf_pairn(e0, e1);
+    const u4 h = __builtin_bit_cast(u4, s.h), l = __builtin_bit_cast(u4, s.l), z = {0u, 0u, 0u, 0u};
+    if constexpr (PF_MMN_TERMS == 3) return __builtin_bit_cast(h8, q == 1 ? l : (q == 3 ? z : h));
+    else return __builtin_bit_cast(h8, q == 0 ? h : z);
+}
+// acc[p][acc0 + ob] += T[ob] e[p] for ob < OB, one MFMA per fragment.  SWAP = true: D[edge][channel] (e is the A operand).
+template <bool SWAP, int OB, class WS, int P, int NACC>
+__device__ __forceinline__ void pf_mm1(const WS& ws, int frag0, const h8 (&e)[P], f4 (&acc)[P][NACC], int acc0 = 0) {
+    h8 w[OB];
+#pragma unroll
+    for (int ob = 0; ob < OB; ++ob) w[ob] = ws.load(frag0 + ob);
+#pragma unroll
+    for (int ob = 0; ob < OB; ++ob) {
+#pragma unroll
+        for (int p = 0; p < P; ++p) {
+            if constexpr (SWAP) acc[p][acc0 + ob] = pf_mfma_f16(e[p], w[ob], acc[p][acc0 + ob]);
+            else acc[p][acc0 + ob] = pf_mfma_f16(w[ob], e[p], acc[p][acc0 + ob]);
+        }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+}
 
 // cooperative global -> LDS copy of n 16-byte words by the whole workgroup (call before a __syncthreads).  D loads per thread
 // are in flight before the first LDS store: a plain load -> store loop pays one full memory latency per iteration, and at

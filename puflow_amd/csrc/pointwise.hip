@@ -216,10 +216,10 @@ __device__ __forceinline__ void cond_body(const CondArgs& a, u4* wl, int tile0, 
             for (int o = 0; o < MB; ++o) m[0][o] = pf_bias(b1, o, q);
             pf_mmn<false, MB, HP, HP>(wsM1, 0, hp, m);
 #pragma unroll
-            for (int o = 0; o < MB; ++o) m[0][o] = pf_relu(pf_scale(m[0][o], iM1));
-            if constexpr (MB & 1) m[0][MB] = pf_splat(0.f);
-#pragma unroll
-            for (int c = 0; c < MP; ++c) mp[0][c] = pf_pairn(m[0][2 * c], m[0][2 * c + 1]);
+            for (int c = 0; c < MP; ++c) {
+                if (2 * c + 1 < MB) mp[0][c] = pf_relu_pairn(m[0][2 * c], m[0][2 * c + 1], iM1);
+                else mp[0][c] = pf_join_halfn(pf_relu_halfn(m[0][2 * c], iM1), PfHalfN{});
+            }
         }
         // c = W2 m is only materialised when the caller wants `cs` (feat_extract API): everything downstream of c
         // is linear in it, so the host folded W2 into those layers (H1 := [s_W0; t_W0; c1_W0c] W2, packing.pack_plan)
@@ -254,15 +254,15 @@ __device__ __forceinline__ void cond_body(const CondArgs& a, u4* wl, int tile0, 
             for (int o = 0; o < 4; ++o) h1[0][o] = pf_splat(0.f);
             pf_mmn<false, 4, MP, MP>(wsH1, (4 * net) * MP, mp, h1);
             PfPairN h1p[1][2];
-            h1p[0][0] = pf_pairn(pf_lrelu(pf_scale(h1[0][0], iH1), 0.01f), pf_lrelu(pf_scale(h1[0][1], iH1), 0.01f));
-            h1p[0][1] = pf_pairn(pf_lrelu(pf_scale(h1[0][2], iH1), 0.01f), pf_lrelu(pf_scale(h1[0][3], iH1), 0.01f));
+            h1p[0][0] = pf_act_pairn(h1[0][0], h1[0][1], iH1, 0.01f);
+            h1p[0][1] = pf_act_pairn(h1[0][2], h1[0][3], iH1, 0.01f);
             f4 h2[1][4];
 #pragma unroll
             for (int o = 0; o < 4; ++o) h2[0][o] = pf_bias(net == 0 ? bS2 : bT2, o, q);
             if constexpr (net == 0) pf_mmn<false, 4, 2, 2>(wsS2, 0, h1p, h2); else pf_mmn<false, 4, 2, 2>(wsT2, 0, h1p, h2);
             const float i2 = net == 0 ? iS2 : iT2;
-            h2p[0][2 * net + 0] = pf_pairn(pf_lrelu(pf_scale(h2[0][0], i2), 0.01f), pf_lrelu(pf_scale(h2[0][1], i2), 0.01f));
-            h2p[0][2 * net + 1] = pf_pairn(pf_lrelu(pf_scale(h2[0][2], i2), 0.01f), pf_lrelu(pf_scale(h2[0][3], i2), 0.01f));
+            h2p[0][2 * net + 0] = pf_act_pairn(h2[0][0], h2[0][1], i2, 0.01f);
+            h2p[0][2 * net + 1] = pf_act_pairn(h2[0][2], h2[0][3], i2, 0.01f);
         });
         {
             f4 acc[1][1];
@@ -428,4 +428,32 @@ extern "C" int pf_post(int unit, const float* h, const float* w, const long long
         if (rc != PF_OK) return rc;
     }
     return pf_cond(unit, h, w, off, c, st, cp, T, stream);
+}
+
+// ---- test entry: the layer epilogue helper (pf_mfma.h pf_act_pairn) against the sequence it replaces -------------------
+// Thread i takes x[8 i .. 8 i + 8) as two 16-channel-block registers and leaves the four hi and four lo words of
+//   old: pf_pairn(pf_lrelu(pf_scale(b0, inv), slope), pf_lrelu(pf_scale(b1, inv), slope))     new: pf_act_pairn(b0, b1, [inv,] slope)
+// (inv == 1 takes the helper's form without the rescale).  tests/test_gpu_epilogue.py wants the images bit-equal.
+namespace {
+__global__ void act_pairn_test_kernel(const float* __restrict__ x, int n8, float inv, float slope, u4* __restrict__ old_h,
+                                      u4* __restrict__ old_l, u4* __restrict__ new_h, u4* __restrict__ new_l) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n8) return;
+    const f4 b0 = *reinterpret_cast<const f4*>(x + (size_t)i * 8), b1 = *reinterpret_cast<const f4*>(x + (size_t)i * 8 + 4);
+    const PfPairN o = pf_pairn(pf_lrelu(pf_scale(b0, inv), slope), pf_lrelu(pf_scale(b1, inv), slope));
+    const PfPairN n = inv == 1.f ? pf_act_pairn(b0, b1, slope) : pf_act_pairn(b0, b1, inv, slope);
+    old_h[i] = __builtin_bit_cast(u4, o.h); old_l[i] = __builtin_bit_cast(u4, o.l);
+    new_h[i] = __builtin_bit_cast(u4, n.h); new_l[i] = __builtin_bit_cast(u4, n.l);
+}
+}  // namespace
+
+extern "C" int pf_test_act_pairn(const float* x, int n, float inv, float slope, unsigned* old_h, unsigned* old_l,
+                                 unsigned* new_h, unsigned* new_l, void* stream) {
+    if (!x || !old_h || !old_l || !new_h || !new_l) return PF_ERR_NULL;
+    if (n <= 0 || n % 8 != 0) return PF_ERR_SHAPE;
+    const int n8 = n / 8;
+    hipLaunchKernelGGL(act_pairn_test_kernel, dim3((n8 + 63) / 64), dim3(64), 0, (hipStream_t)stream, x, n8, inv, slope,
+                       reinterpret_cast<u4*>(old_h), reinterpret_cast<u4*>(old_l), reinterpret_cast<u4*>(new_h),
+                       reinterpret_cast<u4*>(new_l));
+    return pf_last_launch_status();
 }

@@ -385,6 +385,55 @@ def _etab_frag(xi: np.ndarray, xj: np.ndarray, nrm, const: np.ndarray) -> np.nda
     return frag_pack_f16x2(W)
 
 
+_ETAB_COLS = np.array([0, 1, 2, 3, 16, 17, 18, 19])      # the columns an edge table fills (_etab_dense)
+
+
+def _etab_frag1(W: np.ndarray) -> np.ndarray:
+    """Dense edge table (_etab_dense: [rows, 32], columns 0..3 and 16..19) -> its one-MFMA image: ONE fp16 fragment
+    (64 lanes x 8 fp16 = 256 floats) per 16 rows that holds T_hi in the k-slots of the lanes q = 0 and q = 1 and T_lo in
+    q = 2 (the column map of _etab_dense shifted by 4 q; q = 3 stays zero).  Against the operand e_hi | e_lo | e_hi | 0
+    (csrc/pf_mfma.h pf_edge_operand) one MFMA sums T_hi e_hi + T_hi e_lo + T_lo e_hi: the split product of frag_pack_f16n
+    without the 24 empty k-slots per term.  hi / lo as in frag_pack_f16n (natural-scale low half)."""
+    rows = W.shape[0]
+    OB = (rows + 15) // 16
+    Wp = np.zeros((OB * 16, 32), dtype=np.float32)
+    Wp[:rows] = W
+    rest = np.ones(32, bool); rest[_ETAB_COLS] = False
+    if np.any(Wp[:, rest] != 0):
+        raise ValueError("not an edge table: columns outside 0..3 / 16..19 are in use")
+    if np.abs(Wp).max(initial=0.0) >= 65504.0:
+        raise ValueError("scaled weight magnitude exceeds the fp16 range of the f16n path; use ec_mode='f32'")
+    hi = Wp.astype(np.float16)
+    lo = (Wp - hi.astype(np.float32)).astype(np.float32).astype(np.float16)
+    D = np.zeros((OB * 16, 32), dtype=np.float16)
+    D[:, _ETAB_COLS] = hi[:, _ETAB_COLS]
+    D[:, _ETAB_COLS + 4] = hi[:, _ETAB_COLS]
+    D[:, _ETAB_COLS + 8] = lo[:, _ETAB_COLS]
+    # lane = 16 q + row holds k = 16 h + 4 q + jj at slot j = 4 h + jj (the hi plane of frag_pack_f16n with CP = 1)
+    res = D.view(np.uint16).reshape(OB, 16, 2, 4, 4).transpose(0, 3, 1, 2, 4).reshape(OB, 64, 8)
+    return np.ascontiguousarray(res).reshape(-1).view(np.float32)
+
+
+def etab_unpack_frag1(F: np.ndarray, rows: int):
+    """Inverse of _etab_frag1 (tests): (hi of q = 0, hi of q = 1, lo of q = 2, the q = 3 slots) as float64 [rows, 8] each,
+    columns in _ETAB_COLS order."""
+    OB = (rows + 15) // 16
+    img = np.ascontiguousarray(F, dtype=np.float32).view(np.uint16).reshape(OB, 4, 16, 8).view(np.float16).astype(np.float64)
+    return tuple(img[:, q].reshape(OB * 16, 8)[:rows] for q in range(4))
+
+
+def ec1n_unit0_table(u: Dict[str, np.ndarray]):
+    """Unit 0's edge table as edgeconv1n_kernel multiplies it -> (dense [96, 32] table, 2^-sw as float32).  Rows carry the
+    4^t activation scales of ec4_scales (C = 3: every pre-activation, conv_out's P part included, comes from the table, so all
+    rows take the Q scale) and the whole table a power of two 2^sw that brings max |T| into [2^13, 2^14) like every other
+    f16n matrix (f16n_scale): without it the natural-scale low half of every entry below 2^-4 is an fp16 subnormal and the
+    split no longer holds 2^-21 relative.  The kernel multiplies the table products by 2^-sw (exact) before anything else."""
+    _, rq, _ = ec4_scales(4, 16, 32)
+    T = _etab_dense(u["PA"] * rq[:, None], u["QB"] * rq[:, None], None, u["pb"] * rq)
+    sc = f16n_scale(T)
+    return (T.astype(np.float64) * sc).astype(np.float32), np.float32(1.0 / sc)
+
+
 def _ec_frags(u: Dict[str, np.ndarray], nconv: int) -> np.ndarray:
     return np.concatenate([frag_pack(u[f"G{t}"]).reshape(-1) for t in range(1, nconv + 1)])
 
@@ -426,14 +475,14 @@ def pack_plan(plan: Dict[str, object], ec_mode: str = "f16n") -> Dict[str, objec
     out["ec_w"] = [B.add(_ec_frags(units[i], 4)) for i in range(NUM_BLOCKS)]
     out["ec4_w"] = [None, None] + [B.add(ec4_weights(units[i])) for i in range(2, NUM_BLOCKS)]
     # f16n images of the narrow units 0 / 1 (csrc/edgeconv.hip edgeconv1n_kernel): G1 | G2 | G3 | Gout with the same
-    # 4^t activation-scale plan; unit 0 carries its edge table with the rows scaled like the P|Q rows of the other units
+    # 4^t activation-scale plan; unit 0 carries its edge table (one-MFMA image, ec1n_unit0_table) and behind it 2^-sw of the table
     ec1n = []
     for i in range(2):
         parts = [ec4_weights(units[i], 4, 16)]
         if i == 0:
-            rp, rq, _ = ec4_scales(4, 16, 32)
-            # C = 3: every pre-activation (conv_out's P part included) comes from the table, so all its rows take the Q scale
-            parts.append(frag_pack_f16n(_etab_dense(units[0]["PA"] * rq[:, None], units[0]["QB"] * rq[:, None], None, units[0]["pb"] * rq)))
+            tab, inv_tab = ec1n_unit0_table(units[0])
+            parts.append(_etab_frag1(tab))
+            parts.append(_pad_vec(np.array([inv_tab], np.float32), 64))
         ec1n.append(B.add(np.concatenate(parts)))
     out["ec1n_w"] = ec1n + [None] * (NUM_BLOCKS - 2)
     out["ec_mode"] = ec_mode
@@ -490,26 +539,28 @@ def pack_plan(plan: Dict[str, object], ec_mode: str = "f16n") -> Dict[str, objec
     # matrices: f16n fragment images (natural-scale low half) scaled by a power of two per GROUP of matrices that share
     # an accumulator; biases that initialise accumulators are pre-multiplied by the group's 2^sw; "scales" = the 2^-sw
     # factors in INTERP_SCALES order (csrc/interp.hip header lists the slots)
-    def grp(*mats):
+    def grp(*mats, tables=0):                      # the first `tables` matrices are edge tables: one-MFMA images
         sc = min(f16n_scale(m) for m in mats)
-        return sc, [frag_pack_f16n((m.astype(np.float64) * sc).astype(np.float32)) for m in mats]
+        return sc, [(_etab_frag1 if i < tables else frag_pack_f16n)((m.astype(np.float64) * sc).astype(np.float32))
+                    for i, m in enumerate(mats)]
     dtab_d = _etab_dense(ip["d_PA"], ip["d_QB"], ip["d_wn"], ip["d_b0"])
     ectab_d = _etab_dense(ec["PA"][:128], ec["QB"][:128], None, ec["pb"][:128])
     w1tab_d = _etab_dense(ft[:, 0:3], ft[:, 3:6], None, ft[:, 6] + ip["f_b0"])     # W0b.(edge table) + b0 + W0a.b6
-    s_dt, (i_dt,) = grp(dtab_d)
+    s_dt, (i_dt,) = grp(dtab_d, tables=1)
     s_d3, (i_d3,) = grp(ip["d_W3"])
-    s_w1, (i_w1t, i_d6, i_w0) = grp(w1tab_d, ip["f_dW"], ip["f_eW"])
+    s_w1, (i_w1t, i_d6, i_w0) = grp(w1tab_d, ip["f_dW"], ip["f_eW"], tables=1)
     ecG = [ec[f"G{t}"] for t in range(1, 8)]
-    s_ec, ec_imgs = grp(ectab_d, *ecG)
+    s_ec, ec_imgs = grp(ectab_d, *ecG, tables=1)
     s_w3, (i_w3,) = grp(ip["w_W3"])
     s_w6, (i_w6r, i_w6f) = grp(W6r, ip["w_W6"])
     io = {}
-    # the LDS image of interp_kernel, back to back in its order (4 + 8 + 8 + 8 + 16 + 16 + 16 = 76 fragment pairs of 2 KiB):
-    # edge tables (distance encoder, growth pre-activations, w1 bracket), d_W3, the growth chain, (W0a W6), w_W3 - ONE copy
+    # the LDS image of interp_kernel, back to back in its order (2 + 4 + 4 + 8 + 16 + 16 + 16 = 66 slots of 2 KiB): edge tables
+    # (distance encoder, growth pre-activations, w1 bracket: 4 + 8 + 8 one-MFMA fragments of 1 KiB), d_W3, the growth chain,
+    # (W0a W6), w_W3 (fragment pairs) - ONE copy
     for k, im in (("dtab", i_dt), ("ectab", ec_imgs[0]), ("w_b0", i_w1t), ("d_W3", i_d3), ("ec_w", np.concatenate(ec_imgs[1:])),
                   ("d_W6", i_d6), ("w_W3", i_w3)):
         io[k] = B.add(im)
-    assert B.n - io["dtab"] == 76 * 512
+    assert B.n - io["dtab"] == 66 * 512
     io.update({
         "d_b3": B.add(ip["d_b3"] * s_d3),
         "scales": B.add(_pad_vec(np.array([1 / s_dt, 1 / s_d3, 1 / s_w1, 1 / s_ec, 1 / s_w3, 1 / s_w6], np.float32), 16)),
