@@ -33,7 +33,7 @@ from .interpflow import (COND_CHANNELS, FEAT_CHANNELS, GROWTH, NUM_BLOCKS, _Edge
                          _MergeParams)
 from .packing import (CNF_CTX, CNF_GRAD, cnf_hyper_matrix, cnf_split_ok, pack_cnf_block, pack_cnf_context,
                       unpack_cnf_grads)
-from .train_ops import _gemm
+from .train_perop import _gemm
 from .weights import state_dict_spec
 
 ATOL = RTOL = 1e-5                       # continuous/interpflow.py:28

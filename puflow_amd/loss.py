@@ -118,8 +118,8 @@ class ChamferCUDA(nn.Module):
 
 
 def train_ops_deterministic() -> bool:
-    from . import train_ops
-    return train_ops.deterministic()
+    from . import train_state
+    return train_state.deterministic()
 
 
 class PuganLossFn(Function):
@@ -154,7 +154,7 @@ class PuganLossFn(Function):
         i1 = i2 = torch.empty((0,), dtype=torch.int32, device=dev)
         cd_side = None
         if w_cd != 0.0 and pred.is_cuda:
-            from .train_ops import _side_stream
+            from .train_state import _side_stream
             cd_side = _side_stream(dev)
             cd_side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(cd_side):

@@ -42,9 +42,9 @@ def knn_idx32(p1: torch.Tensor, p2: torch.Tensor, K: int, want_dist: bool = Fals
 
 
 def _chamfer_bwd(lib):
-    """pf_chamfer_bwd, or its atomics-free form under train_ops.set_deterministic(True) (a debugging switch)."""
-    from . import train_ops
-    return lib.pf_chamfer_bwd_det if train_ops.deterministic() else lib.pf_chamfer_bwd
+    """pf_chamfer_bwd, or its atomics-free form under train_state.set_deterministic(True) (a debugging switch)."""
+    from . import train_state
+    return lib.pf_chamfer_bwd_det if train_state.deterministic() else lib.pf_chamfer_bwd
 
 
 def knn_points(p1: torch.Tensor, p2: torch.Tensor, K: int, return_nn: bool = False, return_sorted: bool = True,

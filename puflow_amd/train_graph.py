@@ -67,9 +67,9 @@ _GRAD_TABLE = os.environ.get("PF_TRAIN_GRAD_TABLE", "1") != "0"
 
 class GraphedTrainStep:
     def __init__(self, module, optimizer: torch.optim.Optimizer, batch, clip: float = 1e-2, warmup: int = 2):
-        from . import train_ops
+        from . import train_ops, train_state
         from .dist import FlatGradBucket
-        if getattr(getattr(module, "network", module), "sync_batchnorm", False) and train_ops._multi_rank():
+        if getattr(getattr(module, "network", module), "sync_batchnorm", False) and train_state._multi_rank():
             # SyncBN on the fused kernels all-reduces a layer's sums between two launches: RCCL collectives can be captured into
             # the graph, gloo's (host-side) cannot; the un-fused kernels read the global row count on the host
             if not train_ops._FUSED or torch.distributed.get_backend() != "nccl":
@@ -97,7 +97,7 @@ class GraphedTrainStep:
         self.calls = 0
         self.bucket = FlatGradBucket(module.parameters())
         # warm-up AND capture run on this one stream: the fused kernels' zero-initialised scratch words (barrier words, the sticky
-        # time-out word, statistics accumulators: train_ops._zeros_kept) are cached per (device, stream) and must be allocated
+        # time-out word, statistics accumulators: train_state._zeros_kept) are cached per (device, stream) and must be allocated
         # OUTSIDE the capture - inside it their torch.zeros would be a memset node that clears the sticky word on every replay
         side = self.capture_stream = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
@@ -156,7 +156,7 @@ class GraphedTrainStep:
         if len(words) > 1:                                  # 32-bit tensors on the device: one launch of ours for up to 8 of them
             import ctypes
             from . import _lib
-            from .train_ops import _stream
+            from .train_state import _stream
             lib = _lib.load()
             for k in range(0, len(words), 8):
                 grp = words[k:k + 8]

@@ -29,7 +29,7 @@ def default_cfg(**kw):
     # sync_batchnorm: BatchNorm statistics over ALL ranks (an extension: the reference trains on one GPU, where it is
     # the same thing; default False = each rank normalises with its own shard, like DDP without SyncBatchNorm)
     # deterministic: bit-reproducible training steps (a debugging switch: BatchNorm statistics as exact fixed-point sums, the
-    # remaining float-atomic gradients as ordered gathers; slower - no persistent kernels; train_ops.set_deterministic)
+    # remaining float-atomic gradients as ordered gathers; slower - no persistent kernels; train_state.set_deterministic)
     # persistent_kernels: the training step's grid-barrier kernels (EdgeConv units as one launch each).  None = on, unless
     # emd_workgroups == 1 says the device is shared with other processes (grid barriers need every workgroup resident)
     cfg = dict(net="UpsamplingFlow", learning_rate=1e-3, sched_patience=10, sched_factor=0.5, seed=2021, sync_batchnorm=False,
@@ -49,7 +49,7 @@ class TrainerModule(_Base):
         self.network = PointInterpFlow(pc_channel=3)
         self.network.sync_batchnorm = bool(getattr(self.cfg, "sync_batchnorm", False))     # an argument of its train-mode forward
         self.network.deterministic = bool(getattr(self.cfg, "deterministic", False))
-        # weight gradients on their own stream beside the backward chain (train_ops._dw_begin): measured slower at the bench shape
+        # weight gradients on their own stream beside the backward chain (train_state._dw_begin): measured slower at the bench shape
         # (4.54 -> 4.79 ms per step), so an opt-in
         self.network.train_dw_stream = bool(getattr(self.cfg, "dw_stream", False))
         pk = getattr(self.cfg, "persistent_kernels", None)
@@ -215,7 +215,7 @@ class TrainerModule(_Base):
         number of NaN losses a CAPTURED step replaced by the reference's constant 0.1 (train_pu1k.py:71-73) is returned (and
         printed, like the reference's `loss is nan`)."""
         from .loss import check_emd_status
-        from .train_ops import check_persist_status
+        from .train_state import check_persist_status
         check_emd_status(next(self.parameters()).device)
         check_persist_status(next(self.parameters()).device)
         opt = getattr(self, "_fused_opt", None)
