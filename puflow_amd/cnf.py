@@ -7,11 +7,13 @@ differentiable (`PointInterpFlow.flow_block`: taped Dormand-Prince steps, backwa
 What runs where:
   * kNN, the six EdgeConv units, the merge units and the interpolation module are the discrete model's kernels
     (the reference imports those modules from the discrete file too, continuous/interpflow.py:14);
-  * the per-point context terms of every ConcatSquash layer: one GEMM per block (`pf_gemm`);
-  * every ODE right-hand side incl. the Hutchinson term, the Runge-Kutta stages (one fused launch per step attempt),
-    the error / step norms: `pf_cnf_step`, `pf_cnf_rhs`, `pf_lincomb`, `pf_scaled_sumsq` (csrc/cnf.hip);
-  * the adaptive step-size CONTROL of dopri5 (torchdiffeq semantics restated from its published algorithm, see
-    oracle/cnf_ref.py header): a few host scalars per step - one device->host read of the error norm per step.
+  * the per-point context terms of every ConcatSquash layer: one split-fp16 GEMM per block (`pf_cnf_context`);
+  * an integration of the forward: `pf_cnf_init`, then `pf_cnf_steps` - one fused launch per step attempt (six stage
+    evaluations incl. the Hutchinson term, error norm) with dopri5's step-size CONTROL on the device (torchdiffeq semantics
+    restated from its published algorithm, see oracle/cnf_ref.py header).  The controller states of the twelve integrations
+    are read ONCE per forward; one that did not finish inside its attempts falls back to a read per batch of attempts;
+  * only `flow_block` steps from the host: one `pf_cnf_step` per attempt with the error norm read back, `pf_cnf_rhs`,
+    `pf_lincomb`, `pf_scaled_sumsq` around it, and `pf_cnf_rhs_vjp` in its backward (csrc/cnf.hip, csrc/cnf_bwd.hip).
 
 Parity: the right-hand side is pinned to the reference's own ODEfunc (tests/golden/cnf_rhs.npz); the solver is UNPINNED
 (torchdiffeq is not installed and not vendored) - the integrated path is tested against oracle/cnf_ref.py, a from-text
@@ -113,7 +115,8 @@ def _discrete_shell(sd) -> dict:
 class _CnfKernels:
     """Launch wrappers of csrc/cnf.hip shared by the inference engine and the taped single-block engine.  What they read of
     `self` is set by `_init_kernels` (lib, device, the norm kernels' scratch `ws` / `ws1k` / `red`, the counter `nfe`) and by
-    `_add_block`: per block index i the record `rec[i]`, the context GEMM's `Hc[i]`, `Hci[i]`, `hb[i]` and `T_end[i]`."""
+    `_add_block`: per block index i the record `rec[i]`, the context GEMM's `Hc[i]`, `Hci[i]`, `hb[i]` and `T_end[i]`.
+    `_cnf_init` / `_cnf_steps` also take the inference engine's `ws3k` and `split`."""
 
     def _init_kernels(self, device: torch.device) -> None:
         self.lib = _lib.load()
@@ -176,6 +179,22 @@ class _CnfKernels:
                    "pf_scaled_sumsq")
         return float(self.red.item())                       # the one device->host read per norm
 
+    def _cnf_init(self, i, ctl, x, y, f0, ctx, e, t0, t1, n_tot, extra_d0, extra_scale, reverse, rows, R) -> None:
+        """pf_cnf_init: the state rows (x, 0), f0 and torchdiffeq's initial step size, two launches; resets the controller `ctl`."""
+        _lib.check(self.lib.pf_cnf_init(ctl.data_ptr(), x.data_ptr(), int(x.stride(0)), y.data_ptr(), f0.data_ptr(),
+                                        ctx.data_ptr(), e.data_ptr(), self.rec[i].data_ptr(), t0, t1, float(n_tot),
+                                        extra_d0.data_ptr() if extra_d0 is not None else None, float(extra_scale),
+                                        1 if reverse else 0, RTOL, ATOL, rows, R, self.ws3k.data_ptr(), self._stream()),
+                   "pf_cnf_init")
+
+    def _cnf_steps(self, i, ctl, bufs, ctx, e, rows, R, attempts) -> None:
+        """pf_cnf_steps: `attempts` step attempts enqueued back to back on bufs = (y, y1, f0, f1, out) [5, rows, 4]."""
+        y, y1, f0, f1, out = bufs
+        _lib.check(self.lib.pf_cnf_steps(ctl.data_ptr(), y.data_ptr(), y1.data_ptr(), f0.data_ptr(), f1.data_ptr(),
+                                         ctx.data_ptr(), e.data_ptr(), self.rec[i].data_ptr(), out.data_ptr(), RTOL, ATOL,
+                                         rows, R, int(attempts), self.ws1k.data_ptr(), self.split[i], self._stream()),
+                   "pf_cnf_steps")
+
     def context_norm(self, c: Tensor, out: Tensor) -> None:
         """out[0] (device double) = sum (c / (atol + rtol |c|))^2: the context's share of the solver's initial-step norm."""
         _lib.check(self.lib.pf_scaled_sumsq(c.data_ptr(), None, c.data_ptr(), None, None, (ctypes.c_float * 1)(0.0), 0, 0.0,
@@ -196,8 +215,6 @@ class _CnfEngine(_CnfKernels):
             # PF_CNF_SPLIT_GATES (include/puflow_hip.h): only where the factored 2^x cannot overflow; PF_CNF_SPLIT=0 keeps the plain kernel
             self.split.append(int(cnf_split_ok(rec, self.T_end[i]) and os.environ.get("PF_CNF_SPLIT", "1") != "0"))
         self.ws3k = torch.empty(3072, dtype=torch.float64, device=device)
-        self.red = torch.empty(1, dtype=torch.float64, device=device)
-        self.red3 = torch.empty(3, dtype=torch.float64, device=device)
         self.ctl = torch.zeros(16, dtype=torch.float64, device=device)       # dopri5 controller state (csrc/cnf.hip; zero before its first use)
         self.first_batch = int(os.environ.get("PF_CNF_FIRST_BATCH", "8"))    # step attempts enqueued before the first look
         self.next_batch = int(os.environ.get("PF_CNF_NEXT_BATCH", "4"))
@@ -223,41 +240,28 @@ class _CnfEngine(_CnfKernels):
         dev = x.device
         T = self.T_end[i]
         t0, t1 = (0.0, T) if not reverse else (-T, 0.0)
-        sgn = 1.0 if not reverse else -1.0
         n_tot = float(rows * 4 + extra_n)
-
-        def net_t(s: float) -> float:                         # the time the network sees
-            return s if not reverse else -s
-
         if x.dtype != torch.float32 or x.stride(1) != 1 or x.stride(0) not in (3, 4):
             x = x.float().contiguous()[:, :3].contiguous()
         bufs = torch.empty((5, rows, 4), dtype=torch.float32, device=dev)
-        y, y1, f0, f1, out = bufs[0], bufs[1], bufs[2], bufs[3], bufs[4]
+        y, f0, out = bufs[0], bufs[2], bufs[4]
         # the state rows (x, 0), f0 and torchdiffeq's initial step size, on the device in two launches (csrc/cnf.hip:
         # pf_cnf_init); the controller state follows
         ctl = self.ctl if log is None else log
         if not isinstance(extra_d0, torch.Tensor):
             extra_d0 = torch.tensor([float(extra_d0)], dtype=torch.float64, device=dev) if extra_d0 else None
-        _lib.check(self.lib.pf_cnf_init(ctl.data_ptr(), x.data_ptr(), int(x.stride(0)), y.data_ptr(), f0.data_ptr(),
-                                        ctx.data_ptr(), e.data_ptr(), self.rec[i].data_ptr(), t0, t1, n_tot,
-                                        extra_d0.data_ptr() if extra_d0 is not None else None, float(extra_scale),
-                                        1 if reverse else 0, RTOL, ATOL, rows, R, self.ws3k.data_ptr(), self._stream()),
-                   "pf_cnf_init")
+        self._cnf_init(i, ctl, x, y, f0, ctx, e, t0, t1, n_tot, extra_d0, extra_scale, reverse, rows, R)
 
-        # ---- adaptive steps: ONE launch per attempt (six fused stage evaluations) + a one-wave controller kernel; the
-        # accept / reject / next-dt decisions are taken on the device (csrc/cnf.hip: cnf_ctl_update, run by the workgroup of a step attempt that finishes last), the host enqueues a batch
-        # of attempts and reads the controller state once per batch (attempts past the end of the integration are no-ops)
+        # ---- adaptive steps: ONE launch per attempt (six fused stage evaluations); the accept / reject / next-dt decisions are
+        # taken on the device (csrc/cnf.hip: cnf_ctl_update, run by the workgroup of a step attempt that finishes last), the host
+        # enqueues a batch of attempts and reads the controller state once per batch (attempts past the end are no-ops)
         if log is not None:
-            _lib.check(self.lib.pf_cnf_steps(ctl.data_ptr(), y.data_ptr(), y1.data_ptr(), f0.data_ptr(), f1.data_ptr(),
-                                             ctx.data_ptr(), e.data_ptr(), self.rec[i].data_ptr(), out.data_ptr(), RTOL, ATOL,
-                                             rows, R, int(blind), self.ws1k.data_ptr(), self.split[i], self._stream()), "pf_cnf_steps")
+            self._cnf_steps(i, ctl, bufs, ctx, e, rows, R, blind)
             return out
         attempts = 0
         batch = self.first_batch
         while True:
-            _lib.check(self.lib.pf_cnf_steps(ctl.data_ptr(), y.data_ptr(), y1.data_ptr(), f0.data_ptr(), f1.data_ptr(),
-                                             ctx.data_ptr(), e.data_ptr(), self.rec[i].data_ptr(), out.data_ptr(), RTOL, ATOL,
-                                             rows, R, batch, self.ws1k.data_ptr(), self.split[i], self._stream()), "pf_cnf_steps")
+            self._cnf_steps(i, ctl, bufs, ctx, e, rows, R, batch)
             attempts += batch
             st = ctl.cpu()                                      # the one device->host read per batch of attempts
             if st[5] != 0:
@@ -289,17 +293,11 @@ class _CnfEngine(_CnfKernels):
         t0, t1 = (0.0, T) if not reverse else (-T, 0.0)
         x = x.float().contiguous()[:, :3].contiguous()
         bufs = torch.empty((5, rows, 4), dtype=torch.float32, device=x.device)
-        y, y1, f0, f1, out = bufs[0], bufs[1], bufs[2], bufs[3], bufs[4]
         ctl = torch.zeros(16, dtype=torch.float64, device=x.device)
-        _lib.check(self.lib.pf_cnf_init(ctl.data_ptr(), x.data_ptr(), int(x.stride(0)), y.data_ptr(), f0.data_ptr(),
-                                        ctx.data_ptr(), e.data_ptr(), self.rec[i].data_ptr(), t0, t1, float(rows * 4 + extra_n),
-                                        extra_d0.data_ptr() if extra_d0 is not None else None, float(extra_scale),
-                                        1 if reverse else 0, RTOL, ATOL, rows, R, self.ws3k.data_ptr(), self._stream()), "pf_cnf_init")
+        self._cnf_init(i, ctl, x, bufs[0], bufs[2], ctx, e, t0, t1, rows * 4 + extra_n, extra_d0, extra_scale, reverse, rows, R)
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
-        _lib.check(self.lib.pf_cnf_steps(ctl.data_ptr(), y.data_ptr(), y1.data_ptr(), f0.data_ptr(), f1.data_ptr(), ctx.data_ptr(),
-                                         e.data_ptr(), self.rec[i].data_ptr(), out.data_ptr(), RTOL, ATOL, rows, R, int(attempts),
-                                         self.ws1k.data_ptr(), self.split[i], self._stream()), "pf_cnf_steps")
+        self._cnf_steps(i, ctl, bufs, ctx, e, rows, R, attempts)
         b.record()
         torch.cuda.synchronize()
         st = ctl.cpu()

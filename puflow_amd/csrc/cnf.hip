@@ -2,7 +2,7 @@
 // bookkeeping of an adaptive Dormand-Prince solver.  Replaces ODEfunc.forward + ODEnet + ConcatSquashLinear
 // (modules/continuous/odefunc.py:60-148, diffeq_layers.py:72-86) and the arithmetic of torchdiffeq's dopri5
 // stages (called from modules/continuous/cnf.py:97-113).  The step-size CONTROL (a handful of scalars per step)
-// stays on the host: puflow_amd/cnf.py.
+// runs on the device for inference (cnf_ctl_update below) and on the host only under flow_block (puflow_amd/cnf.py).
 //
 // State rows are [y0 y1 y2 logp]; one MFMA column tile = 16 rows.  A ConcatSquash layer is
 //     out = (W x + b) * sigmoid(Wg [t; c] + bg) + Wb [t; c]
@@ -12,21 +12,15 @@
 // plus the Hutchinson term  e^T (d f / d y) e  that the reference obtains with autograd (odefunc.py:9-31):
 // here the vector-Jacobian product is written out (W3^T, tanh', W2^T as a second MFMA image, tanh', W1^T).
 //
-// Weight record of one block (floats; packing.pack_cnf_record), resident in LDS:
-//   [0,4096)      f16x2 image of W2          [4096,8192)  f16x2 image of W2^T
-//   [8192,9216)   f16x2 image of W3 (3 rows replicated into every 4-row q group)
-//   [9216,9472)   [W1 | b1]  [64][4]         [9472,9728)  W3^T [64][4] (3 used, 4th zero)
-//   [9728,9792) b1   [9792,9856) b2   [9856,9872) b3 (replicated)   [9872,10160) time coefficients, ctx layout
-// ctx layout (per point, 288 floats): gate1[64] bias1[64] gate2[64] bias2[64] gate3[16, replicated] bias3[16, replicated]
+// The layouts of the weight record and of the context row: csrc/pf_cnf.h.
 #include <hip/hip_runtime.h>
 #include "pf_api_internal.h"
 #include "pf_mfma.h"
 #include "pf_wave.h"
+#include "pf_cnf.h"
 
 namespace {
 
-constexpr int CNF_REC = 10160;
-constexpr int CNF_CTX = 288;
 #ifndef PF_CNF_SPLIT_FWD
 #define PF_CNF_SPLIT_FWD 1           // 0: A/B builds with the factored gates in the inverse pass only
 #endif
@@ -59,37 +53,24 @@ struct CnfArgs {
     const double* ctl;      // nullable: take h = ctl[CTL_H0] and t = +-(ctl[CTL_T] + h) from the device (initial-step probe)
 };
 
-// sigmoid and tanh on the hardware exp / rcp (1 ulp each): absolute error ~2e-7, against ~25 instructions for tanhf and a
-// full-precision division - the right-hand side is bound by these (32 tanh + 32 sigmoid per lane and evaluation), not by its
-// 54 MFMAs.  tanh(x) = 1 - 2 / (e^{2x} + 1) saturates correctly (e -> inf: 1, e -> 0: -1).
-// The arguments arrive PRESCALED by the host (packing.pack_cnf_block): gates carry -log2e x, the tanh layers' pre-activations
-// 2 log2e x, so each function is v_exp_f32 + add + v_rcp_f32 (+ one fma): one multiply per gate and per tanh saved.
-__device__ __forceinline__ float sigm(float xs) { return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(xs)); }          // xs = -log2e x
-__device__ __forceinline__ float tanh_fast(float xs) { return fmaf(-2.f, __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(xs) + 1.f), 1.f); }   // xs = 2 log2e x
-
-// One evaluation for this lane's row: k = sgn * (f(t, y), -e^T (df/dy) e).  All four q groups of a column return the same f4.
-struct CnfW {
-    const float* rec;          // LDS copy of the record
-    PfW2Lds w2, w2t, w3;
-};
-
 // SPLIT (cnf_step_dev_kernel, context rows in LDS): the gates depend on (point, channel, stage time) only, and
 // 2^(gt (t + alpha h) + gc) = 2^(gt t + gc) x 2^(gt alpha h).  The first factor is computed ONCE per point and tile into the
 // context rows' gate slots (shared by the point's R rows and the step's six evaluations), the second once per launch into a
 // [stage][channel] table `tvg` points at: a gate is fma + v_rcp_f32, without the v_exp_f32 (36 of an evaluation's 135
 // quarter-rate transcendentals, on a kernel the PMC counters show VALU-bound).
 // COMPACT (the forward pass's step kernel, R = 1: 64 points per tile, whose full context rows would not fit in LDS): cx / tvg hold
-// only the 144 gate columns, layer after layer (gate 1 at 0, gate 2 at 64, gate 3 at 128); the bias columns come from cxb (the
+// only the CNF_GATES gate columns, layer after layer (pf_cnf.h: compact gate row); the bias columns come from cxb (the
 // row in global memory, the full 288-column layout).
+// One evaluation for this lane's row: k = sgn * (f(t, y), -e^T (df/dy) e).  All four q groups of a column return the same f4.
 template <bool SPLIT = false, bool COMPACT = false>
 __device__ __forceinline__ f4 cnf_eval(const CnfW& w, int q, f4 y, float t, float sgn, const float* __restrict__ cx,
                                        float e0, float e1, float e2, const float* __restrict__ tvg = nullptr,
                                        const float* __restrict__ cxb = nullptr) {
     const float* rec = w.rec;
-    const float* tv = rec + 9872;
+    const float* tv = rec + CNF_TV;
     if (!SPLIT) tvg = tv;
     if (!COMPACT) cxb = cx;
-    constexpr int G2 = COMPACT ? 64 : 128, G3 = COMPACT ? 128 : 256;
+    constexpr int G1 = COMPACT ? 0 : CNF_CTX_G1, G2 = COMPACT ? CNF_GATE_G2 : CNF_CTX_G2, G3 = COMPACT ? CNF_GATE_G3 : CNF_CTX_G3;
     auto gatef = [](float gt, float tt, float gc) {
         return SPLIT ? __builtin_amdgcn_rcpf(fmaf(gc, gt, 1.f)) : sigm(fmaf(gt, tt, gc));
     };
@@ -102,9 +83,9 @@ __device__ __forceinline__ f4 cnf_eval(const CnfW& w, int q, f4 y, float t, floa
 #pragma unroll
     for (int cb = 0; cb < 4; ++cb) {
         const int ch = cb * 16 + 4 * q;
-        const f4 gc = *reinterpret_cast<const f4*>(cx + ch), bc = *reinterpret_cast<const f4*>(cxb + 64 + ch);
-        const f4 gt = *reinterpret_cast<const f4*>(tvg + ch), bt = *reinterpret_cast<const f4*>(tv + 64 + ch);
-        const f4 lin4 = pf_mfma(rec[9216 + (cb * 16 + col) * 4 + q], yb, pf_splat(0.f));
+        const f4 gc = *reinterpret_cast<const f4*>(cx + G1 + ch), bc = *reinterpret_cast<const f4*>(cxb + CNF_CTX_B1 + ch);
+        const f4 gt = *reinterpret_cast<const f4*>(tvg + G1 + ch), bt = *reinterpret_cast<const f4*>(tv + CNF_CTX_B1 + ch);
+        const f4 lin4 = pf_mfma(rec[CNF_W1B + (cb * 16 + col) * 4 + q], yb, pf_splat(0.f));
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const float lin = lin4[r];
@@ -121,13 +102,13 @@ __device__ __forceinline__ f4 cnf_eval(const CnfW& w, int q, f4 y, float t, floa
         hp[0][1] = pf_pair2(h1[0][2], h1[0][3]);
         f4 a2[1][4];
 #pragma unroll
-        for (int ob = 0; ob < 4; ++ob) a2[0][ob] = pf_bias(rec + 9792, ob, q);
+        for (int ob = 0; ob < 4; ++ob) a2[0][ob] = pf_bias(rec + CNF_B2, ob, q);
         pf_mm2f<4, 2, 2>(w.w2, 0, hp, 0, a2, 0);
 #pragma unroll
         for (int cb = 0; cb < 4; ++cb) {
             const int ch = cb * 16 + 4 * q;
-            const f4 gc = *reinterpret_cast<const f4*>(cx + G2 + ch), bc = *reinterpret_cast<const f4*>(cxb + 192 + ch);
-            const f4 gt = *reinterpret_cast<const f4*>(tvg + G2 + ch), bt = *reinterpret_cast<const f4*>(tv + 192 + ch);
+            const f4 gc = *reinterpret_cast<const f4*>(cx + G2 + ch), bc = *reinterpret_cast<const f4*>(cxb + CNF_CTX_B2 + ch);
+            const f4 gt = *reinterpret_cast<const f4*>(tvg + G2 + ch), bt = *reinterpret_cast<const f4*>(tv + CNF_CTX_B2 + ch);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float gate = gatef(gt[r], t, gc[r]);
@@ -143,10 +124,10 @@ __device__ __forceinline__ f4 cnf_eval(const CnfW& w, int q, f4 y, float t, floa
         hp[0][0] = pf_pair2(h2[0][0], h2[0][1]);
         hp[0][1] = pf_pair2(h2[0][2], h2[0][3]);
         f4 a3[1][1];
-        a3[0][0] = *reinterpret_cast<const f4*>(rec + 9856 + 4 * q);
+        a3[0][0] = *reinterpret_cast<const f4*>(rec + CNF_B3 + 4 * q);
         pf_mm2f<1, 2, 2>(w.w3, 0, hp, 0, a3, 0);
-        const f4 gc = *reinterpret_cast<const f4*>(cx + G3 + 4 * q), bc = *reinterpret_cast<const f4*>(cxb + 272 + 4 * q);
-        const f4 gt = *reinterpret_cast<const f4*>(tvg + G3 + 4 * q), bt = *reinterpret_cast<const f4*>(tv + 272 + 4 * q);
+        const f4 gc = *reinterpret_cast<const f4*>(cx + G3 + 4 * q), bc = *reinterpret_cast<const f4*>(cxb + CNF_CTX_B3 + 4 * q);
+        const f4 gt = *reinterpret_cast<const f4*>(tvg + G3 + 4 * q), bt = *reinterpret_cast<const f4*>(tv + CNF_CTX_B3 + 4 * q);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             g3[r] = gatef(gt[r], t, gc[r]);
@@ -159,7 +140,7 @@ __device__ __forceinline__ f4 cnf_eval(const CnfW& w, int q, f4 y, float t, floa
     f4 w2v[1][4];
 #pragma unroll
     for (int cb = 0; cb < 4; ++cb) {
-        const f4 u4 = pf_mfma(rec[9472 + (cb * 16 + col) * 4 + q], vb, pf_splat(0.f));               // W3[:, ch] (4th column zero)
+        const f4 u4 = pf_mfma(rec[CNF_W3T + (cb * 16 + col) * 4 + q], vb, pf_splat(0.f));               // W3[:, ch] (4th column zero)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const float hh = h2[0][cb][r];
@@ -181,7 +162,7 @@ __device__ __forceinline__ f4 cnf_eval(const CnfW& w, int q, f4 y, float t, floa
             for (int r = 0; r < 4; ++r) {
                 const float hh = h1[0][cb][r];
                 const float w1v = u1[0][cb][r] * (1.f - hh * hh) * g1[cb][r];
-                const f4 wr = *reinterpret_cast<const f4*>(rec + 9216 + (cb * 16 + 4 * q + r) * 4);  // W1[ch, :]
+                const f4 wr = *reinterpret_cast<const f4*>(rec + CNF_W1B + (cb * 16 + 4 * q + r) * 4);  // W1[ch, :]
                 r0 = fmaf(wr.x, w1v, r0); r1 = fmaf(wr.y, w1v, r1); r2 = fmaf(wr.z, w1v, r2);
             }
     }
@@ -190,16 +171,24 @@ __device__ __forceinline__ f4 cnf_eval(const CnfW& w, int q, f4 y, float t, floa
     r0 += __shfl_xor(r0, 16); r1 += __shfl_xor(r1, 16); r2 += __shfl_xor(r2, 16);
     r0 += __shfl_xor(r0, 32); r1 += __shfl_xor(r1, 32); r2 += __shfl_xor(r2, 32);
     // (the W1 rows of the record carry the forward's 2 log2e: taken out of the three sums here)
-    const float div = fmaf(r2, e2, fmaf(r1, e1, r0 * e0)) * 0.34657359027997264f;
+    const float div = fmaf(r2, e2, fmaf(r1, e1, r0 * e0)) * CNF_INV_2LOG2E;
     return (f4){sgn * dy.x, sgn * dy.y, sgn * dy.z, -sgn * div};
 }
 
-__device__ __forceinline__ CnfW cnf_stage_weights(f4* wl, const float* rec_g, int nthreads, int lane) {
-    for (int i = threadIdx.x; i < CNF_REC / 4; i += nthreads) wl[i] = reinterpret_cast<const f4*>(rec_g)[i];
-    __syncthreads();
-    const float* rec = reinterpret_cast<const float*>(wl);
-    return CnfW{rec, PfW2Lds{reinterpret_cast<const u4*>(rec), lane}, PfW2Lds{reinterpret_cast<const u4*>(rec + 4096), lane},
-                PfW2Lds{reinterpret_cast<const u4*>(rec + 8192), lane}};
+// The six stages of one Dormand-Prince attempt from y0 with k[0] = f0 given: fills k[1 .. 6], leaves the step's solution in yi
+// and returns the embedded error estimate.  Net time of stage s: tsign * (t + alpha_s h); stf: [stage][TW] gate factors (SPLIT).
+template <bool SPLIT, bool COMPACT, int TW>
+__device__ __forceinline__ f4 cnf_dopri_stages(const CnfW& w, int q, f4 y0, f4 (&k)[7], f4& yi, float t, float h, float sgn, float tsign,
+                                               const float* cx, float e0, float e1, float e2, const float* stf, const float* cxb) {
+    pf_static_for<0, 6>([&](auto sc) {
+        constexpr int s = decltype(sc)::value;
+        f4 comb = k[0] * CNF_BE[s][0];
+#pragma unroll
+        for (int j = 1; j <= s; ++j) comb += k[j] * CNF_BE[s][j];
+        yi = y0 + comb * h;
+        k[s + 1] = cnf_eval<SPLIT, COMPACT>(w, q, yi, tsign * (t + CNF_AL[s] * h), sgn, cx, e0, e1, e2, stf + s * TW, cxb);
+    });
+    return cnf_comb7(k, CNF_CE) * h;
 }
 
 __global__ __launch_bounds__(CNF_NW * 64) void cnf_rhs_kernel(CnfArgs a) {
@@ -215,10 +204,7 @@ __global__ __launch_bounds__(CNF_NW * 64) void cnf_rhs_kernel(CnfArgs a) {
         t = (float)(a.ctl[CTL_REV] != 0.0 ? -td : td);
     }
     for (int tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
-        const int g = (tile * CNF_NW + wave) * 16 + col;
-        const bool ok = g < a.rows;
-        const int row = ok ? g : a.rows - 1;
-        const int pt = row / a.R;
+        const auto [row, pt, ok] = cnf_tile_row(tile, CNF_NW, wave, col, a.rows, a.R);
         f4 y = *reinterpret_cast<const f4*>(a.y0 + (size_t)row * 4);
         for (int j = 0; j < a.ncoef; ++j) {
             const f4 kj = *reinterpret_cast<const f4*>(a.k + j * kstride + (size_t)row * 4);
@@ -256,52 +242,21 @@ __global__ __launch_bounds__(CNF_NW * 64) void cnf_step_kernel(CnfStepArgs a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int col = lane & 15, q = lane >> 4;
     const CnfW w = cnf_stage_weights(wl, a.rec, CNF_NW * 64, lane);
-    constexpr float AL[6] = {1.f / 5, 3.f / 10, 4.f / 5, 8.f / 9, 1.f, 1.f};
-    constexpr float BE[6][6] = {
-        {1.f / 5, 0, 0, 0, 0, 0},
-        {3.f / 40, 9.f / 40, 0, 0, 0, 0},
-        {44.f / 45, -56.f / 15, 32.f / 9, 0, 0, 0},
-        {19372.f / 6561, -25360.f / 2187, 64448.f / 6561, -212.f / 729, 0, 0},
-        {9017.f / 3168, -355.f / 33, 46732.f / 5247, 49.f / 176, -5103.f / 18656, 0},
-        {35.f / 384, 0, 500.f / 1113, 125.f / 192, -2187.f / 6784, 11.f / 84}};
-    constexpr float CE[7] = {(float)(35. / 384 - 1951. / 21600), 0, (float)(500. / 1113 - 22642. / 50085),
-                             (float)(125. / 192 - 451. / 720), (float)(-2187. / 6784 + 12231. / 42400),
-                             (float)(11. / 84 - 649. / 6300), (float)(-1. / 60)};
-    constexpr float CM[7] = {(float)(6025192743. / 30085553152 / 2), 0, (float)(51252292925. / 65400821598 / 2),
-                             (float)(-2691868925. / 45128329728 / 2), (float)(187940372067. / 1594534317056 / 2),
-                             (float)(-1776094331. / 19743644256 / 2), (float)(11237099. / 235043384 / 2)};
     double acc = 0.0;
     for (int tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
-        const int g = (tile * CNF_NW + wave) * 16 + col;
-        const bool ok = g < a.rows;
-        const int row = ok ? g : a.rows - 1;
-        const int pt = row / a.R;
+        const auto [row, pt, ok] = cnf_tile_row(tile, CNF_NW, wave, col, a.rows, a.R);
         const f4 y0 = *reinterpret_cast<const f4*>(a.y0 + (size_t)row * 4);
         const float* cx = a.ctx + (size_t)pt * CNF_CTX;
         const float e0 = a.e[(size_t)pt * 3 + 0], e1 = a.e[(size_t)pt * 3 + 1], e2 = a.e[(size_t)pt * 3 + 2];
         f4 k[7];
         k[0] = *reinterpret_cast<const f4*>(a.f0 + (size_t)row * 4);
         f4 yi = y0;
-        pf_static_for<0, 6>([&](auto sc) {
-            constexpr int s = decltype(sc)::value;
-            f4 comb = k[0] * BE[s][0];
-#pragma unroll
-            for (int j = 1; j <= s; ++j) comb += k[j] * BE[s][j];
-            yi = y0 + comb * a.h;
-            k[s + 1] = cnf_eval(w, q, yi, a.tsign * (a.t + AL[s] * a.h), a.sgn, cx, e0, e1, e2);
-        });
-        f4 err = k[0] * CE[0];
-#pragma unroll
-        for (int j = 1; j < 7; ++j) err += k[j] * CE[j];
-        err *= a.h;
+        const f4 err = cnf_dopri_stages<false, false, 0>(w, q, y0, k, yi, a.t, a.h, a.sgn, a.tsign, cx, e0, e1, e2, nullptr, cx);
         if (ok && q == 0) {
             *reinterpret_cast<f4*>(a.y1 + (size_t)row * 4) = yi;
             *reinterpret_cast<f4*>(a.f1 + (size_t)row * 4) = k[6];
             if (a.ymid) {
-                f4 m = k[0] * CM[0];
-#pragma unroll
-                for (int j = 1; j < 7; ++j) m += k[j] * CM[j];
-                *reinterpret_cast<f4*>(a.ymid + (size_t)row * 4) = y0 + m * a.h;
+                *reinterpret_cast<f4*>(a.ymid + (size_t)row * 4) = y0 + cnf_comb7(k, CNF_CM) * a.h;
             }
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
@@ -310,9 +265,7 @@ __global__ __launch_bounds__(CNF_NW * 64) void cnf_step_kernel(CnfStepArgs a) {
             }
         }
     }
-    // workgroup sum (fixed order): lanes -> wave -> workgroup (the loop kept: no test launches this host-stepped kernel)
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) acc += __shfl_xor(acc, m);
+    acc = pf_wave_sum(acc);                                          // workgroup sum in a fixed order: lanes -> wave -> workgroup
     if (lane == 0) red[wave] = acc;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -398,14 +351,10 @@ struct CnfDevArgs {
     int rows, R, ntiles;
 };
 
-__device__ __forceinline__ bool cnf_gate_row(int r) { return r < 64 || (r >= 128 && r < 192) || (r >= 256 && r < 272); }
-
 // CTX_LDS (inverse direction, R >= 4 rows per original point): the context rows of the workgroup's 64 / R points are copied
 // to LDS once per tile and all six stage evaluations read them there - each evaluation re-read 1 152 B per row from L2 before
 // SPLIT (the caller's PF_CNF_SPLIT_GATES): see cnf_eval.  Without CTX_LDS (the forward pass, R = 1: 64 points per tile) only the
 // 144 gate columns of a point go to LDS, in the compact layout (cnf_eval<.., COMPACT>); the bias columns stay in global memory.
-constexpr int CNF_GATES = 144;
-__device__ __forceinline__ int cnf_gate_col(int c) { return c < 64 ? c : (c < 128 ? c + 64 : c + 128); }     // compact -> ctx column
 template <bool CTX_LDS, bool SPLIT>
 __global__ __launch_bounds__(CNF_NW * 64, PF_CNF_WPE) void cnf_step_dev_kernel(CnfDevArgs a) {
     constexpr bool COMPACT = SPLIT && !CTX_LDS;
@@ -434,33 +383,16 @@ __global__ __launch_bounds__(CNF_NW * 64, PF_CNF_WPE) void cnf_step_dev_kernel(C
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int col = lane & 15, q = lane >> 4;
     const CnfW w = cnf_stage_weights(wl, a.rec, CNF_NW * 64, lane);
-    constexpr float AL[6] = {1.f / 5, 3.f / 10, 4.f / 5, 8.f / 9, 1.f, 1.f};
-    constexpr float BE[6][6] = {
-        {1.f / 5, 0, 0, 0, 0, 0},
-        {3.f / 40, 9.f / 40, 0, 0, 0, 0},
-        {44.f / 45, -56.f / 15, 32.f / 9, 0, 0, 0},
-        {19372.f / 6561, -25360.f / 2187, 64448.f / 6561, -212.f / 729, 0, 0},
-        {9017.f / 3168, -355.f / 33, 46732.f / 5247, 49.f / 176, -5103.f / 18656, 0},
-        {35.f / 384, 0, 500.f / 1113, 125.f / 192, -2187.f / 6784, 11.f / 84}};
-    constexpr float CE[7] = {(float)(35. / 384 - 1951. / 21600), 0, (float)(500. / 1113 - 22642. / 50085),
-                             (float)(125. / 192 - 451. / 720), (float)(-2187. / 6784 + 12231. / 42400),
-                             (float)(11. / 84 - 649. / 6300), (float)(-1. / 60)};
-    constexpr float CM[7] = {(float)(6025192743. / 30085553152 / 2), 0, (float)(51252292925. / 65400821598 / 2),
-                             (float)(-2691868925. / 45128329728 / 2), (float)(187940372067. / 1594534317056 / 2),
-                             (float)(-1776094331. / 19743644256 / 2), (float)(11237099. / 235043384 / 2)};
     if (SPLIT) {
-        const float* tv = w.rec + 9872;
+        const float* tv = w.rec + CNF_TV;
         for (int i = threadIdx.x; i < 6 * TW; i += CNF_NW * 64) {
             const int s = i / TW, r = COMPACT ? cnf_gate_col(i % TW) : i % TW;
-            stf[i] = cnf_gate_row(r) ? __builtin_amdgcn_exp2f(tv[r] * (tsign * AL[s] * h)) : 0.f;
+            stf[i] = cnf_gate_row(r) ? __builtin_amdgcn_exp2f(tv[r] * (tsign * CNF_AL[s] * h)) : 0.f;
         }                                                             // (visible after the tile loop's barriers)
     }
     double acc = 0.0;
     for (int tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
-        const int g = (tile * CNF_NW + wave) * 16 + col;
-        const bool ok = g < a.rows;
-        const int row = ok ? g : a.rows - 1;
-        const int pt = row / a.R;
+        const auto [row, pt, ok] = cnf_tile_row(tile, CNF_NW, wave, col, a.rows, a.R);
         const f4 y0 = *reinterpret_cast<const f4*>(y0p + (size_t)row * 4);
         const float* cx = a.ctx + (size_t)pt * CNF_CTX;
         const float* cxb = cx;
@@ -478,7 +410,7 @@ __global__ __launch_bounds__(CNF_NW * 64, PF_CNF_WPE) void cnf_step_dev_kernel(C
                 const int pp = i / (CNF_GATES / 4), c4 = (i % (CNF_GATES / 4)) * 4;
                 const int r = cnf_gate_col(c4);
                 const f4 v = *reinterpret_cast<const f4*>(a.ctx + (size_t)(p0 + pp) * CNF_CTX + r);
-                const f4 g4 = *reinterpret_cast<const f4*>(w.rec + 9872 + r);
+                const f4 g4 = *reinterpret_cast<const f4*>(w.rec + CNF_TV + r);
                 f4 o;
 #pragma unroll
                 for (int k = 0; k < 4; ++k) o[k] = __builtin_amdgcn_exp2f(fmaf(g4[k], tt, v[k]));
@@ -497,7 +429,7 @@ __global__ __launch_bounds__(CNF_NW * 64, PF_CNF_WPE) void cnf_step_dev_kernel(C
                 const long long pp = p0 + i / (CNF_CTX / 4);
                 f4 v = reinterpret_cast<const f4*>(a.ctx)[(pp < npts ? pp : npts - 1) * (CNF_CTX / 4) + i % (CNF_CTX / 4)];
                 if (SPLIT && cnf_gate_row(4 * (i % (CNF_CTX / 4)))) {  // the gate rows become 2^(gt tsign t + gc), once per point
-                    const f4 g4 = *reinterpret_cast<const f4*>(w.rec + 9872 + 4 * (i % (CNF_CTX / 4)));
+                    const f4 g4 = *reinterpret_cast<const f4*>(w.rec + CNF_TV + 4 * (i % (CNF_CTX / 4)));
                     const float tt = tsign * t;
 #pragma unroll
                     for (int r = 0; r < 4; ++r) v[r] = __builtin_amdgcn_exp2f(fmaf(g4[r], tt, v[r]));
@@ -512,26 +444,12 @@ __global__ __launch_bounds__(CNF_NW * 64, PF_CNF_WPE) void cnf_step_dev_kernel(C
         f4 k[7];
         k[0] = *reinterpret_cast<const f4*>(f0p + (size_t)row * 4);
         f4 yi = y0;
-        pf_static_for<0, 6>([&](auto sc) {
-            constexpr int s = decltype(sc)::value;
-            f4 comb = k[0] * BE[s][0];
-#pragma unroll
-            for (int j = 1; j <= s; ++j) comb += k[j] * BE[s][j];
-            yi = y0 + comb * h;
-            k[s + 1] = cnf_eval<SPLIT, COMPACT>(w, q, yi, tsign * (t + AL[s] * h), sgn, cx, e0, e1, e2, stf + (SPLIT ? s * TW : 0), cxb);
-        });
-        f4 err = k[0] * CE[0];
-#pragma unroll
-        for (int j = 1; j < 7; ++j) err += k[j] * CE[j];
-        err *= h;
+        const f4 err = cnf_dopri_stages<SPLIT, COMPACT, SPLIT ? TW : 0>(w, q, y0, k, yi, t, h, sgn, tsign, cx, e0, e1, e2, stf, cxb);
         if (ok && q == 0) {
             *reinterpret_cast<f4*>(y1p + (size_t)row * 4) = yi;
             *reinterpret_cast<f4*>(f1p + (size_t)row * 4) = k[6];
             if (cover) {
-                f4 m = k[0] * CM[0];
-#pragma unroll
-                for (int j = 1; j < 7; ++j) m += k[j] * CM[j];
-                const f4 ymid = y0 + m * h;
+                const f4 ymid = y0 + cnf_comb7(k, CNF_CM) * h;
                 // the same term order as the host path's pf_lincomb: ((((w0 y0) + w1 y1) + w2 ymid) + w3 f0) + w4 f1, fused
                 f4 o;
 #pragma unroll
@@ -602,10 +520,7 @@ __global__ __launch_bounds__(CNF_NW * 64) void cnf_init_kernel(CnfInitArgs a) {
     }
     double acc0 = 0.0, acc1 = 0.0;
     for (int tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
-        const int g = (tile * CNF_NW + wave) * 16 + col;
-        const bool ok = g < a.rows;
-        const int row = ok ? g : a.rows - 1;
-        const int pt = row / a.R;
+        const auto [row, pt, ok] = cnf_tile_row(tile, CNF_NW, wave, col, a.rows, a.R);
         f4 y0, f0 = pf_splat(0.f);
         if (PROBE) {
             y0 = *reinterpret_cast<const f4*>(a.y + (size_t)row * 4);
@@ -781,8 +696,7 @@ extern "C" int pf_cnf_rhs(const float* y0, const float* k, const float* coef, in
     a.y0 = y0; a.k = k; a.ncoef = ncoef; a.h = h; a.t = t; a.sgn = sgn; a.ctx = ctx; a.e = e; a.rec = rec;
     a.kout = kout; a.yout = yout; a.rows = rows; a.R = R;
     for (int j = 0; j < ncoef; ++j) a.coef[j] = coef[j];
-    a.ntiles = (rows + CNF_NW * 16 - 1) / (CNF_NW * 16);
-    const int grid = a.ntiles < 1024 ? a.ntiles : 1024;
+    const int grid = cnf_grid(rows, CNF_NW * 16, &a.ntiles);
     hipLaunchKernelGGL(cnf_rhs_kernel, dim3(grid), dim3(CNF_NW * 64), 0, (hipStream_t)stream, a);
     return pf_last_launch_status();
 }
@@ -830,8 +744,7 @@ extern "C" int pf_cnf_step(const float* y0, const float* f0, float t, float h, i
     a.y0 = y0; a.f0 = f0; a.ctx = ctx; a.e = e; a.rec = rec; a.y1 = y1; a.f1 = f1; a.ymid = ymid; a.partial = ws;
     a.t = t; a.h = h; a.sgn = reverse ? -1.f : 1.f; a.tsign = reverse ? -1.f : 1.f; a.rtol = rtol; a.atol = atol;
     a.rows = rows; a.R = R;
-    a.ntiles = (rows + CNF_NW * 16 - 1) / (CNF_NW * 16);
-    const int grid = a.ntiles < 1024 ? a.ntiles : 1024;
+    const int grid = cnf_grid(rows, CNF_NW * 16, &a.ntiles);
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(cnf_step_kernel, dim3(grid), dim3(CNF_NW * 64), 0, s, a);
     hipLaunchKernelGGL(sumsq_final_kernel, dim3(1), dim3(256), 0, s, ws, grid, out);
@@ -852,19 +765,13 @@ extern "C" int pf_cnf_steps(double* ctl, float* ya, float* yb, float* fa, float*
     CnfDevArgs a{};
     a.ctl = ctl; a.yb[0] = ya; a.yb[1] = yb; a.fb[0] = fa; a.fb[1] = fb; a.ctx = ctx; a.e = e; a.rec = rec; a.out = out;
     a.partial = ws; a.rtol = rtol; a.atol = atol; a.rows = rows; a.R = R;
-    a.ntiles = (rows + CNF_NW * 16 - 1) / (CNF_NW * 16);
-    const int grid = a.ntiles < 1024 ? a.ntiles : 1024;
+    const int grid = cnf_grid(rows, CNF_NW * 16, &a.ntiles);
     hipStream_t s = (hipStream_t)stream;
-    for (int i = 0; i < n_attempts; ++i) {
-        // context rows through LDS when a tile's 64 rows belong to <= 16 whole points
-        if (R >= 4 && (CNF_NW * 16) % R == 0) {
-            if (flags & PF_CNF_SPLIT_GATES) hipLaunchKernelGGL((cnf_step_dev_kernel<true, true>), dim3(grid), dim3(CNF_NW * 64), 0, s, a);
-            else hipLaunchKernelGGL((cnf_step_dev_kernel<true, false>), dim3(grid), dim3(CNF_NW * 64), 0, s, a);
-        } else {
-            if ((flags & PF_CNF_SPLIT_GATES) && PF_CNF_SPLIT_FWD) hipLaunchKernelGGL((cnf_step_dev_kernel<false, true>), dim3(grid), dim3(CNF_NW * 64), 0, s, a);
-            else hipLaunchKernelGGL((cnf_step_dev_kernel<false, false>), dim3(grid), dim3(CNF_NW * 64), 0, s, a);
-        }
-    }
+    const bool lds = R >= 4 && (CNF_NW * 16) % R == 0;     // context rows through LDS when a tile's 64 rows belong to <= 16 whole points
+    const bool split = (flags & PF_CNF_SPLIT_GATES) && (lds || PF_CNF_SPLIT_FWD);
+    void (*kern)(CnfDevArgs) = lds ? (split ? cnf_step_dev_kernel<true, true> : cnf_step_dev_kernel<true, false>)
+                                   : (split ? cnf_step_dev_kernel<false, true> : cnf_step_dev_kernel<false, false>);
+    for (int i = 0; i < n_attempts; ++i) hipLaunchKernelGGL(kern, dim3(grid), dim3(CNF_NW * 64), 0, s, a);
     return pf_last_launch_status();
 }
 
@@ -884,8 +791,7 @@ extern "C" int pf_cnf_init(double* ctl, const float* x, int x_stride, float* y, 
     a.ctl = ctl; a.x = x; a.xs = x_stride; a.y = y; a.f0 = f0; a.ctx = ctx; a.e = e; a.rec = rec;
     a.t0 = t0; a.t1 = t1; a.n_tot = n_tot; a.extra_d0 = extra_d0; a.extra_scale = extra_scale; a.reverse = reverse ? 1.0 : 0.0;
     a.sgn = reverse ? -1.f : 1.f; a.rtol = rtol; a.atol = atol; a.rows = rows; a.R = R; a.partial = ws;
-    a.ntiles = (rows + CNF_NW * 16 - 1) / (CNF_NW * 16);
-    const int grid = a.ntiles < 1024 ? a.ntiles : 1024;
+    const int grid = cnf_grid(rows, CNF_NW * 16, &a.ntiles);
     hipLaunchKernelGGL(cnf_init_kernel<false>, dim3(grid), dim3(CNF_NW * 64), 0, s, a);
     hipLaunchKernelGGL(cnf_init_kernel<true>, dim3(grid), dim3(CNF_NW * 64), 0, s, a);
     return pf_last_launch_status();

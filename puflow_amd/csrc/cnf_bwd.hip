@@ -25,31 +25,24 @@
 //
 // Units: the forward record carries folded constants (2 log2e in W1 | b1, W2, b2 and the tanh layers' bias rows, -log2e in
 // the gate rows); everything this file OUTPUTS is in the units of the model's own parameters and pre-activations.
-//   ctxbar [T,288]  += the gradients with respect to the hyper networks' outputs (gate pre-activation, bias), in the ctx
-//                      layout: gate1[64] bias1[64] gate2[64] bias2[64] gate3 bias3; layer 3 uses the FIRST of its four
-//                      replicated slots only (256..258, 272..274), the other twelve + twelve columns are left alone.
-//   grad [4900]     += [0,4096) dW2 [64][64]   [4096,4288) dW1 [64][3]   [4288,4352) db1   [4352,4416) db2
-//                      [4416,4608) dW3 [3][64]  [4608,4611) db3 (4611 unused)
-//                      [4612,4900) gradients of the 288 time coefficients (ctx layout as above): t x this evaluation's
-//                      column sums of the ctxbar contributions.
+//   ctxbar [T,288]  += the gradients with respect to the hyper networks' outputs (gate pre-activation, bias); layer 3 uses the
+//                      FIRST of its four replicated slots only, the other twelve + twelve columns are left alone.
+//   grad [4900]     += the weight gradients, then t x this evaluation's column sums of the ctxbar contributions.
+// The layouts of the record, the context row (ctxbar's too) and the gradient record: csrc/pf_cnf.h.
 #include <hip/hip_runtime.h>
 #include "pf_api_internal.h"
 #include "pf_mfma.h"
 #include "pf_wave.h"
+#include "pf_cnf.h"
 
 namespace {
 
-constexpr int CNF_REC = 10160;            // csrc/cnf.hip's record and context layouts, restated
-constexpr int CNF_CTX = 288;
 constexpr int BW_NW = 4;                  // waves per workgroup
-constexpr int BW_GRAD = 4900;
-constexpr int BW_TV = 4612;               // time-coefficient part of the gradient record
 constexpr int BW_MAX_GRID = 256;          // one workgroup per CU (LDS-bound); also the number of partial slabs
 // Row strides of the staged matrices (floats).  bw_atb reads row 4 kk + q, column c0 + col per lane: with strides of 16 mod 64 the
 // four q groups of a wave sit 16 banks apart and the 64 lanes of a read hit the 64 LDS banks once each.
 constexpr int BW_ST = 80;                 // a staged 64-column stream
 constexpr int BW_SS = 16;                 // the two 16-column side matrices
-constexpr float BW_IC2 = 0.34657359027997264f;     // 1 / (2 log2e): takes the forward's fold out of W1, W2, b2 products
 
 struct BwArgs {
     const float* y;         // [rows,4]
@@ -59,14 +52,10 @@ struct BwArgs {
     const float* rec;       // CNF_REC floats
     float* ybar;            // [rows,4]
     float* ctxbar;          // [T,288]
-    float* slabs;           // [gridDim.x][BW_GRAD]
+    float* slabs;           // [gridDim.x][CNF_GRAD]
     float t, sgn;
     int rows, R, rpt, ntiles;        // rpt: rows of a wave tile = (16 / R) R
 };
-
-// the hardware-exp sigmoid / tanh of cnf.hip (arguments prescaled by the host: -log2e x, 2 log2e x)
-__device__ __forceinline__ float bw_sigm(float xs) { return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(xs)); }
-__device__ __forceinline__ float bw_tanh(float xs) { return fmaf(-2.f, __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(xs) + 1.f), 1.f); }
 
 // acc += A^T B over the workgroup's 64 staged rows: A [64][sa] columns a0 .. a0 + 15 -> D rows, B [64][sb] columns
 // b0 .. b0 + 15 -> D columns.  Lane (col, q): acc[r] = D[4 q + r][col].
@@ -118,12 +107,13 @@ __global__ __launch_bounds__(BW_NW * 64) void cnf_rhs_vjp_kernel(BwArgs a) {
     __shared__ f4 side4[2 * 64 * BW_SS / 4];         // Bs = [y 1 | e 0 | 0 ..] and P3 = [gl3 | gld3 | gate_pre3 | bias_pre3]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int col = lane & 15, q = lane >> 4;
+    // (cnf_stage_weights written out: through the function the views' LDS addresses fold differently and the kernel's stream moves)
     for (int i = threadIdx.x; i < CNF_REC / 4; i += BW_NW * 64) wl[i] = reinterpret_cast<const f4*>(a.rec)[i];
     __syncthreads();
     const float* rec = reinterpret_cast<const float*>(wl);
-    const PfW2Lds w2{reinterpret_cast<const u4*>(rec), lane}, w2t{reinterpret_cast<const u4*>(rec + 4096), lane},
-                  w3{reinterpret_cast<const u4*>(rec + 8192), lane};
-    const float* tv = rec + 9872;
+    const PfW2Lds w2{reinterpret_cast<const u4*>(rec + CNF_W2), lane}, w2t{reinterpret_cast<const u4*>(rec + CNF_W2T), lane},
+                  w3{reinterpret_cast<const u4*>(rec + CNF_W3), lane};
+    const float* tv = rec + CNF_TV;
     float* stg = reinterpret_cast<float*>(stg4);
     float* S0 = stg; float* S1 = stg + 64 * BW_ST; float* S2 = stg + 2 * 64 * BW_ST; float* S3 = stg + 3 * 64 * BW_ST;
     float* Bs = reinterpret_cast<float*>(side4);
@@ -157,17 +147,17 @@ __global__ __launch_bounds__(BW_NW * 64) void cnf_rhs_vjp_kernel(BwArgs a) {
 #pragma unroll
         for (int cb = 0; cb < 4; ++cb) {
             const int ch = cb * 16 + 4 * q;
-            const f4 gc = *reinterpret_cast<const f4*>(cx + ch), bc = *reinterpret_cast<const f4*>(cx + 64 + ch);
-            const f4 gt = *reinterpret_cast<const f4*>(tv + ch), bt = *reinterpret_cast<const f4*>(tv + 64 + ch);
-            const float wa = rec[9216 + (cb * 16 + col) * 4 + q];
+            const f4 gc = *reinterpret_cast<const f4*>(cx + CNF_CTX_G1 + ch), bc = *reinterpret_cast<const f4*>(cx + CNF_CTX_B1 + ch);
+            const f4 gt = *reinterpret_cast<const f4*>(tv + CNF_CTX_G1 + ch), bt = *reinterpret_cast<const f4*>(tv + CNF_CTX_B1 + ch);
+            const float wa = rec[CNF_W1B + (cb * 16 + col) * 4 + q];
             const f4 lin = pf_mfma(wa, yb, pf_splat(0.f)), lind = pf_mfma(wa, eb, pf_splat(0.f));
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float gate = bw_sigm(fmaf(gt[r], t, gc[r]));
-                const float h = bw_tanh(fmaf(lin[r], gate, fmaf(bt[r], t, bc[r])));
+                const float gate = sigm(fmaf(gt[r], t, gc[r]));
+                const float h = tanh_fast(fmaf(lin[r], gate, fmaf(bt[r], t, bc[r])));
                 g1[cb][r] = gate;
                 h1[cb][r] = h;
-                h1d[cb][r] = (1.f - h * h) * (lind[r] * BW_IC2) * gate;
+                h1d[cb][r] = (1.f - h * h) * (lind[r] * CNF_INV_2LOG2E) * gate;
             }
         }
         // ---- layer 2 (64 -> 64)
@@ -178,22 +168,22 @@ __global__ __launch_bounds__(BW_NW * 64) void cnf_rhs_vjp_kernel(BwArgs a) {
             hpd[0][0] = pf_pair2(h1d[0], h1d[1]); hpd[0][1] = pf_pair2(h1d[2], h1d[3]);
             f4 a2[1][4], a2d[1][4];
 #pragma unroll
-            for (int ob = 0; ob < 4; ++ob) { a2[0][ob] = pf_bias(rec + 9792, ob, q); a2d[0][ob] = pf_splat(0.f); }
+            for (int ob = 0; ob < 4; ++ob) { a2[0][ob] = pf_bias(rec + CNF_B2, ob, q); a2d[0][ob] = pf_splat(0.f); }
             pf_mm2f<4, 2, 2>(w2, 0, hp, 0, a2, 0);
             pf_mm2f<4, 2, 2>(w2, 0, hpd, 0, a2d, 0);
 #pragma unroll
             for (int cb = 0; cb < 4; ++cb) {
                 const int ch = cb * 16 + 4 * q;
-                const f4 gc = *reinterpret_cast<const f4*>(cx + 128 + ch), bc = *reinterpret_cast<const f4*>(cx + 192 + ch);
-                const f4 gt = *reinterpret_cast<const f4*>(tv + 128 + ch), bt = *reinterpret_cast<const f4*>(tv + 192 + ch);
+                const f4 gc = *reinterpret_cast<const f4*>(cx + CNF_CTX_G2 + ch), bc = *reinterpret_cast<const f4*>(cx + CNF_CTX_B2 + ch);
+                const f4 gt = *reinterpret_cast<const f4*>(tv + CNF_CTX_G2 + ch), bt = *reinterpret_cast<const f4*>(tv + CNF_CTX_B2 + ch);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const float gate = bw_sigm(fmaf(gt[r], t, gc[r]));
-                    const float h = bw_tanh(fmaf(a2[0][cb][r], gate, fmaf(bt[r], t, bc[r])));
+                    const float gate = sigm(fmaf(gt[r], t, gc[r]));
+                    const float h = tanh_fast(fmaf(a2[0][cb][r], gate, fmaf(bt[r], t, bc[r])));
                     g2[cb][r] = gate;
                     h2[cb][r] = h;
-                    lin2[cb][r] = a2[0][cb][r] * BW_IC2;
-                    lind2[cb][r] = a2d[0][cb][r] * BW_IC2;
+                    lin2[cb][r] = a2[0][cb][r] * CNF_INV_2LOG2E;
+                    lind2[cb][r] = a2d[0][cb][r] * CNF_INV_2LOG2E;
                     h2d[cb][r] = (1.f - h * h) * lind2[cb][r] * gate;
                 }
             }
@@ -205,14 +195,14 @@ __global__ __launch_bounds__(BW_NW * 64) void cnf_rhs_vjp_kernel(BwArgs a) {
             hp[0][0] = pf_pair2(h2[0], h2[1]); hp[0][1] = pf_pair2(h2[2], h2[3]);
             hpd[0][0] = pf_pair2(h2d[0], h2d[1]); hpd[0][1] = pf_pair2(h2d[2], h2d[3]);
             f4 a3[1][1], a3d[1][1];
-            a3[0][0] = *reinterpret_cast<const f4*>(rec + 9856 + 4 * q);
+            a3[0][0] = *reinterpret_cast<const f4*>(rec + CNF_B3 + 4 * q);
             a3d[0][0] = pf_splat(0.f);
             pf_mm2f<1, 2, 2>(w3, 0, hp, 0, a3, 0);
             pf_mm2f<1, 2, 2>(w3, 0, hpd, 0, a3d, 0);
             lin3 = a3[0][0]; lind3 = a3d[0][0];
-            const f4 gc = *reinterpret_cast<const f4*>(cx + 256 + 4 * q), gt = *reinterpret_cast<const f4*>(tv + 256 + 4 * q);
+            const f4 gc = *reinterpret_cast<const f4*>(cx + CNF_CTX_G3 + 4 * q), gt = *reinterpret_cast<const f4*>(tv + CNF_CTX_G3 + 4 * q);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) g3[r] = bw_sigm(fmaf(gt[r], t, gc[r]));
+            for (int r = 0; r < 4; ++r) g3[r] = sigm(fmaf(gt[r], t, gc[r]));
         }
 
         // ---- reverse, layer 3: seeds fbar = sgn kbar[:3], fdotbar = -sgn kbar[3] e
@@ -227,7 +217,7 @@ __global__ __launch_bounds__(BW_NW * 64) void cnf_rhs_vjp_kernel(BwArgs a) {
             const float vdb = q == 0 ? gld3.x : (q == 1 ? gld3.y : (q == 2 ? gld3.z : 0.f));
 #pragma unroll
             for (int cb = 0; cb < 4; ++cb) {
-                const float wa = rec[9472 + (cb * 16 + col) * 4 + q];                 // W3[:, ch] (4th column zero)
+                const float wa = rec[CNF_W3T + (cb * 16 + col) * 4 + q];                 // W3[:, ch] (4th column zero)
                 xb[cb] = pf_mfma(wa, vb, pf_splat(0.f));
                 xdb[cb] = pf_mfma(wa, vdb, pf_splat(0.f));
             }
@@ -270,15 +260,15 @@ __global__ __launch_bounds__(BW_NW * 64) void cnf_rhs_vjp_kernel(BwArgs a) {
             for (int cb = 0; cb < 4; ++cb) {
                 const f4 sg = bw_point_sum(gp2[cb], pos, a.R), sb = bw_point_sum(bp2[cb], pos, a.R);
                 if (ok && pos == 0) {
-                    f4* pg = reinterpret_cast<f4*>(cb_ + 128 + cb * 16 + 4 * q);
-                    f4* pbias = reinterpret_cast<f4*>(cb_ + 192 + cb * 16 + 4 * q);
+                    f4* pg = reinterpret_cast<f4*>(cb_ + CNF_CTX_G2 + cb * 16 + 4 * q);
+                    f4* pbias = reinterpret_cast<f4*>(cb_ + CNF_CTX_B2 + cb * 16 + 4 * q);
                     *pg += sg; *pbias += sb;
                 }
             }
             const f4 sg3 = bw_point_sum(gp3, pos, a.R), sb3 = bw_point_sum(pb3, pos, a.R);
             if (ok && pos == 0 && q == 0) {
-                cb_[256] += sg3.x; cb_[257] += sg3.y; cb_[258] += sg3.z;
-                cb_[272] += sb3.x; cb_[273] += sb3.y; cb_[274] += sb3.z;
+                cb_[CNF_CTX_G3] += sg3.x; cb_[CNF_CTX_G3 + 1] += sg3.y; cb_[CNF_CTX_G3 + 2] += sg3.z;
+                cb_[CNF_CTX_B3] += sb3.x; cb_[CNF_CTX_B3 + 1] += sb3.y; cb_[CNF_CTX_B3 + 2] += sb3.z;
             }
         }
 
@@ -318,8 +308,8 @@ __global__ __launch_bounds__(BW_NW * 64) void cnf_rhs_vjp_kernel(BwArgs a) {
         float r0 = 0.f, r1 = 0.f, r2 = 0.f;
 #pragma unroll
         for (int cb = 0; cb < 4; ++cb) {
-            const float wa = rec[9216 + (cb * 16 + col) * 4 + q];
-            const f4 lin = pf_mfma(wa, yb, pf_splat(0.f)) * BW_IC2, lind = pf_mfma(wa, eb, pf_splat(0.f)) * BW_IC2;
+            const float wa = rec[CNF_W1B + (cb * 16 + col) * 4 + q];
+            const f4 lin = pf_mfma(wa, yb, pf_splat(0.f)) * CNF_INV_2LOG2E, lind = pf_mfma(wa, eb, pf_splat(0.f)) * CNF_INV_2LOG2E;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float h = h1[cb][r], om = 1.f - h * h, gate = g1[cb][r];
@@ -329,13 +319,13 @@ __global__ __launch_bounds__(BW_NW * 64) void cnf_rhs_vjp_kernel(BwArgs a) {
                 gl1[cb][r] = pb * gate;
                 gld1[cb][r] = pdb * gate;
                 gp1[cb][r] = (pb * lin[r] + pdb * lind[r]) * gate * (1.f - gate);
-                const f4 wr = *reinterpret_cast<const f4*>(rec + 9216 + (cb * 16 + 4 * q + r) * 4);      // 2 log2e W1[ch, :]
+                const f4 wr = *reinterpret_cast<const f4*>(rec + CNF_W1B + (cb * 16 + 4 * q + r) * 4);      // 2 log2e W1[ch, :]
                 r0 = fmaf(wr.x, gl1[cb][r], r0); r1 = fmaf(wr.y, gl1[cb][r], r1); r2 = fmaf(wr.z, gl1[cb][r], r2);
             }
         }
         r0 += __shfl_xor(r0, 16); r1 += __shfl_xor(r1, 16); r2 += __shfl_xor(r2, 16);
         r0 += __shfl_xor(r0, 32); r1 += __shfl_xor(r1, 32); r2 += __shfl_xor(r2, 32);
-        if (ok && q == 0) *reinterpret_cast<f4*>(a.ybar + (size_t)row * 4) = (f4){r0 * BW_IC2, r1 * BW_IC2, r2 * BW_IC2, 0.f};
+        if (ok && q == 0) *reinterpret_cast<f4*>(a.ybar + (size_t)row * 4) = (f4){r0 * CNF_INV_2LOG2E, r1 * CNF_INV_2LOG2E, r2 * CNF_INV_2LOG2E, 0.f};
 
         // ---- weights, third part: dW1 | db1 and the layer-1 context sums.  S0 = gl1, S1 = gld1, S2 = gate_pre1, S3 = bias_pre1
         __syncthreads();
@@ -351,8 +341,8 @@ __global__ __launch_bounds__(BW_NW * 64) void cnf_rhs_vjp_kernel(BwArgs a) {
             for (int cb = 0; cb < 4; ++cb) {
                 const f4 sg = bw_point_sum(gp1[cb], pos, a.R), sb = bw_point_sum(bp1[cb], pos, a.R);
                 if (ok && pos == 0) {
-                    f4* pg = reinterpret_cast<f4*>(cb_ + cb * 16 + 4 * q);
-                    f4* pbias = reinterpret_cast<f4*>(cb_ + 64 + cb * 16 + 4 * q);
+                    f4* pg = reinterpret_cast<f4*>(cb_ + CNF_CTX_G1 + cb * 16 + 4 * q);
+                    f4* pbias = reinterpret_cast<f4*>(cb_ + CNF_CTX_B1 + cb * 16 + 4 * q);
                     *pg += sg; *pbias += sb;
                 }
             }
@@ -360,34 +350,34 @@ __global__ __launch_bounds__(BW_NW * 64) void cnf_rhs_vjp_kernel(BwArgs a) {
     }
 
     // ---- this workgroup's slab, in the gradient record's layout.  Lane (col, q) holds D[4 q + r][col] of its wave's blocks.
-    float* sl = a.slabs + (size_t)blockIdx.x * BW_GRAD;
+    float* sl = a.slabs + (size_t)blockIdx.x * CNF_GRAD;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int o = 16 * wave + 4 * q + r;                         // output channel of the layer-1 / layer-2 blocks
 #pragma unroll
-        for (int nb = 0; nb < 4; ++nb) sl[o * 64 + 16 * nb + col] = aW2[nb][r];
+        for (int nb = 0; nb < 4; ++nb) sl[CNF_GRAD_W2 + o * 64 + 16 * nb + col] = aW2[nb][r];
         // dW1[o][j] = (gl1^T y)[o][j] + (gld1^T e)[o][j]: columns j and 4 + j of the two products against Bs; column 3 of a
         // product against Bs is the plain column sum
         const float we = __shfl_down(aW1b[r], 4, 16);
-        if (col < 3) sl[4096 + o * 3 + col] = aW1a[r] + we;
+        if (col < 3) sl[CNF_GRAD_W1 + o * 3 + col] = aW1a[r] + we;
         if (col == 3) {
-            sl[4288 + o] = aW1a[r];
-            sl[4352 + o] = aB2[r];
-            sl[BW_TV + o] = aG1[r]; sl[BW_TV + 64 + o] = aH1[r];
-            sl[BW_TV + 128 + o] = aG2[r]; sl[BW_TV + 192 + o] = aH2[r];
+            sl[CNF_GRAD_B1 + o] = aW1a[r];
+            sl[CNF_GRAD_B2 + o] = aB2[r];
+            sl[CNF_GRAD_TV + CNF_CTX_G1 + o] = aG1[r]; sl[CNF_GRAD_TV + CNF_CTX_B1 + o] = aH1[r];
+            sl[CNF_GRAD_TV + CNF_CTX_G2 + o] = aG2[r]; sl[CNF_GRAD_TV + CNF_CTX_B2 + o] = aH2[r];
         }
         // dW3[j][i] = (gl3^T h2)[j][i] + (gld3^T h2d)[j][i]: D rows j (q = 0) and 4 + j (q = 1) of the two products
         const float w3d = __shfl(aW3b[r], lane + 16);
-        if (q == 0 && r < 3) sl[4416 + r * 64 + 16 * wave + col] = aW3a[r] + w3d;
+        if (q == 0 && r < 3) sl[CNF_GRAD_W3 + r * 64 + 16 * wave + col] = aW3a[r] + w3d;
         if (wave == 0 && col == 3 && r < 3) {
-            if (q == 0) sl[4608 + r] = aS3[r];
-            if (q == 2) sl[BW_TV + 256 + r] = aS3[r];
-            if (q == 3) sl[BW_TV + 272 + r] = aS3[r];
+            if (q == 0) sl[CNF_GRAD_B3 + r] = aS3[r];
+            if (q == 2) sl[CNF_GRAD_TV + CNF_CTX_G3 + r] = aS3[r];
+            if (q == 3) sl[CNF_GRAD_TV + CNF_CTX_B3 + r] = aS3[r];
         }
     }
-    if (threadIdx.x < 27) {                  // the words nothing above writes: 4611 and the replicated layer-3 slots (13 + 13)
-        const int i = threadIdx.x;
-        sl[i == 0 ? 4611 : (i < 14 ? BW_TV + 258 + i : BW_TV + 261 + i)] = 0.f;
+    if (threadIdx.x < 27) {                  // the words nothing above writes: the unused one and the replicated layer-3 slots (13 + 13)
+        const int i = threadIdx.x;                 // 1 .. 13 -> gate3 columns 3 .. 15, 14 .. 26 -> bias3 columns 3 .. 15
+        sl[i == 0 ? CNF_GRAD_UNUSED : (i < 14 ? CNF_GRAD_TV + CNF_CTX_G3 + 2 + i : CNF_GRAD_TV + CNF_CTX_B3 - 11 + i)] = 0.f;
     }
 }
 
@@ -399,15 +389,15 @@ __global__ __launch_bounds__(256) void cnf_rhs_vjp_reduce_kernel(const float* __
     const int o = threadIdx.x & 31, g = threadIdx.x >> 5;
     const int i = blockIdx.x * 32 + o;
     float s = 0.f;
-    if (i < BW_GRAD)
-        for (int j = g; j < n; j += 8) s += slabs[(size_t)j * BW_GRAD + i];
+    if (i < CNF_GRAD)
+        for (int j = g; j < n; j += 8) s += slabs[(size_t)j * CNF_GRAD + i];
     part[g][o] = s;
     __syncthreads();
-    if (g == 0 && i < BW_GRAD) {
+    if (g == 0 && i < CNF_GRAD) {
         float tot = part[0][o];
 #pragma unroll
         for (int k = 1; k < 8; ++k) tot += part[k][o];
-        grad[i] += i >= BW_TV ? t * tot : tot;
+        grad[i] += i >= CNF_GRAD_TV ? t * tot : tot;
     }
 }
 
@@ -423,7 +413,7 @@ inline int bw_grid(int rows, int R, int* rpt, int* ntiles) {
 extern "C" long long pf_cnf_rhs_vjp_workspace_bytes(int rows, int R) {
     if (rows <= 0 || R <= 0 || R > 16 || rows % R != 0) return PF_ERR_SHAPE;
     int rpt, ntiles;
-    return (long long)bw_grid(rows, R, &rpt, &ntiles) * BW_GRAD * (long long)sizeof(float);
+    return (long long)bw_grid(rows, R, &rpt, &ntiles) * CNF_GRAD * (long long)sizeof(float);
 }
 
 extern "C" int pf_cnf_rhs_vjp(const float* y, const float* kbar, float t, float sgn, const float* ctx, const float* e,
@@ -437,6 +427,6 @@ extern "C" int pf_cnf_rhs_vjp(const float* y, const float* kbar, float t, float 
     const int grid = bw_grid(rows, R, &a.rpt, &a.ntiles);
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(cnf_rhs_vjp_kernel, dim3(grid), dim3(BW_NW * 64), 0, s, a);
-    hipLaunchKernelGGL(cnf_rhs_vjp_reduce_kernel, dim3((BW_GRAD + 31) / 32), dim3(256), 0, s, (const float*)ws, grid, t, grad);
+    hipLaunchKernelGGL(cnf_rhs_vjp_reduce_kernel, dim3((CNF_GRAD + 31) / 32), dim3(256), 0, s, (const float*)ws, grid, t, grad);
     return pf_last_launch_status();
 }

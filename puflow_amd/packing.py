@@ -577,8 +577,16 @@ def pack_plan(plan: Dict[str, object], ec_mode: str = "f16n") -> Dict[str, objec
 # ---------------------------------------------------------------------------------------
 # Continuous (CNF) blocks: weight record of csrc/cnf.hip and the per-point context GEMM
 # ---------------------------------------------------------------------------------------
-CNF_REC = 10160
-CNF_CTX = 288
+# The layouts (offsets in floats) are csrc/pf_cnf.h's, name by name, and described there (tests/test_cnf_layout.py holds the two
+# files together): weight record, context row, gradient record of pf_cnf_rhs_vjp (time coefficients from CNF_GRAD_TV on)
+CNF_W2, CNF_W2T, CNF_W3, CNF_W1B, CNF_W3T, CNF_B1, CNF_B2, CNF_B3, CNF_TV, CNF_REC = 0, 4096, 8192, 9216, 9472, 9728, 9792, 9856, 9872, 10160
+CNF_CTX_G1, CNF_CTX_B1, CNF_CTX_G2, CNF_CTX_B2, CNF_CTX_G3, CNF_CTX_B3, CNF_CTX = 0, 64, 128, 192, 256, 272, 288
+CNF_GRAD_W2, CNF_GRAD_W1, CNF_GRAD_B1, CNF_GRAD_B2, CNF_GRAD_W3, CNF_GRAD_B3, CNF_GRAD_UNUSED, CNF_GRAD_TV, CNF_GRAD = \
+    0, 4096, 4288, 4352, 4416, 4608, 4611, 4612, 4900
+# (first ctx column, rows) of the hyper networks' outputs: gate and bias of the three layers; layer 3 = the first of its four slots
+CNF_CTX_SLOTS = ((CNF_CTX_G1, 64), (CNF_CTX_B1, 64), (CNF_CTX_G2, 64), (CNF_CTX_B2, 64), (CNF_CTX_G3, 3), (CNF_CTX_B3, 3))
+_CNF_GATES = ((CNF_CTX_G1, CNF_CTX_B1), (CNF_CTX_G2, CNF_CTX_B2), (CNF_CTX_G3, CNF_CTX_B3))     # [first, end) of the gate columns
+_CNF_TANH_BIAS = ((CNF_CTX_B1, CNF_CTX_G2), (CNF_CTX_B2, CNF_CTX_G3))                           # bias columns of the two tanh layers
 
 
 def _np32(t) -> np.ndarray:
@@ -596,15 +604,9 @@ def pack_cnf_context(Hc: np.ndarray):
 def cnf_split_ok(rec, T_end: float) -> bool:
     """May pf_cnf_steps take PF_CNF_SPLIT_GATES for this record?  The gate rows of its time vector already carry -log2e; the
     per-stage factor 2^(gt alpha h) has |h| <= T_end, and 2^100 x (any fp32 2^x) neither overflows to NaN nor loses a gate bit."""
-    tv = np.asarray(rec[9872:9872 + CNF_CTX], np.float64)
-    g = np.concatenate([tv[0:64], tv[128:192], tv[256:272]])
+    tv = np.asarray(rec[CNF_TV:CNF_REC], np.float64)
+    g = np.concatenate([tv[lo:hi] for lo, hi in _CNF_GATES])
     return bool(np.abs(g).max() * abs(T_end) <= 100.0)
-
-
-CNF_GRAD = 4900                  # gradient record of pf_cnf_rhs_vjp (include/puflow_hip.h), time-coefficient part from CNF_GRAD_TV on
-CNF_GRAD_TV = 4612
-# (first ctx column, rows) of the hyper networks' outputs: gate and bias of the three layers; layer 3 = the first of its four slots
-CNF_CTX_SLOTS = ((0, 64), (64, 64), (128, 64), (192, 64), (256, 3), (272, 3))
 
 
 def cnf_hyper_matrix(sd, i: int) -> np.ndarray:
@@ -615,7 +617,7 @@ def cnf_hyper_matrix(sd, i: int) -> np.ndarray:
     first = _np32(sd[f"{p}.0._hyper_gate.weight"])
     H = np.zeros((CNF_CTX, first.shape[1]), np.float32)
     for l in range(3):
-        for kind, base in (("_hyper_gate", 128 * l), ("_hyper_bias", 128 * l + (64 if l < 2 else 16))):
+        for kind, (base, _) in (("_hyper_gate", CNF_CTX_SLOTS[2 * l]), ("_hyper_bias", CNF_CTX_SLOTS[2 * l + 1])):
             W = _np32(sd[f"{p}.{l}.{kind}.weight"])
             for r0 in ([base] if l < 2 else [base + 4 * qq for qq in range(4)]):
                 H[r0:r0 + W.shape[0]] = W
@@ -626,13 +628,13 @@ def unpack_cnf_grads(i: int, grad, dH, dhb):
     """The outputs of a block's backward -> tensors keyed and shaped like the state dict.
     grad [4900]: pf_cnf_rhs_vjp's gradient record (already in the parameters' units: the kernel takes the forward image's
     2 log2e / -log2e out itself), dH [288, cdim]: ctxbar^T c, dhb [288]: the column sums of ctxbar.  The time coefficients'
-    gradients (grad[4612:]) are column 0 of the hyper weights, as in the reference's cat([t, c])."""
+    gradients (grad[CNF_GRAD_TV:]) are column 0 of the hyper weights, as in the reference's cat([t, c])."""
     import torch
     p = f"flow_blocks.{i}.cnf.odefunc.diffeq.layers"
     out = {
-        f"{p}.1._layer.weight": grad[0:4096].reshape(64, 64), f"{p}.0._layer.weight": grad[4096:4288].reshape(64, 3),
-        f"{p}.0._layer.bias": grad[4288:4352], f"{p}.1._layer.bias": grad[4352:4416],
-        f"{p}.2._layer.weight": grad[4416:4608].reshape(3, 64), f"{p}.2._layer.bias": grad[4608:4611],
+        f"{p}.1._layer.weight": grad[CNF_GRAD_W2:CNF_GRAD_W1].reshape(64, 64), f"{p}.0._layer.weight": grad[CNF_GRAD_W1:CNF_GRAD_B1].reshape(64, 3),
+        f"{p}.0._layer.bias": grad[CNF_GRAD_B1:CNF_GRAD_B2], f"{p}.1._layer.bias": grad[CNF_GRAD_B2:CNF_GRAD_W3],
+        f"{p}.2._layer.weight": grad[CNF_GRAD_W3:CNF_GRAD_B3].reshape(3, 64), f"{p}.2._layer.bias": grad[CNF_GRAD_B3:CNF_GRAD_UNUSED],
     }
     tv = grad[CNF_GRAD_TV:CNF_GRAD]
     for l in range(3):
@@ -665,36 +667,33 @@ def pack_cnf_block(sd, i: int):
             if bg is not None:
                 hb[r0:r0 + rows] = bg
 
-    put(0, L[0]["_hyper_gate.weight"], L[0]["_hyper_gate.bias"], False)
-    put(64, L[0]["_hyper_bias.weight"], None, False)
-    put(128, L[1]["_hyper_gate.weight"], L[1]["_hyper_gate.bias"], False)
-    put(192, L[1]["_hyper_bias.weight"], None, False)
-    put(256, L[2]["_hyper_gate.weight"], L[2]["_hyper_gate.bias"], True)
-    put(272, L[2]["_hyper_bias.weight"], None, True)
+    for l in range(3):                                       # layer 3's three rows go into every 4-row slot
+        put(CNF_CTX_SLOTS[2 * l][0], L[l]["_hyper_gate.weight"], L[l]["_hyper_gate.bias"], l == 2)
+        put(CNF_CTX_SLOTS[2 * l + 1][0], L[l]["_hyper_bias.weight"], None, l == 2)
     # The kernel's sigmoid / tanh run on the hardware 2^x: sigmoid(a) = 1 / (1 + 2^(-log2e a)), tanh(a) = 1 - 2 / (2^(2 log2e a) + 1).
     # The constants are folded HERE (one multiply per gate and per tanh less on a VALU-bound kernel): gate rows carry
     # -log2e x their argument, the pre-activations of the two tanh layers (weights, biases, time / context bias rows) 2 log2e x.
-    for lo, hi, f in ((0, 64, -LOG2E), (128, 192, -LOG2E), (256, 272, -LOG2E), (64, 128, 2 * LOG2E), (192, 256, 2 * LOG2E)):
+    for lo, hi, f in [(lo, hi, -LOG2E) for lo, hi in _CNF_GATES] + [(lo, hi, 2 * LOG2E) for lo, hi in _CNF_TANH_BIAS]:
         Hc[lo:hi] *= np.float32(f); hb[lo:hi] *= np.float32(f); tv[lo:hi] *= np.float32(f)
 
     rec = np.zeros(CNF_REC, np.float32)
     W1, W2, W3 = L[0]["_layer.weight"], L[1]["_layer.weight"], L[2]["_layer.weight"]
-    rec[0:4096] = frag_pack_f16x2((W2.astype(np.float64) * (2 * LOG2E)).astype(np.float32))     # forward image: 2 log2e folded in
-    rec[4096:8192] = frag_pack_f16x2(np.ascontiguousarray(W2.T))                                 # transposed image (VJP): plain
+    rec[CNF_W2:CNF_W2T] = frag_pack_f16x2((W2.astype(np.float64) * (2 * LOG2E)).astype(np.float32))     # forward image: 2 log2e folded in
+    rec[CNF_W2T:CNF_W3] = frag_pack_f16x2(np.ascontiguousarray(W2.T))                             # transposed image (VJP): plain
     W3r = np.zeros((16, 64), np.float32)
     b3r = np.zeros(16, np.float32)
     for qq in range(4):
         W3r[4 * qq:4 * qq + 3] = W3
         b3r[4 * qq:4 * qq + 3] = L[2]["_layer.bias"]
-    rec[8192:9216] = frag_pack_f16x2(W3r)
+    rec[CNF_W3:CNF_W1B] = frag_pack_f16x2(W3r)
     W1t = np.zeros((64, 4), np.float32); W1t[:, :3] = W1; W1t[:, 3] = L[0]["_layer.bias"]     # [W1 | b1]: the kernel's layer 1 is [W1 | b1] [y; 1]
     W1t = (W1t.astype(np.float64) * (2 * LOG2E)).astype(np.float32)                            # (the VJP divides its W1^T sums by 2 log2e again)
     W3t = np.zeros((64, 4), np.float32); W3t[:, :3] = W3.T
-    rec[9216:9472] = W1t.reshape(-1)
-    rec[9472:9728] = W3t.reshape(-1)
-    rec[9728:9792] = L[0]["_layer.bias"]
-    rec[9792:9856] = (L[1]["_layer.bias"].astype(np.float64) * (2 * LOG2E)).astype(np.float32)
-    rec[9856:9872] = b3r
-    rec[9872:10160] = tv
+    rec[CNF_W1B:CNF_W3T] = W1t.reshape(-1)
+    rec[CNF_W3T:CNF_B1] = W3t.reshape(-1)
+    rec[CNF_B1:CNF_B2] = L[0]["_layer.bias"]
+    rec[CNF_B2:CNF_B3] = (L[1]["_layer.bias"].astype(np.float64) * (2 * LOG2E)).astype(np.float32)
+    rec[CNF_B3:CNF_TV] = b3r
+    rec[CNF_TV:CNF_REC] = tv
     T_end = float(_np32(sd[f"flow_blocks.{i}.cnf.sqrt_end_time"])) ** 2
     return rec, Hc, hb, T_end
