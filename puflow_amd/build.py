@@ -8,6 +8,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpuflow_hip.so")
+EXPORTS = os.path.join(CSRC, "exports.map")             # linker version script: only pf_* enters the dynamic symbol table
 SOURCES = ["api.hip", "knn.hip", "edgeconv.hip", "pointwise.hip", "flow.hip", "interp.hip", "chamfer.hip", "emd.hip", "train_ops.hip", "train_fused.hip", "train_ec_fwd.hip", "train_csr.hip", "train_bnmlp.hip", "train_mlp.hip", "train_flow.hip", "train_flowchain.hip", "train_glue.hip", "optim.hip", "patch_ops.hip", "cnf.hip", "cnf_bwd.hip", "xyz_io.hip", "eval_metrics.hip", "data_aug.hip", "eval_uniform.hip", "poisson.hip", "surface_reach.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=on", "-Wno-unused-result"]
 # The fused MFMA kernels never see NaNs; without the flag every fmaxf() is preceded by a canonicalising v_max x,x and
@@ -77,8 +78,8 @@ def build(force: bool = False, verbose: bool = True, defines=(), tag: str = "", 
     for s, p in procs:
         if p.wait() != 0:
             raise RuntimeError(f"hipcc failed on {s}")
-    if force or procs or _stale(lib, objs):
-        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs
+    if force or procs or _stale(lib, objs + [EXPORTS]):
+        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--version-script=" + EXPORTS, "-o", lib] + objs
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)

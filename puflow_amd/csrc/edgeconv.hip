@@ -782,8 +782,6 @@ extern "C" int pf_edgeconv(int cfg, const float* pq_or_xyz, const float* tab, co
 // ONE launch (the fused epilogue above: a 16-point workgroup tile is one MFMA column tile of the GEMM); larger ones as the two
 // kernels (the P|Q GEMM is HBM-write-bound there and its weights would compete with the Q gathers for L2 bandwidth).
 // w: blob base, off[13]: POST_SLOTS of unit `unit` (packing.py).
-extern "C" int pf_pq_gemm(int unit, const float* h, const float* w, const long long* off, float* pq_next, int T, void* stream);
-
 extern "C" int pf_edgeconv_pq(int unit, const float* pq_or_xyz, const int* idx, const float* wfrag, float* out, const float* w,
                               const long long* off, float* pq_next, int B, int N, int fuse, void* stream) {
     if (!pq_or_xyz || !idx || !wfrag || !out || !w || !off || !pq_next) return PF_ERR_NULL;

@@ -2,10 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "../../include/puflow_hip.h"
-#include "pf_grid.h"
-
-// host helpers that cross source files without being part of the C ABI: kept out of the library's dynamic symbol table
-#define PF_INTERNAL __attribute__((visibility("hidden")))
+#include "pf_grid.h"      // PF_INTERNAL: host helpers that cross source files without being part of the C ABI
 
 static inline int pf_last_launch_status() {
     hipError_t e = hipGetLastError();
@@ -18,13 +15,13 @@ static inline int pf_last_launch_status() {
 // the split-K weight-gradient kernels and their reductions are enqueued there, after an event that orders them behind what
 // the calling stream holds at that point; the caller joins the stream once, before the optimizer (puflow_amd/train_ops.py does
 // it at the end of the autograd pass).  Inside a hipGraph capture the event becomes an edge: a parallel branch of the graph.
-void* pf_dw_stream_get();
+PF_INTERNAL void* pf_dw_stream_get();
 // the stream weight-gradient work of a call should go to: s itself when none is set (or it IS s), else the weight-gradient stream,
 // made to wait for everything enqueued on s so far
-hipStream_t pf_dw_fork(hipStream_t s);
+PF_INTERNAL hipStream_t pf_dw_fork(hipStream_t s);
 // pf_gemm_ex with an addend: C = A B + bias + addend (addend [M, ldc] laid out like C, nullable, may alias C) - csrc/train_ops.hip
 // slabs_left: nullable; when given and the product is split over K, the slabs stay in ws ([n][M, N], *slabs_left = n, no reduction
 // launch: the caller sums them where it reads the result) - else *slabs_left = 0 and C holds the product
-int pf_gemm_addend(int arith, const float* A, long long sam, long long sak, const float* B, long long sbk, long long sbn,
-                   float* C, long long ldc, const float* bias, const float* addend, int M, int N, int K, float* ws,
-                   long long ws_floats, void* stream, int* slabs_left);
+PF_INTERNAL int pf_gemm_addend(int arith, const float* A, long long sam, long long sak, const float* B, long long sbk, long long sbn,
+                               float* C, long long ldc, const float* bias, const float* addend, int M, int N, int K, float* ws,
+                               long long ws_floats, void* stream, int* slabs_left);

@@ -35,10 +35,6 @@
 #pragma once
 #include "pf_train_stat.h"
 
-extern "C" int pf_gemm(const float* A, long long sam, long long sak, const float* B, long long sbk, long long sbn, float* C,
-                       long long ldc, const float* bias, int M, int N, int K, float* ws, long long ws_floats, void* stream);
-extern "C" long long pf_gemm_ws_floats(int M, int N, int K);
-
 // shapes of one unit (pf_ec_dims)
 struct EcDims {
     int T, GT, S, nconvs;

@@ -24,6 +24,10 @@
 #include <vector>
 #include "pf_wave.h"
 
+// kept out of the library's dynamic symbol table.  On an inline function it also hides the function's local statics: every
+// library image keeps its own copy of them
+#define PF_INTERNAL __attribute__((visibility("hidden")))
+
 // ---- arrival barrier with a generation word -----------------------------------------------------------------------------------
 // Grid barrier number `gen` (1, 2, ...) of this launch: sync[0] counts arrivals, the workgroup that arrives last publishes the
 // generation word sync[1] at once; sync[3] is the sticky status word (1 = a barrier timed out).  Returns false when the spin gave
@@ -117,7 +121,7 @@ __device__ __forceinline__ bool pf_ring_poll(const unsigned long long* slot, int
 // two host threads interleave set(small) between another thread's set(large) and its launch, cost a driver call on every launch of
 // the 1 ms paths and ran inside graph captures.  Returns the HIP status; only a success is remembered.
 constexpr size_t PF_LDS_CAP = 150 * 1024;
-inline hipError_t pf_allow_lds(const void* kernel, size_t bytes) {
+PF_INTERNAL inline hipError_t pf_allow_lds(const void* kernel, size_t bytes) {
     if (bytes <= 64 * 1024) return hipSuccess;
     static std::mutex mu;
     static std::vector<std::pair<int, const void*>> done;
@@ -147,7 +151,7 @@ void allow_lds(KERNEL k, size_t bytes) {
 // Workgroups of `kernel` (at `threads` per workgroup and `lds` bytes of dynamic LDS) one CU of the current device can hold, and
 // the device's CU count in *ncu (nullable).  0 when any query fails: "does not fit", not cached, the HIP error cleared.  Cached
 // per (device, kernel, threads, LDS) behind one mutex: the queries ran on every call of the 1 ms step and inside graph captures.
-inline int pf_resident_per_cu(const void* kernel, int threads, size_t lds, int* ncu) {
+PF_INTERNAL inline int pf_resident_per_cu(const void* kernel, int threads, size_t lds, int* ncu) {
     struct Entry { int dev; const void* kernel; int threads; size_t lds; int per_cu, ncu; };
     static std::mutex mu;
     static std::vector<Entry> cache;

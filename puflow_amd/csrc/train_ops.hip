@@ -1175,9 +1175,9 @@ extern "C" int pf_scatter_rows(const float* g, const int* idx, int B, int N, int
 // deterministic form (PF_TRAIN_DETERMINISTIC) of the un-fused latent gather's backward.  Accumulated in double and rounded
 // once: a hub row's list holds every edge of its cloud (100 in tests/test_gpu_deterministic.py), and the fp32 sum of such a
 // list missed float64 by 1.2e-6 on one element, past that test's bar
-__global__ __launch_bounds__(256) void scatter_rows_det_kernel(const float* __restrict__ g, const int* __restrict__ off,
-                                                              const int* __restrict__ edge, int C, long long total,
-                                                              float* __restrict__ out) {
+static __global__ __launch_bounds__(256) void scatter_rows_det_kernel(const float* __restrict__ g, const int* __restrict__ off,
+                                                                     const int* __restrict__ edge, int C, long long total,
+                                                                     float* __restrict__ out) {
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     if (t >= total) return;
     const long long j = t / C;

@@ -15,6 +15,8 @@ from typing import Dict, Iterator, Optional, Tuple
 import numpy as np
 import torch
 
+from . import _lib
+
 
 def load_patch_arrays(path: str, num_point: int = 256, up_ratio: int = 4, use_random_input: bool = False,
                       skip_rate: int = 1) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -150,7 +152,8 @@ class SyntheticPatchData(PatchData):
 
 
 # ---- batches assembled on the device (csrc/data_aug.hip: pf_patch_batch) ----------------------------------------------------
-PATCH_SUBSAMPLE, PATCH_JITTER, PATCH_ROTATE, PATCH_Z_ROTATED, PATCH_SCALE, PATCH_SHIFT = 1, 2, 4, 8, 16, 32   # PF_PATCH_*
+PATCH_SUBSAMPLE, PATCH_JITTER, PATCH_ROTATE, PATCH_Z_ROTATED, PATCH_SCALE, PATCH_SHIFT = (
+    _lib.PF_PATCH_SUBSAMPLE, _lib.PF_PATCH_JITTER, _lib.PF_PATCH_ROTATE, _lib.PF_PATCH_Z_ROTATED, _lib.PF_PATCH_SCALE, _lib.PF_PATCH_SHIFT)
 KEYS = ("input_sparse_xyz_pl", "gt_dense_xyz_pl", "up_ratio_pl")
 
 
@@ -162,7 +165,6 @@ def patch_batch(inp: torch.Tensor, gt: torch.Tensor, radius: torch.Tensor, order
     order[(pos + r) % M] with the random numbers of global patch slots slot0 + r.  out: (out_inp, out_gt, out_radius) to write
     into, else fresh tensors.  -> (out_inp [b,n,3], out_gt [b,n_out,3], out_radius [b], params [b,16], idx [b,n] int32 or
     None, cand [b,cand_len] int32 or None).  No host synchronisation."""
-    from . import _lib
     from .ops import _stream
     lib = _lib.load()
     for t, dt in ((inp, torch.float32), (gt, torch.float32), (radius, torch.float32), (order, torch.int32), (status, torch.int32)):

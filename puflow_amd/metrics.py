@@ -253,7 +253,7 @@ def mapped_points(points: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor
     return out
 
 
-REACH_ST_START, REACH_ST_ITER, REACH_ST_ROW = 1, 2, 4          # include/puflow_hip.h: PF_REACH_ST_*
+REACH_ST_START, REACH_ST_ITER, REACH_ST_ROW = _lib.PF_REACH_ST_START, _lib.PF_REACH_ST_ITER, _lib.PF_REACH_ST_ROW
 
 
 def face_adjacency(verts: torch.Tensor, faces: torch.Tensor):

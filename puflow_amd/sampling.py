@@ -22,7 +22,7 @@ import torch
 from . import _lib, metrics, ops
 
 ROUND_BATCH = 16                       # rounds enqueued between two host reads of the "pools unfinished" word
-ST_DEGREE, ST_WEIGHT = 1, 2            # include/puflow_hip.h: PF_POISSON_ST_*
+ST_DEGREE, ST_WEIGHT = _lib.PF_POISSON_ST_DEGREE, _lib.PF_POISSON_ST_WEIGHT
 
 
 def elimination_params(area: float, s: int, m: int):

@@ -54,9 +54,9 @@ class EdgeConvUnitFn(Function):
             d.run_mean[t], d.run_var[t] = _ptr(cfg.run_means[t]), _ptr(cfg.run_vars[t])
         d.stat = _stat(x.device).data_ptr()
         if cfg.persistent and not deterministic():            # the forward / the dense block's backward as one persistent launch where
-            d.flags, d.sync = 1, _sync_words(x.device).data_ptr()        # the library can
+            d.flags, d.sync = _lib.PF_EC_PERSISTENT, _sync_words(x.device).data_ptr()        # the library can
         if deterministic():
-            d.flags |= 2                                      # PF_TRAIN_DETERMINISTIC
+            d.flags |= _lib.PF_TRAIN_DETERMINISTIC
         if cfg.sync_bn:
             _attach_sync(d, x.device)
         return d
@@ -94,7 +94,7 @@ class EdgeConvUnitFn(Function):
         ws = _ws(dev, need)
         d.ws, d.ws_floats = ws.data_ptr(), ws.numel()
         if pre is not None:
-            d.flags |= 4                                      # PF_EC_PREFOLDED
+            d.flags |= _lib.PF_EC_PREFOLDED
         _lib.check(lib.pf_ec_train_fwd(ctypes.byref(d), _stream()), "pf_ec_train_fwd")
         ctx.cfg = cfg
         ctx.has_arg = pooling
@@ -820,7 +820,7 @@ class BnMlpFn(Function):
         d.slope, d.eps, d.momentum = cfg.slope, cfg.eps, cfg.momentum
         d.xa, d.xb = xa.data_ptr(), _ptr(xb)
         d.stat = _stat(xa.device).data_ptr()
-        d.flags = (2 if deterministic() else 0) | (4 if cfg.sum_inputs else 0)
+        d.flags = (_lib.PF_TRAIN_DETERMINISTIC if deterministic() else 0) | (_lib.PF_BNMLP_SUM_INPUTS if cfg.sum_inputs else 0)
         if cfg.sync_bn:
             _attach_sync(d, xa.device)
         return d

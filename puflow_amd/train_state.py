@@ -63,8 +63,8 @@ def _zeros_kept(n: int, dtype, dev) -> Tensor:
 
 
 def _stat(dev) -> Tensor:
-    """4097 doubles (PF_TRAIN_STAT_DOUBLES) per (device, stream): the column-statistics accumulators of the fused training kernels."""
-    return _per_stream(_STAT, dev, lambda: _zeros_kept(4097, torch.float64, dev))
+    """PF_TRAIN_STAT_DOUBLES doubles per (device, stream): the column-statistics accumulators of the fused training kernels."""
+    return _per_stream(_STAT, dev, lambda: _zeros_kept(_lib.PF_TRAIN_STAT_DOUBLES, torch.float64, dev))
 
 
 def _sync_words(dev) -> Tensor:

@@ -1,7 +1,9 @@
-"""Host logic without a GPU: the C-ABI library loads and exports every symbol declared in
-include/puflow_hip.h; the module surface matches the reference state_dict; packing invariants."""
+"""Host logic without a GPU: the C-ABI library loads and exports exactly the symbols declared in include/puflow_hip.h, the ctypes
+binding read from that header agrees with the C compiler; the module surface matches the reference state_dict; packing invariants."""
 import os
 import re
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -16,18 +18,164 @@ def built_lib():
     return build.build(verbose=False)
 
 
-def test_library_exports_every_declared_symbol(built_lib):
-    from puflow_amd import _lib
+def _declared_names():
     hdr = open(os.path.join(ROOT, "include", "puflow_hip.h")).read()
     hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    declared = set(re.findall(r"\b(pf_[a-z0-9_]+)\s*\(", hdr))
+    return set(re.findall(r"\b(pf_[a-z0-9_]+)\s*\(", hdr))
+
+
+def _dynamic_symbols(path):
+    nm = shutil.which("nm") or "/opt/rocm/llvm/bin/llvm-nm"
+    out = subprocess.run([nm, "-D", "--defined-only", path], check=True, capture_output=True, text=True).stdout
+    return {line.split()[-1] for line in out.splitlines() if line.strip()}
+
+
+def test_library_exports_every_declared_symbol(built_lib):
+    """The dynamic symbol table of the library, and of the reduced-precision one, is the set of names the header declares: no
+    declared entry point is missing and no internal helper, inline function's static or kernel stub is exported."""
+    from puflow_amd import _lib, build
+    declared = _declared_names()
     assert declared, "no declarations parsed"
     assert declared == set(_lib.SIGNATURES), (declared ^ set(_lib.SIGNATURES))
+    for path in (built_lib, build.build_f16(verbose=False)):
+        exported = _dynamic_symbols(path)
+        assert exported == declared, (path, sorted(exported ^ declared))
     lib = _lib.load()
-    for name in declared:
-        assert hasattr(lib, name)
     assert lib.pf_version() >= 100
     assert lib.pf_error_string(-2) == b"shape precondition violated"
+
+
+def test_struct_layout_and_constants_match_the_c_compiler(tmp_path):
+    """sizeof and every offsetof of the header's structs, and the value of every #define, as the host C compiler (C99) sees
+    them, against the ctypes classes and constants that _abi.py makes from the same header."""
+    import ctypes
+    from puflow_amd import _abi
+    cc = shutil.which("cc") or shutil.which("gcc") or shutil.which("clang")
+    if cc is None:
+        pytest.skip("no C compiler (cc, gcc, clang) on PATH to compare the struct layout with")
+    consts, structs, _ = _abi.header()
+    assert {"PfEcTrain", "PfBnMlpTrain", "PfMlpTrain", "PfFlowChain", "PfPoissonPool", "PfPoissonState"} <= set(structs)
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "puflow_hip.h"', 'int main(void) {']
+    lines += [f'    printf("{c} %lld\\n", (long long)({c}));' for c in consts]
+    for name, cls in structs.items():
+        lines.append(f'    printf("{name} %zu\\n", sizeof({name}));')
+        lines += [f'    printf("{name}.{f} %zu\\n", offsetof({name}, {f}));' for f, _ in cls._fields_]
+    (tmp_path / "layout.c").write_text("\n".join(lines + ["    return 0;", "}", ""]))
+    subprocess.run([cc, "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-o", str(tmp_path / "layout"),
+                    str(tmp_path / "layout.c")], check=True, capture_output=True, text=True)
+    got = dict(line.split() for line in subprocess.run([str(tmp_path / "layout")], check=True, capture_output=True,
+                                                       text=True).stdout.splitlines())
+    want = {c: str(v) for c, v in consts.items()}
+    for name, cls in structs.items():
+        want[name] = str(ctypes.sizeof(cls))
+        want.update({f"{name}.{f}": str(getattr(cls, f).offset) for f, _ in cls._fields_})
+    assert len(want) > 170 + len(consts) and got == want, sorted(set(got.items()) ^ set(want.items()))
+
+
+@pytest.mark.parametrize("snippet", [
+    "int pf_x(size_t n);",                                       # unknown type
+    "typedef struct PfX { short a; } PfX;",                      # unknown field type
+    "typedef struct PfX { int a[3; } PfX;",                      # malformed declarator
+    "typedef struct PfX { int a, *b c; } PfX;",                  # malformed declarator after a comma
+    "typedef struct PfX { int a; } PfY;",
+    "int pf_x(int (*cb)(int), void* stream);",                   # no function-pointer arguments in this ABI
+    "int pf_x(unsigned char c);",                                # unsigned char exists only behind pointers
+    "float* pf_x(void);",
+    "int pf_x(int n) { return n; }",
+    "int other_name(int n);",
+    "int pf_x(int n);\nint pf_x(int n);",
+    "#define PF_X (1 << PF_Y)",                                   # a name inside the expression
+    "#define PF_X 1.5f",
+    "#define PF_X sizeof(int)",
+    "#define PF_X(a) 1",
+    "#include <stddef.h>",
+    "// a C++ comment\nint pf_x(int n);",
+])
+def test_header_parser_fails_loudly(snippet):
+    """_abi.parse raises on every declaration, field or #define form outside the header's style; it never skips one."""
+    from puflow_amd import _abi
+    with pytest.raises(_abi.AbiError):
+        _abi.parse(snippet)
+
+
+def test_header_parser_reads_the_styles_the_header_uses():
+    import ctypes
+    from puflow_amd import _abi
+    consts, structs, sigs = _abi.parse("""/* c */
+#define PF_A (-3)
+#define PF_B (1 << 4)
+typedef struct PfX { int a, b[PF_B], *c; const float* w[2]; long long n; int (*cb)(void* u, double* s, int n, void* st);
+                     unsigned char* arg; unsigned long long t; } PfX;
+const char* pf_name(int code);
+long long pf_f(const PfX* p, const float* const* hs, void* const* d, const long long* off, unsigned long long seed, void* stream);
+int pf_g(void);""")
+    assert consts == {"PF_A": -3, "PF_B": 16}
+    X = structs["PfX"]
+    assert [(n, t) for n, t in X._fields_] == [
+        ("a", ctypes.c_int), ("b", ctypes.c_int * 16), ("c", ctypes.c_void_p), ("w", ctypes.c_void_p * 2), ("n", ctypes.c_longlong),
+        ("cb", ctypes.c_void_p), ("arg", ctypes.c_void_p), ("t", ctypes.c_ulonglong)]
+    assert sigs["pf_name"] == (ctypes.c_char_p, [ctypes.c_int]) and sigs["pf_g"] == (ctypes.c_int, [])
+    res, args = sigs["pf_f"]
+    assert res is ctypes.c_longlong and args[4] is ctypes.c_ulonglong
+    assert [a.elem for a in args[:4]] == [X, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong] and args[5] is ctypes.c_void_p
+
+
+def test_pointer_arguments_check_the_element_type(built_lib):
+    """A pointer argument takes None, an address, or ctypes storage of the header's pointee type - and nothing else: host
+    arrays of another element type, or another descriptor, are an error at the call, not a wrong pointer in a kernel."""
+    import ctypes
+    from ctypes import c_double, c_float, c_int, c_longlong, c_void_p
+    from puflow_amd import _lib
+    arg = lambda name, i: _lib.SIGNATURES[name][1][i]
+    cases = [(arg("pf_cond_all", 2), c_longlong), (arg("pf_fps_ragged", 1), c_int), (arg("pf_lincomb", 1), c_float),
+             (arg("pf_disk_count", 4), c_double), (arg("pf_sum_n", 0), c_void_p), (arg("pf_cond_all", 3), c_void_p),
+             (arg("pf_ec_train_fwd", 0), _lib.PfEcTrain), (arg("pf_poisson_pools", 5), _lib.PfPoissonPool)]
+    for t, elem in cases:
+        assert issubclass(t, c_void_p) and t.elem is elem
+        one = elem()
+        for ok in (None, 8, 2 ** 47 + 8, (elem * 3)(), ctypes.byref(one), ctypes.pointer(one)):
+            t.from_param(ok)
+        others = [e for e in (c_int, c_longlong, c_float, c_double, c_void_p, _lib.PfMlpTrain) if e is not elem]
+        for bad in [(e * 3)() for e in others] + [ctypes.byref(e()) for e in others] + [one, 1.5, "text", b"bytes", [1, 2]]:
+            with pytest.raises(TypeError):
+                t.from_param(bad)
+    with pytest.raises(TypeError):
+        arg("pf_cond_all", 2).from_param(_lib.counts([1, 2]))                   # c_int array for const long long*
+    with pytest.raises(TypeError):
+        arg("pf_fps_ragged", 1).from_param(_lib.offsets([1, 2]))                # c_longlong array for const int*
+    with pytest.raises(TypeError):
+        arg("pf_ec_train_fwd", 0).from_param(ctypes.byref(_lib.PfMlpTrain()))   # another descriptor for const PfEcTrain*
+    anything = arg("pf_ec_train_fwd", 1)                                        # void* stream
+    assert anything is c_void_p
+    for ok in (None, 8, _lib.counts([1]), ctypes.byref(c_double()), ctypes.addressof(ctypes.create_string_buffer(4))):
+        anything.from_param(ok)
+    # through a real call: the address arrives whole, and a wrong host array never reaches the library
+    lib = _lib.load()
+    stride, word = c_longlong(-1), c_longlong(-1)
+    assert lib.pf_fps_scratch_layout(8192, ctypes.byref(stride), ctypes.byref(word)) == 1 and stride.value > 0
+    assert lib.pf_ec_train_ws_floats(ctypes.byref(_lib.PfEcTrain())) == -1          # all-zero shape, as the validation test
+    with pytest.raises(ctypes.ArgumentError):
+        lib.pf_fps_scratch_layout(8192, ctypes.byref(c_int()), ctypes.byref(word))
+    with pytest.raises(ctypes.ArgumentError):
+        lib.pf_interp(8, 8, 8, 8, _lib.counts([0] * 15), 8, 1, 64, 33, None)
+    with pytest.raises(ctypes.ArgumentError):
+        lib.pf_ec_train_fwd(ctypes.byref(_lib.PfMlpTrain()), None)
+
+
+def test_header_is_parsed_once_and_python_names_alias_its_constants():
+    from puflow_amd import _abi, _lib, cnf, data, metrics, ops, sampling, train_ops      # noqa: F401
+    info = _abi.header.cache_info()
+    assert info.misses == 1 and info.currsize == 1
+    consts, structs, sigs = _abi.header()
+    assert _abi.header.cache_info().misses == 1
+    assert sigs is _lib.SIGNATURES and all(getattr(_lib, n) is c for n, c in structs.items())
+    assert all(getattr(_lib, n) == v for n, v in consts.items())
+    assert (data.PATCH_SUBSAMPLE, data.PATCH_JITTER, data.PATCH_ROTATE, data.PATCH_Z_ROTATED, data.PATCH_SCALE,
+            data.PATCH_SHIFT) == (1, 2, 4, 8, 16, 32)
+    assert (metrics.REACH_ST_START, metrics.REACH_ST_ITER, metrics.REACH_ST_ROW) == (1, 2, 4)
+    assert (sampling.ST_DEGREE, sampling.ST_WEIGHT) == (1, 2)
+    assert (_lib.PF_EC_PERSISTENT, _lib.PF_TRAIN_DETERMINISTIC, _lib.PF_EC_PREFOLDED, _lib.PF_BNMLP_SUM_INPUTS,
+            _lib.PF_TRAIN_STAT_DOUBLES, _lib.PF_FLOWCHAIN_MAXB, _lib.PF_POISSON_MAX_TOTAL) == (1, 2, 4, 4, 4097, 8, 1 << 30)
 
 
 def test_argument_validation_without_gpu(built_lib):

@@ -25,9 +25,7 @@ e._edgeconv(0, xyz.data_ptr(), idx16, h0, B, N, s)
 st = torch.empty((6, T, 8), device="cuda"); cp = torch.empty((6, T, 64), device="cuda")
 _lib.check(lib.pf_post(0, h0.data_ptr(), e.base, e.post[0], None, st[0].data_ptr(), cp[0].data_ptr(), pq.data_ptr(), T, s))
 torch.cuda.synchronize()
-abl = ctypes.CDLL(_lib.LIB_PATH.replace(".so", "_abl.so"))
-for name, (res, args) in _lib.SIGNATURES.items():
-    fn = getattr(abl, name); fn.restype, fn.argtypes = res, args
+abl = _lib.bind(ctypes.CDLL(_lib.LIB_PATH.replace(".so", "_abl.so")))
 shapes = {0: "(P1,NW8)", 1: "(P2,NW8) shipped", 2: "(P1,NW16)", 3: "(P2,NW4)"}
 for unit, cfg, src, od in ((0, 8, xyz, 32), (1, 9, pq, 64)):
     ref = torch.empty((T, od), device="cuda")

@@ -48,9 +48,7 @@ cands = [("f16n v0 (P1,NW16)", 7, 0, en, pqn, "ec4_w", lib)]
 # side-by-side tuning builds: python tools/tune_ec4.py <tag> ...  loads libpuflow_hip_<tag>.so (puflow_amd.build.build(defines, tag))
 import ctypes
 for tag in sys.argv[1:]:
-    l = ctypes.CDLL(_lib.LIB_PATH.replace(".so", f"_{tag}.so"))
-    for name, (res, args) in _lib.SIGNATURES.items():
-        fn = getattr(l, name); fn.restype, fn.argtypes = res, args
+    l = _lib.bind(ctypes.CDLL(_lib.LIB_PATH.replace(".so", f"_{tag}.so")))
     if tag == "abl":       # -DPF_TUNING_VARIANTS build: timing-only ablations of the (P1, NW16) shape
         cands += [(f"[abl] {what}", 7, v, en, pqn, "ec4_w", l) for v, what in
                   ((0, "full"), (1, "shape (P2,NW8)"), (2, "shape (P1,NW8)"), (3, "shape (P2,NW4)"), (8, "no gathers"), (9, "no MFMAs"), (10, "no LDS weight reads"), (11, "no gathers, no LDS reads"),

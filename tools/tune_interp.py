@@ -28,10 +28,7 @@ s = torch.cuda.current_stream().cuda_stream
 
 
 def load(tag):
-    l = ctypes.CDLL(_lib.LIB_PATH.replace(".so", f"_{tag}.so") if tag else _lib.LIB_PATH)
-    for name, (res, args) in _lib.SIGNATURES.items():
-        fn = getattr(l, name); fn.restype, fn.argtypes = res, args
-    return l
+    return _lib.bind(ctypes.CDLL(_lib.LIB_PATH.replace(".so", f"_{tag}.so") if tag else _lib.LIB_PATH))
 
 
 libs = [("shipped", load(""))] + [(f"({p},{nw})", load(f"ip{p}_{nw}")) for p, nw in SHAPES]

@@ -21,10 +21,7 @@ idx = torch.empty((B, N, K), dtype=torch.int32, device="cuda")
 
 
 def load(tag):
-    l = ctypes.CDLL(_lib.LIB_PATH.replace(".so", f"_{tag}.so") if tag else _lib.LIB_PATH)
-    for name, (res, args) in _lib.SIGNATURES.items():
-        fn = getattr(l, name); fn.restype, fn.argtypes = res, args
-    return l
+    return _lib.bind(ctypes.CDLL(_lib.LIB_PATH.replace(".so", f"_{tag}.so") if tag else _lib.LIB_PATH))
 
 
 def timed(fn, iters=50):
