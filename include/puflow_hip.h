@@ -178,9 +178,9 @@ int pf_emd_backward(const float* xyz1, const float* xyz2, float* gradxyz, const 
                     int n, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Training-step building blocks (csrc/train_ops.hip): one kernel pair per eager op the reference's
- * train-mode forward/backward runs (modules/discrete/interpflow.py:203-258, train_pu1k.py:53-74),
- * on channels-last [rows, C] fp32 tensors.  Wired into autograd by puflow_amd/train_ops.py.
+ * Training-step building blocks (csrc/train_gemm.hip: the matrix products, csrc/train_ops.hip: the rest): one kernel pair
+ * per eager op the reference's train-mode forward/backward runs (modules/discrete/interpflow.py:203-258,
+ * train_pu1k.py:53-74), on channels-last [rows, C] fp32 tensors.  Wired into autograd by puflow_amd/train_perop.py.
  * ------------------------------------------------------------------------------------------- */
 
 /* C[M,N] = A(M,K) B(K,N) (+ bias[N]), generic element strides: A(m,k) = A[m*sam + k*sak], B(k,n) = B[k*sbk + n*sbn].
@@ -190,8 +190,9 @@ int pf_gemm(const float* A, long long sam, long long sak, const float* B, long l
             long long ldc, const float* bias, int M, int N, int K, float* ws, long long ws_floats, void* stream);
 /* the split-K reduction of pf_gemm for callers that wrote their own slabs [nslab][M * N]: C [M, ldc] = their sum, fixed order */
 int pf_gemm_reduce(const float* slabs, float* C, int M, int N, long long ldc, int nslab, void* stream);
-/* pf_gemm with the matrix-pipe arithmetic chosen by the caller: 0 = f32 MFMA (what pf_gemm runs), 1 = the same products in the
- * same order on the round-1 kernel (A/B reference: bit-identical to 0), 2 = split-fp16 (operands
+/* pf_gemm with the matrix-pipe arithmetic chosen by the caller: 0 = f32 MFMA (what pf_gemm runs: the float4-load kernel where
+ * the operands allow it, else the general one), 1 = the same products in the same order on the general kernel (any strides,
+ * scalar loads) whatever the operands (reference: bit-identical to 0), 2 = split-fp16 (operands
  * inside the fp16 range: forward GEMMs), 3 = split-bf16 (gradient operands); all fp32-class results. */
 int pf_gemm_ex(int arith, const float* A, long long sam, long long sak, const float* B, long long sbk, long long sbn, float* C,
                long long ldc, const float* bias, int M, int N, int K, float* ws, long long ws_floats, void* stream);

@@ -19,7 +19,7 @@ PF_INTERNAL void* pf_dw_stream_get();
 // the stream weight-gradient work of a call should go to: s itself when none is set (or it IS s), else the weight-gradient stream,
 // made to wait for everything enqueued on s so far
 PF_INTERNAL hipStream_t pf_dw_fork(hipStream_t s);
-// pf_gemm_ex with an addend: C = A B + bias + addend (addend [M, ldc] laid out like C, nullable, may alias C) - csrc/train_ops.hip
+// pf_gemm_ex with an addend: C = A B + bias + addend (addend [M, ldc] laid out like C, nullable, may alias C) - csrc/train_gemm.hip
 // slabs_left: nullable; when given and the product is split over K, the slabs stay in ws ([n][M, N], *slabs_left = n, no reduction
 // launch: the caller sums them where it reads the result) - else *slabs_left = 0 and C holds the product
 PF_INTERNAL int pf_gemm_addend(int arith, const float* A, long long sam, long long sak, const float* B, long long sbk, long long sbn,

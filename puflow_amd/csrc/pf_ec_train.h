@@ -2,14 +2,14 @@
 //
 // Reference: modules/discrete/interpflow.py:190-248 (FeatureExtractUnit.forward in train() mode: edge feature ->
 // [Conv2d 1x1 + BatchNorm2d (batch statistics) + LeakyReLU(0.05), dense concatenation] x nconv -> conv_out -> max over the K
-// neighbours) and the autograd backward PyTorch derives from it.  The un-fused path (train_ops.hip + train_ops.py) runs
+// neighbours) and the autograd backward PyTorch derives from it.  The un-fused path (train_ops.hip, train_gemm.hip + train_perop.py) runs
 // this as ~170 launches per unit and step (GEMM, two-pass statistics, apply, concatenations, gradient adds); at
 // 32 x 256 points every one of those kernels is shorter than the gap between two launches, so the step was bound by the
 // NUMBER of launches.  Here a unit is 7 launches forward and ~12 backward:
 //
 //   forward   fold        Wp = W1 - W3, Wq = W2 + W3 of all convs -> Wpq [2S, C]   (the edge feature [x_i; x_j; x_j - x_i]
 //                         enters every conv only through P = Wp x_i (+ bias) and Q = Wq x_j: packing.fold_edgeconv)
-//             gemm        PQ [T, 2S] = x Wpq^T + bias                              (train_ops.hip: pf_gemm)
+//             gemm        PQ [T, 2S] = x Wpq^T + bias                              (train_gemm.hip: pf_gemm)
 //             layer t     Y[:, g t : g (t+1)] = P_t[i] + Q_t[j] + lrelu(bn(Y[:, :g t])) Wg_t^T   - the BatchNorm of the
 //                         EARLIER layers is applied on load (scale / shift per channel), this layer's pre-activation
 //                         output is stored and its column sums / sums of squares leave in the epilogue

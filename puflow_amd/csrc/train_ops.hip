@@ -1,579 +1,24 @@
-// Building blocks of the TRAINING step (train-mode forward with BatchNorm batch statistics, and the
+// The element-wise building blocks of the TRAINING step (train-mode forward with BatchNorm batch statistics, and the
 // backward of every layer).  The reference trains with eager PyTorch ops on materialised
 // [B,C,N,K] tensors (modules/discrete/interpflow.py:203-258, train_pu1k.py:53-74); here each of those
 // ops is one hand-written kernel pair on channels-last [rows, C] fp32 tensors, wired into autograd
-// by puflow_amd/train_ops.py.  Training runs on 256-point patches (32 x 256 points, 131 072 edges),
-// so this first version is deliberately un-fused; the fused MFMA-chain kernels serve inference.
+// by puflow_amd/train_perop.py.  This is the per-op reference tier of the fused training kernels; the matrix
+// products of both tiers are csrc/train_gemm.hip.
 //
-//   gemm            C = op(A) op(B) (+bias)    every Conv2d(1x1) / Linear forward, dX and dW (split-K slabs,
-//                                              deterministic reduce)            f32 MFMA 16x16x4, 64x64 tiles
-//   colstat / bn    BatchNorm2d(train) + LeakyReLU forward / backward (two-pass mean / variance)
+//   colstat / bn    BatchNorm2d(train) + LeakyReLU forward / backward (two-pass mean / variance), whole and in stages
+//   colsum          per-column sums (bias and flow-parameter gradients)
 //   act             LeakyReLU / ReLU forward / backward
 //   edge_feature    [x_i, x_j, x_j - x_i] gather forward, scatter-add backward   (interpflow.py:223-232)
 //   maxpool_k       max over the K neighbours + argmax, backward                  (interpflow.py:245)
 //   scatter_rows    backward of a row gather (z[idx], interpflow.py:183)
 //   softmax_wsum    softmax over K of R logit channels, weighted sum of neighbour latents, backward (interpflow.py:180-185)
 //   group_sum       backward of repeat_interleave(cs, R) (interpflow.py:319)
+//   flow-block algebra on [R,3] rows (second part): ActNorm, coupling + injector, batch sums, distance features
 #include <hip/hip_runtime.h>
 #include "pf_api_internal.h"
 #include "pf_mfma.h"
 
 namespace {
-
-// ------------------------------------------------------------------------------------------ GEMM
-struct GemmArgs {
-    const float* A; long long sam, sak;      // A(m,k) = A[m*sam + k*sak]
-    const float* B; long long sbk, sbn;      // B(k,n) = B[k*sbk + n*sbn]
-    float* C; long long ldc;                 // C(m,n) = C[m*ldc + n]   (or slab z: C + z*M*ldc)
-    const float* bias;                       // per column n, nullable (ignored when splitk > 1: added by the reduce)
-    int M, N, K, kchunk;                     // kchunk = K range per blockIdx.z
-    const float* add;                        // nullable: C(m,n) += add[m*ldc + n] (same layout as C; may BE C; ignored when splitk > 1:
-};                                           //           added by the reduce) - a gradient that already holds another consumer's part
-
-// Output tile BM x BN per 256-thread workgroup: WAVES_M x WAVES_N waves, each TM x TN MFMA tiles of 16x16; K-step 16.
-// The launcher picks the shape from (M, N): layer GEMMs here are very skinny (N = 8..128 forward, M = 8..128 for dW),
-// so a square tile would waste most of its MFMAs.
-// VEC: both operands are read with float4 loads along their contiguous dimension (requires that dimension's
-// extent and leading stride to be multiples of 4 and 16-byte aligned bases); otherwise scalar guarded loads.
-template <int WAVES_M, int WAVES_N, int TM, int TN, bool VEC>
-__global__ __launch_bounds__(256) void gemm_kernel(GemmArgs g) {
-    constexpr int BM = WAVES_M * TM * 16, BN = WAVES_N * TN * 16;
-    __shared__ float As[BM][20];          // [m][k], row stride 20 floats: 16-B aligned rows
-    __shared__ float Bs[16][BN + 4];      // [k][n]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave / WAVES_N, wn = wave % WAVES_N;
-    const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
-    const int k_lo = blockIdx.z * g.kchunk;
-    const int k_hi = min(g.K, k_lo + g.kchunk);
-    const bool a_kfast = g.sak == 1, b_nfast = g.sbn == 1;
-    f4 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = pf_splat(0.f);
-
-    // VEC: the next K-step's operand tiles are fetched into registers while the current one is multiplied (the layer GEMMs
-    // are 2..32 K-steps long: with load -> barrier -> multiply -> barrier per step every step paid a full memory latency)
-    constexpr int NA = (BM * 4 + 255) / 256, NB = (BN * 4 + 255) / 256;
-    f4 ra[NA], rb[NB];
-    auto fetch = [&](int k0) {
-#pragma unroll
-        for (int i = 0; i < NA; ++i) {
-            const int v = tid + i * 256;
-            f4 x = pf_splat(0.f);
-            if (v < BM * 4) {
-                if (a_kfast) {
-                    const int r = v >> 2, k = (v & 3) * 4;
-                    const int gm = m0 + r, gk = k0 + k;
-                    if (gm < g.M && gk < k_hi) x = *reinterpret_cast<const f4*>(g.A + gm * g.sam + gk);
-                } else {
-                    const int k = v / (BM / 4), r = (v % (BM / 4)) * 4;
-                    const int gm = m0 + r, gk = k0 + k;
-                    if (gm < g.M && gk < k_hi) x = *reinterpret_cast<const f4*>(g.A + gk * g.sak + gm);
-                }
-            }
-            ra[i] = x;
-        }
-#pragma unroll
-        for (int i = 0; i < NB; ++i) {
-            const int v = tid + i * 256;
-            f4 x = pf_splat(0.f);
-            if (v < BN * 4) {
-                if (b_nfast) {
-                    const int k = v / (BN / 4), n = (v % (BN / 4)) * 4;
-                    const int gn = n0 + n, gk = k0 + k;
-                    if (gn < g.N && gk < k_hi) x = *reinterpret_cast<const f4*>(g.B + gk * g.sbk + gn);
-                } else {
-                    const int n = v >> 2, k = (v & 3) * 4;
-                    const int gn = n0 + n, gk = k0 + k;
-                    if (gn < g.N && gk < k_hi) x = *reinterpret_cast<const f4*>(g.B + gn * g.sbn + gk);
-                }
-            }
-            rb[i] = x;
-        }
-    };
-    auto stash = [&]() {
-#pragma unroll
-        for (int i = 0; i < NA; ++i) {
-            const int v = tid + i * 256;
-            if (v < BM * 4) {
-                const f4 x = ra[i];
-                if (a_kfast) {
-                    const int r = v >> 2, k = (v & 3) * 4;
-                    *reinterpret_cast<f4*>(&As[r][k]) = x;
-                } else {
-                    const int k = v / (BM / 4), r = (v % (BM / 4)) * 4;
-                    As[r][k] = x.x; As[r + 1][k] = x.y; As[r + 2][k] = x.z; As[r + 3][k] = x.w;
-                }
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < NB; ++i) {
-            const int v = tid + i * 256;
-            if (v < BN * 4) {
-                const f4 x = rb[i];
-                if (b_nfast) {
-                    const int k = v / (BN / 4), n = (v % (BN / 4)) * 4;
-                    *reinterpret_cast<f4*>(&Bs[k][n]) = x;
-                } else {
-                    const int n = v >> 2, k = (v & 3) * 4;
-                    Bs[k][n] = x.x; Bs[k + 1][n] = x.y; Bs[k + 2][n] = x.z; Bs[k + 3][n] = x.w;
-                }
-            }
-        }
-    };
-    if (VEC) fetch(k_lo);
-    for (int k0 = k_lo; k0 < k_hi; k0 += 16) {
-        if (VEC) {
-            stash();
-        } else {
-            for (int v = tid; v < BM * 16; v += 256) {
-                const int r = a_kfast ? (v >> 4) : (v % BM);
-                const int k = a_kfast ? (v & 15) : (v / BM);
-                const int gm = m0 + r, gk = k0 + k;
-                As[r][k] = (gm < g.M && gk < k_hi) ? g.A[gm * g.sam + gk * g.sak] : 0.f;
-            }
-            for (int v = tid; v < BN * 16; v += 256) {
-                const int n = b_nfast ? (v % BN) : (v >> 4);
-                const int kb = b_nfast ? (v / BN) : (v & 15);
-                const int gn = n0 + n, gkb = k0 + kb;
-                Bs[kb][n] = (gn < g.N && gkb < k_hi) ? g.B[gkb * g.sbk + gn * g.sbn] : 0.f;
-            }
-        }
-        __syncthreads();
-        if (VEC && k0 + 16 < k_hi) fetch(k0 + 16);
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            float a[TM], b[TN];
-#pragma unroll
-            for (int i = 0; i < TM; ++i) a[i] = As[(wm * TM + i) * 16 + (lane & 15)][kk * 4 + (lane >> 4)];
-#pragma unroll
-            for (int j = 0; j < TN; ++j) b[j] = Bs[kk * 4 + (lane >> 4)][(wn * TN + j) * 16 + (lane & 15)];
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = pf_mfma(a[i], b[j], acc[i][j]);
-        }
-        __syncthreads();
-    }
-    float* C = g.C + (long long)blockIdx.z * g.M * g.ldc;
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int n = n0 + (wn * TN + j) * 16 + (lane & 15);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int m = m0 + (wm * TM + i) * 16 + 4 * (lane >> 4) + r;
-                if (m < g.M && n < g.N) C[m * g.ldc + n] = acc[i][j][r] + (g.bias ? g.bias[n] : 0.f) + (g.add ? g.add[m * g.ldc + n] : 0.f);
-            }
-        }
-}
-
-// ---- round 5: the same GEMM (same MFMA chain per output element, bit-identical results) with conflict-free LDS images ----
-// gemm_kernel above stages through As[BM][20] / Bs[16][BN + 4]: an operand whose contiguous dimension is NOT k is transposed
-// with scalar ds_write_b32 at a 20-float stride (8-way bank conflicts), the b32 fragment reads are 2-way (PMC: 54 - 86 % of
-// the LDS cycles were conflict cycles), every 16-deep step pays two barriers and the epilogue stores 64-byte pieces.  Here:
-//   * an operand that is contiguous along k goes to LDS in FRAGMENT order [16-k group][tile][lane = q 16 + row][j]
-//     (element j of lane (row, q) is k = 4 j + q: what MFMA step j of the group reads), written by four ds_write_b32 whose
-//     32-lane groups cover 32 banks, read back as ONE ds_read_b128 per tile and group;
-//   * an operand that is contiguous along its row index (m / n) keeps its memory order [k][rows + 16]: ds_write_b128 rows,
-//     ds_read_b32 fragments whose two k rows of a 32-lane group sit 16 banks apart;
-//   * 32-deep steps, two LDS buffers, ONE barrier per step, the next step's operands in registers during the MFMAs;
-//   * the output tile leaves through LDS as whole rows (float4 per lane).
-// The products and their order are those of gemm_kernel (k ascending through v_mfma_f32_16x16x4_f32, the same split-K chunks).
-template <int WAVES_M, int WAVES_N, int TM, int TN>
-__global__ __launch_bounds__(256) void gemm2_kernel(GemmArgs g, int cvec) {
-    constexpr int BM = WAVES_M * TM * 16, BN = WAVES_N * TN * 16, BK = 32;
-    constexpr int LDA = BM % 32 == 0 ? BM + 16 : BM + 32, LDB = BN % 32 == 0 ? BN + 16 : BN + 32;   // row stride = 16 mod 32 floats
-    constexpr int ASZ = BK * LDA, BSZ = BK * LDB, LDC = BN + 4;
-    extern __shared__ __attribute__((aligned(16))) float g2lds[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, ml = lane & 15, q = lane >> 4;
-    const int wm = wave / WAVES_N, wn = wave % WAVES_N;
-    const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
-    const int k_lo = blockIdx.z * g.kchunk;
-    const int k_hi = min(g.K, k_lo + g.kchunk);
-    const bool a_kfast = g.sak == 1, b_kfast = g.sbk == 1 && g.sbn != 1;
-    f4 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = pf_splat(0.f);
-    constexpr int NA = (BM * 8 + 255) / 256, NB = (BN * 8 + 255) / 256;
-    f4 ra[NA], rb[NB];
-    auto fetch = [&](int k0) {
-#pragma unroll
-        for (int i = 0; i < NA; ++i) {
-            const int v = tid + i * 256;
-            f4 x = pf_splat(0.f);
-            if (v < BM * 8) {
-                if (a_kfast) {
-                    const int gm = m0 + (v >> 3), gk = k0 + (v & 7) * 4;
-                    if (gm < g.M && gk < k_hi) x = *reinterpret_cast<const f4*>(g.A + gm * g.sam + gk);
-                } else {
-                    const int gk = k0 + v / (BM / 4), gm = m0 + (v % (BM / 4)) * 4;
-                    if (gm < g.M && gk < k_hi) x = *reinterpret_cast<const f4*>(g.A + gk * g.sak + gm);
-                }
-            }
-            ra[i] = x;
-        }
-#pragma unroll
-        for (int i = 0; i < NB; ++i) {
-            const int v = tid + i * 256;
-            f4 x = pf_splat(0.f);
-            if (v < BN * 8) {
-                if (b_kfast) {
-                    const int gn = n0 + (v >> 3), gk = k0 + (v & 7) * 4;
-                    if (gn < g.N && gk < k_hi) x = *reinterpret_cast<const f4*>(g.B + gn * g.sbn + gk);
-                } else {
-                    const int gk = k0 + v / (BN / 4), gn = n0 + (v % (BN / 4)) * 4;
-                    if (gn < g.N && gk < k_hi) x = *reinterpret_cast<const f4*>(g.B + gk * g.sbk + gn);
-                }
-            }
-            rb[i] = x;
-        }
-    };
-    auto stash = [&](float* As, float* Bs) {
-#pragma unroll
-        for (int i = 0; i < NA; ++i) {
-            const int v = tid + i * 256;
-            if (v < BM * 8) {
-                const f4 x = ra[i];
-                if (a_kfast) {
-                    const int r = v >> 3, c = v & 7;
-                    float* p = As + (c >> 2) * (BM * 16) + ((r >> 4) * 64 + (r & 15)) * 4 + (c & 3);
-                    p[0] = x.x; p[64] = x.y; p[128] = x.z; p[192] = x.w;
-                } else {
-                    *reinterpret_cast<f4*>(As + (v / (BM / 4)) * LDA + (v % (BM / 4)) * 4) = x;
-                }
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < NB; ++i) {
-            const int v = tid + i * 256;
-            if (v < BN * 8) {
-                const f4 x = rb[i];
-                if (b_kfast) {
-                    const int r = v >> 3, c = v & 7;
-                    float* p = Bs + (c >> 2) * (BN * 16) + ((r >> 4) * 64 + (r & 15)) * 4 + (c & 3);
-                    p[0] = x.x; p[64] = x.y; p[128] = x.z; p[192] = x.w;
-                } else {
-                    *reinterpret_cast<f4*>(Bs + (v / (BN / 4)) * LDB + (v % (BN / 4)) * 4) = x;
-                }
-            }
-        }
-    };
-    fetch(k_lo);
-    stash(g2lds, g2lds + ASZ);
-    __syncthreads();
-    int cur = 0;
-    for (int k0 = k_lo; k0 < k_hi; k0 += BK) {
-        const float* As = g2lds + cur * (ASZ + BSZ);
-        const float* Bs = As + ASZ;
-        const bool more = k0 + BK < k_hi;
-        if (more) fetch(k0 + BK);
-#pragma unroll
-        for (int gq = 0; gq < 2; ++gq) {
-            f4 a[TM], b[TN];
-            if (a_kfast) {
-#pragma unroll
-                for (int i = 0; i < TM; ++i) a[i] = *reinterpret_cast<const f4*>(As + gq * (BM * 16) + ((wm * TM + i) * 64 + lane) * 4);
-            } else {
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int kk = 0; kk < 4; ++kk) a[i][kk] = As[(gq * 16 + kk * 4 + q) * LDA + (wm * TM + i) * 16 + ml];
-            }
-            if (b_kfast) {
-#pragma unroll
-                for (int j = 0; j < TN; ++j) b[j] = *reinterpret_cast<const f4*>(Bs + gq * (BN * 16) + ((wn * TN + j) * 64 + lane) * 4);
-            } else {
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-#pragma unroll
-                    for (int kk = 0; kk < 4; ++kk) b[j][kk] = Bs[(gq * 16 + kk * 4 + q) * LDB + (wn * TN + j) * 16 + ml];
-            }
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j) acc[i][j] = pf_mfma(a[i][kk], b[j][kk], acc[i][j]);
-        }
-        if (more) {
-            float* An = g2lds + (cur ^ 1) * (ASZ + BSZ);
-            stash(An, An + ASZ);
-        }
-        __syncthreads();
-        cur ^= 1;
-    }
-    // ---- the tile through LDS: [BM][BN + 4] (a lane group's two 4-row blocks sit 16 banks apart), then whole rows out
-    float* Cs = g2lds;
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) Cs[((wm * TM + i) * 16 + 4 * q + r) * LDC + (wn * TN + j) * 16 + ml] = acc[i][j][r];
-    __syncthreads();
-    float* C = g.C + (long long)blockIdx.z * g.M * g.ldc;
-    for (int v = tid; v < BM * (BN / 4); v += 256) {
-        const int row = v / (BN / 4), c4 = (v % (BN / 4)) * 4;
-        const int m = m0 + row, n = n0 + c4;
-        if (m >= g.M || n >= g.N) continue;
-        f4 x = *reinterpret_cast<const f4*>(Cs + row * LDC + c4);
-        if (cvec && n + 3 < g.N) {
-            if (g.bias) { const f4 bb = *reinterpret_cast<const f4*>(g.bias + n); x += bb; }
-            if (g.add) { const f4 aa = *reinterpret_cast<const f4*>(g.add + m * g.ldc + n); x += aa; }
-            *reinterpret_cast<f4*>(C + m * g.ldc + n) = x;
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (n + e < g.N) C[m * g.ldc + n + e] = x[e] + (g.bias ? g.bias[n + e] : 0.f) + (g.add ? g.add[m * g.ldc + n + e] : 0.f);
-        }
-    }
-}
-
-template <int WAVES_M, int WAVES_N, int TM, int TN>
-void gemm2_launch(const GemmArgs& g, int split, hipStream_t s) {
-    constexpr int BM = WAVES_M * TM * 16, BN = WAVES_N * TN * 16;
-    constexpr int LDA = BM % 32 == 0 ? BM + 16 : BM + 32, LDB = BN % 32 == 0 ? BN + 16 : BN + 32;
-    constexpr int loop_floats = 2 * 32 * (LDA + LDB), out_floats = BM * (BN + 4);
-    constexpr size_t lds = sizeof(float) * (size_t)(loop_floats > out_floats ? loop_floats : out_floats);
-    allow_lds(gemm2_kernel<WAVES_M, WAVES_N, TM, TN>, lds);
-    auto al16 = [](const void* p) { return (reinterpret_cast<unsigned long long>(p) & 15ull) == 0; };
-    const long long ldc = g.ldc;
-    const int cvec = (ldc % 4 == 0) && al16(g.C) && (!g.bias || al16(g.bias)) && (!g.add || al16(g.add)) && (((long long)g.M * ldc) % 4 == 0);
-    const dim3 grid((g.N + BN - 1) / BN, (g.M + BM - 1) / BM, split);
-    hipLaunchKernelGGL((gemm2_kernel<WAVES_M, WAVES_N, TM, TN>), grid, dim3(256), lds, s, g, cvec);
-}
-
-// ---- split-precision GEMM: the same tiles on the fp16 / bf16 matrix pipe ------------------------------------------
-// The f32 MFMA runs at 1/16 of the 16-bit rate; the big layer GEMMs above already sit near ITS roofline.  Here both
-// operands are split while they are staged into LDS ([row][k] images, k contiguous: one 16-B read per MFMA operand):
-//   NS = 2  x = hi + lo in fp16 (natural-scale low half, pf_mfma.h "f16n"): 3 MFMAs per 32-deep step - forward GEMMs
-//           (activations and weights are O(1e-3 .. 1e2): inside the fp16 range)
-//   NS = 3  x = hi + mid + lo in bf16: 6 MFMAs per step, fp32 exponent range - the GEMMs that take a gradient operand
-//           (dX = dY W, dW = dY^T X: gradients reach 1e-8 and would underflow an fp16 split)
-// Results are fp32-class (>= 22 significant bits per product, fp32 accumulation); 5.3x / 2.7x fewer MFMA cycles than f32.
-template <int NS> struct SplitT;
-template <> struct SplitT<2> { typedef _Float16 T; };
-template <> struct SplitT<3> { typedef __bf16 T; };
-
-template <int NS, int WAVES_M, int WAVES_N, int TM, int TN, bool VEC>
-__global__ __launch_bounds__(256) void gemm_split_kernel(GemmArgs g) {
-    typedef typename SplitT<NS>::T T;
-    typedef T T8 __attribute__((ext_vector_type(8)));
-    constexpr int BM = WAVES_M * TM * 16, BN = WAVES_N * TN * 16, BK = 32, LDK = BK + 8;   // row stride 80 B: 16-B aligned
-    __shared__ T As[NS][BM][LDK];
-    __shared__ T Bs[NS][BN][LDK];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave / WAVES_N, wn = wave % WAVES_N;
-    const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
-    const int k_lo = blockIdx.z * g.kchunk;
-    const int k_hi = min(g.K, k_lo + g.kchunk);
-    const bool a_kfast = g.sak == 1, b_kfast = g.sbk == 1;
-    f4 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = pf_splat(0.f);
-    // one element -> its NS parts
-    auto split_store = [&](T* p0, long long part_stride, float x) {
-        if constexpr (NS == 2) {
-            const _Float16 h = (_Float16)x;
-            p0[0] = h;
-            p0[part_stride] = (_Float16)(x - (float)h);
-        } else {
-            const __bf16 h = (__bf16)x;
-            const float r1 = x - (float)h;
-            const __bf16 m = (__bf16)r1;
-            p0[0] = h;
-            p0[part_stride] = m;
-            p0[2 * part_stride] = (__bf16)(r1 - (float)m);
-        }
-    };
-    constexpr long long PSA = (long long)BM * LDK, PSB = (long long)BN * LDK;
-
-    for (int k0 = k_lo; k0 < k_hi; k0 += BK) {
-        // ---- stage A [BM][BK] and B^T [BN][BK], converting on the way
-        for (int v = tid; v < BM * (BK / 4); v += 256) {
-            int r, k;
-            f4 x = pf_splat(0.f);
-            if (a_kfast) {                                      // 4 consecutive k of one row
-                r = v / (BK / 4); k = (v % (BK / 4)) * 4;
-                const int gm = m0 + r, gk = k0 + k;
-                if (gm < g.M) {
-                    if (VEC && gk + 3 < k_hi) x = *reinterpret_cast<const f4*>(g.A + gm * g.sam + gk);
-                    else
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) if (gk + e < k_hi) x[e] = g.A[gm * g.sam + (gk + e) * g.sak];
-                }
-#pragma unroll
-                for (int e = 0; e < 4; ++e) split_store(&As[0][r][k + e], PSA, x[e]);
-            } else {                                            // 4 consecutive rows of one k
-                k = v / (BM / 4); r = (v % (BM / 4)) * 4;
-                const int gm = m0 + r, gk = k0 + k;
-                if (gk < k_hi) {
-                    if (VEC && gm + 3 < g.M) x = *reinterpret_cast<const f4*>(g.A + gk * g.sak + gm * g.sam);
-                    else
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) if (gm + e < g.M) x[e] = g.A[(gm + e) * g.sam + gk * g.sak];
-                }
-#pragma unroll
-                for (int e = 0; e < 4; ++e) split_store(&As[0][r + e][k], PSA, x[e]);
-            }
-        }
-        for (int v = tid; v < BN * (BK / 4); v += 256) {
-            int n, k;
-            f4 x = pf_splat(0.f);
-            if (b_kfast) {                                      // 4 consecutive k of one column n
-                n = v / (BK / 4); k = (v % (BK / 4)) * 4;
-                const int gn = n0 + n, gk = k0 + k;
-                if (gn < g.N) {
-                    if (VEC && gk + 3 < k_hi) x = *reinterpret_cast<const f4*>(g.B + gn * g.sbn + gk);
-                    else
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) if (gk + e < k_hi) x[e] = g.B[(gk + e) * g.sbk + gn * g.sbn];
-                }
-#pragma unroll
-                for (int e = 0; e < 4; ++e) split_store(&Bs[0][n][k + e], PSB, x[e]);
-            } else {                                            // 4 consecutive n of one k
-                k = v / (BN / 4); n = (v % (BN / 4)) * 4;
-                const int gn = n0 + n, gk = k0 + k;
-                if (gk < k_hi) {
-                    if (VEC && gn + 3 < g.N) x = *reinterpret_cast<const f4*>(g.B + gk * g.sbk + gn * g.sbn);
-                    else
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) if (gn + e < g.N) x[e] = g.B[gk * g.sbk + (gn + e) * g.sbn];
-                }
-#pragma unroll
-                for (int e = 0; e < 4; ++e) split_store(&Bs[0][n + e][k], PSB, x[e]);
-            }
-        }
-        __syncthreads();
-        T8 a[NS][TM], b[NS][TN];
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-#pragma unroll
-            for (int i = 0; i < TM; ++i) a[s][i] = *reinterpret_cast<const T8*>(&As[s][(wm * TM + i) * 16 + (lane & 15)][8 * (lane >> 4)]);
-#pragma unroll
-            for (int j = 0; j < TN; ++j) b[s][j] = *reinterpret_cast<const T8*>(&Bs[s][(wn * TN + j) * 16 + (lane & 15)][8 * (lane >> 4)]);
-        }
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                f4 x = acc[i][j];
-                if constexpr (NS == 2) {
-                    x = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[0][i], b[1][j], x, 0, 0, 0);
-                    x = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[1][i], b[0][j], x, 0, 0, 0);
-                    x = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[0][i], b[0][j], x, 0, 0, 0);
-                } else {
-                    x = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0][i], b[2][j], x, 0, 0, 0);
-                    x = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[2][i], b[0][j], x, 0, 0, 0);
-                    x = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1][i], b[1][j], x, 0, 0, 0);
-                    x = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0][i], b[1][j], x, 0, 0, 0);
-                    x = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1][i], b[0][j], x, 0, 0, 0);
-                    x = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0][i], b[0][j], x, 0, 0, 0);
-                }
-                acc[i][j] = x;
-            }
-        __syncthreads();
-    }
-    float* C = g.C + (long long)blockIdx.z * g.M * g.ldc;
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int n = n0 + (wn * TN + j) * 16 + (lane & 15);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int m = m0 + (wm * TM + i) * 16 + 4 * (lane >> 4) + r;
-                if (m < g.M && n < g.N) C[m * g.ldc + n] = acc[i][j][r] + (g.bias ? g.bias[n] : 0.f) + (g.add ? g.add[m * g.ldc + n] : 0.f);
-            }
-        }
-}
-
-template <int WAVES_M, int WAVES_N, int TM, int TN>
-void gemm_split_launch(int ns, const GemmArgs& g, int split, bool vec, hipStream_t s) {
-    constexpr int BM = WAVES_M * TM * 16, BN = WAVES_N * TN * 16;
-    const dim3 grid((g.N + BN - 1) / BN, (g.M + BM - 1) / BM, split);
-    if (ns == 2) {
-        if (vec) hipLaunchKernelGGL((gemm_split_kernel<2, WAVES_M, WAVES_N, TM, TN, true>), grid, dim3(256), 0, s, g);
-        else hipLaunchKernelGGL((gemm_split_kernel<2, WAVES_M, WAVES_N, TM, TN, false>), grid, dim3(256), 0, s, g);
-    } else {
-        if (vec) hipLaunchKernelGGL((gemm_split_kernel<3, WAVES_M, WAVES_N, TM, TN, true>), grid, dim3(256), 0, s, g);
-        else hipLaunchKernelGGL((gemm_split_kernel<3, WAVES_M, WAVES_N, TM, TN, false>), grid, dim3(256), 0, s, g);
-    }
-}
-
-template <int WAVES_M, int WAVES_N, int TM, int TN>
-void gemm_launch(const GemmArgs& g, int split, bool vec, hipStream_t s) {
-    constexpr int BM = WAVES_M * TM * 16, BN = WAVES_N * TN * 16;
-    const dim3 grid((g.N + BN - 1) / BN, (g.M + BM - 1) / BM, split);
-    if (vec) hipLaunchKernelGGL((gemm_kernel<WAVES_M, WAVES_N, TM, TN, true>), grid, dim3(256), 0, s, g);
-    else hipLaunchKernelGGL((gemm_kernel<WAVES_M, WAVES_N, TM, TN, false>), grid, dim3(256), 0, s, g);
-}
-
-#ifndef PF_GEMM_T9
-#define PF_GEMM_T9 256
-#endif
-#ifndef PF_GEMM_SMALL_TILES
-#define PF_GEMM_SMALL_TILES 1
-#endif
-// 64 x 64 tiles (shape 7), or - where those leave the chip with one 4-wave workgroup per CU or less (the [8192, 32..128] input
-// gradients of the EdgeConv units: 128 / 256 tiles, every k-step's loads exposed) - 32 x 32 (9; 32 x 64 = 8 for N <= 32).  Same box,
-// [8192, C] x K = 4 S: C = 32: 14.4 -> 10.6 us, 64: 24.9 -> 15.7, 128: 25.1 -> 21.9; training step 4.13 -> 4.08 ms
-inline int gemm_small_tile(int M, int N) {
-#if PF_GEMM_SMALL_TILES
-    const long long t64 = (long long)((M + 63) / 64) * ((N + 63) / 64);
-    if (t64 <= PF_GEMM_T9 && M >= 32 && N > 32) return 9;
-    if (t64 <= 256 && M >= 32) return 8;
-#endif
-    return 7;
-}
-// tile shape for (M, N): 0 = 128x128, 1..3 = 256 x {16,32,64} (skinny N), 4..6 = {16,32,64} x 256 (skinny M)
-inline int gemm_shape(int M, int N) {
-    // a skinny output whose 256-row tiles would not even give every second CU a workgroup (the [8192, 16..64] input-gradient
-    // GEMMs of the training step: 32 tiles, 65 us for 0.27 G MAC) takes 64 x 64 tiles instead: 4 x the workgroups, no split-K
-    // reduction, the wasted tile columns cost nothing at this size
-    if (N <= 64 && M > 64 && (M + 255) / 256 < 128 && (M + 63) / 64 >= 64) return gemm_small_tile(M, N);
-    if (N <= 16) return 1;
-    if (N <= 32) return 2;
-    if (N <= 64 && M > 64) return 3;
-    if (M <= 16) return 4;
-    if (M <= 32) return 5;
-    if (M <= 64) return 6;
-    // 128 x 128 tiles leave most CUs idle on the point-level GEMMs of the training step ([8192, 128..512] outputs: 64..256
-    // tiles, one 1-wave-per-SIMD workgroup per CU): 64 x 64 tiles there
-    if ((long long)((M + 127) / 128) * ((N + 127) / 128) < 1024) return gemm_small_tile(M, N);
-    return 0;
-}
-inline void gemm_tile_dims(int shape, int& bm, int& bn) {
-    static const int d[10][2] = {{128, 128}, {256, 16}, {256, 32}, {256, 64}, {16, 256}, {32, 256}, {64, 256}, {64, 64}, {32, 64},
-                                 {32, 32}};
-    bm = d[shape][0]; bn = d[shape][1];
-}
-
-// C = sum over split-K slabs (+ bias): 64 consecutive outputs x 4 slab lanes per workgroup, fixed combine order
-__global__ __launch_bounds__(256) void gemm_reduce_kernel(const float* __restrict__ slabs, float* C,
-                                                         const float* __restrict__ bias, int M, int N, long long ldc,
-                                                         int nslab, const float* add) {
-    __shared__ float sh[4][64];
-    const int l = threadIdx.x & 63, part = threadIdx.x >> 6;
-    const long long t = (long long)blockIdx.x * 64 + l;
-    const long long MN = (long long)M * N;
-    float s = 0.f;
-    if (t < MN)
-        for (int z = part; z < nslab; z += 4) s += slabs[(long long)z * MN + t];
-    sh[part][l] = s;
-    __syncthreads();
-    if (part == 0 && t < MN) {
-        const int m = (int)(t / N), n = (int)(t % N);
-        C[m * ldc + n] = ((sh[0][l] + sh[1][l]) + (sh[2][l] + sh[3][l])) + (bias ? bias[n] : 0.f) + (add ? add[m * ldc + n] : 0.f);
-    }
-}
 
 // ----------------------------------------------------------------------------- column statistics
 // partial[chunk][which][c] over rows [chunk*rows_per, ...): MODE 0: sum x          (1 value)
@@ -902,115 +347,6 @@ inline unsigned grid_for(long long total) {
 }
 
 }  // namespace
-
-// C[M,N] = A(M,K) B(K,N) (+ bias[N]); generic element strides.  ws: split-K slabs (>= pf_gemm_ws_floats).
-extern "C" long long pf_gemm_ws_floats(int M, int N, int K) {
-    int bm, bn;
-    gemm_tile_dims(gemm_shape(M, N), bm, bn);
-    const long long tiles = (long long)((M + bm - 1) / bm) * ((N + bn - 1) / bn);
-    // split-K when the output has too few tiles to fill 256 CUs (dW GEMMs: tiny M x N, K = rows up to 131072):
-    // aim at ~1024 workgroups, K chunks of at least 128, slabs capped at 16 M floats
-    int split = 1;
-    if (tiles < 512 && K >= 1024) {
-        long long sp = (1024 + tiles - 1) / tiles;
-        if (sp > K / 128) sp = K / 128;
-        const long long cap = (16ll << 20) / ((long long)M * N);
-        if (sp > cap) sp = cap;
-        if (sp > 256) sp = 256;
-        split = sp < 1 ? 1 : (int)sp;
-    }
-    return split > 1 ? (long long)split * M * N : 0;
-}
-
-// arith: 0 = f32 MFMA (bit-exact fp32 fma chain; gemm2_kernel when both operands take float4 loads), 1 = the same on the round-1
-// kernel (gemm_kernel: the A/B reference of tests/test_gpu_train_fused.py, bit-identical results), 2 = split-fp16 (forward GEMMs), 3 = split-bf16 (gradient operands)
-extern "C" int pf_gemm_ex(int arith, const float* A, long long sam, long long sak, const float* B, long long sbk, long long sbn,
-                          float* C, long long ldc, const float* bias, int M, int N, int K, float* ws, long long ws_floats,
-                          void* stream) {
-    return pf_gemm_addend(arith, A, sam, sak, B, sbk, sbn, C, ldc, bias, nullptr, M, N, K, ws, ws_floats, stream, nullptr);
-}
-// (internal, pf_api_internal.h) the same with an addend: C = A B + bias + addend, addend [M, ldc] laid out like C (it may be C)
-int pf_gemm_addend(int arith, const float* A, long long sam, long long sak, const float* B, long long sbk, long long sbn,
-                   float* C, long long ldc, const float* bias, const float* addend, int M, int N, int K, float* ws,
-                   long long ws_floats, void* stream, int* slabs_left) {
-    if (slabs_left) *slabs_left = 0;
-    if (arith != 0 && arith != 1 && arith != 2 && arith != 3) return PF_ERR_UNSUPPORTED;
-    if (!A || !B || !C) return PF_ERR_NULL;
-    if (M <= 0 || N <= 0 || K <= 0) return PF_ERR_SHAPE;
-    const long long need = pf_gemm_ws_floats(M, N, K);
-    int split = need ? (int)(need / ((long long)M * N)) : 1;
-    if (need && (!ws || ws_floats < need)) return PF_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    const bool use_ws = split > 1;
-    GemmArgs g{A, sam, sak, B, sbk, sbn, use_ws ? ws : C, use_ws ? (long long)N : ldc, use_ws ? nullptr : bias, M, N, K, 0,
-               use_ws ? nullptr : addend};
-    g.kchunk = ((K + split - 1) / split + 31) / 32 * 32;
-    split = (K + g.kchunk - 1) / g.kchunk;
-    // float4 path: the contiguous dimension of each operand must be 4-aligned in extent, stride and base
-    auto al16 = [](const void* p) { return (reinterpret_cast<unsigned long long>(p) & 15ull) == 0; };
-    const bool va = (sak == 1) ? (K % 4 == 0 && sam % 4 == 0 && g.kchunk % 4 == 0) : (sam == 1 && M % 4 == 0 && sak % 4 == 0);
-    const bool vb = (sbn == 1) ? (N % 4 == 0 && sbk % 4 == 0) : (sbk == 1 && K % 4 == 0 && sbn % 4 == 0);
-    const bool vec = va && vb && al16(A) && al16(B);
-    if (arith >= 2) {
-        // float4 staging of the split kernel: 4 consecutive elements along each operand's contiguous dimension
-        const bool va2 = (sak == 1) ? (sam % 4 == 0) : (sam == 1 && sak % 4 == 0);
-        const bool vb2 = (sbk == 1) ? (sbn % 4 == 0) : (sbn == 1 && sbk % 4 == 0);
-        const bool vec2 = va2 && vb2 && al16(A) && al16(B) && (sak == 1 || sam == 1) && (sbk == 1 || sbn == 1);
-        switch (gemm_shape(M, N)) {
-            case 0: gemm_split_launch<2, 2, 4, 4>(arith, g, split, vec2, s); break;
-            case 1: gemm_split_launch<4, 1, 4, 1>(arith, g, split, vec2, s); break;
-            case 2: gemm_split_launch<4, 1, 4, 2>(arith, g, split, vec2, s); break;
-            case 3: gemm_split_launch<4, 1, 4, 4>(arith, g, split, vec2, s); break;
-            case 4: gemm_split_launch<1, 4, 1, 4>(arith, g, split, vec2, s); break;
-            case 5: gemm_split_launch<1, 4, 2, 4>(arith, g, split, vec2, s); break;
-            case 7: case 8: case 9: gemm_split_launch<2, 2, 2, 2>(arith, g, split, vec2, s); break;
-            default: gemm_split_launch<1, 4, 4, 4>(arith, g, split, vec2, s); break;
-        }
-    } else if (arith == 0 && vec) {
-        switch (gemm_shape(M, N)) {
-            case 0: gemm2_launch<2, 2, 4, 4>(g, split, s); break;
-            case 1: gemm2_launch<4, 1, 4, 1>(g, split, s); break;
-            case 2: gemm2_launch<4, 1, 4, 2>(g, split, s); break;
-            case 3: gemm2_launch<4, 1, 4, 4>(g, split, s); break;
-            case 4: gemm2_launch<1, 4, 1, 4>(g, split, s); break;
-            case 5: gemm2_launch<1, 4, 2, 4>(g, split, s); break;
-            case 7: gemm2_launch<2, 2, 2, 2>(g, split, s); break;
-            case 8: gemm2_launch<2, 2, 1, 2>(g, split, s); break;
-            case 9: gemm2_launch<2, 2, 1, 1>(g, split, s); break;
-            default: gemm2_launch<1, 4, 4, 4>(g, split, s); break;
-        }
-    } else
-    switch (gemm_shape(M, N)) {
-        case 0: gemm_launch<2, 2, 4, 4>(g, split, vec, s); break;
-        case 1: gemm_launch<4, 1, 4, 1>(g, split, vec, s); break;
-        case 2: gemm_launch<4, 1, 4, 2>(g, split, vec, s); break;
-        case 3: gemm_launch<4, 1, 4, 4>(g, split, vec, s); break;
-        case 4: gemm_launch<1, 4, 1, 4>(g, split, vec, s); break;
-        case 5: gemm_launch<1, 4, 2, 4>(g, split, vec, s); break;
-        case 7: case 8: case 9: gemm_launch<2, 2, 2, 2>(g, split, vec, s); break;
-        default: gemm_launch<1, 4, 4, 4>(g, split, vec, s); break;
-    }
-    if (use_ws && slabs_left && !bias && !addend) *slabs_left = split;       // the caller sums the slabs itself
-    else if (use_ws)
-        hipLaunchKernelGGL(gemm_reduce_kernel, dim3((unsigned)(((long long)M * N + 63) / 64)), dim3(256), 0, s, ws, C, bias, M,
-                           N, ldc, split, addend);
-    return pf_last_launch_status();
-}
-
-// C [M, ldc] = sum of nslab split-K slabs [nslab][M * N] (fixed combine order): the reduction step of pf_gemm, for callers that
-// produce their own slabs (csrc/train_fused.hip)
-extern "C" int pf_gemm_reduce(const float* slabs, float* C, int M, int N, long long ldc, int nslab, void* stream) {
-    if (!slabs || !C) return PF_ERR_NULL;
-    if (M <= 0 || N <= 0 || nslab <= 0) return PF_ERR_SHAPE;
-    hipLaunchKernelGGL(gemm_reduce_kernel, dim3((unsigned)(((long long)M * N + 63) / 64)), dim3(256), 0, (hipStream_t)stream, slabs, C,
-                       (const float*)nullptr, M, N, ldc, nslab, (const float*)nullptr);
-    return pf_last_launch_status();
-}
-
-extern "C" int pf_gemm(const float* A, long long sam, long long sak, const float* B, long long sbk, long long sbn, float* C,
-                       long long ldc, const float* bias, int M, int N, int K, float* ws, long long ws_floats, void* stream) {
-    return pf_gemm_ex(0, A, sam, sak, B, sbk, sbn, C, ldc, bias, M, N, K, ws, ws_floats, stream);
-}
 
 // BatchNorm(train) + LeakyReLU forward on x [R,C].  save [2][C] = mean, invstd (out); running stats updated in place
 // (nullable); ws >= 2*nchunk*C + 2*C floats with nchunk = pf_bn_chunks(R).

@@ -1,7 +1,7 @@
 """The training step: its switches and the train-mode forward of PointInterpFlow, assembled from the autograd nodes of the HIP
 training kernels.  Four modules, each importing only the ones before it:
   train_state    per-(device, stream) caches, SyncBN callback, weight-gradient stream, per-call state; no autograd node
-  train_perop    the per-op reference tier: one kernel pair per eager op (csrc/train_ops.hip)
+  train_perop    the per-op reference tier: one kernel pair per eager op (csrc/train_ops.hip, csrc/train_gemm.hip)
   train_fusedfn  the fused nodes (unit, MLP, flow block piece, flow chain); they read no switch
   train_ops      every switch and every function that reads one, forward_train and its stages; re-exports the names above
 The tests assign to the switches on THIS module (train_ops._FUSED = False): a copy elsewhere would not see it.

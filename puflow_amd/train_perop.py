@@ -1,5 +1,5 @@
-"""The per-op reference tier of the training step: one kernel pair per eager op of the reference (csrc/train_ops.hip), wired into
-autograd.  The fused tiers (train_fusedfn) are tested against it; RepeatRowsFn, GatherRowsFn, SoftmaxWsumFn and BatchSumFn
+"""The per-op reference tier of the training step: one kernel pair per eager op of the reference (csrc/train_ops.hip; the GEMM:
+csrc/train_gemm.hip), wired into autograd.  The fused tiers (train_fusedfn) are tested against it; RepeatRowsFn, GatherRowsFn, SoftmaxWsumFn and BatchSumFn
 also serve the default path.  Reads no switch of train_ops (PF_TRAIN_GEMM is its own).  Activations are channels-last [rows, C] fp32."""
 from __future__ import annotations
 
@@ -15,7 +15,7 @@ from .train_state import _ptr, _stream, _sync_bn_active, _ws, deterministic
 
 # Matrix-pipe arithmetic of the training GEMMs: "f32" (default) = every GEMM on the f32 MFMA (bit-exact fp32 fma chains);
 # "split" = forward GEMMs as split-fp16 products (3 fp16 MFMAs per 32-deep step), GEMMs with a gradient operand as
-# split-bf16 (6 bf16 MFMAs, fp32 exponent range) - csrc/train_ops.hip gemm_split_kernel.  Measured at 32 x (256 -> 1024):
+# split-bf16 (6 bf16 MFMAs, fp32 exponent range) - csrc/train_gemm.hip gemm_split_kernel.  Measured at 32 x (256 -> 1024):
 # the same step time (the layer GEMMs of this un-fused path are bound by staging and launch count, not by the MFMA rate:
 # profiles/r2_train), so the exact arithmetic stays the default; the gradient tests pass in both modes.
 _GEMM_MODE = os.environ.get("PF_TRAIN_GEMM", "f32")

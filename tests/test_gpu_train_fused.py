@@ -486,10 +486,11 @@ def test_edgeconv_unit_persistent_forward_matches_the_per_layer_kernels(cin, odi
     train_ops.check_persist_status()
 
 
-# ---- round 5: pf_gemm on conflict-free LDS images (gemm2_kernel) = the round-1 kernel bit for bit ---------------------------
+# ---- pf_gemm: the fast path (gemm2_kernel: float4 loads, conflict-free LDS images) = the general kernel (gemm_kernel) bit for bit ----
 # operand orientations of the three point GEMMs of an EdgeConv unit (train_ec_fwd.hip / train_fused.hip: PQ = x Wpq^T + b, dx = dPQ Wpq,
-# dWpq = dPQ^T x with split-K) plus ragged shapes, every tile shape of gemm_shape()
-@pytest.mark.parametrize("M,N,K,a_kfast,b_nfast,bias", [
+# dWpq = dPQ^T x with split-K) plus ragged shapes, every tile shape of gemm_shape(); the last three take no float4 loads, so
+# arith 0 itself runs the general kernel there (the path of cnf.py's cd + 1 strides)
+_GEMM_SHAPES = [
     (8192, 512, 128, True, False, True),        # PQ forward, 128-channel unit
     (8192, 128, 512, True, True, False),        # dx
     (512, 128, 8192, False, True, False),       # dWpq (split-K slabs + reduce)
@@ -502,26 +503,59 @@ def test_edgeconv_unit_persistent_forward_matches_the_per_layer_kernels(cin, odi
     (1000, 72, 100, True, False, True),         # ragged rows / columns, K not a multiple of 32
     (260, 260, 36, False, True, True),
     (4096, 512, 512, True, False, False),       # 128 x 128 tiles
-])
-def test_gemm_conflict_free_kernel_is_bit_identical(M, N, K, a_kfast, b_nfast, bias):
+    (67, 33, 45, True, False, True),            # odd strides, ragged 256 x 64 tile, K not a multiple of 16
+    (33, 70, 50, True, True, True),             # N not a multiple of 4 with an n-contiguous B
+    (130, 20, 1030, False, True, False),        # M not a multiple of 4 with an m-contiguous A; split-K slabs + reduce
+]
+_GEMM_CASES = {}
+
+
+def _gemm_case(M, N, K, a_kfast, b_nfast, bias):
+    """Operands, strides and the float64 product of one shape: made once, shared by the GEMM tests, never written."""
+    key = (M, N, K, a_kfast, b_nfast, bias)
+    if key not in _GEMM_CASES:
+        g = torch.Generator().manual_seed(M + 3 * N + 7 * K)
+        A = torch.randn((M, K) if a_kfast else (K, M), generator=g).cuda()
+        Bm = torch.randn((K, N) if b_nfast else (N, K), generator=g).cuda()
+        b = torch.randn(N, generator=g).cuda() if bias else None
+        ref = (A if a_kfast else A.t()).double() @ (Bm if b_nfast else Bm.t()).double()
+        if bias:
+            ref = ref + b.double()
+        _GEMM_CASES[key] = (A, (K, 1) if a_kfast else (1, M), Bm, (N, 1) if b_nfast else (1, K), b, ref)
+    return _GEMM_CASES[key]
+
+
+def _gemm_run(case, M, N, K, arith):
     from puflow_amd import train_ops as T
-    g = torch.Generator().manual_seed(M + 3 * N + 7 * K)
-    A = torch.randn((M, K) if a_kfast else (K, M), generator=g).cuda()
-    Bm = torch.randn((K, N) if b_nfast else (N, K), generator=g).cuda()
-    b = torch.randn(N, generator=g).cuda() if bias else None
-    sam, sak = (K, 1) if a_kfast else (1, M)
-    sbk, sbn = (N, 1) if b_nfast else (1, K)
-    out = []
-    for arith in (0, 1):
-        C = torch.full((M, N), float("nan"), device="cuda")
-        T._gemm(A, sam, sak, Bm, sbk, sbn, C, N, b, M, N, K, arith)
-        out.append(C)
+    A, (sam, sak), Bm, (sbk, sbn), b, _ = case
+    C = torch.full((M, N), float("nan"), device="cuda")
+    T._gemm(A, sam, sak, Bm, sbk, sbn, C, N, b, M, N, K, arith)
+    return C
+
+
+@pytest.mark.parametrize("M,N,K,a_kfast,b_nfast,bias", _GEMM_SHAPES)
+def test_gemm_fast_path_is_bit_identical_to_the_general_kernel(M, N, K, a_kfast, b_nfast, bias):
+    case = _gemm_case(M, N, K, a_kfast, b_nfast, bias)
+    ref = case[-1]
+    out = [_gemm_run(case, M, N, K, arith) for arith in (0, 1)]
     torch.cuda.synchronize()
-    ref = (A if a_kfast else A.t()).double() @ (Bm if b_nfast else Bm.t()).double()
-    if bias:
-        ref = ref + b.double()
     assert torch.equal(out[0], out[1]), float((out[0] - out[1]).abs().max())
     assert float((out[0].double() - ref).abs().max()) <= 2e-6 * K ** 0.5 * float(ref.abs().max() + 1)
+
+
+@pytest.mark.parametrize("M,N,K,a_kfast,b_nfast,bias", _GEMM_SHAPES[-3:] + [_GEMM_SHAPES[9], _GEMM_SHAPES[2]])
+def test_gemm_split_precision_kernels_are_fp32_class(M, N, K, a_kfast, b_nfast, bias):
+    """gemm_split_kernel (PF_TRAIN_GEMM=split): arith 2 = hi / lo fp16 parts, 3 products; arith 3 = hi / mid / lo bf16 parts,
+    6 products - with and without float4 staging, ragged tiles, split-K slabs with the reduce.  Every output element is written
+    (NaN prefill) and lies inside the f32 path's own float64 bound: the dropped lo x lo terms are 2^-22 relative per product
+    (a CPU emulation of both arithmetics on these shapes stays at <= 2.5 % of the bound, the f32 path at <= 2.3 %)."""
+    case = _gemm_case(M, N, K, a_kfast, b_nfast, bias)
+    ref = case[-1]
+    bound = 2e-6 * K ** 0.5 * float(ref.abs().max() + 1)
+    for arith in (2, 3):
+        err = float((_gemm_run(case, M, N, K, arith).double() - ref).abs().max())            # NaN if an element was left out
+        print(f"arith {arith} [{M} x {N} x {K}] max error {err:.3e} bound {bound:.3e}")
+        assert err <= bound, (arith, err, bound)
 
 
 @pytest.mark.gpu

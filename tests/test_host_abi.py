@@ -240,6 +240,19 @@ def test_training_entry_points_validate_their_descriptors(built_lib):
     assert lib.pf_cnf_steps(None, None, None, None, None, None, None, None, None, 1e-5, 1e-5, 16, 1, 1, None, 0, None) == -1
 
 
+def test_gemm_workspace_plan_is_pinned(built_lib):
+    """pf_gemm_ws_floats (csrc/train_gemm.hip gemm_plan: tile shape id -> tiles -> split-K count) on the 15 shapes of the GPU GEMM
+    tests: callers size their workspaces with it, and the split count behind it fixes the K chunks and so the bits of every
+    split-K product.  No launch.  (512, 128, 8192): 32 x 32 tiles, 64 of them, 16 slabs of M N floats."""
+    from puflow_amd import _lib
+    lib = _lib.load()
+    want = {(8192, 512, 128): 0, (8192, 128, 512): 0, (512, 128, 8192): 1048576, (8192, 128, 64): 0, (8192, 64, 32): 0,
+            (8192, 16, 128): 0, (8192, 32, 64): 0, (16, 256, 8192): 262144, (64, 128, 8192): 524288, (1000, 72, 100): 0,
+            (260, 260, 36): 0, (4096, 512, 512): 0, (67, 33, 45): 0, (33, 70, 50): 0, (130, 20, 1030): 20800}
+    got = {s: lib.pf_gemm_ws_floats(*s) for s in want}
+    assert got == want, {s: (got[s], want[s]) for s in want if got[s] != want[s]}
+
+
 def test_reduced_precision_library_has_the_same_surface(built_lib):
     """libpuflow_hip_f16.so (bench.py's secondary line) exports every symbol of the main library."""
     import ctypes

@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """Check A: compare kernels of two source trees (resources + instruction streams) for the default, bwdf32, gradf32 and f16 builds.
-python tools/cmp_isa.py PARENT_ROOT BRANCH_ROOT [--dump DIR]   (two checkouts; build container, no GPU)
+python tools/cmp_isa.py PARENT_ROOT BRANCH_ROOT [--dump DIR] [--removed REGEX] [--renamed REGEX REPL]
+(two checkouts; build container, no GPU)
+  --removed REGEX        kernel names that may exist at the parent only (a deleted kernel or template copy)
+  --renamed REGEX REPL   re.sub(REGEX, REPL, name) on the parent's kernel names before the two sides are matched
 
 A source is compiled when its own text differs between the trees or ANY header under csrc/ or include/ does (a header edit
 changes every kernel that includes it).  Verdict per kernel copy:
@@ -8,9 +11,9 @@ changes every kernel that includes it).  Verdict per kernel copy:
   reordered   same resource record, same instruction count, same multiset of (mnemonic, operand count): the streams differ by
               register names and the order of independent instructions only
   ISA DIFFERS anything else
-Exit status 0 only when every kernel is identical or reordered, none appeared or disappeared and none uses scratch that did
-not at the parent."""
-import collections, concurrent.futures, filecmp, hashlib, importlib.util, os, re, subprocess, sys, tempfile
+Exit status 0 only when every kernel is identical or reordered, none appeared or disappeared (--removed apart) and none uses
+scratch that did not at the parent."""
+import argparse, collections, concurrent.futures, filecmp, hashlib, importlib.util, os, re, subprocess, sys, tempfile
 
 # variant -> (defines, the sources build.py recompiles for it: None = all, a str = that attribute of build.py)
 VARIANTS = {"default": ([], None),
@@ -85,8 +88,14 @@ def histogram(lines):
 
 
 def main():
-    parent, branch = sys.argv[1], sys.argv[2]
-    dump = sys.argv[sys.argv.index("--dump") + 1] if "--dump" in sys.argv else None
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("parent")
+    ap.add_argument("branch")
+    ap.add_argument("--dump")
+    ap.add_argument("--removed")
+    ap.add_argument("--renamed", nargs=2, metavar=("REGEX", "REPL"))
+    args = ap.parse_args()
+    parent, branch, dump = args.parent, args.branch, args.dump
     trees = {"parent": parent, "branch": branch}
     Bs = {k: load_build(v) for k, v in trees.items()}
     hp, hb = headers(parent), headers(branch)
@@ -126,13 +135,15 @@ def main():
             for s in vfiles(k, v):
                 for name, lst in parse(jobs[(k, v, s)].result()).items():
                     allk.setdefault(name, []).extend([(s,) + x[1:] for x in lst])
+            if k == "parent" and args.renamed:
+                allk = {re.sub(args.renamed[0], args.renamed[1], name): lst for name, lst in allk.items()}
             side[k] = allk
         P, Bk = side["parent"], side["branch"]
         print(f"\n== {v}: parent {sum(map(len, P.values()))} kernels ({len(P)} names), branch {sum(map(len, Bk.values()))} kernels ({len(Bk)} names)")
         only_p, only_b = sorted(set(P) - set(Bk)), sorted(set(Bk) - set(P))
         print("   only in parent:", only_p or "none")
         print("   only in branch:", only_b or "none")
-        if only_b or [n for n in only_p if not re.search(r"::(ec_dw4_kernel|ec_dw5_kernel|ec_bwd_kernel<)", n)]:
+        if only_b or [n for n in only_p if not (args.removed and re.search(args.removed, n))]:
             ok = False
         nsame, reordered, differs = 0, [], []
         for name in sorted(set(P) & set(Bk)):

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """GPU box: the three point GEMMs of every EdgeConv unit of the training step (32 x 256 points), pf_gemm_ex arith 0
-(gemm2_kernel: conflict-free LDS images, round 5) against arith 1 (gemm_kernel, round 1): HIP events, interleaved rounds, one
-process, bit equality.   python tools/time_gemm.py"""
+(gemm2_kernel, the fast path: float4 loads, conflict-free LDS images) against arith 1 (gemm_kernel, the general path: any
+strides, scalar guarded loads - what arith 0 runs only where an operand takes no float4 loads, so this column is the cost of
+that path and not a rival of the first): HIP events, interleaved rounds, one process, bit equality.  Then arith 0, 2
+(split-fp16) and 3 (split-bf16) with their error against float64.   python tools/time_gemm.py"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -34,8 +36,8 @@ for name, M, N, K, akf, bnf in shapes:
     same = torch.equal(Cs[0], Cs[1])
     m0, m1 = sorted(ts[0])[len(ts[0]) // 2], sorted(ts[1])[len(ts[1]) // 2]
     tot[0] += m0; tot[1] += m1
-    print(f"{name:12s} [{M} x {N} x {K}]  gemm2 {m0:7.1f} us   gemm(v1) {m1:7.1f} us   {'bit-identical' if same else 'DIFFERENT'}", flush=True)
-print(f"sum          gemm2 {tot[0]:7.1f} us   gemm(v1) {tot[1]:7.1f} us")
+    print(f"{name:12s} [{M} x {N} x {K}]  gemm2 {m0:7.1f} us   general {m1:7.1f} us   {'bit-identical' if same else 'DIFFERENT'}", flush=True)
+print(f"sum          gemm2 {tot[0]:7.1f} us   general {tot[1]:7.1f} us")
 # the same shapes on the 16-bit pipe: arith 2 = split-fp16 (three products per term), 3 = split-bf16; error against float64
 for name, M, N, K, akf, bnf in shapes:
     A = torch.randn((M, K) if akf else (K, M), device="cuda")
