@@ -712,6 +712,25 @@ long long pf_cnf_rhs_vjp_workspace_bytes(int rows, int R);
 int pf_cnf_rhs_vjp(const float* y, const float* kbar, float t, float sgn, const float* ctx, const float* e, const float* rec,
                    float* ybar, float* ctxbar, float* grad, int rows, int R, void* ws, void* stream);
 
+/* The reverse sweep of n_steps recorded Dormand-Prince steps in ONE launch (+ one slab reduction): what 6 n_steps calls of
+ * pf_cnf_rhs_vjp, the stage recomputation by pf_cnf_rhs and the pf_lincomb combinations between them compute, with the step
+ * sizes as constants.  Per step, last to first: the stage states Y_1 .. Y_6 are recomputed from the step's start (FSAL is an
+ * ordinary dependence on it), then for j = 6 .. 1
+ *   kbar_j = h b_j y1bar + h sum_{m > j} a_mj Ybar_m,   Ybar_j = VJP_F(Y_j, sgn (s + alpha_j h); kbar_j),
+ * and y0bar = y1bar + sum_j Ybar_j is the cotangent the step before starts from (column 3 passes through: log p never enters f).
+ *   states [n_steps, rows, 4]  the state at the START of each accepted step, forward order
+ *   steps  [n_steps, 2]        DEVICE floats (s, h) in solver time, the fp32 values the forward was given (pf_cnf_steps_taped
+ *                              writes both arrays)
+ *   ybar   [rows,4]            in: the cotangent of the final state; out: the cotangent of states[0]
+ *   ctxbar, grad               +=, layout and units of pf_cnf_rhs_vjp; every evaluation's share of the 288 time-coefficient
+ *                              gradients carries that evaluation's own net time
+ * A workgroup keeps a 64-row tile's stage states and cotangents in LDS and its weight-gradient sums in registers over all
+ * stages, steps and tiles, and writes one slab: no grid barrier, no float atomics, the same bits from run to run.
+ * rows, R, ws: as pf_cnf_rhs_vjp (the workspace sizes are equal); n_steps >= 1. */
+long long pf_cnf_tape_vjp_workspace_bytes(int rows, int R);
+int pf_cnf_tape_vjp(const float* states, const float* steps, int n_steps, float sgn, const float* ctx, const float* e,
+                    const float* rec, float* ybar, float* ctxbar, float* grad, int rows, int R, void* ws, void* stream);
+
 /* One whole Dormand-Prince 5(4) step attempt per launch (the six stage evaluations fused, stage derivatives in
  * registers): y1 = y0 + h sum b_j k_j with k_1 = f0 (FSAL), f1 = k_7, ymid (nullable) = dense-output mid-point,
  * out[0] (double, device) = sum_i (err_i / (atol + rtol max(|y0_i|, |y1_i|)))^2 of the embedded error estimate.
@@ -738,6 +757,17 @@ int pf_cnf_context(const float* c, int cd, const float* hc_image, const float* h
 #define PF_CNF_SPLIT_GATES 1
 int pf_cnf_steps(double* ctl, float* ya, float* yb, float* fa, float* fb, const float* ctx, const float* e, const float* rec,
                  float* out, float rtol, float atol, int rows, int R, int n_attempts, double* ws, int flags, void* stream);
+
+/* pf_cnf_steps for an integration that pf_cnf_tape_vjp differentiates: the same controller state and batches of attempts, but
+ *   - the states go to a tape: states [cap + 1, rows, 4], the state at the start of accepted step k in states[k] (pf_cnf_init
+ *     writes states[0]); only fa / fb ping-pong;
+ *   - an accepted step is recorded, steps [cap, 2] = (s, h): the fp32 values the kernel computed with.  The time advances in
+ *     that arithmetic, s' = s + h in fp32, so the list is contiguous bit for bit;
+ *   - the step that would cover t1 is cut to END there (h = t1 - t): no dense output, the result is states[ctl[6]];
+ *   - status (ctl[9]) 3: cap steps are recorded and t1 is not reached - start again with a larger tape;
+ *   - plain gates (no PF_CNF_SPLIT_GATES): the arithmetic the sweep recomputes. */
+int pf_cnf_steps_taped(double* ctl, float* states, float* steps, int cap, float* fa, float* fb, const float* ctx, const float* e,
+                       const float* rec, float rtol, float atol, int rows, int R, int n_attempts, double* ws, void* stream);
 
 /* The start of that integration over [t0, t1] on the device, in two launches: the state rows y = (x, 0) from the points x
  * (row stride x_stride = 3 or 4 floats - a previous block's [rows,4] state is read in place), f0 = f(t0, y), ctl reset,

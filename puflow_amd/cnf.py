@@ -2,7 +2,7 @@
 
 Same constructor, methods and the 390 state-dict keys of the reference's continuous `PointInterpFlow`
 (`pretrain/puflow-x4-cnf-pu1k.pt` loads with `load_state_dict`).  The whole model is eval / inference only; ONE flow block is
-differentiable (`PointInterpFlow.flow_block`: taped Dormand-Prince steps, backward by `pf_cnf_rhs_vjp`, csrc/cnf_bwd.hip).
+differentiable (`PointInterpFlow.flow_block`: taped Dormand-Prince steps, backward by `pf_cnf_tape_vjp`, csrc/cnf_bwd.hip).
 
 What runs where:
   * kNN, the six EdgeConv units, the merge units and the interpolation module are the discrete model's kernels
@@ -12,8 +12,9 @@ What runs where:
     evaluations incl. the Hutchinson term, error norm) with dopri5's step-size CONTROL on the device (torchdiffeq semantics
     restated from its published algorithm, see oracle/cnf_ref.py header).  The controller states of the twelve integrations
     are read ONCE per forward; one that did not finish inside its attempts falls back to a read per batch of attempts;
-  * only `flow_block` steps from the host: one `pf_cnf_step` per attempt with the error norm read back, `pf_cnf_rhs`,
-    `pf_lincomb`, `pf_scaled_sumsq` around it, and `pf_cnf_rhs_vjp` in its backward (csrc/cnf.hip, csrc/cnf_bwd.hip).
+  * `flow_block`: the same controller recording a tape (`pf_cnf_steps_taped`) and ONE launch that sweeps the tape in reverse
+    (`pf_cnf_tape_vjp`, csrc/cnf_bwd.hip).  Its A/B references step from the host: one `pf_cnf_step` per attempt with the error
+    norm read back, `pf_cnf_rhs`, `pf_lincomb`, `pf_scaled_sumsq` around it, and `pf_cnf_rhs_vjp` per evaluation in the backward.
 
 Parity: the right-hand side is pinned to the reference's own ODEfunc (tests/golden/cnf_rhs.npz); the solver is UNPINNED
 (torchdiffeq is not installed and not vendored) - the integrated path is tested against oracle/cnf_ref.py, a from-text
@@ -195,6 +196,13 @@ class _CnfKernels:
                                          rows, R, int(attempts), self.ws1k.data_ptr(), self.split[i], self._stream()),
                    "pf_cnf_steps")
 
+    def _cnf_steps_taped(self, i, ctl, states, steps, fbuf, ctx, e, rows, R, attempts) -> None:
+        """pf_cnf_steps_taped: `attempts` attempts on the tape states [cap + 1, rows, 4] / steps [cap, 2], fbuf = (f0, f1) [2, rows, 4]."""
+        _lib.check(self.lib.pf_cnf_steps_taped(ctl.data_ptr(), states.data_ptr(), steps.data_ptr(), int(steps.shape[0]),
+                                               fbuf[0].data_ptr(), fbuf[1].data_ptr(), ctx.data_ptr(), e.data_ptr(),
+                                               self.rec[i].data_ptr(), RTOL, ATOL, rows, R, int(attempts), self.ws1k.data_ptr(),
+                                               self._stream()), "pf_cnf_steps_taped")
+
     def context_norm(self, c: Tensor, out: Tensor) -> None:
         """out[0] (device double) = sum (c / (atol + rtol |c|))^2: the context's share of the solver's initial-step norm."""
         _lib.check(self.lib.pf_scaled_sumsq(c.data_ptr(), None, c.data_ptr(), None, None, (ctypes.c_float * 1)(0.0), 0, 0.0,
@@ -328,6 +336,9 @@ class _BlockTapeEngine(_CnfKernels):
         self._init_kernels(device)
         self._add_block(sd_block, i)
         self.Hplain = torch.from_numpy(cnf_hyper_matrix(sd_block, i)[:, 1:].copy()).to(device)      # [288, cd], no folded constants
+        self.ws3k = torch.empty(3072, dtype=torch.float64, device=device)
+        self.ctl = torch.zeros(16, dtype=torch.float64, device=device)       # dopri5 controller state of the device-side tape
+        self.first_batch, self.next_batch = 8, 4                             # step attempts enqueued per look at the controller
 
     def step(self, i, y, f0, t, h, reverse, ctx, e, y1, f1, rows, R) -> float:
         """One Dormand-Prince attempt (pf_cnf_step) -> the scaled error sum, read back (one host read per attempt)."""
@@ -337,8 +348,56 @@ class _BlockTapeEngine(_CnfKernels):
         self.nfe += 6
         return float(self.red.item())
 
-    def tape_forward(self, i: int, x: Tensor, c: Tensor, e: Tensor, R: int, reverse: bool):
-        """dopri5 on block i with ONE attempt per launch and the control on the host (oracle/cnf_ref.py::dopri5 restated), except
+    def tape_forward(self, i: int, x: Tensor, c: Tensor, e: Tensor, R: int, reverse: bool, cap: int = 32):
+        """dopri5 on block i with the control on the DEVICE (pf_cnf_init, then batches of pf_cnf_steps_taped attempts with one read
+        of the controller per batch, as `_CnfEngine.integrate`), the step that would cover the end time cut to END there: the
+        result is the last accepted step's solution, so the forward is exactly the recorded steps.  cap: steps the tape is
+        allocated for; a tape that fills up (status 3) is allocated anew at twice the size and the integration starts again.
+        -> (state [rows,4], tape): (s, h) per accepted step on the device (`steps_dev` [n,2], the fp32 values the kernels
+        computed with) and as host floats (`steps`, one read when done), the state at the start of each step (`states` [n,rows,4]),
+        the context rows and the derivatives at both ends."""
+        rows = x.shape[0]
+        dev = x.device
+        T = self.T_end[i]
+        t0, t1 = (0.0, T) if not reverse else (-T, 0.0)
+        ctx = self.context(i, c)
+        n_tot = float(rows * 4 + c.numel() * R)                 # the context is a state of the reference's ODE: it enters the norms
+        d0c = torch.empty(1, dtype=torch.float64, device=dev)
+        self.context_norm(c, d0c)
+        fbuf = torch.empty((2, rows, 4), dtype=torch.float32, device=dev)
+        cap = max(1, int(cap))
+        while True:
+            states = torch.empty((cap + 1, rows, 4), dtype=torch.float32, device=dev)
+            steps = torch.empty((cap, 2), dtype=torch.float32, device=dev)
+            self._cnf_init(i, self.ctl, x, states[0], fbuf[0], ctx, e, t0, t1, n_tot, d0c, float(R), reverse, rows, R)
+            f_start = fbuf[0].clone()                           # needed for dT when reversed; fbuf ping-pongs from here on
+            attempts, batch = 0, self.first_batch
+            while True:
+                self._cnf_steps_taped(i, self.ctl, states, steps, fbuf, ctx, e, rows, R, batch)
+                attempts += batch
+                st = self.ctl.cpu()                             # the one device->host read per batch of attempts
+                if st[5] != 0:
+                    break
+                if attempts > MAX_NUM_STEPS:
+                    raise _lib.PuflowHipError(f"dopri5: more than {MAX_NUM_STEPS} step attempts in block {i}")
+                batch = self.next_batch
+            self.nfe += int(st[8])
+            if st[9] != 3:
+                break
+            if cap > MAX_NUM_STEPS:
+                raise _lib.PuflowHipError(f"dopri5: more than {MAX_NUM_STEPS} accepted steps in block {i}")
+            cap *= 2
+        t, dt = float(st[0]), float(st[1])
+        if st[9] == 1:
+            raise _lib.PuflowHipError(f"dopri5: non-finite error norm in block {i} at t = {t:g}")
+        if st[9] == 2:
+            raise _lib.PuflowHipError(f"dopri5: underflow in dt ({dt:g}) at t = {t:g}, block {i}")
+        n = int(st[6])
+        host = [(float(s), float(h)) for s, h in steps[:n].cpu().tolist()]
+        return states[n], dict(steps=host, steps_dev=steps[:n], states=states[:n], ctx=ctx, f_start=f_start, f_end=fbuf[int(st[4])])
+
+    def tape_forward_host(self, i: int, x: Tensor, c: Tensor, e: Tensor, R: int, reverse: bool):
+        """The A/B reference of `tape_forward` (flow_block's controller="host"): ONE attempt per launch and the control on the host (oracle/cnf_ref.py::dopri5 restated), except
         that the step which would cover the end time is cut to END there: the result is the last accepted step's solution, not
         a dense-output value inside it, so the forward is exactly the recorded steps.
         -> (state [rows,4], tape): tape holds (s, h) per accepted step as host floats (the fp32 values the kernels were given),
@@ -387,19 +446,33 @@ class _BlockTapeEngine(_CnfKernels):
             raise _lib.PuflowHipError(f"dopri5: more than {MAX_NUM_STEPS} step attempts in block {i}")
         return y, dict(steps=steps, states=states, ctx=ctx, f_start=f_start, f_end=f0)
 
-    def vjp(self, i, y, kbar, t, sgn, ctx, e, ybar, ctxbar, grad, rows, R) -> None:
+    def _vjp_workspace(self, rows, R, dev) -> Tensor:
+        """The slab workspace of pf_cnf_rhs_vjp and pf_cnf_tape_vjp (the same size), kept per shape."""
         if getattr(self, "_vjp_shape", None) != (rows, R):
             need = self.lib.pf_cnf_rhs_vjp_workspace_bytes(rows, R)
             if need < 0:
                 raise _lib.PuflowHipError(f"pf_cnf_rhs_vjp: rows = {rows} must be a multiple of R = {R} <= 16")
-            self._vjp_ws = torch.empty(need // 4, dtype=torch.float32, device=y.device)
+            self._vjp_ws = torch.empty(need // 4, dtype=torch.float32, device=dev)
             self._vjp_shape = (rows, R)
+        return self._vjp_ws
+
+    def tape_vjp(self, i, states, steps_dev, sgn, ctx, e, ybar, ctxbar, grad, rows, R) -> None:
+        """pf_cnf_tape_vjp: the reverse sweep of the recorded steps in one launch; ybar [rows,4] in / out."""
+        ws = self._vjp_workspace(rows, R, ybar.device)
+        _lib.check(self.lib.pf_cnf_tape_vjp(states.data_ptr(), steps_dev.data_ptr(), int(steps_dev.shape[0]), float(sgn),
+                                            ctx.data_ptr(), e.data_ptr(), self.rec[i].data_ptr(), ybar.data_ptr(),
+                                            ctxbar.data_ptr(), grad.data_ptr(), rows, R, ws.data_ptr(), self._stream()),
+                   "pf_cnf_tape_vjp")
+
+    def vjp(self, i, y, kbar, t, sgn, ctx, e, ybar, ctxbar, grad, rows, R) -> None:
+        self._vjp_workspace(rows, R, y.device)
         _lib.check(self.lib.pf_cnf_rhs_vjp(y.data_ptr(), kbar.data_ptr(), float(t), float(sgn), ctx.data_ptr(), e.data_ptr(),
                                            self.rec[i].data_ptr(), ybar.data_ptr(), ctxbar.data_ptr(), grad.data_ptr(), rows, R,
                                            self._vjp_ws.data_ptr(), self._stream()), "pf_cnf_rhs_vjp")
 
-    def tape_backward(self, i: int, tape: dict, ybar: Tensor, c: Tensor, e: Tensor, R: int, reverse: bool):
-        """The recorded steps in reverse, step sizes as constants.  Per step the stage states are recomputed
+    def tape_backward(self, i: int, tape: dict, ybar: Tensor, c: Tensor, e: Tensor, R: int, reverse: bool, sweep: str = "fused"):
+        """The recorded steps in reverse, step sizes as constants.  sweep = "fused": one pf_cnf_tape_vjp launch for
+        the whole tape.  sweep = "per_eval", its A/B reference, launch by launch: per step the stage states are recomputed
         (pf_cnf_rhs), then for j = 6 .. 1:  kbar_j = h b_j y1bar + h sum_{m > j} a_mj Ybar_m  (pf_lincomb),
         Ybar_j = VJP_F(Y_j, t_j; kbar_j)  (pf_cnf_rhs_vjp, which also adds the evaluation's weight / context gradients), and
         y0bar = y1bar + sum_j Ybar_j.  -> (y0bar [rows,4], grad record [4900], ctxbar [T,288])."""
@@ -409,13 +482,23 @@ class _BlockTapeEngine(_CnfKernels):
         ctx = tape["ctx"]
         grad = torch.zeros(CNF_GRAD, dtype=torch.float32, device=dev)
         ctxbar = torch.zeros((c.shape[0], CNF_CTX), dtype=torch.float32, device=dev)
+        if sweep == "fused":
+            states, steps_dev = tape["states"], tape.get("steps_dev")
+            if not isinstance(states, Tensor):                                     # the host controller's tape: a list of states
+                states = torch.stack(states)
+            if steps_dev is None:
+                steps_dev = torch.tensor(tape["steps"], dtype=torch.float32, device=dev).reshape(-1, 2)
+            y0bar = ybar.clone()
+            self.tape_vjp(i, states.contiguous(), steps_dev.contiguous(), sgn, ctx, e, y0bar, ctxbar, grad, rows, R)
+            return y0bar, grad, ctxbar
         K = torch.empty((5, rows, 4), dtype=torch.float32, device=dev)             # k_1 .. k_5 of the step being swept
         Y = torch.empty((6, rows, 4), dtype=torch.float32, device=dev)
         Yb = torch.empty((6, rows, 4), dtype=torch.float32, device=dev)
         kb = torch.empty((rows, 4), dtype=torch.float32, device=dev)
         b = DP_BETA[5]
         alpha = [0.0] + DP_ALPHA[:5]
-        for (s, h), y0 in zip(reversed(tape["steps"]), reversed(tape["states"])):
+        for n in reversed(range(len(tape["steps"]))):
+            (s, h), y0 = tape["steps"][n], tape["states"][n]
             self._rhs(i, y0, y0, [], 0.0, sgn * s, sgn, ctx, e, K[0], None, rows, R)
             for j in range(1, 5):
                 self._rhs(i, y0, K, DP_BETA[j - 1], h, sgn * (s + alpha[j] * h), sgn, ctx, e, K[j], Y[j], rows, R)
@@ -438,12 +521,15 @@ class _FlowBlockFn(torch.autograd.Function):
     """(x, c, parameters of block i) -> (x', delta logp): `PointInterpFlow.flow_block`."""
 
     @staticmethod
-    def forward(fctx, x, c, e, i, R, reverse, keys, record, *params):
+    def forward(fctx, x, c, e, i, R, reverse, keys, record, opts, *params):
         sd = {k: p.detach().cpu() for k, p in zip(keys, params)}
         eng = _BlockTapeEngine(sd, i, x.device)
         x32, c32, e32 = x.detach().float().contiguous(), c.detach().float().contiguous(), e.detach().float().contiguous()
-        y, tape = eng.tape_forward(i, x32, c32, e32, R, reverse)
-        fctx.eng, fctx.tape, fctx.args = eng, tape, (i, R, reverse, keys, x.dtype, c.dtype)
+        if opts["controller"] == "device":
+            y, tape = eng.tape_forward(i, x32, c32, e32, R, reverse, opts["cap"])
+        else:
+            y, tape = eng.tape_forward_host(i, x32, c32, e32, R, reverse)
+        fctx.eng, fctx.tape, fctx.args = eng, tape, (i, R, reverse, keys, x.dtype, c.dtype, opts["sweep"])
         fctx.save_for_backward(c32, e32, *params)
         record.extend(tape["steps"])
         return y[:, :3].contiguous(), y[:, 3].contiguous()
@@ -451,16 +537,16 @@ class _FlowBlockFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(fctx, gx, gl):
-        i, R, reverse, keys, xdt, cdt = fctx.args
+        i, R, reverse, keys, xdt, cdt, sweep = fctx.args
         c, e, *params = fctx.saved_tensors
         eng, tape = fctx.eng, fctx.tape
-        rows = tape["states"][0].shape[0]
+        rows = tape["f_end"].shape[0]
         ybar = torch.zeros((rows, 4), dtype=torch.float32, device=c.device)
         if gx is not None:
             ybar[:, :3] = gx
         if gl is not None:
             ybar[:, 3] = gl
-        y0bar, grad, ctxbar = eng.tape_backward(i, tape, ybar, c, e, R, reverse)
+        y0bar, grad, ctxbar = eng.tape_backward(i, tape, ybar, c, e, R, reverse, sweep)
         # ctx = [1 | c] [hb | Hc]^T:  one GEMM for d(hb | Hc) = ctxbar^T [1 | c] (column 0: the column sums), one for dc
         T, cd = c.shape
         c1 = torch.cat([torch.ones((T, 1), dtype=torch.float32, device=c.device), c], dim=1).contiguous()
@@ -478,7 +564,7 @@ class _FlowBlockFn(torch.autograd.Function):
                 out.append((dT * 2.0 * p.detach()).reshape(p.shape).to(p.dtype))
             else:
                 out.append(grads[k].reshape(p.shape).to(p.dtype))
-        return (y0bar[:, :3].contiguous().to(xdt), dc.to(cdt), None, None, None, None, None, None, *out)
+        return (y0bar[:, :3].contiguous().to(xdt), dc.to(cdt), None, None, None, None, None, None, None, *out)
 
 
 class PointInterpFlow(nn.Module):
@@ -498,6 +584,8 @@ class PointInterpFlow(nn.Module):
         self.flow_blocks = nn.ModuleList([_CNFBlockParams(COND_CHANNELS[i]) for i in range(NUM_BLOCKS)])
         self._engine_cache: Optional[_CnfEngine] = None
         self.last_stats: dict = {}
+        # flow_block's device-side tape: steps to allocate it for, per (block, reverse) - what the last call took + an eighth + 2
+        self.tape_capacity: dict = {}
 
     def invalidate_plan(self) -> None:
         self._engine_cache = None
@@ -614,14 +702,18 @@ class PointInterpFlow(nn.Module):
             return dict(idx16=idx16, cs=cs, z=z, ldj=ldj, logp=logp, x=x, **self.last_stats)
         return x, logp
 
-    def flow_block(self, i: int, x: Tensor, c: Tensor, e: Tensor, R: int = 1, reverse: bool = False):
+    def flow_block(self, i: int, x: Tensor, c: Tensor, e: Tensor, R: int = 1, reverse: bool = False, sweep: str = "fused",
+                   controller: str = "device"):
         """One CNF flow block, differentiable: x [rows,3] (rows = T R, the R rows of a point adjacent), c [T,cd] context,
         e [T,3] Hutchinson vector -> (x' [rows,3], delta logp [rows]).  An autograd function over x, c and the parameters of
         `self.flow_blocks[i]` (e gets no gradient), whatever `self.training` says; the weight record is packed from the live
         parameters on every call, so an optimizer step needs no `invalidate_plan`.
         Forward: adaptive Dormand-Prince steps, one attempt per launch, the last step cut to end at the end time.  Backward: the
-        recorded steps in reverse, differentiating exactly what the forward computed with the step sizes as constants
-        (pf_cnf_rhs_vjp).  `sqrt_end_time` gets the CONTINUOUS formula dL/dT = sum(ybar(T) . k(T)) (reversed: -sum(xbar_in . k(T))
+        recorded steps in reverse, differentiating exactly what the forward computed with the step sizes as constants.
+        controller = "device": the step-size control runs on the device and records the tape there (pf_cnf_steps_taped, one host
+        read per batch of attempts; `self.tape_capacity` remembers how long a tape to allocate); "host": one host read per
+        attempt (pf_cnf_step).  sweep = "fused": the whole tape in one launch (pf_cnf_tape_vjp); "per_eval": pf_cnf_rhs_vjp per
+        evaluation with pf_cnf_rhs / pf_lincomb between them.  "host" and "per_eval" are the in-library A/B references.  `sqrt_end_time` gets the CONTINUOUS formula dL/dT = sum(ybar(T) . k(T)) (reversed: -sum(xbar_in . k(T))
         at the start) x 2 sqrt_end_time - NOT the derivative of the discrete scheme, whose step sizes do not depend on T here.
         `self.last_block_steps`: the (s, h) of the accepted steps in solver time (s = -t when reversed)."""
         if not (x.is_cuda and c.is_cuda and e.is_cuda):
@@ -630,11 +722,16 @@ class PointInterpFlow(nn.Module):
             raise ValueError("flow_block: x [T R,3], c [T,cd], e [T,3]")
         if not 1 <= R <= 16:
             raise ValueError("flow_block: 1 <= R <= 16 (pf_cnf_rhs_vjp keeps a point's R rows inside one 16-row MFMA tile)")
+        if sweep not in ("fused", "per_eval") or controller not in ("device", "host"):
+            raise ValueError('flow_block: sweep is "fused" or "per_eval", controller is "device" or "host"')
         pfx = f"flow_blocks.{i}."
         named = list(self.flow_blocks[i].named_parameters())
         keys = tuple(pfx + n for n, _ in named)
         steps: list = []
-        out = _FlowBlockFn.apply(x, c, e, int(i), int(R), bool(reverse), keys, steps, *[p for _, p in named])
+        opts = dict(sweep=sweep, controller=controller, cap=self.tape_capacity.get((int(i), bool(reverse)), 32))
+        out = _FlowBlockFn.apply(x, c, e, int(i), int(R), bool(reverse), keys, steps, opts, *[p for _, p in named])
+        if controller == "device":
+            self.tape_capacity[(int(i), bool(reverse))] = len(steps) + len(steps) // 8 + 2
         self.last_block_steps = steps
         return out
 

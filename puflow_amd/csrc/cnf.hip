@@ -2,7 +2,8 @@
 // bookkeeping of an adaptive Dormand-Prince solver.  Replaces ODEfunc.forward + ODEnet + ConcatSquashLinear
 // (modules/continuous/odefunc.py:60-148, diffeq_layers.py:72-86) and the arithmetic of torchdiffeq's dopri5
 // stages (called from modules/continuous/cnf.py:97-113).  The step-size CONTROL (a handful of scalars per step)
-// runs on the device for inference (cnf_ctl_update below) and on the host only under flow_block (puflow_amd/cnf.py).
+// runs on the device, for inference (cnf_ctl_update below) and for flow_block's tape (cnf_ctl_update_taped); on the host
+// only under flow_block's controller="host" reference path (puflow_amd/cnf.py).
 //
 // State rows are [y0 y1 y2 logp]; one MFMA column tile = 16 rows.  A ConcatSquash layer is
 //     out = (W x + b) * sigmoid(Wg [t; c] + bg) + Wb [t; c]
@@ -282,7 +283,7 @@ __global__ __launch_bounds__(CNF_NW * 64) void cnf_step_kernel(CnfStepArgs a) {
 // puflow_amd/cnf.py); the step kernel reads (t, dt, which buffer is current) from that state and is a no-op once the
 // integration is done, so the host can enqueue a batch of attempts and look at the state once per batch.
 //   ctl (doubles): [0] t  [1] dt  [2] t1  [3] n_tot  [4] cur (0/1)  [5] done  [6] accepted  [7] rejected  [8] nfe
-//                  [9] status (0 ok, 1 non-finite error norm, 2 dt underflow)  [10] reverse (0/1)
+//                  [9] status (0 ok, 1 non-finite error norm, 2 dt underflow, 3 tape full: taped variant only)  [10] reverse (0/1)
 // The step that covers t1 writes the dense-output value at t1 (quartic through y0, y_mid, y1: torchdiffeq's interpolation)
 // straight into `out`; if that attempt is rejected a later covering attempt overwrites it.
 
@@ -340,6 +341,52 @@ __device__ __forceinline__ void cnf_ctl_update(double* ctl, const double* partia
     if (!(t1 > tn)) ctl[CTL_DONE] = 1.0;
 }
 
+// The step size a taped attempt takes from the controller state: the step that would cover t1 is cut to end there.
+__device__ __forceinline__ float cnf_taped_h(const double* ctl, bool& cover) {
+    cover = ctl[CTL_T1] <= ctl[CTL_T] + ctl[CTL_DT];
+    return (float)(cover ? ctl[CTL_T1] - ctl[CTL_T] : ctl[CTL_DT]);
+}
+
+// The same decisions for the TAPED integration (pf_cnf_steps_taped; puflow_amd/cnf.py tape_forward's rule): the covering step is
+// cut, not interpolated, an accepted step is recorded as the fp32 pair (s, h) the kernel computed with, and the time advances in
+// that fp32 arithmetic, s' = s + h, so that the recorded list is contiguous bit for bit; the last step lands on t1 itself.
+// Status 3: the tape is full (cap steps recorded, t1 not reached).
+__device__ __forceinline__ void cnf_ctl_update_taped(double* ctl, const double* partial, int nblocks, double* red4, float* steps, int cap) {
+    const double sum = cnf_partial_total(partial, nblocks, red4);
+    if (threadIdx.x != 0) return;
+    const double ratio = sqrt(sum / ctl[CTL_NTOT]);
+    const double t = ctl[CTL_T], t1 = ctl[CTL_T1];
+    bool cover;
+    const float hf = cnf_taped_h(ctl, cover);
+    const float sf = (float)t;
+    const double tn = cover ? t1 : (double)(sf + hf);
+    ctl[CTL_NFE] += 6.0;
+    if (!(ratio == ratio) || ratio > 1.7e308) { ctl[CTL_STATUS] = 1.0; ctl[CTL_DONE] = 1.0; return; }
+    if (!(tn > t)) { ctl[CTL_STATUS] = 2.0; ctl[CTL_DONE] = 1.0; return; }
+    if (ratio <= 1.0) {
+        const int acc = (int)ctl[CTL_ACC];
+        steps[2 * acc] = sf; steps[2 * acc + 1] = hf;
+        ctl[CTL_ACC] = (double)(acc + 1);
+        ctl[CTL_T] = tn;
+        ctl[CTL_CUR] = 1.0 - ctl[CTL_CUR];                       // FSAL: f1 becomes the next f0 (the states go to the tape)
+        if (cover) ctl[CTL_DONE] = 1.0;
+        else if (acc + 1 >= cap) { ctl[CTL_STATUS] = 3.0; ctl[CTL_DONE] = 1.0; }
+    } else {
+        ctl[CTL_REJ] += 1.0;
+    }
+    const double h = (double)hf;
+    double ndt;
+    if (ratio == 0.0) ndt = h * 10.0;
+    else {
+        const double dfac = ratio < 1.0 ? 1.0 : 0.2;
+        double fac = 0.9 / pow(ratio, 1.0 / 5.0);
+        fac = fac > dfac ? fac : dfac;
+        fac = fac < 10.0 ? fac : 10.0;
+        ndt = h * fac;
+    }
+    ctl[CTL_DT] = ndt;
+}
+
 struct CnfDevArgs {
     double* ctl;
     float* yb[2];
@@ -349,13 +396,19 @@ struct CnfDevArgs {
     double* partial;
     float rtol, atol;
     int rows, R, ntiles;
+    float* states;           // TAPED: [cap + 1][rows][4], the state at the start of accepted step k in states[k]
+    float* steps;            // TAPED: [cap][2] (s, h) of the accepted steps
+    int cap;
 };
 
 // CTX_LDS (inverse direction, R >= 4 rows per original point): the context rows of the workgroup's 64 / R points are copied
 // to LDS once per tile and all six stage evaluations read them there - each evaluation re-read 1 152 B per row from L2 before
 // SPLIT (the caller's PF_CNF_SPLIT_GATES): see cnf_eval.  Without CTX_LDS (the forward pass, R = 1: 64 points per tile) only the
 // 144 gate columns of a point go to LDS, in the compact layout (cnf_eval<.., COMPACT>); the bias columns stay in global memory.
-template <bool CTX_LDS, bool SPLIT>
+// TAPED (pf_cnf_steps_taped, the forward a backward sweep replays): the states do not ping-pong, attempt number acc reads
+// states[acc] and writes states[acc + 1] (acc = accepted steps so far; a rejected attempt's result is overwritten by the next),
+// the covering step is cut to end at t1 and no dense output is written - the result is states[accepted].
+template <bool CTX_LDS, bool SPLIT, bool TAPED = false>
 __global__ __launch_bounds__(CNF_NW * 64, PF_CNF_WPE) void cnf_step_dev_kernel(CnfDevArgs a) {
     constexpr bool COMPACT = SPLIT && !CTX_LDS;
     constexpr int TW = COMPACT ? CNF_GATES : CNF_CTX;               // width of a stage's row of the factor table
@@ -365,12 +418,14 @@ __global__ __launch_bounds__(CNF_NW * 64, PF_CNF_WPE) void cnf_step_dev_kernel(C
     __shared__ float stf[SPLIT ? 6 * TW : 1];                        // [stage][column]: 2^(gt tsign alpha_s h) of the gate columns
     if (a.ctl[CTL_DONE] != 0.0) return;                              // uniform over the grid
     const int cur = (int)a.ctl[CTL_CUR];
-    const float t = (float)a.ctl[CTL_T], h = (float)a.ctl[CTL_DT];
+    const float t = (float)a.ctl[CTL_T];
+    float h = (float)a.ctl[CTL_DT];
     const bool reverse = a.ctl[CTL_REV] != 0.0;
     const float sgn = reverse ? -1.f : 1.f, tsign = sgn;
-    const bool cover = a.ctl[CTL_T1] <= a.ctl[CTL_T] + a.ctl[CTL_DT];
+    bool cover = a.ctl[CTL_T1] <= a.ctl[CTL_T] + a.ctl[CTL_DT];
+    if constexpr (TAPED) h = cnf_taped_h(a.ctl, cover);
     float wd[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    if (cover) {                                                     // weights of (y0, y1, y_mid, dt f0, dt f1) at x = (t1 - t) / dt
+    if (!TAPED && cover) {                                                     // weights of (y0, y1, y_mid, dt f0, dt f1) at x = (t1 - t) / dt
         const double x = (a.ctl[CTL_T1] - a.ctl[CTL_T]) / a.ctl[CTL_DT], x2 = x * x, x3 = x2 * x, x4 = x2 * x2, dt = a.ctl[CTL_DT];
         wd[0] = (float)(-8 * x4 + 18 * x3 - 11 * x2 + 1); wd[1] = (float)(-8 * x4 + 14 * x3 - 5 * x2);
         wd[2] = (float)(16 * x4 - 32 * x3 + 16 * x2);
@@ -380,6 +435,12 @@ __global__ __launch_bounds__(CNF_NW * 64, PF_CNF_WPE) void cnf_step_dev_kernel(C
     const float* f0p = a.fb[cur];
     float* y1p = a.yb[1 - cur];
     float* f1p = a.fb[1 - cur];
+    if constexpr (TAPED) {
+        const int acc = (int)a.ctl[CTL_ACC];
+        if (acc >= a.cap) return;                                    // (the controller sets `done` before this can happen)
+        y0p = a.states + (size_t)acc * a.rows * 4;
+        y1p = a.states + (size_t)(acc + 1) * a.rows * 4;
+    }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int col = lane & 15, q = lane >> 4;
     const CnfW w = cnf_stage_weights(wl, a.rec, CNF_NW * 64, lane);
@@ -448,7 +509,7 @@ __global__ __launch_bounds__(CNF_NW * 64, PF_CNF_WPE) void cnf_step_dev_kernel(C
         if (ok && q == 0) {
             *reinterpret_cast<f4*>(y1p + (size_t)row * 4) = yi;
             *reinterpret_cast<f4*>(f1p + (size_t)row * 4) = k[6];
-            if (cover) {
+            if (!TAPED && cover) {
                 const f4 ymid = y0 + cnf_comb7(k, CNF_CM) * h;
                 // the same term order as the host path's pf_lincomb: ((((w0 y0) + w1 y1) + w2 ymid) + w3 f0) + w4 f1, fused
                 f4 o;
@@ -481,7 +542,10 @@ __global__ __launch_bounds__(CNF_NW * 64, PF_CNF_WPE) void cnf_step_dev_kernel(C
         if (last) *counter = 0u;
     }
     __syncthreads();
-    if (last) cnf_ctl_update(a.ctl, a.partial, (int)gridDim.x, red);                     // `last` is uniform over the workgroup
+    if (last) {                                                                          // `last` is uniform over the workgroup
+        if constexpr (TAPED) cnf_ctl_update_taped(a.ctl, a.partial, (int)gridDim.x, red, a.steps, a.cap);
+        else cnf_ctl_update(a.ctl, a.partial, (int)gridDim.x, red);
+    }
 }
 
 // torchdiffeq's `_select_initial_step` (oracle/cnf_ref.py::dopri5, first lines) around the probe evaluation
@@ -771,6 +835,24 @@ extern "C" int pf_cnf_steps(double* ctl, float* ya, float* yb, float* fa, float*
     const bool split = (flags & PF_CNF_SPLIT_GATES) && (lds || PF_CNF_SPLIT_FWD);
     void (*kern)(CnfDevArgs) = lds ? (split ? cnf_step_dev_kernel<true, true> : cnf_step_dev_kernel<true, false>)
                                    : (split ? cnf_step_dev_kernel<false, true> : cnf_step_dev_kernel<false, false>);
+    for (int i = 0; i < n_attempts; ++i) hipLaunchKernelGGL(kern, dim3(grid), dim3(CNF_NW * 64), 0, s, a);
+    return pf_last_launch_status();
+}
+
+// pf_cnf_steps for an integration whose accepted steps a backward sweep replays (pf_cnf_tape_vjp): plain gates, the states on a
+// tape instead of two buffers, the covering step cut to end at t1 (include/puflow_hip.h).
+extern "C" int pf_cnf_steps_taped(double* ctl, float* states, float* steps, int cap, float* fa, float* fb, const float* ctx,
+                                  const float* e, const float* rec, float rtol, float atol, int rows, int R, int n_attempts,
+                                  double* ws, void* stream) {
+    if (!ctl || !states || !steps || !fa || !fb || !ctx || !e || !rec || !ws) return PF_ERR_NULL;
+    if (rows <= 0 || R <= 0 || n_attempts <= 0 || cap <= 0) return PF_ERR_SHAPE;
+    CnfDevArgs a{};
+    a.ctl = ctl; a.yb[0] = states; a.yb[1] = states; a.fb[0] = fa; a.fb[1] = fb; a.ctx = ctx; a.e = e; a.rec = rec; a.out = nullptr;
+    a.partial = ws; a.rtol = rtol; a.atol = atol; a.rows = rows; a.R = R; a.states = states; a.steps = steps; a.cap = cap;
+    const int grid = cnf_grid(rows, CNF_NW * 16, &a.ntiles);
+    hipStream_t s = (hipStream_t)stream;
+    const bool lds = R >= 4 && (CNF_NW * 16) % R == 0;
+    void (*kern)(CnfDevArgs) = lds ? cnf_step_dev_kernel<true, false, true> : cnf_step_dev_kernel<false, false, true>;
     for (int i = 0; i < n_attempts; ++i) hipLaunchKernelGGL(kern, dim3(grid), dim3(CNF_NW * 64), 0, s, a);
     return pf_last_launch_status();
 }

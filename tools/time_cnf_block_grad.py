@@ -1,7 +1,11 @@
 """Time one differentiable CNF flow block (PointInterpFlow.flow_block: taped forward, backward, pf_cnf_rhs_vjp alone) beside the
-inference integration of the same block and shape.
+inference integration of the same block and shape, for both reverse sweeps (one pf_cnf_tape_vjp launch / pf_cnf_rhs_vjp per
+evaluation) and both step-size controllers (device / host).
 
-  python tools/time_cnf_block_grad.py --out profiles/cnf_grad/time_cnf_block_grad.json
+  python tools/time_cnf_block_grad.py --out profiles/cnf_grad/time_cnf_block_grad.json [--parent PARENT.json --parent-commit HASH]
+
+--parent: the result file the PARENT commit's copy of this tool wrote on the same box in the same session; it is embedded and the
+text file sets the default path's forward + backward beside it.
 
 Block 5 of the bench workload's weights (weights.CNF_PU1K_DYNAMICS / CNF_PU1K_END_TIMES: the block with the longest integration) at
 the training shape, 32 patches x 256 points: forward direction at R = 1 (8 192 rows) and reversed at R = 4 (32 768 rows).  Every
@@ -22,6 +26,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 BLOCK, B, N = 5, 32, 256
 CASES = (("forward_R1", 1, False), ("reversed_R4", 4, True))
+CONFIGS = (("fused", "device"), ("per_eval", "device"), ("fused", "host"), ("per_eval", "host"))      # the first: flow_block's default
 
 
 def spread(times):
@@ -62,22 +67,24 @@ def run(a):
         e = torch.randn(T, 3, generator=g).to(dev)
         gx = torch.randn(rows, 3, generator=g).to(dev)
         state = {}
+        paths = {}
+        for sweep, controller in CONFIGS:
+            def forward():
+                xr, cr = x.clone().requires_grad_(True), c.clone().requires_grad_(True)
+                ox, ol = net.flow_block(BLOCK, xr, cr, e, R, reverse, sweep=sweep, controller=controller)
+                state["loss"] = (ox * gx).sum() + ol.sum()
 
-        def forward():
-            xr, cr = x.clone().requires_grad_(True), c.clone().requires_grad_(True)
-            ox, ol = net.flow_block(BLOCK, xr, cr, e, R, reverse)
-            state["loss"] = (ox * gx).sum() + ol.sum()
+            def forward_backward():
+                forward()
+                state["loss"].backward()
 
-        def backward():
-            state["loss"].backward()
-
-        def forward_backward():
-            forward()
-            backward()
-
-        fwd = timed(forward, a.reps)
-        steps = len(net.last_block_steps)
-        both = timed(forward_backward, a.reps)
+            f = timed(forward, a.reps)
+            n = len(net.last_block_steps)
+            fb = timed(forward_backward, a.reps)
+            paths[f"{sweep}/{controller}"] = {"sweep": sweep, "controller": controller, "accepted_steps": n, "taped_forward": f,
+                                              "forward_plus_backward": fb, "backward_ms_median": fb["ms_median"] - f["ms_median"]}
+        default = paths["/".join(CONFIGS[0])]
+        fwd, both, steps = default["taped_forward"], default["forward_plus_backward"], default["accepted_steps"]
         # the inference integration of the same block and shape (device-side controller, dense output at the end time)
         eng = net._engine(4)
         ctx = eng.context(BLOCK, c)
@@ -112,7 +119,7 @@ def run(a):
         row = {"case": name, "rows": rows, "R": R, "reverse": reverse, "accepted_steps": steps, "taped_forward": fwd,
                "forward_plus_backward": both, "backward_ms_median": both["ms_median"] - fwd["ms_median"],
                "inference_integrate": infer, "inference_attempts": attempts, "vjp_launch": vjp, "rhs_launch": rhs,
-               "launches_per_batch": a.launches}
+               "launches_per_batch": a.launches, "paths": paths}
         res["cases"].append(row)
         print(json.dumps(row), flush=True)
     return res
@@ -126,6 +133,21 @@ def text(res):
             t = r[k]
             lines.append(f"  {k:22s} {t['ms_median']:10.3f} ({t['ms_min']:.3f} .. {t['ms_max']:.3f}) x{t['repeats']}")
         lines.append(f"  {'backward (difference)':22s} {r['backward_ms_median']:10.3f}")
+        for name, p in r.get("paths", {}).items():
+            f, fb = p["taped_forward"], p["forward_plus_backward"]
+            lines.append(f"  sweep/controller {name:16s} {p['accepted_steps']:3d} steps  forward {f['ms_median']:8.3f} ({f['ms_min']:.3f} .. {f['ms_max']:.3f})"
+                         f"  forward+backward {fb['ms_median']:8.3f} ({fb['ms_min']:.3f} .. {fb['ms_max']:.3f})  backward {p['backward_ms_median']:8.3f}")
+    par = res.get("parent")
+    if par:
+        lines.append(f"parent commit {par['commit']} (its own copy of this tool, same box, same session):")
+        for r, q in zip(res["cases"], par["cases"]):
+            n, o = r["forward_plus_backward"], q["forward_plus_backward"]
+            spread = max(n["ms_max"] - n["ms_min"], o["ms_max"] - o["ms_min"])
+            lines.append(f"  {r['case']}: forward+backward parent {o['ms_median']:.3f} ({o['ms_min']:.3f} .. {o['ms_max']:.3f}), "
+                         f"{q['accepted_steps']} steps -> default path {n['ms_median']:.3f} ({n['ms_min']:.3f} .. {n['ms_max']:.3f}), "
+                         f"{r['accepted_steps']} steps: gain {o['ms_median'] - n['ms_median']:.3f} ms against a spread of {spread:.3f} ms; "
+                         f"taped forward {q['taped_forward']['ms_median']:.3f} -> {r['taped_forward']['ms_median']:.3f}, "
+                         f"vjp_launch {q['vjp_launch']['ms_median']:.3f} -> {r['vjp_launch']['ms_median']:.3f}")
     return "\n".join(lines) + "\n"
 
 
@@ -134,8 +156,13 @@ def main():
     ap.add_argument("--out", required=True)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--launches", type=int, default=20)
+    ap.add_argument("--parent", help="result file of the parent commit's run of this tool")
+    ap.add_argument("--parent-commit", default="?")
     a = ap.parse_args()
     res = run(a)
+    if a.parent:
+        with open(a.parent) as fh:
+            res["parent"] = {"commit": a.parent_commit, "cases": json.load(fh)["cases"]}
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as fh:
         json.dump(res, fh, indent=1)
