@@ -59,9 +59,12 @@ int pf_edgeconv_tuned(int cfg, int variant, const float* pq_or_xyz, const float*
                       const float* wfrag, float* out, int B, int N, void* stream);
 
 /* EdgeConv unit `unit` (0..4, product arithmetic) AND the next unit's P|Q vectors: out [B*N, odim] as pf_edgeconv, pq_next
- * [B*N, rows] as pf_pq_gemm(unit, out, ...) - bit-identical to that pair.  fuse: -1 = one launch when B*N <= 16 384 (the GEMM
- * runs on each 16-point workgroup tile inside the EdgeConv kernel), otherwise the two kernels; 0 = never; 1 = always.
- * w: weight blob base, off[13]: POST_SLOTS offsets of unit `unit`. */
+ * [B*N, rows] as pf_pq_gemm(unit, out, ...) - bit-identical to that pair in every form.  fuse: 0 = the two kernels; 1 = one
+ * launch, the GEMM on each 16-point workgroup tile inside the EdgeConv tile loop; 2 = one launch, the GEMM as a tail phase: every
+ * workgroup multiplies the tiles it computed itself once its tile loop is done (weights in registers, the LDS weight image as
+ * staging area, no synchronisation between workgroups); -1 = by size: form 1 when B*N <= 16 384, above it form 2 for units 0
+ * and 2..4 and the two kernels for unit 1; > 2: PF_ERR_UNSUPPORTED.  Forms 1 / 2 fall back to the two kernels when the table is
+ * too large for the kernel's 32-bit offsets.  w: weight blob base, off[13]: POST_SLOTS offsets of unit `unit`. */
 int pf_edgeconv_pq(int unit, const float* pq_or_xyz, const int* idx, const float* wfrag, float* out, const float* w,
                    const long long* off, float* pq_next, int B, int N, int fuse, void* stream);
 

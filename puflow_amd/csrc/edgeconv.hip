@@ -31,7 +31,7 @@ struct EcArgs {
     int N;               // points per batch item
     int chunk;           // ceil(ntiles / 8) for the XCD-aware tile order
     int ntiles;          // workgroup tiles
-    // fused next-unit P|Q GEMM (PQF kernels, small batches): the arguments of pointwise.hip pq_gemm_kernel
+    // fused next-unit P|Q GEMM (PQF kernels): the arguments of pointwise.hip pq_gemm_kernel
     const u4* pqf_w;     // f16n fragment image [ROWS/16][CP][hi / lo][64 lanes]
     const float* pqf_bias;
     const float* pqf_scales;
@@ -124,6 +124,90 @@ struct PqfState {
         ++nst;
     }
 };
+
+// ---- the same product as the TAIL of the producing EdgeConv launch (PQF = 2) ---------------------------------------------
+// The tile loop is the plain one (no staging, no flush); when a workgroup has finished its tiles, one barrier makes its waves'
+// stores of h visible to the whole workgroup (nothing else: no other workgroup reads these rows in this launch) and the
+// workgroup runs the body of pointwise.hip pq_gemm_kernel over the tiles it computed itself - the same v = blockIdx.x + k gridDim.x
+// walk.  By then the EdgeConv registers are dead, so every wave keeps its RB x CP weight fragment pairs resident (one L2 fetch
+// per launch, as the stand-alone kernel; the biases come from L1 per tile), and the LDS weight image is dead too: `bl` IS that
+// image, reused as the staging area [NT tiles][CP][hi / lo][64 lanes] x 16 B.  A round stages up to NT tiles (every wave converts 1 / NW of the
+// round's (tile, channel pair) units: pf_pairn on the rows re-read from L2), one barrier, then every wave multiplies every
+// staged tile by its rows.  Per accumulator: cp ascending, hi.lo, lo.hi, hi.hi, then fmaf(acc, inv, bias) - the bits of
+// pq_gemm_kernel (tests/test_gpu_pq_tail.py keeps the two copies in step).  A slot of a round is skipped when its tile is a
+// hole of the XCD-aware order or lies behind the list; a workgroup without tiles passes the barriers and stores nothing.
+template <int ODIM, int ROWS, int NW, int NT>
+__device__ __forceinline__ void pq_tail(const EcArgs& a, u4* bl, int wave_u, int lane) {
+    constexpr int CP = ODIM / 32, RB = ROWS / 16 / NW, NU = NT * CP;
+    static_assert(ODIM % 32 == 0 && ROWS % (16 * NW) == 0, "rows split evenly over the waves");
+    const int col = lane & 15, q = lane >> 4;
+    const int vend = 8 * a.chunk, vstep = gridDim.x;
+    h8 wh[RB][CP], wl[RB][CP];
+#pragma unroll
+    for (int ob = 0; ob < RB; ++ob)
+#pragma unroll
+        for (int cp = 0; cp < CP; ++cp) {
+            const u4* f = a.pqf_w + (size_t)(((wave_u * RB + ob) * CP + cp) * 2) * 64 + lane;
+            wh[ob][cp] = __builtin_bit_cast(h8, f[0]);
+            wl[ob][cp] = __builtin_bit_cast(h8, f[64]);
+        }
+    const float* biasp = a.pqf_bias + wave_u * RB * 16 + 4 * q;       // read per tile (L1-resident): RB x 4 registers less
+    const float inv = a.pqf_scales[6];
+    for (int v0 = blockIdx.x; v0 < vend; v0 += NT * vstep) {
+        // ---- stage: this wave converts units wave, wave + NW, ... (unit = tile slot x 32-channel pair)
+#pragma unroll
+        for (int u0 = 0; u0 < NU; u0 += NW) {
+            const int u = u0 + wave_u, t = u / CP, cp = u % CP;
+            const int vt = v0 + t * vstep;
+            if (u >= NU || vt >= vend) continue;                // uniform
+            const int tile = pf_xcd_tile(vt, a.chunk);
+            if (tile >= a.ntiles) continue;                     // uniform
+            int pt = tile * 16 + col;
+            pt = pt < a.T ? pt : tile * 16;                     // a column past the end: a row of this tile (never stored)
+            const float* hr = a.out + (size_t)pt * ODIM + cp * 32 + 4 * q;
+            const PfPairN p = pf_pairn(*reinterpret_cast<const f4*>(hr), *reinterpret_cast<const f4*>(hr + 16));
+            bl[(u * 2 + 0) * 64 + lane] = __builtin_bit_cast(u4, p.h);
+            bl[(u * 2 + 1) * 64 + lane] = __builtin_bit_cast(u4, p.l);
+        }
+        __syncthreads();
+        for (int t = 0; t < NT; ++t) {
+            const int vt = v0 + t * vstep;
+            if (vt >= vend) break;                              // uniform
+            const int tile = pf_xcd_tile(vt, a.chunk);
+            if (tile >= a.ntiles) continue;                     // uniform
+            const u4* blt = bl + t * (CP * 2 * 64);
+            f4 acc[RB];
+#pragma unroll
+            for (int ob = 0; ob < RB; ++ob) acc[ob] = pf_splat(0.f);
+#pragma unroll
+            for (int cp = 0; cp < CP; ++cp) {
+                const h8 fh = __builtin_bit_cast(h8, blt[(cp * 2 + 0) * 64 + lane]), fl = __builtin_bit_cast(h8, blt[(cp * 2 + 1) * 64 + lane]);
+#pragma unroll
+                for (int ob = 0; ob < RB; ++ob) {
+                    f4 x = acc[ob];
+                    if constexpr (PF_MMN_TERMS == 3) {
+                        x = pf_mfma_f16(wh[ob][cp], fl, x);
+                        x = pf_mfma_f16(wl[ob][cp], fh, x);
+                    }
+                    x = pf_mfma_f16(wh[ob][cp], fh, x);
+                    acc[ob] = x;
+                }
+            }
+            const int pt = tile * 16 + col;
+            if (pt < a.T) {
+#pragma unroll
+                for (int ob = 0; ob < RB; ++ob) {
+                    const f4 bias = *reinterpret_cast<const f4*>(biasp + ob * 16);
+                    f4 o;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) o[r] = fmaf(acc[ob][r], inv, bias[r]);
+                    *reinterpret_cast<f4*>(a.pqf_out + (size_t)pt * ROWS + (wave_u * RB + ob) * 16 + 4 * q) = o;
+                }
+            }
+        }
+        __syncthreads();                                   // the next round overwrites the staged tiles
+    }
+}
 
 template <int GB, int NCONV, int ODIM, bool C3, int P, int NW>
 __global__ __launch_bounds__(NW * 64) void edgeconv_kernel(EcArgs a) {
@@ -288,9 +372,9 @@ constexpr float EC4_OUT_INV = 1.f / 256.f;       // conv_out accumulators hold 4
 
 // This kernel keeps packed fp32 (the rest of the file is built without it, build.py): un-packed it measured 136.2 us against
 // 135.2 us per launch - its epilogues are short (31 packed ops per point) and sit between gathers, not in a chain.
-template <int P, int NW, int DBG = 0, bool PQF = false>      // DBG bit mask (-DPF_TUNING_VARIANTS timing builds only; wrong results): 1 no gathers, 2 no MFMAs, 4 no LDS weight reads;  PQF: + the next unit's P|Q vectors (pqf_gemm)
+template <int P, int NW, int DBG = 0, int PQF = 0>      // DBG bit mask (-DPF_TUNING_VARIANTS timing builds only; wrong results): 1 no gathers, 2 no MFMAs, 4 no LDS weight reads;  PQF: + the next unit's P|Q vectors: 1 = inside the tile loop (pqf_gemm), 2 = as a tail phase (pq_tail)
 __global__ __launch_bounds__(NW * 64) PF_PACKED_FP32_FN void edgeconv4_kernel(EcArgs a) {
-    static_assert(!PQF || NW * P == 16, "the fused P|Q GEMM takes a workgroup tile of 16 points as one MFMA column tile");
+    static_assert(PQF == 0 || NW * P == 16, "the fused P|Q GEMM takes a workgroup tile of 16 points as one MFMA column tile");
     constexpr int NCONV = 4, G = 32, S = 256, OBO = 8, OCH = 2, ODIM = 128;
     constexpr int NWF = 2 * (NCONV * (NCONV - 1) / 2) + OBO * NCONV;      // 44 (ob, pair) fragments, 2 KiB each
     constexpr int ROWB = 2 * S * 4;                                       // bytes per point of the P|Q table
@@ -302,7 +386,7 @@ __global__ __launch_bounds__(NW * 64) PF_PACKED_FP32_FN void edgeconv4_kernel(Ec
     // (edge, 4-channel) lane layout cost as many texture-addresser cycles as the Q gathers themselves (16 lanes fetching
     // the same 16 bytes still take a full quad-lane slot each): 392 -> 272 TA cycles per point.
     __shared__ f4 plds[NW * P][64];
-    __shared__ u4 hb[PQF ? PQF_NT * (ODIM / 32) * 2 * 64 : 1];            // PQF: the staged tiles' pooled features as B operands
+    __shared__ u4 hb[PQF == 1 ? PQF_NT * (ODIM / 32) * 2 * 64 : 1];       // PQF 1: the staged tiles' pooled features as B operands
     PqfState pqf;
     pf_stage_lds(wlds, reinterpret_cast<const u4*>(a.wg), NWF * 2 * 64);
     __syncthreads();
@@ -430,13 +514,13 @@ __global__ __launch_bounds__(NW * 64) PF_PACKED_FP32_FN void edgeconv4_kernel(Ec
                 o[0] = h0;
                 o[64] = h1;
             }
-            if constexpr (PQF) {
+            if constexpr (PQF == 1) {
                 u4* hbt = hb + pqf.nst * ((ODIM / 32) * 2 * 64);
                 pqf_stage<ODIM>(hbt, ch, wave * P + p, h0);
                 pqf_stage<ODIM>(hbt, ch + 64, wave * P + p, h1);
             }
         }
-        if constexpr (PQF) {
+        if constexpr (PQF == 1) {
             pqf.push(pf_xcd_tile(v, a.chunk) * NW * P);
             if (pqf.nst == PQF_NT || vn >= vend) {             // uniform: flush the staged tiles (two barriers per flush)
                 __syncthreads();
@@ -447,9 +531,15 @@ __global__ __launch_bounds__(NW * 64) PF_PACKED_FP32_FN void edgeconv4_kernel(Ec
         }
         v = vn;
     }
+    if constexpr (PQF == 2) {
+        constexpr int NT = 8;                                  // 8 KiB per staged tile
+        static_assert(NT * (ODIM / 32) * 2 * 64 <= NWF * 2 * 64, "the staged tiles fit the dead weight image");
+        __syncthreads();                                       // h of this workgroup's tiles is written, wlds is no longer read
+        pq_tail<ODIM, 2 * S, NW, NT>(a, wlds, __builtin_amdgcn_readfirstlane(wave), lane);
+    }
 }
 
-template <int P, int NW, int DBG = 0, bool PQF = false>
+template <int P, int NW, int DBG = 0, int PQF = 0>
 int launch4(const EcArgs& a0, hipStream_t s) {
     EcArgs a = a0;
     a.ntiles = (a.T + NW * P - 1) / (NW * P);
@@ -470,9 +560,10 @@ int launch4(const EcArgs& a0, hipStream_t s) {
 // PQ (unit 1): Q[j] gathers as accumulator initialisers, P[i] staged per wave in LDS (one load per point).
 // Fragments in LDS: G1 | G2 | G3 (2 pairs) | Gout (OBO x 2 pairs) | [C3: edge table, S/16 one-MFMA fragments of 1 KiB];
 // C3: one float behind the image = 2^-sw of the table (the table products are multiplied by it before anything else).
-template <int ODIM, bool C3, int P, int NW, bool PQF = false>      // PQF: + the next unit's P|Q vectors (pqf_gemm; ROWS = 256 after unit 0, 512 after unit 1)
-__global__ __launch_bounds__(NW * 64) void edgeconv1n_kernel(EcArgs a) {
-    static_assert(!PQF || NW * P == 16, "the fused P|Q GEMM takes a workgroup tile of 16 points as one MFMA column tile");
+template <int ODIM, bool C3, int P, int NW, int PQF = 0>      // PQF: + the next unit's P|Q vectors (ROWS = 256 after unit 0, 512 after unit 1): 1 = inside the tile loop (pqf_gemm), 2 = as a tail phase (pq_tail)
+// PQF 2: at least 4 waves per SIMD, i.e. 128 VGPRs as the plain kernel (unit 1's tail would take 132 and lose a wave otherwise)
+__global__ __launch_bounds__(NW * 64, PQF == 2 ? 4 : 1) void edgeconv1n_kernel(EcArgs a) {
+    static_assert(PQF == 0 || NW * P == 16, "the fused P|Q GEMM takes a workgroup tile of 16 points as one MFMA column tile");
     constexpr int NCONV = 4, S = 16 * NCONV + ODIM, SB = S / 16, OBO = ODIM / 16;
     constexpr int PQ_ROWS = ODIM == 32 ? 256 : 512;
     constexpr int FO = 4, FT = FO + OBO * 2, NWF = FT + (C3 ? SB / 2 : 0);            // C3: SB one-MFMA table fragments of 1 KiB
@@ -483,7 +574,7 @@ __global__ __launch_bounds__(NW * 64) void edgeconv1n_kernel(EcArgs a) {
     const int col = lane & 15, q = lane >> 4;
     __shared__ u4 wlds[NWF * 128];
     __shared__ float plds[C3 ? 1 : NW * P][C3 ? 1 : S];
-    __shared__ u4 hb[PQF ? PQF_NT * (ODIM / 32) * 2 * 64 : 1];
+    __shared__ u4 hb[PQF == 1 ? PQF_NT * (ODIM / 32) * 2 * 64 : 1];
     PqfState pqf;
     pf_stage_lds(wlds, reinterpret_cast<const u4*>(a.wg), NWF * 128);
     __syncthreads();
@@ -613,11 +704,11 @@ __global__ __launch_bounds__(NW * 64) void edgeconv1n_kernel(EcArgs a) {
             const float hv = fmaf(o, EC4_OUT_INV, pv);
             if (pt0 + p < a.T && (OBO == 4 || (q & 1) == 0))
                 a.out[(size_t)gi[p] * ODIM + ch] = hv;
-            if constexpr (PQF) {
+            if constexpr (PQF == 1) {
                 if (OBO == 4 || (q & 1) == 0) pqf_stage<ODIM>(hb + pqf.nst * ((ODIM / 32) * 2 * 64), ch, wave * P + p, hv);
             }
         }
-        if constexpr (PQF) {
+        if constexpr (PQF == 1) {
             pqf.push(tile * NW * P);
             if (pqf.nst == PQF_NT) {                 // uniform: flush (the tail is flushed after the loop)
                 __syncthreads();
@@ -627,15 +718,21 @@ __global__ __launch_bounds__(NW * 64) void edgeconv1n_kernel(EcArgs a) {
             }
         }
     }
-    if constexpr (PQF) {
+    if constexpr (PQF == 1) {
         if (pqf.nst > 0) {
             __syncthreads();
             pqf_gemm<ODIM, PQ_ROWS, NW>(a, hb, pqf.nst, pqf.tpt, __builtin_amdgcn_readfirstlane(wave), lane);
         }
     }
+    if constexpr (PQF == 2) {
+        constexpr int NT = ODIM == 32 ? 8 : 4;                 // 2 KiB (unit 0) / 4 KiB (unit 1) per staged tile
+        static_assert(NT * (ODIM / 32) * 2 * 64 <= NWF * 128, "the staged tiles fit the dead weight image");
+        __syncthreads();                                       // h of this workgroup's tiles is written, wlds is no longer read
+        pq_tail<ODIM, PQ_ROWS, NW, NT>(a, wlds, __builtin_amdgcn_readfirstlane(wave), lane);
+    }
 }
 
-template <int ODIM, bool C3, int P, int NW, bool PQF = false>
+template <int ODIM, bool C3, int P, int NW, int PQF = 0>
 int launch1n(const EcArgs& a0, hipStream_t s) {
     EcArgs a = a0;
     a.ntiles = (a.T + NW * P - 1) / (NW * P);
@@ -778,21 +875,29 @@ extern "C" int pf_edgeconv(int cfg, const float* pq_or_xyz, const float* tab, co
 }
 
 // EdgeConv unit `unit` (0..4) in the product arithmetic AND the next unit's P|Q vectors: out [B*N, odim] as pf_edgeconv (cfg 8 /
-// 9 / 7), pq_next [B*N, rows] as pf_pq_gemm(unit, out, ...) - bit-identical to that pair of calls.  Small batches run both in
-// ONE launch (the fused epilogue above: a 16-point workgroup tile is one MFMA column tile of the GEMM); larger ones as the two
-// kernels (the P|Q GEMM is HBM-write-bound there and its weights would compete with the Q gathers for L2 bandwidth).
+// 9 / 7), pq_next [B*N, rows] as pf_pq_gemm(unit, out, ...) - bit-identical to that pair of calls in every form:
+//   two launches   the EdgeConv kernel, then the HBM-write-bound P|Q GEMM of pointwise.hip
+//   interleaved    one launch, the GEMM inside the tile loop (pqf_gemm: a 16-point workgroup tile is one MFMA column tile, four
+//                  tiles per flush, weights from L2 per flush) - removes a launch where a workgroup has few tiles
+//   tail           one launch, the plain tile loop and then the body of the GEMM kernel over the workgroup's own tiles (pq_tail:
+//                  weights register-resident, the dead LDS weight image as staging area) - removes the hand-over; the tails of
+//                  all workgroups coincide at large batches, so the HBM write itself stays exposed
 // w: blob base, off[13]: POST_SLOTS of unit `unit` (packing.py).
+// fuse: 0 = two launches, 1 = interleaved, 2 = tail (1 / 2: whenever the 32-bit offsets of the kernel allow), -1 = by size:
+// interleaved up to PQ_FUSE_MAX_T points (8 tiles per workgroup); above it the tail form for units 0 and 2 - 4 and two launches
+// for unit 1, whose tail form measured slower than the pair it replaces (profiles/pq_tail/).
+constexpr long long PQ_FUSE_MAX_T = 16384;
 extern "C" int pf_edgeconv_pq(int unit, const float* pq_or_xyz, const int* idx, const float* wfrag, float* out, const float* w,
                               const long long* off, float* pq_next, int B, int N, int fuse, void* stream) {
     if (!pq_or_xyz || !idx || !wfrag || !out || !w || !off || !pq_next) return PF_ERR_NULL;
     if (unit < 0 || unit > 4) return PF_ERR_UNSUPPORTED;
     if (B <= 0 || N < 16 || (long long)B * N > (1ll << 30)) return PF_ERR_SHAPE;
+    if (fuse > 2) return PF_ERR_UNSUPPORTED;
     const long long T = (long long)B * N;
-    // fuse: 0 = never, 1 = always (when the shape allows), -1 = by size: up to 16 384 points (8 tiles per workgroup)
     const bool fits32 = unit == 0 ? T * 12 <= 0x7fffffffll : (unit == 1 ? T * 1024 <= 0x7fffffffll : T * 2048 <= 0x7fffffffll);
-    const bool fused = fits32 && (fuse == 1 || (fuse < 0 && T <= 16384));
+    const int form = !fits32 ? 0 : (fuse >= 0 ? fuse : (T <= PQ_FUSE_MAX_T ? 1 : (unit == 1 ? 0 : 2)));
     const int cfg = unit == 0 ? 8 : (unit == 1 ? 9 : 7);
-    if (!fused) {
+    if (form == 0) {
         const int rc = pf_edgeconv(cfg, pq_or_xyz, nullptr, idx, wfrag, out, B, N, stream);
         return rc != PF_OK ? rc : pf_pq_gemm(unit, out, w, off, pq_next, (int)T, stream);
     }
@@ -800,8 +905,8 @@ extern "C" int pf_edgeconv_pq(int unit, const float* pq_or_xyz, const int* idx, 
     a.idx = idx; a.wg = reinterpret_cast<const f4*>(wfrag); a.out = out; a.T = (int)T; a.N = N;
     a.pqf_w = reinterpret_cast<const u4*>(w + off[10]); a.pqf_bias = w + off[11]; a.pqf_scales = w + off[12]; a.pqf_out = pq_next;
     hipStream_t s = (hipStream_t)stream;
-    if (unit == 0) { a.xyz = pq_or_xyz; return launch1n<32, true, 2, 8, true>(a, s); }
+    if (unit == 0) { a.xyz = pq_or_xyz; return form == 1 ? launch1n<32, true, 2, 8, 1>(a, s) : launch1n<32, true, 2, 8, 2>(a, s); }
     a.pq = pq_or_xyz;
-    if (unit == 1) return launch1n<64, false, 2, 8, true>(a, s);
-    return launch4<1, 16, 0, true>(a, s);
+    if (unit == 1) return form == 1 ? launch1n<64, false, 2, 8, 1>(a, s) : launch1n<64, false, 2, 8, 2>(a, s);
+    return form == 1 ? launch4<1, 16, 0, 1>(a, s) : launch4<1, 16, 0, 2>(a, s);
 }

@@ -178,7 +178,10 @@ class _Engine:
         # branch only time-slices the CUs and pays a fork / join.  Kept because a caller that has no other use for the wait
         # (e.g. z produced elsewhere, later) can start the weights early; bit-identical either way (tests/test_gpu_parity.py).
         self.split_interp = 0
-        self.fuse_pq = -1          # pf_edgeconv_pq: -1 = fuse the P|Q GEMM into the EdgeConv launch for small batches, 0 never, 1 always
+        # pf_edgeconv_pq, the next unit's P|Q GEMM inside the EdgeConv launch: 0 = never (two launches), 1 = inside the tile loop,
+        # 2 = as a tail phase of the launch, -1 = by size (1 up to 16 384 points; above it 2 for units 0 and 2 - 4, 0 for unit 1).
+        # Bit-identical in every form (tests/test_gpu_parity.py, tests/test_gpu_pq_tail.py).
+        self.fuse_pq = -1
 
     def _p(self, off: int) -> int:
         return self.base + 4 * off
@@ -225,7 +228,7 @@ class _Engine:
             if u + 1 == NUM_BLOCKS:
                 self._edgeconv(u, src, idx16, h, B, N, s)
             elif self.ec_mode == "f16n":
-                # EdgeConv u + the next unit's P|Q vectors: one launch for small batches, two kernels otherwise (pf_edgeconv_pq)
+                # EdgeConv u + the next unit's P|Q vectors: one launch or two by unit and size (pf_edgeconv_pq, self.fuse_pq)
                 w = self.ec1n_w[u] if u < 2 else self.ec4_w[u]
                 _lib.check(self.lib.pf_edgeconv_pq(u, src, idx16.data_ptr(), self._p(w), h.data_ptr(), self.base, self.post[u],
                                                    nxt.data_ptr(), B, N, self.fuse_pq, s), f"pf_edgeconv_pq[{u}]")
@@ -332,7 +335,7 @@ class _Engine:
             pq = torch.empty((T, 512), dtype=torch.float32, device=dev)
             hs = []
             pq2 = torch.empty((T, 512), dtype=torch.float32, device=dev)
-            fused = self.ec_mode == "f16n" and (self.fuse_pq == 1 or (self.fuse_pq < 0 and T <= 16384))
+            fused = self.ec_mode == "f16n" and self.fuse_pq != 0        # as features(): pf_edgeconv_pq picks the form
             for u in range(NUM_BLOCKS):
                 h = torch.empty((T, FEAT_CHANNELS[u + 1]), dtype=torch.float32, device=dev)
                 src = xyz.data_ptr() if u == 0 else (pq if u % 2 else pq2).data_ptr()
@@ -340,7 +343,7 @@ class _Engine:
                 if fused and u + 1 < NUM_BLOCKS:
                     w = self.ec1n_w[u] if u < 2 else self.ec4_w[u]
                     timed(f"edgeconv{u}+pq", lambda: _lib.check(self.lib.pf_edgeconv_pq(
-                        u, src, idx16.data_ptr(), self._p(w), h.data_ptr(), self.base, self.post[u], nxt.data_ptr(), B, N, 1, s)))
+                        u, src, idx16.data_ptr(), self._p(w), h.data_ptr(), self.base, self.post[u], nxt.data_ptr(), B, N, self.fuse_pq, s)))
                 else:
                     timed(f"edgeconv{u}", lambda: self._edgeconv(u, src, idx16, h, B, N, s))
                     if u + 1 < NUM_BLOCKS:
