@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include "pf_api_internal.h"
 #include "pf_mfma.h"
+#include "pf_pq.h"
 
 // per-function override of the file's no-packed-fp32 build switch (device pass only: the host knows no such feature)
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -32,7 +33,7 @@ struct EcArgs {
     int chunk;           // ceil(ntiles / 8) for the XCD-aware tile order
     int ntiles;          // workgroup tiles
     // fused next-unit P|Q GEMM (PQF kernels): the arguments of pointwise.hip pq_gemm_kernel
-    const u4* pqf_w;     // f16n fragment image [ROWS/16][CP][hi / lo][64 lanes]
+    const u4* pqf_w;     // f16n fragment image (pf_pq.h)
     const float* pqf_bias;
     const float* pqf_scales;
     float* pqf_out;      // [T, ROWS]
@@ -44,18 +45,8 @@ struct EcArgs {
 // B operands (fp32 -> hi / natural lo, the split of pf_pairn), one barrier, then every wave multiplies the tile by ITS rows of
 // the [ROWS x ODIM] matrix (fragments straight from L2: 16 KiB per wave and tile - fine for a few tiles per workgroup, too
 // much L2 traffic next to the Q gathers at 32 x 2048, where the separate HBM-bound kernel stays).  Up to PQF_NT tiles are
-// staged before the GEMM runs (one weight fetch and its L2 latency per flush, not per tile).  Products, order and rescale
-// are those of pq_gemm_kernel: the table is bit-identical.  hb: [PQF_NT tiles][CP][hi / lo][64 lanes] x 16 B.
-template <int ODIM>
-__device__ __forceinline__ void pqf_stage(u4* hb, int ch, int pt, float v) {
-    _Float16* h = reinterpret_cast<_Float16*>(hb);
-    const int cp = ch >> 5, j = ((ch >> 4) & 1) * 4 + (ch & 3), slot = 16 * ((ch & 15) >> 2) + pt;
-    const _Float16 hi = (_Float16)v;
-    const _Float16 lo = (_Float16)(v - (float)hi);
-    h[((cp * 2 + 0) * 64 + slot) * 8 + j] = hi;
-    h[((cp * 2 + 1) * 64 + slot) * 8 + j] = lo;
-}
-
+// staged before the GEMM runs (one weight fetch and its L2 latency per flush, not per tile).  The product, its order, the
+// rescale and the layouts are pf_pq.h's, as in pq_gemm_kernel: the table is bit-identical.  hb: PQF_NT staged tiles.
 constexpr int PQF_NT = 4;      // workgroup tiles staged before the GEMM runs on them (its weights come from L2 once per flush)
 
 template <int ODIM, int ROWS, int NW>
@@ -70,87 +61,83 @@ __device__ __forceinline__ void pqf_gemm(const EcArgs& a, const u4* hb, int nst,
     const float inv = a.pqf_scales[6];
 #pragma unroll
     for (int ob0 = 0; ob0 < RB; ob0 += OBW) {
+        const int blk0 = wave_u * RB + ob0;
         h8 wh[OBW][CP], wl[OBW][CP];
 #pragma unroll
         for (int o = 0; o < OBW; ++o)
 #pragma unroll
             for (int cp = 0; cp < CP; ++cp) {
-                wh[o][cp] = ws.load((wave_u * RB + ob0 + o) * CP + cp, 0);
-                wl[o][cp] = ws.load((wave_u * RB + ob0 + o) * CP + cp, 1);
+                wh[o][cp] = ws.load((blk0 + o) * CP + cp, 0);
+                wl[o][cp] = ws.load((blk0 + o) * CP + cp, 1);
             }
 #pragma unroll
         for (int t = 0; t < PQF_NT; ++t) {
             if (t >= nst) break;                              // uniform
-            const u4* hbt = hb + t * (CP * 2 * 64);
             f4 acc[OBW];
-#pragma unroll
-            for (int o = 0; o < OBW; ++o) acc[o] = pf_splat(0.f);
-#pragma unroll
-            for (int cp = 0; cp < CP; ++cp) {
-                const h8 fh = __builtin_bit_cast(h8, hbt[(cp * 2 + 0) * 64 + lane]), fl = __builtin_bit_cast(h8, hbt[(cp * 2 + 1) * 64 + lane]);
-#pragma unroll
-                for (int o = 0; o < OBW; ++o) {
-                    f4 x = acc[o];
-                    if constexpr (PF_MMN_TERMS == 3) {
-                        x = pf_mfma_f16(wh[o][cp], fl, x);
-                        x = pf_mfma_f16(wl[o][cp], fh, x);
-                    }
-                    x = pf_mfma_f16(wh[o][cp], fh, x);
-                    acc[o] = x;
-                }
-            }
+            pq_tile_product(hb + t * PQ_TILE_U4<CP>, lane, wh, wl, acc);
             const int pt = tpt[t] + col;
-            if (pt < a.T) {
-#pragma unroll
-                for (int o = 0; o < OBW; ++o) {
-                    const f4 bias = *reinterpret_cast<const f4*>(a.pqf_bias + (wave_u * RB + ob0 + o) * 16 + 4 * q);     // L1-resident
-                    f4 v;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = fmaf(acc[o][r], inv, bias[r]);
-                    *reinterpret_cast<f4*>(a.pqf_out + (size_t)pt * ROWS + (wave_u * RB + ob0 + o) * 16 + 4 * q) = v;
-                }
-            }
+            if (pt < a.T) pq_tile_store<ROWS>(a.pqf_out, pt, blk0, q, acc, inv, a.pqf_bias + blk0 * 16 + 4 * q);
         }
     }
 }
 
-// staged-tile bookkeeping of a PQF kernel: slot of the current tile, first point of every staged tile (uniform values)
+// The interleaved form's side of a PQF = 1 kernel: the staged-tile list (slot of the current tile, first point of every
+// staged tile: uniform values) and the flush.  A kernel says stage() per pooled value, tile_done() per tile and loop_done().
+template <int ODIM, int ROWS, int NW>
 struct PqfState {
+    static constexpr int CP = ODIM / 32, LDS_U4 = PQF_NT * PQ_TILE_U4<CP>;
     int nst = 0;
     int tpt[PQF_NT] = {0, 0, 0, 0};
-    __device__ __forceinline__ void push(int pt0) {
+    // channel ch of point column pt of the current tile: the scalar form of pf_pairn's split, scattered into the B operand
+    __device__ __forceinline__ void stage(u4* hb, int ch, int pt, float v) const {
+        _Float16* h = reinterpret_cast<_Float16*>(hb + nst * PQ_TILE_U4<CP>);
+        const _Float16 hi = (_Float16)v;
+        const _Float16 lo = (_Float16)(v - (float)hi);
+        h[pq_frag_u4(ch >> 5, 0, pq_b_lane(ch, pt)) * 8 + pq_b_elem(ch)] = hi;
+        h[pq_frag_u4(ch >> 5, 1, pq_b_lane(ch, pt)) * 8 + pq_b_elem(ch)] = lo;
+    }
+    // the tile whose first point is pt0 is staged; flush (uniform: two barriers) when the list is full or `last` says that
+    // the workgroup has no further tile.  A kernel that cannot tell passes false and calls loop_done() behind its loop.
+    __device__ __forceinline__ void tile_done(const EcArgs& a, const u4* hb, int pt0, bool last, int wave, int lane) {
 #pragma unroll
         for (int k = 0; k < PQF_NT; ++k) tpt[k] = k == nst ? pt0 : tpt[k];
         ++nst;
+        if (nst == PQF_NT || last) {
+            __syncthreads();
+            pqf_gemm<ODIM, ROWS, NW>(a, hb, nst, tpt, __builtin_amdgcn_readfirstlane(wave), lane);
+            __syncthreads();
+            nst = 0;
+        }
+    }
+    __device__ __forceinline__ void loop_done(const EcArgs& a, const u4* hb, int wave, int lane) {
+        if (nst > 0) {
+            __syncthreads();
+            pqf_gemm<ODIM, ROWS, NW>(a, hb, nst, tpt, __builtin_amdgcn_readfirstlane(wave), lane);
+        }
     }
 };
 
 // ---- the same product as the TAIL of the producing EdgeConv launch (PQF = 2) ---------------------------------------------
 // The tile loop is the plain one (no staging, no flush); when a workgroup has finished its tiles, one barrier makes its waves'
 // stores of h visible to the whole workgroup (nothing else: no other workgroup reads these rows in this launch) and the
-// workgroup runs the body of pointwise.hip pq_gemm_kernel over the tiles it computed itself - the same v = blockIdx.x + k gridDim.x
+// workgroup runs the rounds of pointwise.hip pq_gemm_kernel over the tiles it computed itself - the same v = blockIdx.x + k gridDim.x
 // walk.  By then the EdgeConv registers are dead, so every wave keeps its RB x CP weight fragment pairs resident (one L2 fetch
 // per launch, as the stand-alone kernel; the biases come from L1 per tile), and the LDS weight image is dead too: `bl` IS that
-// image, reused as the staging area [NT tiles][CP][hi / lo][64 lanes] x 16 B.  A round stages up to NT tiles (every wave converts 1 / NW of the
+// image (IMG_U4 words), reused as the staging area of NT tiles.  A round stages up to NT tiles (every wave converts 1 / NW of the
 // round's (tile, channel pair) units: pf_pairn on the rows re-read from L2), one barrier, then every wave multiplies every
-// staged tile by its rows.  Per accumulator: cp ascending, hi.lo, lo.hi, hi.hi, then fmaf(acc, inv, bias) - the bits of
-// pq_gemm_kernel (tests/test_gpu_pq_tail.py keeps the two copies in step).  A slot of a round is skipped when its tile is a
+// staged tile by its rows: the pieces of pf_pq.h, hence the bits of pq_gemm_kernel.  A slot of a round is skipped when its tile is a
 // hole of the XCD-aware order or lies behind the list; a workgroup without tiles passes the barriers and stores nothing.
-template <int ODIM, int ROWS, int NW, int NT>
-__device__ __forceinline__ void pq_tail(const EcArgs& a, u4* bl, int wave_u, int lane) {
+template <int ODIM, int ROWS, int NW, int NT, int IMG_U4>
+__device__ __forceinline__ void pq_tail(const EcArgs& a, u4* bl, int wave, int lane) {
     constexpr int CP = ODIM / 32, RB = ROWS / 16 / NW, NU = NT * CP;
     static_assert(ODIM % 32 == 0 && ROWS % (16 * NW) == 0, "rows split evenly over the waves");
+    static_assert(NT * PQ_TILE_U4<CP> <= IMG_U4, "the staged tiles fit the dead weight image");
+    __syncthreads();                                       // h of this workgroup's tiles is written, the weight image is no longer read
+    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     const int col = lane & 15, q = lane >> 4;
     const int vend = 8 * a.chunk, vstep = gridDim.x;
     h8 wh[RB][CP], wl[RB][CP];
-#pragma unroll
-    for (int ob = 0; ob < RB; ++ob)
-#pragma unroll
-        for (int cp = 0; cp < CP; ++cp) {
-            const u4* f = a.pqf_w + (size_t)(((wave_u * RB + ob) * CP + cp) * 2) * 64 + lane;
-            wh[ob][cp] = __builtin_bit_cast(h8, f[0]);
-            wl[ob][cp] = __builtin_bit_cast(h8, f[64]);
-        }
+    pq_load_w(a.pqf_w, wave_u * RB, lane, wh, wl);
     const float* biasp = a.pqf_bias + wave_u * RB * 16 + 4 * q;       // read per tile (L1-resident): RB x 4 registers less
     const float inv = a.pqf_scales[6];
     for (int v0 = blockIdx.x; v0 < vend; v0 += NT * vstep) {
@@ -164,10 +151,7 @@ __device__ __forceinline__ void pq_tail(const EcArgs& a, u4* bl, int wave_u, int
             if (tile >= a.ntiles) continue;                     // uniform
             int pt = tile * 16 + col;
             pt = pt < a.T ? pt : tile * 16;                     // a column past the end: a row of this tile (never stored)
-            const float* hr = a.out + (size_t)pt * ODIM + cp * 32 + 4 * q;
-            const PfPairN p = pf_pairn(*reinterpret_cast<const f4*>(hr), *reinterpret_cast<const f4*>(hr + 16));
-            bl[(u * 2 + 0) * 64 + lane] = __builtin_bit_cast(u4, p.h);
-            bl[(u * 2 + 1) * 64 + lane] = __builtin_bit_cast(u4, p.l);
+            pq_stage_unit(bl + t * PQ_TILE_U4<CP> + pq_frag_u4(cp, 0, 0), a.out + (size_t)pt * ODIM + cp * 32 + 4 * q, lane);
         }
         __syncthreads();
         for (int t = 0; t < NT; ++t) {
@@ -175,35 +159,10 @@ __device__ __forceinline__ void pq_tail(const EcArgs& a, u4* bl, int wave_u, int
             if (vt >= vend) break;                              // uniform
             const int tile = pf_xcd_tile(vt, a.chunk);
             if (tile >= a.ntiles) continue;                     // uniform
-            const u4* blt = bl + t * (CP * 2 * 64);
             f4 acc[RB];
-#pragma unroll
-            for (int ob = 0; ob < RB; ++ob) acc[ob] = pf_splat(0.f);
-#pragma unroll
-            for (int cp = 0; cp < CP; ++cp) {
-                const h8 fh = __builtin_bit_cast(h8, blt[(cp * 2 + 0) * 64 + lane]), fl = __builtin_bit_cast(h8, blt[(cp * 2 + 1) * 64 + lane]);
-#pragma unroll
-                for (int ob = 0; ob < RB; ++ob) {
-                    f4 x = acc[ob];
-                    if constexpr (PF_MMN_TERMS == 3) {
-                        x = pf_mfma_f16(wh[ob][cp], fl, x);
-                        x = pf_mfma_f16(wl[ob][cp], fh, x);
-                    }
-                    x = pf_mfma_f16(wh[ob][cp], fh, x);
-                    acc[ob] = x;
-                }
-            }
+            pq_tile_product(bl + t * PQ_TILE_U4<CP>, lane, wh, wl, acc);
             const int pt = tile * 16 + col;
-            if (pt < a.T) {
-#pragma unroll
-                for (int ob = 0; ob < RB; ++ob) {
-                    const f4 bias = *reinterpret_cast<const f4*>(biasp + ob * 16);
-                    f4 o;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) o[r] = fmaf(acc[ob][r], inv, bias[r]);
-                    *reinterpret_cast<f4*>(a.pqf_out + (size_t)pt * ROWS + (wave_u * RB + ob) * 16 + 4 * q) = o;
-                }
-            }
+            if (pt < a.T) pq_tile_store<ROWS>(a.pqf_out, pt, wave_u * RB, q, acc, inv, biasp);
         }
         __syncthreads();                                   // the next round overwrites the staged tiles
     }
@@ -386,8 +345,8 @@ __global__ __launch_bounds__(NW * 64) PF_PACKED_FP32_FN void edgeconv4_kernel(Ec
     // (edge, 4-channel) lane layout cost as many texture-addresser cycles as the Q gathers themselves (16 lanes fetching
     // the same 16 bytes still take a full quad-lane slot each): 392 -> 272 TA cycles per point.
     __shared__ f4 plds[NW * P][64];
-    __shared__ u4 hb[PQF == 1 ? PQF_NT * (ODIM / 32) * 2 * 64 : 1];       // PQF 1: the staged tiles' pooled features as B operands
-    PqfState pqf;
+    PqfState<ODIM, 2 * S, NW> pqf;
+    __shared__ u4 hb[PQF == 1 ? pqf.LDS_U4 : 1];                          // PQF 1: the staged tiles' pooled features as B operands
     pf_stage_lds(wlds, reinterpret_cast<const u4*>(a.wg), NWF * 2 * 64);
     __syncthreads();
     const PfW2Lds ws_lds{wlds, lane};
@@ -515,28 +474,14 @@ __global__ __launch_bounds__(NW * 64) PF_PACKED_FP32_FN void edgeconv4_kernel(Ec
                 o[64] = h1;
             }
             if constexpr (PQF == 1) {
-                u4* hbt = hb + pqf.nst * ((ODIM / 32) * 2 * 64);
-                pqf_stage<ODIM>(hbt, ch, wave * P + p, h0);
-                pqf_stage<ODIM>(hbt, ch + 64, wave * P + p, h1);
+                pqf.stage(hb, ch, wave * P + p, h0);
+                pqf.stage(hb, ch + 64, wave * P + p, h1);
             }
         }
-        if constexpr (PQF == 1) {
-            pqf.push(pf_xcd_tile(v, a.chunk) * NW * P);
-            if (pqf.nst == PQF_NT || vn >= vend) {             // uniform: flush the staged tiles (two barriers per flush)
-                __syncthreads();
-                pqf_gemm<ODIM, 2 * S, NW>(a, hb, pqf.nst, pqf.tpt, __builtin_amdgcn_readfirstlane(wave), lane);
-                __syncthreads();
-                pqf.nst = 0;
-            }
-        }
+        if constexpr (PQF == 1) pqf.tile_done(a, hb, pf_xcd_tile(v, a.chunk) * NW * P, vn >= vend, wave, lane);      // the walk knows its last tile
         v = vn;
     }
-    if constexpr (PQF == 2) {
-        constexpr int NT = 8;                                  // 8 KiB per staged tile
-        static_assert(NT * (ODIM / 32) * 2 * 64 <= NWF * 2 * 64, "the staged tiles fit the dead weight image");
-        __syncthreads();                                       // h of this workgroup's tiles is written, wlds is no longer read
-        pq_tail<ODIM, 2 * S, NW, NT>(a, wlds, __builtin_amdgcn_readfirstlane(wave), lane);
-    }
+    if constexpr (PQF == 2) pq_tail<ODIM, 2 * S, NW, 8, NWF * 2 * 64>(a, wlds, wave, lane);      // NT = 8: 8 KiB per staged tile
 }
 
 template <int P, int NW, int DBG = 0, int PQF = 0>
@@ -574,8 +519,8 @@ __global__ __launch_bounds__(NW * 64, PQF == 2 ? 4 : 1) void edgeconv1n_kernel(E
     const int col = lane & 15, q = lane >> 4;
     __shared__ u4 wlds[NWF * 128];
     __shared__ float plds[C3 ? 1 : NW * P][C3 ? 1 : S];
-    __shared__ u4 hb[PQF == 1 ? PQF_NT * (ODIM / 32) * 2 * 64 : 1];
-    PqfState pqf;
+    PqfState<ODIM, PQ_ROWS, NW> pqf;
+    __shared__ u4 hb[PQF == 1 ? pqf.LDS_U4 : 1];
     pf_stage_lds(wlds, reinterpret_cast<const u4*>(a.wg), NWF * 128);
     __syncthreads();
     const PfW2Lds ws{wlds, lane};
@@ -705,31 +650,14 @@ __global__ __launch_bounds__(NW * 64, PQF == 2 ? 4 : 1) void edgeconv1n_kernel(E
             if (pt0 + p < a.T && (OBO == 4 || (q & 1) == 0))
                 a.out[(size_t)gi[p] * ODIM + ch] = hv;
             if constexpr (PQF == 1) {
-                if (OBO == 4 || (q & 1) == 0) pqf_stage<ODIM>(hb + pqf.nst * ((ODIM / 32) * 2 * 64), ch, wave * P + p, hv);
+                if (OBO == 4 || (q & 1) == 0) pqf.stage(hb, ch, wave * P + p, hv);
             }
         }
-        if constexpr (PQF == 1) {
-            pqf.push(tile * NW * P);
-            if (pqf.nst == PQF_NT) {                 // uniform: flush (the tail is flushed after the loop)
-                __syncthreads();
-                pqf_gemm<ODIM, PQ_ROWS, NW>(a, hb, pqf.nst, pqf.tpt, __builtin_amdgcn_readfirstlane(wave), lane);
-                __syncthreads();
-                pqf.nst = 0;
-            }
-        }
+        if constexpr (PQF == 1) pqf.tile_done(a, hb, tile * NW * P, false, wave, lane);      // a short list is flushed after the loop
     }
-    if constexpr (PQF == 1) {
-        if (pqf.nst > 0) {
-            __syncthreads();
-            pqf_gemm<ODIM, PQ_ROWS, NW>(a, hb, pqf.nst, pqf.tpt, __builtin_amdgcn_readfirstlane(wave), lane);
-        }
-    }
-    if constexpr (PQF == 2) {
-        constexpr int NT = ODIM == 32 ? 8 : 4;                 // 2 KiB (unit 0) / 4 KiB (unit 1) per staged tile
-        static_assert(NT * (ODIM / 32) * 2 * 64 <= NWF * 128, "the staged tiles fit the dead weight image");
-        __syncthreads();                                       // h of this workgroup's tiles is written, wlds is no longer read
-        pq_tail<ODIM, PQ_ROWS, NW, NT>(a, wlds, __builtin_amdgcn_readfirstlane(wave), lane);
-    }
+    if constexpr (PQF == 1) pqf.loop_done(a, hb, wave, lane);
+    // NT: 2 KiB (unit 0) / 4 KiB (unit 1) per staged tile
+    if constexpr (PQF == 2) pq_tail<ODIM, PQ_ROWS, NW, ODIM == 32 ? 8 : 4, NWF * 128>(a, wlds, wave, lane);
 }
 
 template <int ODIM, bool C3, int P, int NW, int PQF = 0>
@@ -877,9 +805,10 @@ extern "C" int pf_edgeconv(int cfg, const float* pq_or_xyz, const float* tab, co
 // EdgeConv unit `unit` (0..4) in the product arithmetic AND the next unit's P|Q vectors: out [B*N, odim] as pf_edgeconv (cfg 8 /
 // 9 / 7), pq_next [B*N, rows] as pf_pq_gemm(unit, out, ...) - bit-identical to that pair of calls in every form:
 //   two launches   the EdgeConv kernel, then the HBM-write-bound P|Q GEMM of pointwise.hip
+// (the product is pf_pq.h's in all three; they differ in the tile walk, in where the weights live and in the staging split)
 //   interleaved    one launch, the GEMM inside the tile loop (pqf_gemm: a 16-point workgroup tile is one MFMA column tile, four
 //                  tiles per flush, weights from L2 per flush) - removes a launch where a workgroup has few tiles
-//   tail           one launch, the plain tile loop and then the body of the GEMM kernel over the workgroup's own tiles (pq_tail:
+//   tail           one launch, the plain tile loop and then the GEMM kernel's rounds over the workgroup's own tiles (pq_tail:
 //                  weights register-resident, the dead LDS weight image as staging area) - removes the hand-over; the tails of
 //                  all workgroups coincide at large batches, so the HBM write itself stays exposed
 // w: blob base, off[13]: POST_SLOTS of unit `unit` (packing.py).

@@ -36,36 +36,16 @@ __device__ __forceinline__ f4 pf_lrelu(f4 v, float slope) {
     return r;
 }
 
-__device__ __forceinline__ f4 pf_relu(f4 v) {
-    f4 r;
-    r.x = fmaxf(v.x, 0.f); r.y = fmaxf(v.y, 0.f); r.z = fmaxf(v.z, 0.f); r.w = fmaxf(v.w, 0.f);
-    return r;
-}
-
-__device__ __forceinline__ float pf_lrelu1(float v, float slope) { return fmaxf(v, v * slope); }
-
 // ---- weight fragment sources -----------------------------------------------------------
 // Every lane-address of a weight fragment is (wave-uniform base) + lane*16.  hipcc otherwise
 // hoists one 64-bit VGPR address pair PER FRAGMENT out of the persistent tile loop (hundreds of
-// VGPRs); both sources below keep it to ONE VGPR:
-//   PfWLds : fragments resident in LDS, ds_read_b128 with a 16-bit immediate offset
-//   PfWBuf : fragments in global memory through a buffer descriptor (SGPRs), uniform soffset
+// VGPRs); the sources here keep it to ONE VGPR:
+//   PfWLds             : fragments resident in LDS, ds_read_b128 with a 16-bit immediate offset
+//   PfW2BufD (f16 path): fragments in global memory through a buffer descriptor (SGPRs), uniform soffset
 struct PfWLds {
     const f4* base;     // LDS
     int lane;
     __device__ __forceinline__ f4 load(int frag) const { return base[frag * PF_WAVE + lane]; }
-};
-
-struct PfWBuf {
-    __amdgpu_buffer_rsrc_t rsrc;
-    int voff;           // lane * 16
-    __device__ __forceinline__ PfWBuf(const void* p, int lane)
-        : rsrc(__builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, 0x7fffffff, 0x00020000)), voff(lane * 16) {}
-    __device__ __forceinline__ f4 load(int frag) const {
-        typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-        u4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, frag * (PF_WAVE * 16), 0);
-        return __builtin_bit_cast(f4, v);
-    }
 };
 
 // acc[p][acc0+ob] += W[ob][cb] * in[p][in0+cb]  for ob < OB, cb < CB.
@@ -134,9 +114,6 @@ __device__ __forceinline__ f4 pf_mfma_f16(h8 a, h8 b, f4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
 }
 
-#ifndef PF_MM2_DEPTH
-#define PF_MM2_DEPTH 8
-#endif
 #ifndef PF_W2LDS_DEPTH
 #define PF_W2LDS_DEPTH 2
 #endif
@@ -162,20 +139,9 @@ struct PfW2BufD {
     }
 };
 
-struct PfW2Buf {
-    static constexpr int DEPTH = PF_MM2_DEPTH;   // L2 latency wants ~500 cycles of MFMA work in flight
-    __amdgpu_buffer_rsrc_t rsrc;
-    int voff;           // lane * 16
-    __device__ __forceinline__ PfW2Buf(const void* p, int lane)
-        : rsrc(__builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, 0x7fffffff, 0x00020000)), voff(lane * 16) {}
-    __device__ __forceinline__ h8 load(int frag, int split) const {
-        return __builtin_bit_cast(h8, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, (frag * 2 + split) * (PF_WAVE * 16), 0));
-    }
-};
-
 // acc[p][acc0+ob] += Wh xh ;  accx[p][acc0+ob] += Wh xl' + Wl' xh   over block PAIRS cp < CP.
 // Caller folds:  value = acc + accx * PF_LO_INV.  D fragments (two 16-B reads each) are kept in flight: 2 is enough
-// for LDS-resident weights, L2-resident weights behind buffer loads want ~500 cycles of cover (PF_MM2_DEPTH).
+// for LDS-resident weights, L2-resident weights behind buffer loads want ~500 cycles of cover (a deeper PfW2BufD).
 template <int OB, int CP, int WCP, int D = 2, class WS2, int P, int NIN, int NACC>
 __device__ __forceinline__ void pf_mm2(const WS2& ws, int frag0, const PfPair2 (&in)[P][NIN], int in0,
                                        f4 (&acc)[P][NACC], f4 (&accx)[P][NACC], int acc0) {
@@ -205,16 +171,6 @@ __device__ __forceinline__ void pf_mm2(const WS2& ws, int frag0, const PfPair2 (
         }
         __builtin_amdgcn_sched_barrier(0);
     }
-}
-
-// NB 16-channel blocks in[p][in0 .. in0+NB) -> (NB+1)/2 split block pairs (an odd tail pairs with a zero block)
-template <int NB, int P, int NIN>
-__device__ __forceinline__ void pf_pairs2(const f4 (&in)[P][NIN], int in0, PfPair2 (&out)[P][(NB + 1) / 2]) {
-#pragma unroll
-    for (int p = 0; p < P; ++p)
-#pragma unroll
-        for (int c = 0; c < (NB + 1) / 2; ++c)
-            out[p][c] = pf_pair2(in[p][in0 + 2 * c], 2 * c + 1 < NB ? in[p][in0 + 2 * c + 1] : pf_splat(0.f));
 }
 
 // acc[p][acc0+ob] += W[ob][cp] in[p][cp] with the cross accumulator folded in (complete split-fp16 product)
@@ -337,7 +293,7 @@ __device__ __forceinline__ PfHalfN pf_act_halfn_t(f4 b, float inv, float slope) 
 __device__ __forceinline__ PfPairN pf_act_pairn(f4 b0, f4 b1, float inv, float slope) { return pf_act_pairn_t<true, PF_ACT_LRELU>(b0, b1, inv, slope); }
 // inv == 1 (the EdgeConv kernels: the scale plan leaves nothing to undo)
 __device__ __forceinline__ PfPairN pf_act_pairn(f4 b0, f4 b1, float slope) { return pf_act_pairn_t<false, PF_ACT_LRELU>(b0, b1, 1.f, slope); }
-// == pf_pairn(pf_relu(b0 * inv), pf_relu(b1 * inv))
+// == pf_pairn(max(b0 * inv, 0), max(b1 * inv, 0))
 __device__ __forceinline__ PfPairN pf_relu_pairn(f4 b0, f4 b1, float inv) { return pf_act_pairn_t<true, PF_ACT_RELU>(b0, b1, inv, 0.f); }
 // one block at a time, for the 16-channel layers whose blocks reach a pair one layer apart: the earlier block's half is kept
 // and joined with the next one instead of being split a second time.  A missing block is PfHalfN{} (the split of zeros).
@@ -366,35 +322,28 @@ __device__ __forceinline__ float pf_rsmax16(float a, float b) {
 }
 
 // acc[p][o] += W[o][cp] feat[p][cp] over CP block pairs, three fp16 MFMAs per pair into the one accumulator (small terms
-// first).  SWAP = false: D[channel][edge] (weights are the A operand);  SWAP = true: D[edge][channel].
-#ifndef PF_MMN_CPMAJOR
-#define PF_MMN_CPMAJOR 0
-#endif
+// first).  SWAP = false: D[channel][edge] (weights are the A operand);  SWAP = true: D[edge][channel].  The fragment walk is
+// ob-major (one accumulator's whole chain, then the next); s_setprio around the chain was measured and dropped,
+// as was a cp-major walk.  The non-SWAP step is pf_pq.h pq_step spelled out (that header sits above this one; SWAP adds
+// its two small terms in the other order, lo.hi first).
 // Products per 32-channel step: 3 = split-fp16 with the natural-scale low half (hi*lo + lo*hi + hi*hi: fp32-grade results,
 // the parity mode and the default); 1 = hi*hi only - plain fp16 operands, fp32 accumulation: the reduced-precision THROUGHPUT
 // build (`libpuflow_hip_f16.so`, BASELINE configs[1] "bf16/fp16" line; judged by Chamfer distance, never the headline)
 #ifndef PF_MMN_TERMS
 #define PF_MMN_TERMS 3
 #endif
-#ifndef PF_MMN_PRIO
-#define PF_MMN_PRIO 0
-#endif
 template <bool SWAP, int OB, int CP, int WCP, bool FENCE = true, class WS, int P, int NIN, int NACC>
 __device__ __forceinline__ void pf_mmn(const WS& ws, int frag0, const PfPairN (&feat)[P][NIN], f4 (&acc)[P][NACC], int in0 = 0, int acc0 = 0) {
     constexpr int D = WS::DEPTH;                  // fragments in flight: 2 from LDS, 8 behind buffer loads (L2 latency)
     constexpr int NFRAG = OB * CP;
     constexpr int DD = D < NFRAG ? D : NFRAG;
-    // fragment walk: ob-major (one accumulator's whole chain, then the next) or cp-major (accumulators alternate)
-    auto OBI = [](int i) { return PF_MMN_CPMAJOR ? i % OB : i / CP; };
-    auto CPI = [](int i) { return PF_MMN_CPMAJOR ? i / OB : i % CP; };
+    auto OBI = [](int i) { return i / CP; };
+    auto CPI = [](int i) { return i % CP; };
     h8 wb[DD][2];
 #pragma unroll
     for (int i = 0; i < DD; ++i)
 #pragma unroll
         for (int s = 0; s < 2; ++s) wb[i][s] = ws.load(frag0 + OBI(i) * WCP + CPI(i), s);
-#if PF_MMN_PRIO
-    __builtin_amdgcn_s_setprio(PF_MMN_PRIO);      // tuning build: a wave inside an MFMA chain wins the issue arbitration
-#endif
 #pragma unroll
     for (int i = 0; i < NFRAG; ++i) {
         const int ob = OBI(i), cp = CPI(i);
@@ -424,9 +373,6 @@ __device__ __forceinline__ void pf_mmn(const WS& ws, int frag0, const PfPairN (&
         }
         if constexpr (FENCE) __builtin_amdgcn_sched_barrier(0);      // FENCE = false: the caller interleaves two streams itself
     }
-#if PF_MMN_PRIO
-    __builtin_amdgcn_s_setprio(0);
-#endif
 }
 
 // ---- edge-table products as ONE MFMA ------------------------------------------------------------------------------------

@@ -19,20 +19,21 @@
 // B operands (every wave converts 1 / NW of the round's tiles: fp32 -> (hi, lo) once per point, not once per consumer),
 // then every wave multiplies every tile by its rows.  LDS bytes per MFMA are half of what streaming the weights would
 // need, no weight byte is re-read from L2 after the prologue, and the operand split costs 1/16 of the VALU work.
+// The product itself - layouts, three-term step, weight load, staging unit, tile product, rescale and store - is pf_pq.h's,
+// shared with the two fused forms of edgeconv.hip; this kernel is the walk over linear rounds of tiles around it.
 //
 // pf_cond keeps its 120 KiB of weights in LDS for the life of a persistent workgroup (one wave = 16 points).
 #include <hip/hip_runtime.h>
 #include "pf_api_internal.h"
 #include "pf_mfma.h"
+#include "pf_pq.h"
 
 namespace {
-
-__device__ __forceinline__ h8 pf_ldw(const u4* p) { return __builtin_bit_cast(h8, *p); }
 
 // ---------------------------------------------------------------------------------------------------------------------
 struct PqArgs {
     const float* h;       // [T, ODIM]
-    const u4* w;          // f16n fragment image [ROWS/16][CP][hi / lo][64 lanes]
+    const u4* w;          // f16n fragment image (pf_pq.h)
     const float* bias;    // [ROWS]   true scale, added after the rescale
     const float* scales;  // POST_SCALES: [6] = 2^-sw of the PQ matrix
     float* pq;            // [T, ROWS]
@@ -46,19 +47,12 @@ __global__ __launch_bounds__(NW * 64) void pq_gemm_kernel(PqArgs a) {
     static_assert(OBT % NW == 0, "rows split evenly over the waves");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int col = lane & 15, q = lane >> 4;
-    __shared__ u4 bl[NTMAX][CP][2][64];
+    __shared__ u4 bl[NTMAX * PQ_TILE_U4<CP>];
     h8 wh[RB][CP], wl[RB][CP];
     f4 bias[RB];
 #pragma unroll
-    for (int ob = 0; ob < RB; ++ob) {
-#pragma unroll
-        for (int cp = 0; cp < CP; ++cp) {
-            const u4* f = a.w + (size_t)(((wave * RB + ob) * CP + cp) * 2) * 64 + lane;
-            wh[ob][cp] = pf_ldw(f);
-            wl[ob][cp] = pf_ldw(f + 64);
-        }
-        bias[ob] = *reinterpret_cast<const f4*>(a.bias + (wave * RB + ob) * 16 + 4 * q);
-    }
+    for (int ob = 0; ob < RB; ++ob) bias[ob] = *reinterpret_cast<const f4*>(a.bias + (wave * RB + ob) * 16 + 4 * q);
+    pq_load_w(a.w, wave * RB, lane, wh, wl);
     const float inv = a.scales ? a.scales[6] : a.inv;
     for (int round = blockIdx.x; round < a.nrounds; round += gridDim.x) {
         const int tile0 = round * a.NT;
@@ -67,77 +61,35 @@ __global__ __launch_bounds__(NW * 64) void pq_gemm_kernel(PqArgs a) {
         for (int t = wave; t < nt; t += NW) {
             int pt = (tile0 + t) * 16 + col;
             pt = pt < a.T ? pt : a.T - 1;
-            f4 hb[HB + (HB & 1)];
+            f4 hb[HB + (HB & 1)];                             // every block of the row first: one memory latency per tile
 #pragma unroll
             for (int b = 0; b < HB; ++b) hb[b] = *reinterpret_cast<const f4*>(a.h + (size_t)pt * ODIM + b * 16 + 4 * q);
             if constexpr (HB & 1) hb[HB] = pf_splat(0.f);
 #pragma unroll
-            for (int cp = 0; cp < CP; ++cp) {
-                const PfPairN p = pf_pairn(hb[2 * cp], hb[2 * cp + 1]);
-                bl[t][cp][0][lane] = __builtin_bit_cast(u4, p.h);
-                bl[t][cp][1][lane] = __builtin_bit_cast(u4, p.l);
-            }
+            for (int cp = 0; cp < CP; ++cp) pq_stage_unit(bl + t * PQ_TILE_U4<CP> + pq_frag_u4(cp, 0, 0), hb[2 * cp], hb[2 * cp + 1], lane);
         }
         __syncthreads();
         for (int t = 0; t < nt; ++t) {
             f4 acc[RB];
-#pragma unroll
-            for (int ob = 0; ob < RB; ++ob) acc[ob] = pf_splat(0.f);
-#pragma unroll
-            for (int cp = 0; cp < CP; ++cp) {
-                const h8 fh = __builtin_bit_cast(h8, bl[t][cp][0][lane]), fl = __builtin_bit_cast(h8, bl[t][cp][1][lane]);
-#pragma unroll
-                for (int ob = 0; ob < RB; ++ob) {
-                    f4 x = acc[ob];
-                    if constexpr (PF_MMN_TERMS == 3) {
-                        x = pf_mfma_f16(wh[ob][cp], fl, x);
-                        x = pf_mfma_f16(wl[ob][cp], fh, x);
-                    }
-                    x = pf_mfma_f16(wh[ob][cp], fh, x);
-                    acc[ob] = x;
-                }
-            }
+            pq_tile_product(bl + t * PQ_TILE_U4<CP>, lane, wh, wl, acc);
             const int pt = (tile0 + t) * 16 + col;
-            if (pt < a.T) {
-#pragma unroll
-                for (int ob = 0; ob < RB; ++ob) {
-                    f4 o;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) o[r] = fmaf(acc[ob][r], inv, bias[ob][r]);
-                    *reinterpret_cast<f4*>(a.pq + (size_t)pt * ROWS + (wave * RB + ob) * 16 + 4 * q) = o;
-                }
-            }
+            if (pt < a.T) pq_tile_store<ROWS>(a.pq, pt, wave * RB, q, acc, inv, bias);
         }
         __syncthreads();                                   // the next round overwrites the staged tiles
     }
 }
 
-template <int ODIM, int ROWS>
+// tiles per round: as many as LDS holds when there is plenty of work, fewer when that would leave CUs idle; one workgroup per
+// CU (LDS, up to 16 waves).  pf_pq_gemm: NW = 16; pf_cnf_context (ROWS = 288: 18 row blocks): 9 waves x 2
+template <int ODIM, int ROWS, int NW>
 int launch_pq(PqArgs a, hipStream_t s) {
-    constexpr int NW = 16;
-    a.ntiles = (a.T + 15) / 16;
-    // tiles per round: as many as LDS holds when there is plenty of work, fewer when that would leave CUs idle
-    int nt = a.ntiles / 256;
-    nt = nt < 1 ? 1 : (nt > 16 ? 16 : nt);
-    a.NT = nt;
-    a.nrounds = (a.ntiles + nt - 1) / nt;
-    const int grid = a.nrounds < 256 ? a.nrounds : 256;    // one workgroup per CU (LDS, 16 waves)
-    hipLaunchKernelGGL((pq_gemm_kernel<ODIM, ROWS, NW>), dim3(grid), dim3(NW * 64), 0, s, a);
-    return pf_last_launch_status();
-}
-
-// the same kernel for the continuous model's context GEMM ctx = c Hc^T + hb ([288 x cd] x [cd x T], 75 MB written per
-// block at 32 x 2048): 18 row blocks = 9 waves x 2
-template <int ODIM>
-int launch_ctx(PqArgs a, hipStream_t s) {
-    constexpr int NW = 9;
     a.ntiles = (a.T + 15) / 16;
     int nt = a.ntiles / 256;
     nt = nt < 1 ? 1 : (nt > 16 ? 16 : nt);
     a.NT = nt;
     a.nrounds = (a.ntiles + nt - 1) / nt;
     const int grid = a.nrounds < 256 ? a.nrounds : 256;
-    hipLaunchKernelGGL((pq_gemm_kernel<ODIM, 288, NW>), dim3(grid), dim3(NW * 64), 0, s, a);
+    hipLaunchKernelGGL((pq_gemm_kernel<ODIM, ROWS, NW>), dim3(grid), dim3(NW * 64), 0, s, a);
     return pf_last_launch_status();
 }
 
@@ -347,9 +299,9 @@ extern "C" int pf_pq_gemm(int unit, const float* h, const float* w, const long l
     a.h = h; a.w = reinterpret_cast<const u4*>(w + off[10]); a.bias = w + off[11]; a.scales = w + off[12]; a.pq = pq_next; a.T = T;
     hipStream_t s = (hipStream_t)stream;
     switch (unit) {
-        case 0: return launch_pq<32, 256>(a, s);
-        case 1: return launch_pq<64, 512>(a, s);
-        case 2: case 3: case 4: return launch_pq<128, 512>(a, s);
+        case 0: return launch_pq<32, 256, 16>(a, s);
+        case 1: return launch_pq<64, 512, 16>(a, s);
+        case 2: case 3: case 4: return launch_pq<128, 512, 16>(a, s);
         default: return PF_ERR_UNSUPPORTED;
     }
 }
@@ -365,9 +317,9 @@ extern "C" int pf_cnf_context(const float* c, int cd, const float* hc_image, con
     a.h = c; a.w = reinterpret_cast<const u4*>(hc_image); a.bias = hb; a.scales = nullptr; a.inv = inv_scale; a.pq = ctx; a.T = T;
     hipStream_t s = (hipStream_t)stream;
     switch (cd) {
-        case 32: return launch_ctx<32>(a, s);
-        case 64: return launch_ctx<64>(a, s);
-        case 128: return launch_ctx<128>(a, s);
+        case 32: return launch_pq<32, 288, 9>(a, s);
+        case 64: return launch_pq<64, 288, 9>(a, s);
+        case 128: return launch_pq<128, 288, 9>(a, s);
         default: return PF_ERR_UNSUPPORTED;
     }
 }

@@ -208,6 +208,41 @@ class _Engine:
                    "pf_knn")
         return idx
 
+    def _unit_chain(self, xyz: Tensor, idx16: Tensor, split_two_launch: bool = False):
+        """The six-unit EdgeConv -> next unit's P|Q chain, one unit per step: yields (h, calls) with h [T, odim_u] the unit's
+        output buffer and calls the unit's launches in order as (stage name, thunk) - `edgeconv{u}+pq` (pf_edgeconv_pq: one launch
+        or two by unit and size, self.fuse_pq) in the product arithmetic, else `edgeconv{u}` and, before the last unit, `pq{u}`
+        (pf_pq_gemm).  split_two_launch (the profiler): fuse_pq == 0 is issued as its two launches, each under its own name.
+        The tables: units read their P|Q table while the next one's is written: two tables, alternating (the fused kernel reads
+        and writes tables in the same launch; the two-kernel path would get by with one)."""
+        B, N, _ = xyz.shape
+        T, dev, s = B * N, xyz.device, self._stream()
+        pq = torch.empty((T, 512), dtype=torch.float32, device=dev)
+        pq2 = torch.empty((T, 512), dtype=torch.float32, device=dev)
+        fused = self.ec_mode == "f16n" and not (split_two_launch and self.fuse_pq == 0)
+        for u in range(NUM_BLOCKS):
+            h = torch.empty((T, FEAT_CHANNELS[u + 1]), dtype=torch.float32, device=dev)
+            src = xyz.data_ptr() if u == 0 else (pq if u % 2 else pq2).data_ptr()
+            nxt = pq2 if u % 2 else pq
+
+            def ec(u=u, src=src, h=h):
+                self._edgeconv(u, src, idx16, h, B, N, s)
+
+            def ec_pq(u=u, src=src, h=h, nxt=nxt):
+                w = self.ec1n_w[u] if u < 2 else self.ec4_w[u]
+                _lib.check(self.lib.pf_edgeconv_pq(u, src, idx16.data_ptr(), self._p(w), h.data_ptr(), self.base, self.post[u],
+                                                   nxt.data_ptr(), B, N, self.fuse_pq, s), f"pf_edgeconv_pq[{u}]")
+
+            def pq_gemm(u=u, h=h, nxt=nxt):
+                _lib.check(self.lib.pf_pq_gemm(u, h.data_ptr(), self.base, self.post[u], nxt.data_ptr(), T, s), f"pf_pq_gemm[{u}]")
+
+            if u + 1 == NUM_BLOCKS:
+                yield h, [(f"edgeconv{u}", ec)]
+            elif fused:
+                yield h, [(f"edgeconv{u}+pq", ec_pq)]
+            else:
+                yield h, [(f"edgeconv{u}", ec), (f"pq{u}", pq_gemm)]
+
     def features(self, xyz: Tensor, idx16: Tensor, want_cs: bool, cs_only: bool = False):
         """6x (EdgeConv -> next unit's P|Q GEMM), then the six conditioner stages (they only feed the flow kernels, so they
         stay off the EdgeConv -> P|Q -> EdgeConv chain).  Returns cs (or None), cp [6,T,64], st [6,T,8].
@@ -216,25 +251,10 @@ class _Engine:
         T, dev, s = B * N, xyz.device, self._stream()
         cp = torch.empty((NUM_BLOCKS, T, 64), dtype=torch.float32, device=dev) if not (cs_only and want_cs) else None
         st = torch.empty((NUM_BLOCKS, T, 8), dtype=torch.float32, device=dev) if not (cs_only and want_cs) else None
-        pq = torch.empty((T, 512), dtype=torch.float32, device=dev)
         hs: List[Tensor] = []
-        # units read their P|Q table while the next one's is written: two tables, alternating (the fused kernel reads and writes
-        # tables in the same launch; the two-kernel path would get by with one)
-        pq2 = torch.empty((T, 512), dtype=torch.float32, device=dev)
-        for u in range(NUM_BLOCKS):
-            h = torch.empty((T, FEAT_CHANNELS[u + 1]), dtype=torch.float32, device=dev)
-            src = xyz.data_ptr() if u == 0 else (pq if u % 2 else pq2).data_ptr()
-            nxt = pq2 if u % 2 else pq
-            if u + 1 == NUM_BLOCKS:
-                self._edgeconv(u, src, idx16, h, B, N, s)
-            elif self.ec_mode == "f16n":
-                # EdgeConv u + the next unit's P|Q vectors: one launch or two by unit and size (pf_edgeconv_pq, self.fuse_pq)
-                w = self.ec1n_w[u] if u < 2 else self.ec4_w[u]
-                _lib.check(self.lib.pf_edgeconv_pq(u, src, idx16.data_ptr(), self._p(w), h.data_ptr(), self.base, self.post[u],
-                                                   nxt.data_ptr(), B, N, self.fuse_pq, s), f"pf_edgeconv_pq[{u}]")
-            else:
-                self._edgeconv(u, src, idx16, h, B, N, s)
-                _lib.check(self.lib.pf_pq_gemm(u, h.data_ptr(), self.base, self.post[u], nxt.data_ptr(), T, s), f"pf_pq_gemm[{u}]")
+        for h, calls in self._unit_chain(xyz, idx16):
+            for _, call in calls:
+                call()
             hs.append(h)
         cs: List[Optional[Tensor]] = [torch.empty((B, N, COND_CHANNELS[u]), dtype=torch.float32, device=dev) if want_cs else None
                                       for u in range(NUM_BLOCKS)]
@@ -332,22 +352,10 @@ class _Engine:
             idx16 = timed("knn", lambda: self.knn(xyz))
             cp = torch.empty((NUM_BLOCKS, T, 64), dtype=torch.float32, device=dev)
             st = torch.empty((NUM_BLOCKS, T, 8), dtype=torch.float32, device=dev)
-            pq = torch.empty((T, 512), dtype=torch.float32, device=dev)
             hs = []
-            pq2 = torch.empty((T, 512), dtype=torch.float32, device=dev)
-            fused = self.ec_mode == "f16n" and self.fuse_pq != 0        # as features(): pf_edgeconv_pq picks the form
-            for u in range(NUM_BLOCKS):
-                h = torch.empty((T, FEAT_CHANNELS[u + 1]), dtype=torch.float32, device=dev)
-                src = xyz.data_ptr() if u == 0 else (pq if u % 2 else pq2).data_ptr()
-                nxt = pq2 if u % 2 else pq
-                if fused and u + 1 < NUM_BLOCKS:
-                    w = self.ec1n_w[u] if u < 2 else self.ec4_w[u]
-                    timed(f"edgeconv{u}+pq", lambda: _lib.check(self.lib.pf_edgeconv_pq(
-                        u, src, idx16.data_ptr(), self._p(w), h.data_ptr(), self.base, self.post[u], nxt.data_ptr(), B, N, self.fuse_pq, s)))
-                else:
-                    timed(f"edgeconv{u}", lambda: self._edgeconv(u, src, idx16, h, B, N, s))
-                    if u + 1 < NUM_BLOCKS:
-                        timed(f"pq{u}", lambda: _lib.check(self.lib.pf_pq_gemm(u, h.data_ptr(), self.base, self.post[u], nxt.data_ptr(), T, s)))
+            for h, calls in self._unit_chain(xyz, idx16, split_two_launch=True):      # the launches of features(), each timed
+                for name, call in calls:
+                    timed(name, call)
                 hs.append(h)
             timed("cond_all", lambda: self._cond_all(hs, None, st, cp, T, s))
             z, _, _ = timed("flow_f+logp", lambda: self.flow_f(xyz, cp, st))

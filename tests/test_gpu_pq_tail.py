@@ -1,11 +1,12 @@
-"""The next unit's P|Q vectors as the TAIL phase of the producing EdgeConv launch (pf_edgeconv_pq fuse = 2, csrc/edgeconv.hip
-pq_tail): the bits of the two-launch path (fuse = 0: the EdgeConv kernel, then pointwise.hip pq_gemm_kernel), for the three
-kernel instantiations (unit 0, unit 1, units 2 - 4) at the smallest shapes that reach each corner of the tail:
+"""The next unit's P|Q vectors from inside the producing EdgeConv launch (pf_edgeconv_pq, csrc/edgeconv.hip), interleaved with
+the tile loop (fuse = 1, pqf_gemm) and as the launch's TAIL phase (fuse = 2, pq_tail): the bits of the two-launch path (fuse = 0:
+the EdgeConv kernel, then pointwise.hip pq_gemm_kernel; all three forms walk tiles around the one product of csrc/pf_pq.h), for
+the three kernel instantiations (unit 0, unit 1, units 2 - 4) at the smallest shapes that reach each corner of the tile walks:
   (3, 24)      T = 72 is no multiple of 16, batch items straddle a tile, and there are fewer tiles than workgroups: most
-               workgroups reach the tail with an empty tile list
-  (1, 272)     17 tiles: workgroups with one tile and with none, a partial staging round
+               workgroups reach the tail, or the flush behind the loop, with an empty tile list
+  (1, 272)     17 tiles: workgroups with one tile and with none, a partial staging round / a partial flush
   (17, 2048)   2 176 tiles: 8 or 9 per workgroup of the 128-channel kernel - more than one staging round, the second one partial,
-               and holes in the XCD-aware tile walk
+               and holes in the XCD-aware tile walk; fuse = 1 is forced here (the size policy leaves it at 16 384 points)
 Needs a real MI355X:  python -m pytest tests -m gpu"""
 import pytest
 import torch
@@ -68,17 +69,18 @@ def chain(net):
 
 @pytest.mark.parametrize("B,N", SHAPES)
 @pytest.mark.parametrize("unit", [0, 1, 2])
-def test_tail_form_returns_the_two_launch_bits(net, chain, unit, B, N):
+@pytest.mark.parametrize("fuse", [1, 2])
+def test_fused_forms_return_the_two_launch_bits(net, chain, fuse, unit, B, N):
     e = net._engine(4)
     idx16, units = chain(B, N)
     src, out0, nxt0 = units[unit]
     assert not torch.isnan(out0).any() and not torch.isnan(nxt0).any()       # the reference itself wrote every row
-    out2, nxt2 = _unit(e, unit, src, idx16, B, N, 2)
+    out2, nxt2 = _unit(e, unit, src, idx16, B, N, fuse)
     torch.cuda.synchronize()
     assert torch.equal(out0, out2), "out"
     bad = (nxt0 != nxt2) | torch.isnan(nxt2)
     rows = torch.nonzero(bad.any(dim=1)).flatten()
-    print(f"unit {unit} ({B}, {N}): pq_next rows that differ {rows.numel()} of {B * N}", rows[:8].tolist())
+    print(f"fuse {fuse} unit {unit} ({B}, {N}): pq_next rows that differ {rows.numel()} of {B * N}", rows[:8].tolist())
     assert torch.equal(nxt0, nxt2), "pq_next"
 
 

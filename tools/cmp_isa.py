@@ -49,7 +49,7 @@ def parse(asm_path):
     dm = demangle(kernels)
     res = {}
     for k in kernels:
-        m = re.search(r"^" + re.escape(k) + r":[^\n]*\n(.*?)^\.Lfunc_end\d+:\n(.*?)(?=^\s*\.(?:section|text|protected|globl)\b)", text, re.S | re.M)
+        m = re.search(r"^" + re.escape(k) + r":[^\n]*\n(.*?)^\.Lfunc_end\d+:\n(.*?)(?=^\s*\.(?:section(?!\s+\.AMDGPU\.csdata)|text|protected|globl)\b)", text, re.S | re.M)
         assert m, k
         body, tail = m.group(1), m.group(2)
         body = body[:body.rindex("s_endpgm") + len("s_endpgm")]
