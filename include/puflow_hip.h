@@ -749,6 +749,24 @@ int pf_cnf_step(const float* y0, const float* f0, float t, float h, int reverse,
  * power-of-two scale.  cd: 32, 64 or 128. */
 int pf_cnf_context(const float* c, int cd, const float* hc_image, const float* hb, float inv_scale, float* ctx, int T, void* stream);
 
+/* The weight records of nb <= 6 blocks from their LIVE parameter tensors, on the device, in one launch (csrc/cnf_pack.hip): what
+ * packing.pack_cnf_block, pack_cnf_context and cnf_hyper_matrix make on the host, bit for bit.  A training step packs here: the
+ * host packers cost a device -> host copy of every parameter and ~70 small uploads per block and call.
+ *   params  HOST array of 16 nb DEVICE pointers (contiguous fp32), per block: for layer l = 0, 1, 2 of odefunc.diffeq.layers
+ *           _layer.weight, _layer.bias, _hyper_gate.weight [out, 1 + cd], _hyper_gate.bias, _hyper_bias.weight [out, 1 + cd];
+ *           then sqrt_end_time
+ *   cd      HOST array [nb]: the context width of each block, 32, 64 or 128
+ *   rec     [nb, 10160]   the weight records (csrc/pf_cnf.h: CNF_REC)
+ *   hb      [nb, 288]     the context GEMM's bias (folded)
+ *   hc, hplain, image     HOST arrays [nb] of DEVICE pointers to [288, cd[b]] floats each: the folded hyper matrix, the unfolded
+ *           one (the backward of the context GEMM multiplies by it) and the f16n fragment image of hc x 2^sw for pf_cnf_context
+ *   meta    [nb, 4] DEVICE doubles: [0] T_end = sqrt_end_time^2 (exact), [1] 2^-sw = pf_cnf_context's inv_scale, [2] status: bit 0
+ *           an f16x2 image of the record, bit 1 the f16n image holds a magnitude >= 65504 (the host packers raise ValueError
+ *           there; the outputs of such a block are not to be used), [3] zero.  The caller reads it once for all blocks.
+ * No grid barrier, no atomics, no residency requirement. */
+int pf_cnf_pack_blocks(const float* const* params, const int* cd, int nb, float* rec, float* hb, void* const* hc,
+                       void* const* hplain, void* const* image, double* meta, void* stream);
+
 /* n_attempts dopri5 step attempts with the step-size controller ON THE DEVICE (no host read between attempts).
  * ctl: 16 doubles - [0] t [1] dt [2] t1 [3] n_tot (elements of the RMS norm) [4] cur (which of ya / yb, fa / fb is current)
  * [5] done [6] accepted [7] rejected [8] nfe [9] status (0 ok, 1 non-finite error norm, 2 dt underflow) [10] reverse.

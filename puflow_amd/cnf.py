@@ -1,8 +1,10 @@
 """Continuous (CNF) PU-Flow: `modules/continuous/interpflow.py` on the HIP library.
 
 Same constructor, methods and the 390 state-dict keys of the reference's continuous `PointInterpFlow`
-(`pretrain/puflow-x4-cnf-pu1k.pt` loads with `load_state_dict`).  The whole model is eval / inference only; ONE flow block is
-differentiable (`PointInterpFlow.flow_block`: taped Dormand-Prince steps, backward by `pf_cnf_tape_vjp`, csrc/cnf_bwd.hip).
+(`pretrain/puflow-x4-cnf-pu1k.pt` loads with `load_state_dict`).  eval(): the inference plan below.  train(): the forward with
+gradients (`forward_train`: the discrete training step's extractor and interpolation branch, then `flow_train` - twelve taped
+integrations, backward by `pf_cnf_tape_vjp`, csrc/cnf_bwd.hip, weights packed from the live parameters on the device by
+`pf_cnf_pack_blocks`, csrc/cnf_pack.hip); `PointInterpFlow.flow_block` is ONE such block as an autograd function.
 
 What runs where:
   * kNN, the six EdgeConv units, the merge units and the interpolation module are the discrete model's kernels
@@ -34,7 +36,7 @@ from torch import Tensor
 from . import _lib
 from .interpflow import (COND_CHANNELS, FEAT_CHANNELS, GROWTH, NUM_BLOCKS, _EdgeConvParams, _Engine, _InterpParams,
                          _MergeParams)
-from .packing import (CNF_CTX, CNF_GRAD, cnf_hyper_matrix, cnf_split_ok, pack_cnf_block, pack_cnf_context,
+from .packing import (CNF_CTX, CNF_GRAD, CNF_REC, cnf_hyper_matrix, cnf_split_ok, pack_cnf_block, pack_cnf_context,
                       unpack_cnf_grads)
 from .train_perop import _gemm
 from .weights import state_dict_spec
@@ -113,6 +115,57 @@ def _discrete_shell(sd) -> dict:
     return out
 
 
+_PACK_NAMES = ("_layer.weight", "_layer.bias", "_hyper_gate.weight", "_hyper_gate.bias", "_hyper_bias.weight")
+
+
+def _pack_params(block: "_CNFBlockParams") -> List[Tensor]:
+    """The sixteen tensors of a block in the order pf_cnf_pack_blocks (and `_CnfPackFn`) takes them: per layer the five of
+    `_PACK_NAMES`, then sqrt_end_time."""
+    out = []
+    for layer in block.cnf.odefunc.diffeq.layers:
+        out += [layer._layer.weight, layer._layer.bias, layer._hyper_gate.weight, layer._hyper_gate.bias, layer._hyper_bias.weight]
+    return out + [block.cnf.sqrt_end_time]
+
+
+def _pack_keys(i: int) -> List[str]:
+    p = f"flow_blocks.{i}.cnf.odefunc.diffeq.layers"
+    return [f"{p}.{l}.{n}" for l in range(3) for n in _PACK_NAMES] + [f"flow_blocks.{i}.cnf.sqrt_end_time"]
+
+
+class _DevicePack:
+    """pf_cnf_pack_blocks (csrc/cnf_pack.hip): the weight records, context matrices and fragment images of up to six blocks from
+    their live parameter tensors in ONE launch, bit for bit what packing.pack_cnf_block / pack_cnf_context / cnf_hyper_matrix make
+    on the host.  `blocks`: per block the sixteen tensors of `_pack_params`.  The meta rows (end time, image scale, status) are the
+    one device -> host read; a status word raises the host packers' ValueError."""
+
+    def __init__(self, blocks: List[List[Tensor]], device: torch.device):
+        nb = len(blocks)
+        f32 = dict(dtype=torch.float32, device=device)
+        keep = [[t.detach().to(**f32).contiguous() for t in blk] for blk in blocks]      # parameters as they are: no copy
+        for blk in keep:
+            if len(blk) != 16 or blk[2].dim() != 2 or blk[2].shape[1] - 1 not in (32, 64, 128):
+                raise ValueError("pf_cnf_pack_blocks: sixteen tensors per block, context width 32, 64 or 128")
+        cds = [int(blk[2].shape[1]) - 1 for blk in keep]
+        self.rec = torch.empty((nb, CNF_REC), **f32)
+        self.hb = torch.empty((nb, CNF_CTX), **f32)
+        self.Hc = [torch.empty((CNF_CTX, cd), **f32) for cd in cds]
+        self.Hplain = [torch.empty((CNF_CTX, cd), **f32) for cd in cds]
+        self.image = [torch.empty(CNF_CTX * cd, **f32) for cd in cds]
+        self.meta = torch.empty((nb, 4), dtype=torch.float64, device=device)
+        ptrs = lambda ts: (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+        _lib.check(_lib.load().pf_cnf_pack_blocks(ptrs([t for blk in keep for t in blk]), _lib.counts(cds), nb, self.rec.data_ptr(),
+                                                  self.hb.data_ptr(), ptrs(self.Hc), ptrs(self.Hplain), ptrs(self.image),
+                                                  self.meta.data_ptr(), torch.cuda.current_stream().cuda_stream), "pf_cnf_pack_blocks")
+        meta = self.meta.cpu()                                  # the one read: all blocks
+        self.T_end = [float(v) for v in meta[:, 0]]
+        self.inv_scale = [float(v) for v in meta[:, 1]]
+        for j, st in enumerate(int(v) for v in meta[:, 2]):     # the messages of packing.frag_pack_f16x2 / frag_pack_f16n
+            if st & 1:
+                raise ValueError(f"block {j}: weight magnitude exceeds the fp16 range of the f16x2 path; use ec_mode='f32'")
+            if st & 2:
+                raise ValueError(f"block {j}: scaled weight magnitude exceeds the fp16 range of the f16n path; use ec_mode='f32'")
+
+
 class _CnfKernels:
     """Launch wrappers of csrc/cnf.hip shared by the inference engine and the taped single-block engine.  What they read of
     `self` is set by `_init_kernels` (lib, device, the norm kernels' scratch `ws` / `ws1k` / `red`, the counter `nfe`) and by
@@ -123,7 +176,7 @@ class _CnfKernels:
         self.lib = _lib.load()
         self.device = device
         self.rec, self.Hc, self.Hci, self.hb, self.T_end = {}, {}, {}, {}, {}
-        self.ws = torch.empty(256, dtype=torch.float64, device=device)
+        self.ws =torch.empty(256, dtype=torch.float64, device=device)
         self.ws1k = torch.empty(1024, dtype=torch.float64, device=device)
         self.red = torch.empty(1, dtype=torch.float64, device=device)
         self.nfe = 0
@@ -138,6 +191,12 @@ class _CnfKernels:
         self.hb[i] = torch.from_numpy(hb).to(self.device)
         self.T_end[i] = T_end
         return rec
+
+    def _add_packed(self, i: int, pack: "_DevicePack", j: int) -> None:
+        """Block i = entry j of a device-side pack (pf_cnf_pack_blocks): views of its outputs, nothing is copied."""
+        self.rec[i], self.Hc[i], self.hb[i] = pack.rec[j], pack.Hc[j], pack.hb[j]
+        self.Hci[i] = (pack.image[j], pack.inv_scale[j])
+        self.T_end[i] = pack.T_end[j]
 
     @staticmethod
     def _stream() -> int:
@@ -330,15 +389,27 @@ class _CnfEngine(_CnfKernels):
 
 class _BlockTapeEngine(_CnfKernels):
     """The kernels of ONE block around weights packed from the live parameters: the taped integration of
-    `PointInterpFlow.flow_block` and its backward."""
+    `PointInterpFlow.flow_block` and of the train-mode forward, and their backward.  sd_block: a host copy of the block's
+    parameters for the numpy packers (the A/B reference), or None with pack = (a `_DevicePack`, the block's entry in it).
+    scratch: another engine of the same device and stream whose controller, norm and slab workspaces this one shares (the six
+    engines of a train-mode forward run one after the other)."""
 
-    def __init__(self, sd_block, i: int, device: torch.device):
+    def __init__(self, sd_block, i: int, device: torch.device, pack=None, scratch: Optional["_BlockTapeEngine"] = None):
         self._init_kernels(device)
-        self._add_block(sd_block, i)
-        self.Hplain = torch.from_numpy(cnf_hyper_matrix(sd_block, i)[:, 1:].copy()).to(device)      # [288, cd], no folded constants
+        if pack is None:
+            self._add_block(sd_block, i)
+            self.Hplain = torch.from_numpy(cnf_hyper_matrix(sd_block, i)[:, 1:].copy()).to(device)      # [288, cd], no folded constants
+        else:
+            self._add_packed(i, *pack)
+            self.Hplain = pack[0].Hplain[pack[1]]
+        self.first_batch, self.next_batch = 8, 4                             # step attempts enqueued per look at the controller
+        self._vjp_wss: dict = {}
+        if scratch is not None:
+            self.ws, self.ws1k, self.red, self.ws3k, self.ctl, self._vjp_wss = (scratch.ws, scratch.ws1k, scratch.red, scratch.ws3k,
+                                                                                 scratch.ctl, scratch._vjp_wss)
+            return
         self.ws3k = torch.empty(3072, dtype=torch.float64, device=device)
         self.ctl = torch.zeros(16, dtype=torch.float64, device=device)       # dopri5 controller state of the device-side tape
-        self.first_batch, self.next_batch = 8, 4                             # step attempts enqueued per look at the controller
 
     def step(self, i, y, f0, t, h, reverse, ctx, e, y1, f1, rows, R) -> float:
         """One Dormand-Prince attempt (pf_cnf_step) -> the scaled error sum, read back (one host read per attempt)."""
@@ -348,23 +419,28 @@ class _BlockTapeEngine(_CnfKernels):
         self.nfe += 6
         return float(self.red.item())
 
-    def tape_forward(self, i: int, x: Tensor, c: Tensor, e: Tensor, R: int, reverse: bool, cap: int = 32):
+    def tape_forward(self, i: int, x: Tensor, c: Tensor, e: Tensor, R: int, reverse: bool, cap: int = 32, ctx: Optional[Tensor] = None,
+                     d0c: Optional[Tensor] = None):
         """dopri5 on block i with the control on the DEVICE (pf_cnf_init, then batches of pf_cnf_steps_taped attempts with one read
         of the controller per batch, as `_CnfEngine.integrate`), the step that would cover the end time cut to END there: the
         result is the last accepted step's solution, so the forward is exactly the recorded steps.  cap: steps the tape is
         allocated for; a tape that fills up (status 3) is allocated anew at twice the size and the integration starts again.
         -> (state [rows,4], tape): (s, h) per accepted step on the device (`steps_dev` [n,2], the fp32 values the kernels
         computed with) and as host floats (`steps`, one read when done), the state at the start of each step (`states` [n,rows,4]),
-        the context rows and the derivatives at both ends."""
+        the context rows and the derivatives at both ends.
+        ctx, d0c: block i's context rows and the context's norm word where the caller has them already (the train-mode forward
+        computes both once per block for f and g)."""
         rows = x.shape[0]
         dev = x.device
         T = self.T_end[i]
         t0, t1 = (0.0, T) if not reverse else (-T, 0.0)
-        ctx = self.context(i, c)
+        if ctx is None:
+            ctx = self.context(i, c)
         n_tot = float(rows * 4 + c.numel() * R)                 # the context is a state of the reference's ODE: it enters the norms
-        d0c = torch.empty(1, dtype=torch.float64, device=dev)
-        self.context_norm(c, d0c)
-        fbuf = torch.empty((2, rows, 4), dtype=torch.float32, device=dev)
+        if d0c is None:
+            d0c = torch.empty(1, dtype=torch.float64, device=dev)
+            self.context_norm(c, d0c)
+        fbuf =torch.empty((2, rows, 4), dtype=torch.float32, device=dev)
         cap = max(1, int(cap))
         while True:
             states = torch.empty((cap + 1, rows, 4), dtype=torch.float32, device=dev)
@@ -448,13 +524,12 @@ class _BlockTapeEngine(_CnfKernels):
 
     def _vjp_workspace(self, rows, R, dev) -> Tensor:
         """The slab workspace of pf_cnf_rhs_vjp and pf_cnf_tape_vjp (the same size), kept per shape."""
-        if getattr(self, "_vjp_shape", None) != (rows, R):
+        if (rows, R) not in self._vjp_wss:
             need = self.lib.pf_cnf_rhs_vjp_workspace_bytes(rows, R)
             if need < 0:
                 raise _lib.PuflowHipError(f"pf_cnf_rhs_vjp: rows = {rows} must be a multiple of R = {R} <= 16")
-            self._vjp_ws = torch.empty(need // 4, dtype=torch.float32, device=dev)
-            self._vjp_shape = (rows, R)
-        return self._vjp_ws
+            self._vjp_wss[(rows, R)] = torch.empty(need // 4, dtype=torch.float32, device=dev)
+        return self._vjp_wss[(rows, R)]
 
     def tape_vjp(self, i, states, steps_dev, sgn, ctx, e, ybar, ctxbar, grad, rows, R) -> None:
         """pf_cnf_tape_vjp: the reverse sweep of the recorded steps in one launch; ybar [rows,4] in / out."""
@@ -465,10 +540,10 @@ class _BlockTapeEngine(_CnfKernels):
                    "pf_cnf_tape_vjp")
 
     def vjp(self, i, y, kbar, t, sgn, ctx, e, ybar, ctxbar, grad, rows, R) -> None:
-        self._vjp_workspace(rows, R, y.device)
+        ws = self._vjp_workspace(rows, R, y.device)
         _lib.check(self.lib.pf_cnf_rhs_vjp(y.data_ptr(), kbar.data_ptr(), float(t), float(sgn), ctx.data_ptr(), e.data_ptr(),
                                            self.rec[i].data_ptr(), ybar.data_ptr(), ctxbar.data_ptr(), grad.data_ptr(), rows, R,
-                                           self._vjp_ws.data_ptr(), self._stream()), "pf_cnf_rhs_vjp")
+                                           ws.data_ptr(), self._stream()), "pf_cnf_rhs_vjp")
 
     def tape_backward(self, i: int, tape: dict, ybar: Tensor, c: Tensor, e: Tensor, R: int, reverse: bool, sweep: str = "fused"):
         """The recorded steps in reverse, step sizes as constants.  sweep = "fused": one pf_cnf_tape_vjp launch for
@@ -522,8 +597,11 @@ class _FlowBlockFn(torch.autograd.Function):
 
     @staticmethod
     def forward(fctx, x, c, e, i, R, reverse, keys, record, opts, *params):
-        sd = {k: p.detach().cpu() for k, p in zip(keys, params)}
-        eng = _BlockTapeEngine(sd, i, x.device)
+        if opts["pack"] == "device":                             # one launch on the live parameters, one read of its meta row
+            by_key = dict(zip(keys, params))
+            eng = _BlockTapeEngine(None, i, x.device, pack=(_DevicePack([[by_key[k] for k in _pack_keys(i)]], x.device), 0))
+        else:                                                    # the numpy packers on a host copy: ~70 small uploads
+            eng = _BlockTapeEngine({k: p.detach().cpu() for k, p in zip(keys, params)}, i, x.device)
         x32, c32, e32 = x.detach().float().contiguous(), c.detach().float().contiguous(), e.detach().float().contiguous()
         if opts["controller"] == "device":
             y, tape = eng.tape_forward(i, x32, c32, e32, R, reverse, opts["cap"])
@@ -565,6 +643,191 @@ class _FlowBlockFn(torch.autograd.Function):
             else:
                 out.append(grads[k].reshape(p.shape).to(p.dtype))
         return (y0bar[:, :3].contiguous().to(xdt), dc.to(cdt), None, None, None, None, None, None, None, *out)
+
+
+# ---- the train-mode forward: f, interpolation, g over all blocks ---------------------------------------------------
+# Three kinds of autograd node.  `_CnfPackFn` stands between the parameters and everything that reads their packed form: per block
+# it hands out two stand-in tensors whose GRADIENTS are what the kernels produce - the 4 900-float gradient record and
+# d[hb | Hc] - and turns their sums over both directions into the parameters' gradients once.  `_CnfContextFn` is the context
+# GEMM of a block, `_CnfIntegrateFn` one taped integration.  Autograd adds the two directions' ctxbar and records.
+class _CnfPackFn(torch.autograd.Function):
+    """(the sixteen parameters of every block) -> per block (grec [4900], h1 [288, 1 + cd]): stand-ins, their values are never
+    read.  One pf_cnf_pack_blocks launch; the engines are left in `engs`."""
+
+    @staticmethod
+    def forward(fctx, engs, *params):
+        nb = len(params) // 16
+        dev = params[0].device
+        pack = _DevicePack([list(params[16 * j:16 * j + 16]) for j in range(nb)], dev)
+        for j in range(nb):
+            engs.append(_BlockTapeEngine(None, j, dev, pack=(pack, j), scratch=engs[0] if engs else None))
+        fctx.meta = [(p.shape, p.dtype) for p in params]
+        fctx.set_materialize_grads(False)
+        outs = [torch.empty(CNF_GRAD, dtype=torch.float32, device=dev) for _ in range(nb)]
+        outs += [torch.empty((CNF_CTX, params[16 * j + 2].shape[1]), dtype=torch.float32, device=dev) for j in range(nb)]
+        return tuple(outs)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(fctx, *grads):
+        nb = len(grads) // 2
+        out = []
+        for j in range(nb):
+            grec, dH1 = grads[j], grads[nb + j]
+            meta = fctx.meta[16 * j:16 * j + 16]
+            if grec is None and dH1 is None:
+                out += [None] * 16
+                continue
+            dev = (grec if grec is not None else dH1).device
+            if grec is None:
+                grec = torch.zeros(CNF_GRAD, dtype=torch.float32, device=dev)
+            if dH1 is None:
+                dH1 = torch.zeros((CNF_CTX, meta[2][0][1]), dtype=torch.float32, device=dev)
+            g = unpack_cnf_grads(j, grec, dH1[:, 1:], dH1[:, 0])
+            out += [g[k].reshape(s).to(dt) for k, (s, dt) in zip(_pack_keys(j)[:15], meta)] + [None]   # sqrt_end_time: _CnfIntegrateFn
+        return (None, *out)
+
+
+class _CnfContextFn(torch.autograd.Function):
+    """ctx [T,288] = c Hc^T + hb of one block, once for f and g.  Backward, on the sum of both directions' ctxbar:
+    d[hb | Hc] = ctxbar^T [1 | c] (one GEMM, handed to `_CnfPackFn` through h1) and dc = ctxbar Hplain (one GEMM)."""
+
+    @staticmethod
+    def forward(fctx, eng, i, c, h1):
+        c32 = c.detach().float().contiguous()
+        fctx.eng, fctx.cdt = eng, c.dtype
+        fctx.save_for_backward(c32)
+        return eng.context(i, c32)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(fctx, ctxbar):
+        (c,) = fctx.saved_tensors
+        T, cd = c.shape
+        ctxbar = ctxbar.contiguous()
+        c1 = torch.cat([torch.ones((T, 1), dtype=torch.float32, device=c.device), c], dim=1).contiguous()
+        dH1 = torch.empty((CNF_CTX, cd + 1), dtype=torch.float32, device=c.device)
+        _gemm(ctxbar, 1, CNF_CTX, c1, cd + 1, 1, dH1, cd + 1, None, CNF_CTX, cd + 1, T)
+        dc = torch.empty((T, cd), dtype=torch.float32, device=c.device)
+        _gemm(ctxbar, CNF_CTX, 1, fctx.eng.Hplain, cd, 1, dc, cd, None, T, cd, CNF_CTX)
+        return None, None, dc.to(fctx.cdt), dH1
+
+
+class _CnfIntegrateFn(torch.autograd.Function):
+    """One taped integration of block i: (x [rows,3], ctx [T,288]) -> (x' [rows,3], delta logp [rows]).  Backward: one
+    pf_cnf_tape_vjp launch -> xbar, this direction's ctxbar and gradient record (through grec to `_CnfPackFn`), and
+    sqrt_end_time's gradient by the continuous formula."""
+
+    @staticmethod
+    def forward(fctx, eng, i, R, reverse, caps, steps_out, c, d0c, e, x, ctx, grec, sqrt_t):
+        x32 = x.detach().float().contiguous()
+        y, tape = eng.tape_forward(i, x32, c, e, R, reverse, caps.get((i, reverse), 32), ctx=ctx.detach(), d0c=d0c)
+        n = len(tape["steps"])
+        caps[(i, reverse)] = n + n // 8 + 2
+        steps_out.append(tape["steps"])
+        fctx.eng, fctx.tape, fctx.args = eng, tape, (i, R, reverse, x.dtype, c.shape[0])
+        fctx.save_for_backward(e, sqrt_t)
+        return y[:, :3].contiguous(), y[:, 3].contiguous()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(fctx, gx, gl):
+        i, R, reverse, xdt, T = fctx.args
+        e, sqrt_t = fctx.saved_tensors
+        eng, tape = fctx.eng, fctx.tape
+        rows = tape["f_end"].shape[0]
+        dev = e.device
+        ybar = torch.zeros((rows, 4), dtype=torch.float32, device=dev)
+        if gx is not None:
+            ybar[:, :3] = gx
+        if gl is not None:
+            ybar[:, 3] = gl
+        y0bar = ybar.clone()
+        grad = torch.zeros(CNF_GRAD, dtype=torch.float32, device=dev)
+        ctxbar = torch.zeros((T, CNF_CTX), dtype=torch.float32, device=dev)
+        eng.tape_vjp(i, tape["states"].contiguous(), tape["steps_dev"].contiguous(), 1.0 if not reverse else -1.0, tape["ctx"], e,
+                     y0bar, ctxbar, grad, rows, R)
+        dT = (ybar * tape["f_end"]).sum() if not reverse else (y0bar * tape["f_start"]).sum()      # as _FlowBlockFn
+        dsq = (dT * 2.0 * sqrt_t.detach()).reshape(sqrt_t.shape).to(sqrt_t.dtype)
+        return (None,) * 9 + (y0bar[:, :3].contiguous().to(xdt), ctxbar, grad, dsq)
+
+
+def flow_train(net: "PointInterpFlow", xyz: Tensor, R: int, cs: List[Tensor], branch, noise: Optional[List[Tensor]] = None):
+    """f over the blocks, the log-likelihood, the interpolation of the latent, g over the blocks in reverse: the flow part of the
+    train-mode forward, differentiable in xyz, cs[i] [B,N,cd_i], the interpolation logits and the flow blocks' parameters.
+    branch = (side stream | None, w [B N 8, >= R] logits, csr16, csr8, idx8): train_ops' interpolation branch.
+    noise[i] [B,N,3]: block i's Hutchinson vector, used by f and g (default: torch.randn, drawn once per block).
+    -> (x [B, N R, 3], logp); `net.last_train_steps`: the twelve recorded step lists, f's blocks 0 .. 5 then g's 5 .. 0."""
+    from . import train_ops
+    B, N, _ = xyz.shape
+    T, nb = B * N, net.num_blocks
+    dev = xyz.device
+    if noise is None:
+        noise = [torch.randn(B, N, 3, device=dev) for _ in range(nb)]
+    es = [n.detach().reshape(T, 3).contiguous().float() for n in noise]
+    engs: List[_BlockTapeEngine] = []
+    params = [p for blk in net.flow_blocks for p in _pack_params(blk)]
+    stand = _CnfPackFn.apply(engs, *params)
+    cflat, ctx, d0c = [], [], torch.empty(nb, dtype=torch.float64, device=dev)
+    for i in range(nb):
+        ci = cs[i].reshape(T, -1)
+        cflat.append(ci.detach().float().contiguous())
+        ctx.append(_CnfContextFn.apply(engs[i], i, ci, stand[nb + i]))
+        engs[i].context_norm(cflat[i], d0c[i:i + 1])         # the context is a state of the reference's ODE: it enters the norms
+    steps: list = []
+    caps = net.tape_capacity
+    # ---- f + log-likelihood (oracle/cnf_ref.py::forward)
+    p = xyz.reshape(T, 3)
+    ldj = None
+    for i in range(nb):
+        p, dl = _CnfIntegrateFn.apply(engs[i], i, 1, False, caps, steps, cflat[i], d0c[i:i + 1], es[i], p, ctx[i], stand[i],
+                                      net.flow_blocks[i].cnf.sqrt_end_time)
+        ldj = dl if ldj is None else ldj + dl
+    z = p.view(B, N, 3)
+    logp = -torch.mean(torch.sum(-0.5 * (z ** 2 + math.log(2 * math.pi)), dim=(1, 2)) - ldj.view(B, N).sum(dim=1))
+    # ---- interpolation of the latent: the discrete training step's node
+    _, w, _, csr8, idx8 = branch
+    if train_ops._GLUE and R <= 8:
+        train_ops._join_side(*branch)
+        u = train_ops.InterpWsumFn.apply(w.view(T, 8, -1), z, idx8, R, csr8 if train_ops.deterministic() else None)
+    else:
+        u = train_ops._interp_latent(branch, z, R)
+    # ---- g: the blocks in reverse, integrated backwards in time, the R rows of a point sharing its context row and vector
+    u = u.reshape(T * R, 3)
+    for i in reversed(range(nb)):
+        u, _ = _CnfIntegrateFn.apply(engs[i], i, R, True, caps, steps, cflat[i], d0c[i:i + 1], es[i], u, ctx[i], stand[i],
+                                     net.flow_blocks[i].cnf.sqrt_end_time)
+    net.last_train_steps = steps
+    return u.view(B, N * R, 3), logp
+
+
+def forward_train(net: "PointInterpFlow", xyz: Tensor, upratio: int, noise: Optional[List[Tensor]] = None):
+    """`PointInterpFlow.forward` in train() mode: kNN, the feature extractor and the interpolation weights exactly as the discrete
+    model's training step runs them (train_ops._forward_train: side stream, prefold, `train_persistent`, `deterministic`,
+    `train_dw_stream`), then `flow_train`.  Eager only: the taped integrations read their controllers."""
+    from . import ops, train_ops
+    train_ops.begin_forward(getattr(net, "deterministic", False), getattr(net, "train_dw_stream", False))
+    try:
+        with train_ops.sync_bn(getattr(net, "sync_batchnorm", False)):
+            xyz = xyz.detach().contiguous().float()
+            idx16, _ = ops.knn_idx32(xyz, xyz, 16)
+            side = (train_ops._side_stream(xyz.device)
+                    if getattr(net, "train_streams", True) and not train_ops._sync_bn_active() else None)
+            if side is None:
+                idx8, csr16, csr8 = train_ops._neighbour_lists(idx16)
+            pre = (train_ops.ec_prefold(list(net.feat_convs), xyz, 16)
+                   if (train_ops._FUSED and not train_ops._sync_bn_active()) else None)
+            if side is not None:
+                side.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side):
+                    idx8, csr16, csr8 = train_ops._neighbour_lists(idx16)
+                    w = train_ops._interp_weights(net, xyz, idx8, csr8)
+            else:
+                w = train_ops._interp_weights(net, xyz, idx8, csr8)
+            cs, _ = train_ops._features(net, xyz, idx16, csr16, pre)
+            return flow_train(net, xyz, upratio, cs, (side, w, csr16, csr8, idx8), noise)
+    finally:
+        train_ops.end_forward()
 
 
 class PointInterpFlow(nn.Module):
@@ -611,15 +874,27 @@ class PointInterpFlow(nn.Module):
     def set_to_initialized_state(self) -> None:      # continuous/interpflow.py:113-114: nothing to initialise
         pass
 
-    @torch.no_grad()
+    def train(self, mode: bool = True):
+        if bool(mode) != self.training:     # a switch: the eval plan holds packed copies of the weights - eval after an optimizer
+            self.invalidate_plan()          # step packs anew (validation batches in a row, no switch between them, share one plan)
+        return super().train(mode)
+
     def forward(self, xyz: Tensor, upratio: int = 4, noise: Optional[List[Tensor]] = None,
                 stages: bool = False):
         """-> (x [B, N*upratio, 3], logp).  `noise[i]` [B,N,3]: block i's Hutchinson vector (default: torch.randn,
-        like the reference, which draws it at the first right-hand-side call of f and re-uses it in g)."""
-        if self.training:
-            raise RuntimeError("the continuous model is built for inference only (call .eval())")
+        like the reference, which draws it at the first right-hand-side call of f and re-uses it in g).
+        In train() mode with gradients (`forward_train`: taped integrations, weights packed from the live parameters on the
+        device); in eval() mode the inference plan, no autograd."""
         if not xyz.is_cuda:
             raise _lib.PuflowHipError("input must be a GPU tensor (no CPU fallback)")
+        if self.training:
+            if stages:
+                raise ValueError("stages=True is an eval-mode option")
+            return forward_train(self, xyz, upratio, noise)
+        return self._forward_eval(xyz, upratio, noise, stages)
+
+    @torch.no_grad()
+    def _forward_eval(self, xyz: Tensor, upratio: int, noise: Optional[List[Tensor]], stages: bool):
         xyz = xyz.detach().contiguous().float()
         B, N, _ = xyz.shape
         T = B * N
@@ -703,7 +978,7 @@ class PointInterpFlow(nn.Module):
         return x, logp
 
     def flow_block(self, i: int, x: Tensor, c: Tensor, e: Tensor, R: int = 1, reverse: bool = False, sweep: str = "fused",
-                   controller: str = "device"):
+                   controller: str = "device", pack: str = "device"):
         """One CNF flow block, differentiable: x [rows,3] (rows = T R, the R rows of a point adjacent), c [T,cd] context,
         e [T,3] Hutchinson vector -> (x' [rows,3], delta logp [rows]).  An autograd function over x, c and the parameters of
         `self.flow_blocks[i]` (e gets no gradient), whatever `self.training` says; the weight record is packed from the live
@@ -713,7 +988,10 @@ class PointInterpFlow(nn.Module):
         controller = "device": the step-size control runs on the device and records the tape there (pf_cnf_steps_taped, one host
         read per batch of attempts; `self.tape_capacity` remembers how long a tape to allocate); "host": one host read per
         attempt (pf_cnf_step).  sweep = "fused": the whole tape in one launch (pf_cnf_tape_vjp); "per_eval": pf_cnf_rhs_vjp per
-        evaluation with pf_cnf_rhs / pf_lincomb between them.  "host" and "per_eval" are the in-library A/B references.  `sqrt_end_time` gets the CONTINUOUS formula dL/dT = sum(ybar(T) . k(T)) (reversed: -sum(xbar_in . k(T))
+        evaluation with pf_cnf_rhs / pf_lincomb between them.  "host" and "per_eval" are the in-library A/B references.
+        pack = "device": the weight record is made from the live parameters on the device (pf_cnf_pack_blocks, one launch and one
+        read of its meta row); "host", its A/B reference: the numpy packers on a host copy of the parameters.  The same bits.
+        `sqrt_end_time` gets the CONTINUOUS formula dL/dT = sum(ybar(T) . k(T)) (reversed: -sum(xbar_in . k(T))
         at the start) x 2 sqrt_end_time - NOT the derivative of the discrete scheme, whose step sizes do not depend on T here.
         `self.last_block_steps`: the (s, h) of the accepted steps in solver time (s = -t when reversed)."""
         if not (x.is_cuda and c.is_cuda and e.is_cuda):
@@ -722,13 +1000,13 @@ class PointInterpFlow(nn.Module):
             raise ValueError("flow_block: x [T R,3], c [T,cd], e [T,3]")
         if not 1 <= R <= 16:
             raise ValueError("flow_block: 1 <= R <= 16 (pf_cnf_rhs_vjp keeps a point's R rows inside one 16-row MFMA tile)")
-        if sweep not in ("fused", "per_eval") or controller not in ("device", "host"):
-            raise ValueError('flow_block: sweep is "fused" or "per_eval", controller is "device" or "host"')
+        if sweep not in ("fused", "per_eval") or controller not in ("device", "host") or pack not in ("device", "host"):
+            raise ValueError('flow_block: sweep is "fused" or "per_eval", controller and pack are "device" or "host"')
         pfx = f"flow_blocks.{i}."
         named = list(self.flow_blocks[i].named_parameters())
         keys = tuple(pfx + n for n, _ in named)
         steps: list = []
-        opts = dict(sweep=sweep, controller=controller, cap=self.tape_capacity.get((int(i), bool(reverse)), 32))
+        opts = dict(sweep=sweep, controller=controller, pack=pack, cap=self.tape_capacity.get((int(i), bool(reverse)), 32))
         out = _FlowBlockFn.apply(x, c, e, int(i), int(R), bool(reverse), keys, steps, opts, *[p for _, p in named])
         if controller == "device":
             self.tape_capacity[(int(i), bool(reverse))] = len(steps) + len(steps) // 8 + 2

@@ -11,7 +11,9 @@
 
 One process per GPU under `torchrun` (batches are sharded by the data object, gradients averaged by one all-reduce);
 rank 0 saves.  CLI:  python -m puflow_amd.train --dataset pu1k --data data/pu1k_...h5 [--synthetic] [--max_epochs 100]
-                     [--graph] [--device_data] [--random_input]
+                     [--graph] [--device_data] [--random_input] [--model continuous]
+--model continuous trains cnf.PointInterpFlow (modules/continuous/train_interp.py: the same loss mix 1e-4 logp + 5e-2 EMD, clip
+and Adam); its checkpoint is the state dict `python -m puflow_amd.upsample_cnf` and `cnf.PointInterpFlow.load_state_dict` take.
 """
 from __future__ import annotations
 
@@ -21,7 +23,7 @@ from typing import Iterable, Optional
 
 import torch
 
-from .trainer import TrainerModule, default_cfg
+from .trainer import GRAPH_ERROR, MODELS, TrainerModule, default_cfg
 
 LOSS_MIX = {"pu1k": "pu1k", "pugeo": "pugeo", "pugan": "pugan"}
 DEFAULT_CKPT = {"pu1k": "runs/ckpt/puflow-pu1k.ckpt", "pugeo": "runs/ckpt/puflow-pugeo.ckpt", "pugan": "runs/ckpt/puflow-pugan.ckpt"}
@@ -31,6 +33,8 @@ def model_specific_args() -> argparse.ArgumentParser:
     """The reference's flags and defaults (train_pu1k.py:109-121) plus what its script hard-codes."""
     p = argparse.ArgumentParser()
     p.add_argument("--net", type=str, default="UpsamplingFlow")
+    p.add_argument("--model", default="discrete", choices=MODELS, help="continuous: the CNF variant (cnf.PointInterpFlow, "
+                   "modules/continuous/train_interp.py); eager steps only, no --graph")
     p.add_argument("--learning_rate", default=1e-3, type=float)
     p.add_argument("--sched_patience", default=10, type=int)
     p.add_argument("--sched_factor", default=0.5, type=float)
@@ -100,7 +104,9 @@ def fit(module: TrainerModule, train_data: Iterable, val_data: Optional[Iterable
                     raise RuntimeError(f"the device data pipeline reported status {st} (bit 1: a patch ran out of distinct subsample "
                                        "candidates, bit 2: corrupt permutation)")
             if val_data is not None:
+                module.eval()                       # once for the pass: validation_step then switches nothing, one eval plan serves every batch
                 outs = [module.validation_step(b, i) for i, b in enumerate(val_data)]
+                module.train()
                 cd = module.validation_epoch_end(outs)["CD"]
                 if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
                     t = torch.tensor([cd], dtype=torch.float64, device=next(module.parameters()).device)
@@ -129,6 +135,8 @@ def train(phase: str = "Train", checkpoint_path: Optional[str] = None, begin_che
     torch.manual_seed(int(getattr(cfg, "seed", 2021)))
     dev = device or (f"cuda:{int(os.environ.get('LOCAL_RANK', 0))}" if torch.cuda.is_available() else "cpu")
     module = (module or TrainerModule(cfg, loss_mix=LOSS_MIX[dataset])).to(dev)
+    if graph and getattr(module, "continuous", False):
+        raise RuntimeError(GRAPH_ERROR)
     hist = None
     if phase == "Train":
         if begin_checkpoint is not None:
@@ -147,7 +155,8 @@ def train(phase: str = "Train", checkpoint_path: Optional[str] = None, begin_che
     return module, hist
 
 
-def main(argv=None) -> None:
+def main(argv=None):
+    """-> (module, history) of `train`."""
     from .data import SyntheticDevicePatchData, SyntheticPatchData, patch_data_from_file
     a = model_specific_args().parse_args(argv)
     from ._host import limit_host_threads
@@ -158,7 +167,7 @@ def main(argv=None) -> None:
     dev = f"cuda:{int(os.environ.get('LOCAL_RANK', 0))}" if torch.cuda.is_available() else "cpu"
     if dev.startswith("cuda"):
         torch.cuda.set_device(dev)
-    cfg = default_cfg(learning_rate=a.learning_rate, sched_patience=a.sched_patience, sched_factor=a.sched_factor,
+    cfg = default_cfg(model=a.model, learning_rate=a.learning_rate, sched_patience=a.sched_patience, sched_factor=a.sched_factor,
                       seed=a.seed, sync_batchnorm=a.sync_batchnorm)
     kw = dict(batch_size=a.batch_size, num_point_patch=256, device=dev, seed=a.seed, rank=rank, world=world,
               is_augment=True, jitter_sigma=0.01, jitter_max=0.03)            # train_pu1k.py:132-141
@@ -169,8 +178,10 @@ def main(argv=None) -> None:
     else:
         tr = patch_data_from_file(a.data, up_ratio=4, on_device=a.device_data, **tkw)
         va = patch_data_from_file(a.data, up_ratio=4, num_batches=a.val_batches, **{**kw, "is_augment": False})
-    train("Train", a.checkpoint_path or DEFAULT_CKPT[a.dataset], a.begin_checkpoint, cfg, tr, va, a.max_epochs, a.dataset, dev,
-          graph=a.graph)
+    ckpt = a.checkpoint_path or DEFAULT_CKPT[a.dataset]
+    if a.model == "continuous" and not a.checkpoint_path:
+        ckpt = ckpt.replace("puflow-", "puflow-cnf-")             # runs/ckpt/puflow-cnf-<dataset>.ckpt
+    return train("Train", ckpt, a.begin_checkpoint, cfg, tr, va, a.max_epochs, a.dataset, dev, graph=a.graph)
 
 
 if __name__ == "__main__":

@@ -25,14 +25,23 @@ except Exception:                        # pragma: no cover - not installed in t
     _Base = nn.Module
 
 
-def default_cfg(**kw):
+MODELS = ("discrete", "continuous")
+GRAPH_ERROR = ("the continuous model's training step cannot be captured in a graph: its taped integrations read their "
+               "step-size controllers on the host (train it eagerly, without --graph)")
+
+
+def default_cfg(model: str = "discrete", **kw):
+    # model: "discrete" = interpflow.PointInterpFlow (affine coupling blocks), "continuous" = cnf.PointInterpFlow (CNF blocks,
+    # modules/continuous/train_interp.py); same loss mix, optimizer and NaN guard
     # sync_batchnorm: BatchNorm statistics over ALL ranks (an extension: the reference trains on one GPU, where it is
     # the same thing; default False = each rank normalises with its own shard, like DDP without SyncBatchNorm)
     # deterministic: bit-reproducible training steps (a debugging switch: BatchNorm statistics as exact fixed-point sums, the
     # remaining float-atomic gradients as ordered gathers; slower - no persistent kernels; train_state.set_deterministic)
     # persistent_kernels: the training step's grid-barrier kernels (EdgeConv units as one launch each).  None = on, unless
     # emd_workgroups == 1 says the device is shared with other processes (grid barriers need every workgroup resident)
-    cfg = dict(net="UpsamplingFlow", learning_rate=1e-3, sched_patience=10, sched_factor=0.5, seed=2021, sync_batchnorm=False,
+    if model not in MODELS:
+        raise ValueError(f"model is one of {MODELS}, not {model!r}")
+    cfg = dict(net="UpsamplingFlow", model=model, learning_rate=1e-3, sched_patience=10, sched_factor=0.5, seed=2021, sync_batchnorm=False,
                fused_optimizer=True, emd_workgroups=0, persistent_kernels=None, deterministic=False, dw_stream=False)
     cfg.update(kw)
     return SimpleNamespace(**cfg)
@@ -46,7 +55,12 @@ class TrainerModule(_Base):
         super().__init__()
         self.cfg = cfg or default_cfg()
         self.loss_mix = loss_mix
-        self.network = PointInterpFlow(pc_channel=3)
+        self.continuous = getattr(self.cfg, "model", "discrete") == "continuous"
+        if self.continuous:
+            from .cnf import PointInterpFlow as ContinuousInterpFlow
+            self.network = ContinuousInterpFlow(pc_channel=3)
+        else:
+            self.network = PointInterpFlow(pc_channel=3)
         self.network.sync_batchnorm = bool(getattr(self.cfg, "sync_batchnorm", False))     # an argument of its train-mode forward
         self.network.deterministic = bool(getattr(self.cfg, "deterministic", False))
         # weight gradients on their own stream beside the backward chain (train_state._dw_begin): measured slower at the bench shape
@@ -192,8 +206,8 @@ class TrainerModule(_Base):
     def _sync_actnorm_init(self, batch) -> None:
         """ActNorm's data-dependent first-batch init (normalize.py:45-54) would differ per rank under batch sharding and
         gradient averaging never reconciles parameters: run the init forward once, then broadcast rank 0's module."""
-        if all(b.actnorm.is_inited for b in self.network.flow_blocks):
-            return
+        if self.continuous or all(b.actnorm.is_inited for b in self.network.flow_blocks):
+            return                      # the continuous blocks have no ActNorm: nothing is initialised from data
         from .dist import multi_rank
         if not multi_rank():
             return                      # single process: the init happens inside the first real forward, as in the reference
@@ -238,6 +252,8 @@ class TrainerModule(_Base):
     def graphed_train_step(self, batch, optimizer: torch.optim.Optimizer, clip: float = 1e-2, warmup: int = 2):
         """`train_step` for a fixed batch shape captured in hipGraphs (puflow_amd/train_graph.py): returns
         `step(batch) -> loss` that replays forward + backward (+ clip + Adam) with one launch instead of ~3 500."""
+        if self.continuous:
+            raise RuntimeError(GRAPH_ERROR)
         from .optim import FusedClipAdam
         from .train_graph import GraphedTrainStep
         if isinstance(optimizer, FusedClipAdam):
