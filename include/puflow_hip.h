@@ -800,6 +800,41 @@ int pf_cnf_init(double* ctl, const float* x, int x_stride, float* y, float* f0, 
                 const float* rec, double t0, double t1, double n_tot, const double* extra_d0, double extra_scale, int reverse,
                 float rtol, float atol, int rows, int R, double* ws, void* stream);
 
+/* ---- a taped integration WITHOUT a look at its controller (the deferred training forward): pf_cnf_init_dev, ONE
+ * pf_cnf_steps_taped call of as many attempts as the integration is expected to need (attempts after `done` return at once),
+ * pf_cnf_tape_close; backward by pf_cnf_tape_vjp_dev.  The host reads the controller rows and the sticky table when it likes.
+ *
+ * pf_cnf_tape_close: the integration is CLEAN when ctl[5] != 0 and ctl[9] == 0.  Clean: y_out [rows,4] = states[(int)ctl[6]],
+ * f_end [rows,4] = (ctl[4] ? fb : fa) - the result and the derivative at the end, at addresses that do not depend on the step
+ * count.  Otherwise (attempts ran out, status 1 / 2, status 3 = tape full) both are filled with quiet NaN.
+ *   sticky [4] ints, zero before the first use, never cleared by a launch: [0] runs, [1] runs that were not clean, [2] the last
+ *   non-zero status, 4 = the attempts ran out, [3] the largest accepted + rejected count seen.  One lane, ordinary stores. */
+int pf_cnf_tape_close(const double* ctl, const float* states, int cap, const float* fa, const float* fb, int rows, float* y_out,
+                      float* f_end, int* sticky, void* stream);
+
+/* pf_cnf_tape_vjp with the step count on the device: n = (int)ctl[6], read once per workgroup.  states [cap + 1, rows, 4] and
+ * steps [cap, 2] are the whole tape.  A clean integration with 1 <= n <= cap gives the bits of pf_cnf_tape_vjp(.., n, ..).
+ * Otherwise the kernel runs zero steps: ybar passes through, ctxbar and grad get nothing added (the slabs are written as zeros,
+ * so the reduction reads initialised memory). */
+int pf_cnf_tape_vjp_dev(const float* states, const float* steps, const double* ctl, int cap, float sgn, const float* ctx,
+                        const float* e, const float* rec, float* ybar, float* ctxbar, float* grad, int rows, int R, void* ws,
+                        void* stream);
+
+/* pf_cnf_init over [0, T] (reverse: [-T, 0]) with T = t_end[0], a DEVICE double: word 0 of a pf_cnf_pack_blocks meta row. */
+int pf_cnf_init_dev(double* ctl, const float* x, int x_stride, float* y, float* f0, const float* ctx, const float* e,
+                    const float* rec, const double* t_end, double n_tot, const double* extra_d0, double extra_scale, int reverse,
+                    float rtol, float atol, int rows, int R, double* ws, void* stream);
+
+/* pf_cnf_context with inv_scale = scales[6], a DEVICE float (a row of pf_cnf_pack_status). */
+int pf_cnf_context_dev(const float* c, int cd, const float* hc_image, const float* hb, const float* scales, float* ctx, int T,
+                       void* stream);
+
+/* Behind pf_cnf_pack_blocks, for a caller that never reads meta on the host: scales [nb, 8] floats, word 6 of row b = meta[b][1]
+ * (pf_cnf_context_dev's argument).  A block with a non-zero status gets a record of NaN - every integration on it then ends with
+ * status 1 - and sticky [4] ints (zero before the first use, never cleared here) latches it: [0] blocks seen, [1] blocks with a
+ * status, [2] the last status, [3] its block. */
+int pf_cnf_pack_status(const double* meta, int nb, float* rec, float* scales, int* sticky, void* stream);
+
 /* out[i] = sum_{j<n_terms} w[j] * ptrs[j][i]   (n_terms <= 8; ptrs / w are HOST arrays).  Runge-Kutta solution,
  * mid-point and dense-output combinations of torchdiffeq's dopri5 (cnf.py:97-113 call site). */
 int pf_lincomb(const float* const* ptrs, const float* w, int n_terms, float* out, long long n, void* stream);

@@ -4,7 +4,9 @@ Same constructor, methods and the 390 state-dict keys of the reference's continu
 (`pretrain/puflow-x4-cnf-pu1k.pt` loads with `load_state_dict`).  eval(): the inference plan below.  train(): the forward with
 gradients (`forward_train`: the discrete training step's extractor and interpolation branch, then `flow_train` - twelve taped
 integrations, backward by `pf_cnf_tape_vjp`, csrc/cnf_bwd.hip, weights packed from the live parameters on the device by
-`pf_cnf_pack_blocks`, csrc/cnf_pack.hip); `PointInterpFlow.flow_block` is ONE such block as an autograd function.
+`pf_cnf_pack_blocks`, csrc/cnf_pack.hip); `PointInterpFlow.flow_block` is ONE such block as an autograd function.  With
+`net.train_deferred` (off by default) the taped integrations run against learnt budgets without a host read -
+`pf_cnf_tape_close`, `pf_cnf_tape_vjp_dev`, `check_train_logs` - which is what a captured training step needs.
 
 What runs where:
   * kNN, the six EdgeConv units, the merge units and the interpolation module are the discrete model's kernels
@@ -136,9 +138,12 @@ class _DevicePack:
     """pf_cnf_pack_blocks (csrc/cnf_pack.hip): the weight records, context matrices and fragment images of up to six blocks from
     their live parameter tensors in ONE launch, bit for bit what packing.pack_cnf_block / pack_cnf_context / cnf_hyper_matrix make
     on the host.  `blocks`: per block the sixteen tensors of `_pack_params`.  The meta rows (end time, image scale, status) are the
-    one device -> host read; a status word raises the host packers' ValueError."""
+    one device -> host read; a status word raises the host packers' ValueError.
+    sticky (the deferred training forward): an int32 [4] device row.  pf_cnf_pack_status then leaves the image scales
+    as device floats (`scales` [nb, 8], word 6), turns a block with a status into NaN and latches the status in that row;
+    read_meta=False skips the host read altogether - `T_end` / `inv_scale` are None and the kernels take both from the device."""
 
-    def __init__(self, blocks: List[List[Tensor]], device: torch.device):
+    def __init__(self, blocks: List[List[Tensor]], device: torch.device, sticky: Optional[Tensor] = None, read_meta: bool = True):
         nb = len(blocks)
         f32 = dict(dtype=torch.float32, device=device)
         keep = [[t.detach().to(**f32).contiguous() for t in blk] for blk in blocks]      # parameters as they are: no copy
@@ -156,14 +161,29 @@ class _DevicePack:
         _lib.check(_lib.load().pf_cnf_pack_blocks(ptrs([t for blk in keep for t in blk]), _lib.counts(cds), nb, self.rec.data_ptr(),
                                                   self.hb.data_ptr(), ptrs(self.Hc), ptrs(self.Hplain), ptrs(self.image),
                                                   self.meta.data_ptr(), torch.cuda.current_stream().cuda_stream), "pf_cnf_pack_blocks")
+        self.scales: Optional[Tensor] = None
+        if sticky is not None:
+            self.scales = torch.empty((nb, 8), **f32)
+            _lib.check(_lib.load().pf_cnf_pack_status(self.meta.data_ptr(), nb, self.rec.data_ptr(), self.scales.data_ptr(),
+                                                      sticky.data_ptr(), torch.cuda.current_stream().cuda_stream), "pf_cnf_pack_status")
+        if not read_meta:
+            if sticky is None:
+                raise ValueError("_DevicePack: read_meta=False needs the sticky row that takes the status")
+            self.T_end = self.inv_scale = [None] * nb
+            return
         meta = self.meta.cpu()                                  # the one read: all blocks
         self.T_end = [float(v) for v in meta[:, 0]]
         self.inv_scale = [float(v) for v in meta[:, 1]]
-        for j, st in enumerate(int(v) for v in meta[:, 2]):     # the messages of packing.frag_pack_f16x2 / frag_pack_f16n
-            if st & 1:
-                raise ValueError(f"block {j}: weight magnitude exceeds the fp16 range of the f16x2 path; use ec_mode='f32'")
-            if st & 2:
-                raise ValueError(f"block {j}: scaled weight magnitude exceeds the fp16 range of the f16n path; use ec_mode='f32'")
+        for j, st in enumerate(int(v) for v in meta[:, 2]):
+            self.raise_status(j, st)
+
+    @staticmethod
+    def raise_status(j: int, st: int) -> None:
+        """The messages of packing.frag_pack_f16x2 / frag_pack_f16n for block j's status word."""
+        if st & 1:
+            raise ValueError(f"block {j}: weight magnitude exceeds the fp16 range of the f16x2 path; use ec_mode='f32'")
+        if st & 2:
+            raise ValueError(f"block {j}: scaled weight magnitude exceeds the fp16 range of the f16n path; use ec_mode='f32'")
 
 
 class _CnfKernels:
@@ -176,6 +196,7 @@ class _CnfKernels:
         self.lib = _lib.load()
         self.device = device
         self.rec, self.Hc, self.Hci, self.hb, self.T_end = {}, {}, {}, {}, {}
+        self.T_dev, self.scales_dev = {}, {}                     # a device-side pack's end time / image scale ON the device
         self.ws =torch.empty(256, dtype=torch.float64, device=device)
         self.ws1k = torch.empty(1024, dtype=torch.float64, device=device)
         self.red = torch.empty(1, dtype=torch.float64, device=device)
@@ -197,6 +218,8 @@ class _CnfKernels:
         self.rec[i], self.Hc[i], self.hb[i] = pack.rec[j], pack.Hc[j], pack.hb[j]
         self.Hci[i] = (pack.image[j], pack.inv_scale[j])
         self.T_end[i] = pack.T_end[j]
+        if pack.scales is not None:                              # pf_cnf_pack_status ran: the deferred kernels' arguments
+            self.T_dev[i], self.scales_dev[i] = pack.meta[j], pack.scales[j]
 
     @staticmethod
     def _stream() -> int:
@@ -209,11 +232,24 @@ class _CnfKernels:
         ctx = torch.empty((T, CNF_CTX), dtype=torch.float32, device=c.device)
         if cd in (32, 64, 128) and c.is_contiguous():            # split-fp16 GEMM with register-resident weights (pf_pq_gemm's kernel)
             img, inv = self.Hci[i]
+            if inv is None:                                      # packed without a host read: the scale is a device word
+                _lib.check(self.lib.pf_cnf_context_dev(c.data_ptr(), cd, img.data_ptr(), self.hb[i].data_ptr(),
+                                                       self.scales_dev[i].data_ptr(), ctx.data_ptr(), T, self._stream()),
+                           "pf_cnf_context_dev")
+                return ctx
             _lib.check(self.lib.pf_cnf_context(c.data_ptr(), cd, img.data_ptr(), self.hb[i].data_ptr(), inv, ctx.data_ptr(), T,
                                                self._stream()), "pf_cnf_context")
         else:
             _gemm(c, cd, 1, self.Hc[i], 1, cd, ctx, CNF_CTX, self.hb[i], T, CNF_CTX, cd)
         return ctx
+
+    def _cnf_init_dev(self, i, ctl, x, y, f0, ctx, e, n_tot, extra_d0, extra_scale, reverse, rows, R) -> None:
+        """pf_cnf_init_dev: `_cnf_init` over [0, T] / [-T, 0] with T read on the device (`T_dev[i]`, the pack's meta row)."""
+        _lib.check(self.lib.pf_cnf_init_dev(ctl.data_ptr(), x.data_ptr(), int(x.stride(0)), y.data_ptr(), f0.data_ptr(),
+                                            ctx.data_ptr(), e.data_ptr(), self.rec[i].data_ptr(), self.T_dev[i].data_ptr(),
+                                            float(n_tot), extra_d0.data_ptr() if extra_d0 is not None else None,
+                                            float(extra_scale), 1 if reverse else 0, RTOL, ATOL, rows, R, self.ws3k.data_ptr(),
+                                            self._stream()), "pf_cnf_init_dev")
 
     def _rhs(self, i, y0, K, coef, h, t, sgn, ctx, e, kout, yout, rows, R):
         n = len(coef)
@@ -470,7 +506,45 @@ class _BlockTapeEngine(_CnfKernels):
             raise _lib.PuflowHipError(f"dopri5: underflow in dt ({dt:g}) at t = {t:g}, block {i}")
         n = int(st[6])
         host = [(float(s), float(h)) for s, h in steps[:n].cpu().tolist()]
-        return states[n], dict(steps=host, steps_dev=steps[:n], states=states[:n], ctx=ctx, f_start=f_start, f_end=fbuf[int(st[4])])
+        return states[n], dict(steps=host, steps_dev=steps[:n], states=states[:n], ctx=ctx, f_start=f_start, f_end=fbuf[int(st[4])],
+                               took=int(st[6]) + int(st[7]))
+
+    def tape_forward_deferred(self, i: int, x: Tensor, c: Tensor, e: Tensor, R: int, reverse: bool, attempts: int, cap: int,
+                              log: Tensor, sticky: Tensor, ctx: Optional[Tensor] = None, d0c: Optional[Tensor] = None):
+        """`tape_forward` WITHOUT a host read: pf_cnf_init(_dev) into `log` - a [16] double device row, zero before its first
+        use, which IS this integration's controller, as in `_CnfEngine.integrate(log=...)` - then ONE pf_cnf_steps_taped call of
+        `attempts` attempts (those past the end return at once) on a tape of `cap` steps, then pf_cnf_tape_close: the result and
+        the derivative at the end at fixed addresses, NaN when the integration did not end cleanly inside (attempts, cap), and
+        the run entered in `sticky` (int32 [4]).  -> (state [rows,4], tape): the WHOLE tape (`states` [cap + 1, rows, 4],
+        `steps_dev` [cap, 2]; the valid prefix is log[6], known to the device alone), `log`, `cap`, `ctx`, `f_start`, `f_end`.
+        The caller reads log rows and sticky table when it likes (`PointInterpFlow.check_train_logs`)."""
+        rows = x.shape[0]
+        dev = x.device
+        attempts, cap = int(attempts), int(cap)
+        if attempts < 1 or cap < 1:
+            raise ValueError("tape_forward_deferred: attempts >= 1 and cap >= 1")
+        if ctx is None:
+            ctx = self.context(i, c)
+        n_tot = float(rows * 4 + c.numel() * R)
+        if d0c is None:
+            d0c = torch.empty(1, dtype=torch.float64, device=dev)
+            self.context_norm(c, d0c)
+        fbuf = torch.empty((2, rows, 4), dtype=torch.float32, device=dev)
+        states = torch.empty((cap + 1, rows, 4), dtype=torch.float32, device=dev)
+        steps = torch.empty((cap, 2), dtype=torch.float32, device=dev)
+        if self.T_end[i] is None:
+            self._cnf_init_dev(i, log, x, states[0], fbuf[0], ctx, e, n_tot, d0c, float(R), reverse, rows, R)
+        else:
+            T = self.T_end[i]
+            t0, t1 = (0.0, T) if not reverse else (-T, 0.0)
+            self._cnf_init(i, log, x, states[0], fbuf[0], ctx, e, t0, t1, n_tot, d0c, float(R), reverse, rows, R)
+        f_start = fbuf[0].clone()
+        self._cnf_steps_taped(i, log, states, steps, fbuf, ctx, e, rows, R, attempts)
+        end = torch.empty((2, rows, 4), dtype=torch.float32, device=dev)
+        _lib.check(self.lib.pf_cnf_tape_close(log.data_ptr(), states.data_ptr(), cap, fbuf[0].data_ptr(), fbuf[1].data_ptr(), rows,
+                                              end[0].data_ptr(), end[1].data_ptr(), sticky.data_ptr(), self._stream()),
+                   "pf_cnf_tape_close")
+        return end[0], dict(deferred=True, states=states, steps_dev=steps, log=log, cap=cap, ctx=ctx, f_start=f_start, f_end=end[1])
 
     def tape_forward_host(self, i: int, x: Tensor, c: Tensor, e: Tensor, R: int, reverse: bool):
         """The A/B reference of `tape_forward` (flow_block's controller="host"): ONE attempt per launch and the control on the host (oracle/cnf_ref.py::dopri5 restated), except
@@ -539,6 +613,14 @@ class _BlockTapeEngine(_CnfKernels):
                                             ctxbar.data_ptr(), grad.data_ptr(), rows, R, ws.data_ptr(), self._stream()),
                    "pf_cnf_tape_vjp")
 
+    def tape_vjp_dev(self, i, tape, sgn, e, ybar, ctxbar, grad, rows, R) -> None:
+        """pf_cnf_tape_vjp_dev on a tape of `tape_forward_deferred`: the step count is the controller row's, read on the device."""
+        ws = self._vjp_workspace(rows, R, ybar.device)
+        _lib.check(self.lib.pf_cnf_tape_vjp_dev(tape["states"].data_ptr(), tape["steps_dev"].data_ptr(), tape["log"].data_ptr(),
+                                                int(tape["cap"]), float(sgn), tape["ctx"].data_ptr(), e.data_ptr(),
+                                                self.rec[i].data_ptr(), ybar.data_ptr(), ctxbar.data_ptr(), grad.data_ptr(), rows, R,
+                                                ws.data_ptr(), self._stream()), "pf_cnf_tape_vjp_dev")
+
     def vjp(self, i, y, kbar, t, sgn, ctx, e, ybar, ctxbar, grad, rows, R) -> None:
         ws = self._vjp_workspace(rows, R, y.device)
         _lib.check(self.lib.pf_cnf_rhs_vjp(y.data_ptr(), kbar.data_ptr(), float(t), float(sgn), ctx.data_ptr(), e.data_ptr(),
@@ -557,6 +639,12 @@ class _BlockTapeEngine(_CnfKernels):
         ctx = tape["ctx"]
         grad = torch.zeros(CNF_GRAD, dtype=torch.float32, device=dev)
         ctxbar = torch.zeros((c.shape[0], CNF_CTX), dtype=torch.float32, device=dev)
+        if tape.get("deferred"):
+            if sweep != "fused":
+                raise ValueError('a deferred tape is swept by pf_cnf_tape_vjp_dev: sweep="fused"')
+            y0bar = ybar.clone()
+            self.tape_vjp_dev(i, tape, sgn, e, y0bar, ctxbar, grad, rows, R)
+            return y0bar, grad, ctxbar
         if sweep == "fused":
             states, steps_dev = tape["states"], tape.get("steps_dev")
             if not isinstance(states, Tensor):                                     # the host controller's tape: a list of states
@@ -592,24 +680,56 @@ class _BlockTapeEngine(_CnfKernels):
         return ybar, grad, ctxbar
 
 
+# ---- the deferred controller: twelve log rows + the sticky table, one read ------------------------------------------
+PACK_ROW = 2 * NUM_BLOCKS                  # the sticky table's row of pf_cnf_pack_status, behind the twelve integrations'
+
+
+def _log_row(i: int, reverse: bool) -> int:
+    """Row of integration (block i, direction) in the log and sticky tables: the order they run in, f's 0 .. 5 then g's 5 .. 0."""
+    return 2 * NUM_BLOCKS - 1 - i if reverse else i
+
+
+def _row_key(k: int):
+    return (k, False) if k < NUM_BLOCKS else (2 * NUM_BLOCKS - 1 - k, True)
+
+
+class _DeferredPlan:
+    """What a deferred train-mode forward hands its nodes: the net's tape budgets, its log rows and sticky table."""
+
+    def __init__(self, net: "PointInterpFlow", dev: torch.device):
+        self.logs, self.sticky = net._train_tables(dev)
+        self.budget = net.tape_budget
+        self.budget_cap0 = 32
+        self.learning = any((i, r) not in self.budget for i in range(net.num_blocks) for r in (False, True))
+
+
 class _FlowBlockFn(torch.autograd.Function):
     """(x, c, parameters of block i) -> (x', delta logp): `PointInterpFlow.flow_block`."""
 
     @staticmethod
     def forward(fctx, x, c, e, i, R, reverse, keys, record, opts, *params):
-        if opts["pack"] == "device":                             # one launch on the live parameters, one read of its meta row
+        if opts["controller"] == "deferred":                     # the same launch, its meta row stays on the device
+            by_key = dict(zip(keys, params))
+            pack = _DevicePack([[by_key[k] for k in _pack_keys(i)]], x.device, sticky=opts["sticky"][PACK_ROW], read_meta=False)
+            eng = _BlockTapeEngine(None, i, x.device, pack=(pack, 0))
+        elif opts["pack"] == "device":                           # one launch on the live parameters, one read of its meta row
             by_key = dict(zip(keys, params))
             eng = _BlockTapeEngine(None, i, x.device, pack=(_DevicePack([[by_key[k] for k in _pack_keys(i)]], x.device), 0))
         else:                                                    # the numpy packers on a host copy: ~70 small uploads
             eng = _BlockTapeEngine({k: p.detach().cpu() for k, p in zip(keys, params)}, i, x.device)
         x32, c32, e32 = x.detach().float().contiguous(), c.detach().float().contiguous(), e.detach().float().contiguous()
-        if opts["controller"] == "device":
+        if opts["controller"] == "deferred":
+            k = _log_row(i, reverse)
+            y, tape = eng.tape_forward_deferred(i, x32, c32, e32, R, reverse, opts["attempts"], opts["cap"], opts["logs"][k],
+                                                opts["sticky"][k])
+            opts["tape"] = tape
+        elif opts["controller"] == "device":
             y, tape = eng.tape_forward(i, x32, c32, e32, R, reverse, opts["cap"])
         else:
             y, tape = eng.tape_forward_host(i, x32, c32, e32, R, reverse)
         fctx.eng, fctx.tape, fctx.args = eng, tape, (i, R, reverse, keys, x.dtype, c.dtype, opts["sweep"])
         fctx.save_for_backward(c32, e32, *params)
-        record.extend(tape["steps"])
+        record.extend(tape.get("steps", ()))                     # (a deferred tape's steps are on the device: `last_train_steps`)
         return y[:, :3].contiguous(), y[:, 3].contiguous()
 
     @staticmethod
@@ -655,10 +775,14 @@ class _CnfPackFn(torch.autograd.Function):
     read.  One pf_cnf_pack_blocks launch; the engines are left in `engs`."""
 
     @staticmethod
-    def forward(fctx, engs, *params):
+    def forward(fctx, engs, plan, *params):
         nb = len(params) // 16
         dev = params[0].device
-        pack = _DevicePack([list(params[16 * j:16 * j + 16]) for j in range(nb)], dev)
+        # plan (a deferred forward): the status goes to the sticky table; the meta row is read only by a forward that still has
+        # an integration to run through the host-read loop (no budget yet), which needs the end times as host floats
+        pack = (_DevicePack([list(params[16 * j:16 * j + 16]) for j in range(nb)], dev) if plan is None else
+                _DevicePack([list(params[16 * j:16 * j + 16]) for j in range(nb)], dev, sticky=plan.sticky[PACK_ROW],
+                            read_meta=plan.learning))
         for j in range(nb):
             engs.append(_BlockTapeEngine(None, j, dev, pack=(pack, j), scratch=engs[0] if engs else None))
         fctx.meta = [(p.shape, p.dtype) for p in params]
@@ -685,7 +809,7 @@ class _CnfPackFn(torch.autograd.Function):
                 dH1 = torch.zeros((CNF_CTX, meta[2][0][1]), dtype=torch.float32, device=dev)
             g = unpack_cnf_grads(j, grec, dH1[:, 1:], dH1[:, 0])
             out += [g[k].reshape(s).to(dt) for k, (s, dt) in zip(_pack_keys(j)[:15], meta)] + [None]   # sqrt_end_time: _CnfIntegrateFn
-        return (None, *out)
+        return (None, None, *out)
 
 
 class _CnfContextFn(torch.autograd.Function):
@@ -721,10 +845,25 @@ class _CnfIntegrateFn(torch.autograd.Function):
     @staticmethod
     def forward(fctx, eng, i, R, reverse, caps, steps_out, c, d0c, e, x, ctx, grec, sqrt_t):
         x32 = x.detach().float().contiguous()
-        y, tape = eng.tape_forward(i, x32, c, e, R, reverse, caps.get((i, reverse), 32), ctx=ctx.detach(), d0c=d0c)
-        n = len(tape["steps"])
-        caps[(i, reverse)] = n + n // 8 + 2
-        steps_out.append(tape["steps"])
+        plan = caps if isinstance(caps, _DeferredPlan) else None
+        budget = plan.budget.get((i, reverse)) if plan is not None else None
+        if budget is not None:                                   # no look at the controller: `check_train_logs` reads it later
+            k = _log_row(i, reverse)
+            y, tape = eng.tape_forward_deferred(i, x32, c, e, R, reverse, budget[0], budget[1], plan.logs[k], plan.sticky[k],
+                                                ctx=ctx.detach(), d0c=d0c)
+            steps_out.append(tape)
+        else:
+            if plan is not None and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(f"deferred CNF training: block {i} ({'g' if reverse else 'f'}) has no tape budget yet - run one "
+                                   "eager step before capturing (graphed_train_step's warm-up does)")
+            cap0 = plan.budget_cap0 if plan is not None else caps.get((i, reverse), 32)
+            y, tape = eng.tape_forward(i, x32, c, e, R, reverse, cap0, ctx=ctx.detach(), d0c=d0c)
+            n = len(tape["steps"])
+            if plan is not None:                                 # learn: attempts taken + a quarter + 2, steps + an eighth + 2
+                plan.budget[(i, reverse)] = (tape["took"] + tape["took"] // 4 + 2, n + n // 8 + 2)
+            else:
+                caps[(i, reverse)] = n + n // 8 + 2
+            steps_out.append(tape["steps"])
         fctx.eng, fctx.tape, fctx.args = eng, tape, (i, R, reverse, x.dtype, c.shape[0])
         fctx.save_for_backward(e, sqrt_t)
         return y[:, :3].contiguous(), y[:, 3].contiguous()
@@ -745,8 +884,11 @@ class _CnfIntegrateFn(torch.autograd.Function):
         y0bar = ybar.clone()
         grad = torch.zeros(CNF_GRAD, dtype=torch.float32, device=dev)
         ctxbar = torch.zeros((T, CNF_CTX), dtype=torch.float32, device=dev)
-        eng.tape_vjp(i, tape["states"].contiguous(), tape["steps_dev"].contiguous(), 1.0 if not reverse else -1.0, tape["ctx"], e,
-                     y0bar, ctxbar, grad, rows, R)
+        if tape.get("deferred"):
+            eng.tape_vjp_dev(i, tape, 1.0 if not reverse else -1.0, e, y0bar, ctxbar, grad, rows, R)
+        else:
+            eng.tape_vjp(i, tape["states"].contiguous(), tape["steps_dev"].contiguous(), 1.0 if not reverse else -1.0, tape["ctx"], e,
+                         y0bar, ctxbar, grad, rows, R)
         dT = (ybar * tape["f_end"]).sum() if not reverse else (y0bar * tape["f_start"]).sum()      # as _FlowBlockFn
         dsq = (dT * 2.0 * sqrt_t.detach()).reshape(sqrt_t.shape).to(sqrt_t.dtype)
         return (None,) * 9 + (y0bar[:, :3].contiguous().to(xdt), ctxbar, grad, dsq)
@@ -763,11 +905,14 @@ def flow_train(net: "PointInterpFlow", xyz: Tensor, R: int, cs: List[Tensor], br
     T, nb = B * N, net.num_blocks
     dev = xyz.device
     if noise is None:
+        noise = getattr(net, "train_noise", None)                # fixed vectors for every step (a reproducibility switch)
+    if noise is None:
         noise = [torch.randn(B, N, 3, device=dev) for _ in range(nb)]
     es = [n.detach().reshape(T, 3).contiguous().float() for n in noise]
     engs: List[_BlockTapeEngine] = []
     params = [p for blk in net.flow_blocks for p in _pack_params(blk)]
-    stand = _CnfPackFn.apply(engs, *params)
+    plan = _DeferredPlan(net, dev) if getattr(net, "train_deferred", False) else None
+    stand = _CnfPackFn.apply(engs, plan, *params)
     cflat, ctx, d0c = [], [], torch.empty(nb, dtype=torch.float64, device=dev)
     for i in range(nb):
         ci = cs[i].reshape(T, -1)
@@ -775,7 +920,7 @@ def flow_train(net: "PointInterpFlow", xyz: Tensor, R: int, cs: List[Tensor], br
         ctx.append(_CnfContextFn.apply(engs[i], i, ci, stand[nb + i]))
         engs[i].context_norm(cflat[i], d0c[i:i + 1])         # the context is a state of the reference's ODE: it enters the norms
     steps: list = []
-    caps = net.tape_capacity
+    caps = net.tape_capacity if plan is None else plan
     # ---- f + log-likelihood (oracle/cnf_ref.py::forward)
     p = xyz.reshape(T, 3)
     ldj = None
@@ -804,7 +949,8 @@ def flow_train(net: "PointInterpFlow", xyz: Tensor, R: int, cs: List[Tensor], br
 def forward_train(net: "PointInterpFlow", xyz: Tensor, upratio: int, noise: Optional[List[Tensor]] = None):
     """`PointInterpFlow.forward` in train() mode: kNN, the feature extractor and the interpolation weights exactly as the discrete
     model's training step runs them (train_ops._forward_train: side stream, prefold, `train_persistent`, `deterministic`,
-    `train_dw_stream`), then `flow_train`.  Eager only: the taped integrations read their controllers."""
+    `train_dw_stream`), then `flow_train`.  Eager only - the taped integrations read their controllers - unless `net.train_deferred`
+    is set and every integration has its budget (`tape_forward_deferred`): then nothing here reads the device."""
     from . import ops, train_ops
     train_ops.begin_forward(getattr(net, "deterministic", False), getattr(net, "train_dw_stream", False))
     try:
@@ -849,6 +995,105 @@ class PointInterpFlow(nn.Module):
         self.last_stats: dict = {}
         # flow_block's device-side tape: steps to allocate it for, per (block, reverse) - what the last call took + an eighth + 2
         self.tape_capacity: dict = {}
+        # ---- the deferred controller of the train-mode forward, off by default
+        self.train_deferred = False               # no look at a controller inside the forward: `check_train_logs` reads them all, later
+        self.tape_budget: dict = {}               # (block, reverse) -> (attempts to enqueue, tape capacity); learnt from a host-read run
+        self.train_noise: Optional[List[Tensor]] = None       # fixed Hutchinson vectors for every training forward (default: drawn)
+        self._train_tab: Optional[Tensor] = None  # the twelve log rows and the sticky table, one buffer = one read
+        self._sticky_seen = None                  # the sticky table at the last `check_train_logs`
+        self._logs_host = None
+        self._last_steps = None
+        self.last_skipped_steps = 0
+
+    # -- the deferred controller's tables
+    def _train_tables(self, dev: torch.device):
+        """(logs [12, 16] float64, sticky [13, 4] int32): views of one zero-initialised buffer that outlives every hipGraph
+        capture (train_state._zeros_kept: inside a capture it would be a memset node that clears the sticky counts per replay)."""
+        nl = 2 * NUM_BLOCKS * 16 * 2                             # the log rows, in 32-bit words
+        if self._train_tab is None or self._train_tab.device != dev:
+            from .train_state import _zeros_kept
+            self._train_tab = _zeros_kept(nl + (2 * NUM_BLOCKS + 1) * 4, torch.int32, dev)
+            self._sticky_seen = torch.zeros((2 * NUM_BLOCKS + 1, 4), dtype=torch.int32)
+        t = self._train_tab
+        return t[:nl].view(torch.float64).view(2 * NUM_BLOCKS, 16), t[nl:].view(2 * NUM_BLOCKS + 1, 4)
+
+    def check_train_logs(self) -> int:
+        """The ONE device -> host read of a deferred training forward (or of the replays of a captured step since the last
+        call): the twelve controller rows and the sticky table.  Since the last call:
+          * a weight pack with a status raises the host packers' ValueError;
+          * an integration that ended with status 1 or 2 raises PuflowHipError, the eager path's messages - unless an
+            integration BEFORE it in the forward fell short: its NaN output is what the later one choked on;
+          * an integration that fell short - its attempts ran out (sticky status 4) or its tape filled (3) - gets that budget
+            doubled (up to MAX_NUM_STEPS); -> how many integrations fell short.  Their outputs were NaN: the step is void.
+        `last_skipped_steps`: forwards since the last call with at least one integration that was not clean."""
+        if self._train_tab is None:
+            return 0
+        host = self._train_tab.cpu()                             # the one read
+        nl = 2 * NUM_BLOCKS * 16 * 2
+        logs = host[:nl].view(torch.float64).view(2 * NUM_BLOCKS, 16)
+        sticky = host[nl:].view(2 * NUM_BLOCKS + 1, 4)
+        new_bad = (sticky[:, 1] - self._sticky_seen[:, 1]).tolist()
+        self._sticky_seen = sticky.clone()
+        self._logs_host = logs
+        self.last_skipped_steps = max(new_bad[:PACK_ROW])
+        if new_bad[PACK_ROW]:
+            _DevicePack.raise_status(int(sticky[PACK_ROW, 3]), int(sticky[PACK_ROW, 2]))
+        short = 0
+        for k in range(PACK_ROW):
+            if not new_bad[k]:
+                continue
+            i, reverse = _row_key(k)
+            status = int(sticky[k, 2])
+            if status in (3, 4):
+                short += 1
+                a, c = self.tape_budget.get((i, reverse), (0, 0))
+                if status == 4:
+                    a = min(max(2 * a, 2), MAX_NUM_STEPS)
+                else:
+                    c = min(max(2 * c, 2), MAX_NUM_STEPS)
+                    a = max(a, c)                                # an accepted step is an attempt
+                if (i, reverse) in self.tape_budget:
+                    self.tape_budget[(i, reverse)] = (a, c)
+            elif not short:
+                t, dt = float(logs[k, 0]), float(logs[k, 1])
+                if status == 1:
+                    raise _lib.PuflowHipError(f"dopri5: non-finite error norm in block {i} at t = {t:g}")
+                raise _lib.PuflowHipError(f"dopri5: underflow in dt ({dt:g}) at t = {t:g}, block {i}")
+        return short
+
+    def train_log_stats(self) -> dict:
+        """From the tables as `check_train_logs` last read them: per integration, in running order, the attempts enqueued
+        (budget), the most attempts any run took (the sticky table's max column) and the runs; `noop` = attempts enqueued per
+        forward that returned at once because the integration was done (against the LARGEST count seen: a lower bound)."""
+        if self._sticky_seen is None:
+            return {}
+        rows = []
+        for k in range(PACK_ROW):
+            a, c = self.tape_budget.get(_row_key(k), (0, 0))
+            rows.append(dict(key=_row_key(k), attempts=a, cap=c, runs=int(self._sticky_seen[k, 0]), not_clean=int(self._sticky_seen[k, 1]),
+                             max_took=int(self._sticky_seen[k, 3])))
+        return dict(rows=rows, noop=sum(max(r["attempts"] - r["max_took"], 0) for r in rows if r["runs"]))
+
+    @property
+    def last_train_steps(self):
+        """The twelve recorded step lists of the last train-mode forward, f's blocks 0 .. 5 then g's 5 .. 0.  After a deferred
+        forward they are on the device: fetched on first access (one read per integration, and one of the log rows if
+        `check_train_logs` has not run since)."""
+        st = self._last_steps
+        if st is not None and any(isinstance(t, dict) for t in st):
+            out = []
+            for t in st:
+                if isinstance(t, dict):
+                    ctl = t["log"].cpu()
+                    n = int(ctl[6]) if (ctl[5] != 0 and ctl[9] == 0) else 0
+                    t = [(float(s), float(h)) for s, h in t["steps_dev"][:n].cpu().tolist()]
+                out.append(t)
+            st = self._last_steps = out
+        return st
+
+    @last_train_steps.setter
+    def last_train_steps(self, steps) -> None:
+        self._last_steps = steps
 
     def invalidate_plan(self) -> None:
         self._engine_cache = None
@@ -978,7 +1223,7 @@ class PointInterpFlow(nn.Module):
         return x, logp
 
     def flow_block(self, i: int, x: Tensor, c: Tensor, e: Tensor, R: int = 1, reverse: bool = False, sweep: str = "fused",
-                   controller: str = "device", pack: str = "device"):
+                   controller: str = "device", pack: str = "device", attempts: Optional[int] = None, cap: Optional[int] = None):
         """One CNF flow block, differentiable: x [rows,3] (rows = T R, the R rows of a point adjacent), c [T,cd] context,
         e [T,3] Hutchinson vector -> (x' [rows,3], delta logp [rows]).  An autograd function over x, c and the parameters of
         `self.flow_blocks[i]` (e gets no gradient), whatever `self.training` says; the weight record is packed from the live
@@ -987,7 +1232,10 @@ class PointInterpFlow(nn.Module):
         recorded steps in reverse, differentiating exactly what the forward computed with the step sizes as constants.
         controller = "device": the step-size control runs on the device and records the tape there (pf_cnf_steps_taped, one host
         read per batch of attempts; `self.tape_capacity` remembers how long a tape to allocate); "host": one host read per
-        attempt (pf_cnf_step).  sweep = "fused": the whole tape in one launch (pf_cnf_tape_vjp); "per_eval": pf_cnf_rhs_vjp per
+        attempt (pf_cnf_step); "deferred" (DESIGN 9b): NO host read - `attempts` attempts are enqueued on a tape of `cap` steps
+        (default: `self.tape_budget[(i, reverse)]`), the weights' pack status stays on the device too, the same tensors come back
+        when the integration ends inside that budget and NaN when it does not; `self.check_train_logs()` reads what happened
+        and `self.last_block_tape` holds the tape (the step list is on the device).  sweep = "fused": the whole tape in one launch (pf_cnf_tape_vjp); "per_eval": pf_cnf_rhs_vjp per
         evaluation with pf_cnf_rhs / pf_lincomb between them.  "host" and "per_eval" are the in-library A/B references.
         pack = "device": the weight record is made from the live parameters on the device (pf_cnf_pack_blocks, one launch and one
         read of its meta row); "host", its A/B reference: the numpy packers on a host copy of the parameters.  The same bits.
@@ -1000,17 +1248,28 @@ class PointInterpFlow(nn.Module):
             raise ValueError("flow_block: x [T R,3], c [T,cd], e [T,3]")
         if not 1 <= R <= 16:
             raise ValueError("flow_block: 1 <= R <= 16 (pf_cnf_rhs_vjp keeps a point's R rows inside one 16-row MFMA tile)")
-        if sweep not in ("fused", "per_eval") or controller not in ("device", "host") or pack not in ("device", "host"):
-            raise ValueError('flow_block: sweep is "fused" or "per_eval", controller and pack are "device" or "host"')
+        if sweep not in ("fused", "per_eval") or controller not in ("device", "host", "deferred") or pack not in ("device", "host"):
+            raise ValueError('flow_block: sweep is "fused" or "per_eval", controller "device", "host" or "deferred", pack "device" or "host"')
         pfx = f"flow_blocks.{i}."
         named = list(self.flow_blocks[i].named_parameters())
         keys = tuple(pfx + n for n, _ in named)
         steps: list = []
         opts = dict(sweep=sweep, controller=controller, pack=pack, cap=self.tape_capacity.get((int(i), bool(reverse)), 32))
+        if controller == "deferred":
+            if sweep != "fused" or pack != "device":
+                raise ValueError('flow_block: controller="deferred" goes with sweep="fused" and pack="device"')
+            known = self.tape_budget.get((int(i), bool(reverse)), (None, None))
+            attempts, cap = attempts if attempts is not None else known[0], cap if cap is not None else known[1]
+            if attempts is None or cap is None or int(attempts) < 1 or int(cap) < 1:
+                raise ValueError('flow_block: controller="deferred" needs attempts >= 1 and cap >= 1 (or a learnt tape_budget entry)')
+            self.tape_budget[(int(i), bool(reverse))] = (int(attempts), int(cap))
+            logs, sticky = self._train_tables(x.device)
+            opts.update(attempts=int(attempts), cap=int(cap), logs=logs, sticky=sticky)
         out = _FlowBlockFn.apply(x, c, e, int(i), int(R), bool(reverse), keys, steps, opts, *[p for _, p in named])
         if controller == "device":
             self.tape_capacity[(int(i), bool(reverse))] = len(steps) + len(steps) // 8 + 2
         self.last_block_steps = steps
+        self.last_block_tape = opts.get("tape")
         return out
 
     def sample(self, sparse: Tensor, upratio: int = 4) -> Tensor:

@@ -566,9 +566,12 @@ struct CnfInitArgs {
     float sgn, rtol, atol;
     int rows, R, ntiles;
     double* partial;          // [3][1024]
+    const double* t_end;      // TDEV: the block's end time T on the device (pf_cnf_pack_blocks' meta row); [t0, t1] = [0, T] / [-T, 0]
 };
 
-template <bool PROBE>
+// TDEV (pf_cnf_init_dev): t0 / t1 from the device word a.t_end instead of the arguments - nothing of the weights' pack is read
+// on the host.  Only launch A reads the interval; launch B takes it from ctl.
+template <bool PROBE, bool TDEV = false>
 __global__ __launch_bounds__(CNF_NW * 64) void cnf_init_kernel(CnfInitArgs a) {
     __shared__ f4 wl[CNF_REC / 4];
     __shared__ double red[2][CNF_NW];
@@ -576,7 +579,13 @@ __global__ __launch_bounds__(CNF_NW * 64) void cnf_init_kernel(CnfInitArgs a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int col = lane & 15, q = lane >> 4;
     const CnfW w = cnf_stage_weights(wl, a.rec, CNF_NW * 64, lane);
-    float h = 0.f, t = (float)(a.reverse != 0.0 ? -a.t0 : a.t0);
+    double t0 = a.t0, t1 = a.t1;
+    if constexpr (TDEV) {
+        const double T = a.t_end[0];
+        t0 = a.reverse != 0.0 ? -T : 0.0;
+        t1 = a.reverse != 0.0 ? 0.0 : T;
+    }
+    float h = 0.f, t = (float)(a.reverse != 0.0 ? -t0 : t0);
     if (PROBE) {
         const double hd = a.ctl[CTL_H0], td = a.ctl[CTL_T] + hd;
         h = (float)hd;
@@ -645,7 +654,7 @@ __global__ __launch_bounds__(CNF_NW * 64) void cnf_init_kernel(CnfInitArgs a) {
         const double r1 = cnf_partial_total(a.partial + 1024, (int)gridDim.x, red[0]);
         if (threadIdx.x != 0) return;
         for (int i = 0; i < 16; ++i)
-            ctl[i] = i == CTL_T ? a.t0 : i == CTL_T1 ? a.t1 : i == CTL_NTOT ? a.n_tot : i == CTL_REV ? a.reverse : 0.0;
+            ctl[i] = i == CTL_T ? t0 : i == CTL_T1 ? t1 : i == CTL_NTOT ? a.n_tot : i == CTL_REV ? a.reverse : 0.0;
         const double extra = a.extra_d0 ? a.extra_d0[0] * a.extra_scale : 0.0;
         const double d0 = sqrt((r0 + extra) / a.n_tot), d1 = sqrt(r1 / a.n_tot);
         ctl[CTL_H0] = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
@@ -748,6 +757,34 @@ __global__ __launch_bounds__(256) void sumsq_final_kernel(const double* __restri
 }
 
 constexpr int SUMSQ_BLOCKS = 256;
+
+// The end of a taped integration whose attempts were enqueued without a look at the controller (pf_cnf_tape_close): the result
+// and the derivative at the end go to buffers of FIXED address, whatever the number of accepted steps turned out to be - or quiet
+// NaNs when the integration is not clean (attempts ran out, an error status, tape full), so that whatever is computed from it is
+// visibly void.  One lane keeps the books in `sticky` (ordinary stores; launches on one stream are ordered).
+__global__ __launch_bounds__(256) void cnf_tape_close_kernel(const double* __restrict__ ctl, const float* __restrict__ states, int cap,
+                                                             const float* __restrict__ fa, const float* __restrict__ fb, int rows,
+                                                             float* __restrict__ y_out, float* __restrict__ f_end, int* sticky) {
+    const double done = ctl[CTL_DONE], status = ctl[CTL_STATUS];
+    const int n = (int)ctl[CTL_ACC];
+    const bool clean = done != 0.0 && status == 0.0 && n >= 0 && n <= cap;      // (n <= cap always: the bound guards the read below)
+    const f4 nan4 = pf_splat(__builtin_nanf(""));
+    const f4* ys = reinterpret_cast<const f4*>(states) + (size_t)(clean ? n : 0) * rows;
+    const f4* fs = reinterpret_cast<const f4*>(ctl[CTL_CUR] != 0.0 ? fb : fa);
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < rows; i += gridDim.x * 256) {
+        reinterpret_cast<f4*>(y_out)[i] = clean ? ys[i] : nan4;
+        reinterpret_cast<f4*>(f_end)[i] = clean ? fs[i] : nan4;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        sticky[0] += 1;
+        if (!clean) {
+            sticky[1] += 1;
+            sticky[2] = done == 0.0 ? 4 : (status != 0.0 ? (int)status : 3);
+        }
+        const int took = (int)(ctl[CTL_ACC] + ctl[CTL_REJ]);
+        if (took > sticky[3]) sticky[3] = took;
+    }
+}
 
 }  // namespace
 
@@ -863,18 +900,50 @@ extern "C" int pf_cnf_steps_taped(double* ctl, float* states, float* steps, int 
 // context rows torchdiffeq integrates alongside), extra_d0 (a DEVICE double, nullable) x extra_scale: what those extra rows
 // add to the squared norm of y0 (pf_scaled_sumsq of the context with itself as the scale; the host never reads it).
 // ws: >= 3072 doubles.  ctl: 16 doubles, ALL ZERO before its first use (the arrival word at [13] is left zero by every launch).
-extern "C" int pf_cnf_init(double* ctl, const float* x, int x_stride, float* y, float* f0, const float* ctx, const float* e,
-                           const float* rec, double t0, double t1, double n_tot, const double* extra_d0, double extra_scale,
-                           int reverse, float rtol, float atol, int rows, int R, double* ws, void* stream) {
+// Both entry points launch from here: pf_cnf_init with (t0, t1) from the host, pf_cnf_init_dev with t_end, a device word.
+namespace {
+int cnf_init_launch(double* ctl, const float* x, int x_stride, float* y, float* f0, const float* ctx, const float* e,
+                    const float* rec, double t0, double t1, const double* t_end, double n_tot, const double* extra_d0,
+                    double extra_scale, int reverse, float rtol, float atol, int rows, int R, double* ws, void* stream) {
     if (!ctl || !x || !y || !f0 || !ctx || !e || !rec || !ws) return PF_ERR_NULL;
     if (rows <= 0 || R <= 0 || !(n_tot > 0.0) || (x_stride != 3 && x_stride != 4)) return PF_ERR_SHAPE;
     hipStream_t s = (hipStream_t)stream;
     CnfInitArgs a{};
     a.ctl = ctl; a.x = x; a.xs = x_stride; a.y = y; a.f0 = f0; a.ctx = ctx; a.e = e; a.rec = rec;
-    a.t0 = t0; a.t1 = t1; a.n_tot = n_tot; a.extra_d0 = extra_d0; a.extra_scale = extra_scale; a.reverse = reverse ? 1.0 : 0.0;
+    a.t0 = t0; a.t1 = t1; a.t_end = t_end; a.n_tot = n_tot; a.extra_d0 = extra_d0; a.extra_scale = extra_scale; a.reverse = reverse ? 1.0 : 0.0;
     a.sgn = reverse ? -1.f : 1.f; a.rtol = rtol; a.atol = atol; a.rows = rows; a.R = R; a.partial = ws;
     const int grid = cnf_grid(rows, CNF_NW * 16, &a.ntiles);
-    hipLaunchKernelGGL(cnf_init_kernel<false>, dim3(grid), dim3(CNF_NW * 64), 0, s, a);
+    if (t_end) hipLaunchKernelGGL((cnf_init_kernel<false, true>), dim3(grid), dim3(CNF_NW * 64), 0, s, a);
+    else hipLaunchKernelGGL(cnf_init_kernel<false>, dim3(grid), dim3(CNF_NW * 64), 0, s, a);
     hipLaunchKernelGGL(cnf_init_kernel<true>, dim3(grid), dim3(CNF_NW * 64), 0, s, a);
+    return pf_last_launch_status();
+}
+}  // namespace
+
+extern "C" int pf_cnf_init(double* ctl, const float* x, int x_stride, float* y, float* f0, const float* ctx, const float* e,
+                           const float* rec, double t0, double t1, double n_tot, const double* extra_d0, double extra_scale,
+                           int reverse, float rtol, float atol, int rows, int R, double* ws, void* stream) {
+    return cnf_init_launch(ctl, x, x_stride, y, f0, ctx, e, rec, t0, t1, nullptr, n_tot, extra_d0, extra_scale, reverse, rtol, atol,
+                           rows, R, ws, stream);
+}
+
+// pf_cnf_init with the interval taken from the device: t_end[0] = T (a word of pf_cnf_pack_blocks' meta row), [t0, t1] = [0, T],
+// reversed [-T, 0].  Nothing about the block's weights passes through the host.
+extern "C" int pf_cnf_init_dev(double* ctl, const float* x, int x_stride, float* y, float* f0, const float* ctx, const float* e,
+                               const float* rec, const double* t_end, double n_tot, const double* extra_d0, double extra_scale,
+                               int reverse, float rtol, float atol, int rows, int R, double* ws, void* stream) {
+    if (!t_end) return PF_ERR_NULL;
+    return cnf_init_launch(ctl, x, x_stride, y, f0, ctx, e, rec, 0.0, 0.0, t_end, n_tot, extra_d0, extra_scale, reverse, rtol, atol,
+                           rows, R, ws, stream);
+}
+
+// One launch behind a blind batch of pf_cnf_steps_taped attempts (include/puflow_hip.h).
+extern "C" int pf_cnf_tape_close(const double* ctl, const float* states, int cap, const float* fa, const float* fb, int rows,
+                                 float* y_out, float* f_end, int* sticky, void* stream) {
+    if (!ctl || !states || !fa || !fb || !y_out || !f_end || !sticky) return PF_ERR_NULL;
+    if (cap <= 0 || rows <= 0) return PF_ERR_SHAPE;
+    const int grid = (rows + 255) / 256 < 256 ? (rows + 255) / 256 : 256;
+    hipLaunchKernelGGL(cnf_tape_close_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, ctl, states, cap, fa, fb, rows, y_out,
+                       f_end, sticky);
     return pf_last_launch_status();
 }

@@ -501,6 +501,17 @@ __device__ __forceinline__ void bw_sweep(const Args& a) {
 
 __global__ __launch_bounds__(BW_NW * 64) void cnf_rhs_vjp_kernel(BwArgs a) { bw_sweep<false>(a); }
 __global__ __launch_bounds__(BW_NW * 64) void cnf_tape_vjp_kernel(BwTapeArgs a) { bw_sweep<true>(a); }
+// The same sweep with the number of recorded steps taken from the integration's controller row (csrc/cnf.hip: [5] done,
+// [6] accepted, [9] status) - a kernel of its own, so that cnf_tape_vjp_kernel keeps its code.  Read once per workgroup and made
+// provably wave-uniform: it bounds the step loop.  Not clean, or outside [1, cap]: zero steps - ybar passes through, the slab
+// is still written (zeros) for the reduction.
+__global__ __launch_bounds__(BW_NW * 64) void cnf_tape_vjp_dev_kernel(BwTapeArgs a, const double* __restrict__ ctl, int cap) {
+    int n = (int)ctl[6];
+    n = (ctl[5] != 0.0 && ctl[9] == 0.0 && n >= 1 && n <= cap) ? n : 0;
+    BwTapeArgs b = a;
+    b.n_steps = __builtin_amdgcn_readfirstlane(n);
+    bw_sweep<true>(b);
+}
 
 // grad[i] += (i in the time-coefficient part ? t : 1) x sum of the slabs.  32 outputs per workgroup, eight threads per output take
 // every eighth slab each (eight loads in flight per output instead of one thread walking all slabs), then the eight partial
@@ -565,6 +576,23 @@ extern "C" int pf_cnf_tape_vjp(const float* states, const float* steps, int n_st
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(cnf_tape_vjp_kernel, dim3(grid), dim3(BW_NW * 64), 0, s, a);
     // every evaluation's time-coefficient share left the kernel multiplied by its own t: the reduction's factor is 1
+    hipLaunchKernelGGL(cnf_rhs_vjp_reduce_kernel, dim3((CNF_GRAD + 31) / 32), dim3(256), 0, s, (const float*)ws, grid, 1.f, grad);
+    return pf_last_launch_status();
+}
+
+// pf_cnf_tape_vjp for a tape recorded without a look at the controller: the step count is ctl[6] of the integration's controller
+// row, read on the device; states / steps are the whole tape of `cap` steps (include/puflow_hip.h).
+extern "C" int pf_cnf_tape_vjp_dev(const float* states, const float* steps, const double* ctl, int cap, float sgn, const float* ctx,
+                                   const float* e, const float* rec, float* ybar, float* ctxbar, float* grad, int rows, int R,
+                                   void* ws, void* stream) {
+    if (!states || !steps || !ctl || !ctx || !e || !rec || !ybar || !ctxbar || !grad || !ws) return PF_ERR_NULL;
+    if (rows <= 0 || R <= 0 || R > 16 || rows % R != 0 || cap <= 0) return PF_ERR_SHAPE;
+    BwTapeArgs a{};
+    a.states = states; a.steps = steps; a.ctx = ctx; a.e = e; a.rec = rec; a.ybar = ybar; a.ctxbar = ctxbar; a.slabs = (float*)ws;
+    a.sgn = sgn; a.n_steps = 0; a.rows = rows; a.R = R;
+    const int grid = bw_grid(rows, R, &a.rpt, &a.ntiles);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(cnf_tape_vjp_dev_kernel, dim3(grid), dim3(BW_NW * 64), 0, s, a, ctl, cap);
     hipLaunchKernelGGL(cnf_rhs_vjp_reduce_kernel, dim3((CNF_GRAD + 31) / 32), dim3(256), 0, s, (const float*)ws, grid, 1.f, grad);
     return pf_last_launch_status();
 }

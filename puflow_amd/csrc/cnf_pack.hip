@@ -171,3 +171,33 @@ extern "C" int pf_cnf_pack_blocks(const float* const* params, const int* cd, int
     hipLaunchKernelGGL(cnf_pack_kernel, dim3(CNF_PACK_PARTS, nb), dim3(CNF_PACK_THREADS), 0, (hipStream_t)stream, a);
     return pf_last_launch_status();
 }
+
+namespace {
+// What a training step that never reads `meta` on the host needs of it (pf_cnf_pack_status): the context GEMM's scale as the
+// float word pf_cnf_context_dev reads, and a status that cannot be raised there made visible on the device - the block's
+// record becomes NaN (every integration on it then ends with status 1) and the sticky row latches it.  One workgroup walks the
+// blocks, so the row has one writer.
+__global__ __launch_bounds__(256) void cnf_pack_status_kernel(const double* __restrict__ meta, int nb, float* __restrict__ rec,
+                                                              float* __restrict__ scales, int* sticky) {
+    for (int b = 0; b < nb; ++b) {
+        const int status = (int)meta[4 * b + 2];
+        if (threadIdx.x < 8) scales[8 * b + threadIdx.x] = threadIdx.x == 6 ? (float)meta[4 * b + 1] : 0.f;
+        if (status != 0)
+            for (int k = threadIdx.x; k < CNF_REC; k += 256) rec[(size_t)b * CNF_REC + k] = __builtin_nanf("");
+        if (threadIdx.x == 0) {
+            sticky[0] += 1;
+            if (status != 0) { sticky[1] += 1; sticky[2] = status; sticky[3] = b; }
+        }
+    }
+}
+}  // namespace
+
+// After pf_cnf_pack_blocks, for a caller that does not read meta: scales [nb, 8] floats, word 6 of a row = meta[b][1] (the layout
+// of the P|Q scale rows, which pf_cnf_context_dev's kernel reads); a non-zero status turns block b's record into NaN and is
+// latched in sticky [4] = (calls x blocks, blocks with a status, last status, its block).
+extern "C" int pf_cnf_pack_status(const double* meta, int nb, float* rec, float* scales, int* sticky, void* stream) {
+    if (!meta || !rec || !scales || !sticky) return PF_ERR_NULL;
+    if (nb < 1 || nb > CNF_PACK_MAXB) return PF_ERR_SHAPE;
+    hipLaunchKernelGGL(cnf_pack_status_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, meta, nb, rec, scales, sticky);
+    return pf_last_launch_status();
+}

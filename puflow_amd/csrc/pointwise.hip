@@ -324,6 +324,23 @@ extern "C" int pf_cnf_context(const float* c, int cd, const float* hc_image, con
     }
 }
 
+// pf_cnf_context with the image's inverse scale on the device: scales[6], the word pf_pq_gemm's scale rows keep theirs in
+// (pf_cnf_pack_status writes such a row per block), so the kernel is the same one.
+extern "C" int pf_cnf_context_dev(const float* c, int cd, const float* hc_image, const float* hb, const float* scales, float* ctx,
+                                  int T, void* stream) {
+    if (!c || !hc_image || !hb || !scales || !ctx) return PF_ERR_NULL;
+    if (T <= 0) return PF_ERR_SHAPE;
+    PqArgs a{};
+    a.h = c; a.w = reinterpret_cast<const u4*>(hc_image); a.bias = hb; a.scales = scales; a.pq = ctx; a.T = T;
+    hipStream_t s = (hipStream_t)stream;
+    switch (cd) {
+        case 32: return launch_pq<32, 288, 9>(a, s);
+        case 64: return launch_pq<64, 288, 9>(a, s);
+        case 128: return launch_pq<128, 288, 9>(a, s);
+        default: return PF_ERR_UNSUPPORTED;
+    }
+}
+
 // unit: 0..5 selects (ODIM, CDIM) = (32,32) (64,64) (128,128) x 4.
 extern "C" int pf_cond(int unit, const float* h, const float* w, const long long* off, float* c, float* st, float* cp,
                        int T, void* stream) {

@@ -11,7 +11,7 @@
 
 One process per GPU under `torchrun` (batches are sharded by the data object, gradients averaged by one all-reduce);
 rank 0 saves.  CLI:  python -m puflow_amd.train --dataset pu1k --data data/pu1k_...h5 [--synthetic] [--max_epochs 100]
-                     [--graph] [--device_data] [--random_input] [--model continuous]
+                     [--graph] [--device_data] [--random_input] [--model continuous [--cnf_deferred]]
 --model continuous trains cnf.PointInterpFlow (modules/continuous/train_interp.py: the same loss mix 1e-4 logp + 5e-2 EMD, clip
 and Adam); its checkpoint is the state dict `python -m puflow_amd.upsample_cnf` and `cnf.PointInterpFlow.load_state_dict` take.
 """
@@ -34,7 +34,9 @@ def model_specific_args() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser()
     p.add_argument("--net", type=str, default="UpsamplingFlow")
     p.add_argument("--model", default="discrete", choices=MODELS, help="continuous: the CNF variant (cnf.PointInterpFlow, "
-                   "modules/continuous/train_interp.py); eager steps only, no --graph")
+                   "modules/continuous/train_interp.py); eager steps only, no --graph, unless --cnf_deferred")
+    p.add_argument("--cnf_deferred", action="store_true", help="continuous model: run the taped integrations without reading their "
+                   "controllers, against learnt budgets, one read per step (cfg.cnf_deferred); with it --graph captures the step")
     p.add_argument("--learning_rate", default=1e-3, type=float)
     p.add_argument("--sched_patience", default=10, type=int)
     p.add_argument("--sched_factor", default=0.5, type=float)
@@ -79,6 +81,7 @@ def fit(module: TrainerModule, train_data: Iterable, val_data: Optional[Iterable
     rank, _ = _dist()
     graphs = {}
     use_graph = graph and next(module.parameters()).is_cuda
+    deferred = use_graph and bool(getattr(getattr(module, "network", None), "train_deferred", False))
     try:
         for epoch in range(max_epochs):
             module.train()
@@ -86,6 +89,8 @@ def fit(module: TrainerModule, train_data: Iterable, val_data: Optional[Iterable
             for bi, batch in enumerate(train_data):
                 if use_graph:
                     key = _batch_key(batch)
+                    if key in graphs and getattr(graphs[key], "stale", False):
+                        del graphs[key]                          # an integration outgrew its captured budget: capture anew with the grown ones
                     if key not in graphs:
                         graphs[key] = module.graphed_train_step(batch, optimizer, clip, warmup=1)
                         last = graphs[key].warmup_loss
@@ -96,6 +101,9 @@ def fit(module: TrainerModule, train_data: Iterable, val_data: Optional[Iterable
                     continue
                 last = module.train_step(batch, optimizer, clip)
             hist["loss"].append(float(last) if last is not None else float("nan"))
+            if deferred:
+                for g in graphs.values():             # (an epoch may be shorter than CHECK_EVERY replays)
+                    g.check()
             if next(module.parameters()).is_cuda:
                 module.check_device_status()          # end of epoch, the host just synchronised: EMD barrier time-outs raise, NaN substitutions are printed
             if hasattr(train_data, "status"):
@@ -135,7 +143,7 @@ def train(phase: str = "Train", checkpoint_path: Optional[str] = None, begin_che
     torch.manual_seed(int(getattr(cfg, "seed", 2021)))
     dev = device or (f"cuda:{int(os.environ.get('LOCAL_RANK', 0))}" if torch.cuda.is_available() else "cpu")
     module = (module or TrainerModule(cfg, loss_mix=LOSS_MIX[dataset])).to(dev)
-    if graph and getattr(module, "continuous", False):
+    if graph and getattr(module, "continuous", False) and not getattr(module.network, "train_deferred", False):
         raise RuntimeError(GRAPH_ERROR)
     hist = None
     if phase == "Train":
@@ -168,7 +176,7 @@ def main(argv=None):
     if dev.startswith("cuda"):
         torch.cuda.set_device(dev)
     cfg = default_cfg(model=a.model, learning_rate=a.learning_rate, sched_patience=a.sched_patience, sched_factor=a.sched_factor,
-                      seed=a.seed, sync_batchnorm=a.sync_batchnorm)
+                      seed=a.seed, sync_batchnorm=a.sync_batchnorm, cnf_deferred=a.cnf_deferred)
     kw = dict(batch_size=a.batch_size, num_point_patch=256, device=dev, seed=a.seed, rank=rank, world=world,
               is_augment=True, jitter_sigma=0.01, jitter_max=0.03)            # train_pu1k.py:132-141
     tkw = {**kw, "use_random_input": True} if a.random_input else kw          # the validation set: no subsample, no augmentation

@@ -95,6 +95,8 @@ class GraphedTrainStep:
         if hasattr(module, "_nan_subs") and (module._nan_subs is None or module._nan_subs.device != dev):
             module._nan_subs = torch.zeros((), dtype=torch.int64, device=dev)     # NaN losses replaced inside the capture
         self.calls = 0
+        self.stale = False            # the continuous model's deferred controller outgrew a captured budget: capture anew (train.fit)
+        self.skipped = 0              # replays whose step was void for that reason (NaN loss, update skipped on the device)
         self.bucket = FlatGradBucket(module.parameters())
         # warm-up AND capture run on this one stream: the fused kernels' zero-initialised scratch words (barrier words, the sticky
         # time-out word, statistics accumulators: train_state._zeros_kept) are cached per (device, stream) and must be allocated
@@ -105,6 +107,9 @@ class GraphedTrainStep:
             for _ in range(max(warmup, 1)):               # ActNorm init, library loads, workspaces, Adam state
                 module._sync_actnorm_init(self.static)
                 self.warmup_loss = self._fwd_bwd()        # these ARE optimisation steps on `batch` (the fit loop counts them)
+                if self._deferred_short():                # (continuous model, deferred controller: budgets learnt / grown here)
+                    self.warmup_loss = self._fwd_bwd()
+                    self._deferred_short(final=True)
                 self._reduce()
                 self._update()
         torch.cuda.current_stream(dev).wait_stream(side)
@@ -182,6 +187,10 @@ class GraphedTrainStep:
             self.bucket.pack()
         return loss.detach()
 
+    def _deferred_short(self, final: bool = False) -> int:
+        fn = getattr(self.module, "deferred_short", None)
+        return fn(final) if fn is not None else 0
+
     def _reduce(self) -> None:
         if self.multi:
             torch.distributed.all_reduce(self.bucket.flat)
@@ -224,10 +233,21 @@ class GraphedTrainStep:
 
     CHECK_EVERY = 64          # replays between two reads of the device status words (each read is a synchronisation)
 
-    def check(self) -> int:
-        """A timed-out EMD barrier raises; returns the NaN losses replaced since the last check (trainer.check_device_status)."""
+    def check(self):
+        """A timed-out EMD barrier raises; returns the NaN losses replaced since the last check (trainer.check_device_status).
+        The continuous model under its deferred controller: also the one read of the log rows and the sticky table
+        (cnf.PointInterpFlow.check_train_logs: error states raise); a replay in which an integration outgrew its captured budget
+        was void - `stale` is set, the budgets are grown, `train.fit` captures anew - and the return value is the pair
+        (NaN losses, void replays)."""
         fn = getattr(self.module, "check_device_status", None)
-        return fn() if fn is not None else 0
+        n = fn() if fn is not None else 0
+        net = getattr(self.module, "network", None)
+        if getattr(net, "train_deferred", False) and hasattr(net, "check_train_logs"):
+            if net.check_train_logs():
+                self.stale = True
+            self.skipped += net.last_skipped_steps
+            return n, net.last_skipped_steps
+        return n
 
     def set_lr(self, lr: float) -> None:
         if self.fused:

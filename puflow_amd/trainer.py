@@ -27,7 +27,8 @@ except Exception:                        # pragma: no cover - not installed in t
 
 MODELS = ("discrete", "continuous")
 GRAPH_ERROR = ("the continuous model's training step cannot be captured in a graph: its taped integrations read their "
-               "step-size controllers on the host (train it eagerly, without --graph)")
+               "step-size controllers on the host (train it eagerly, without --graph, or switch the deferred controller on: "
+               "cfg.cnf_deferred=True / --cnf_deferred)")
 
 
 def default_cfg(model: str = "discrete", **kw):
@@ -39,10 +40,13 @@ def default_cfg(model: str = "discrete", **kw):
     # remaining float-atomic gradients as ordered gathers; slower - no persistent kernels; train_state.set_deterministic)
     # persistent_kernels: the training step's grid-barrier kernels (EdgeConv units as one launch each).  None = on, unless
     # emd_workgroups == 1 says the device is shared with other processes (grid barriers need every workgroup resident)
+    # cnf_deferred (continuous model): the taped integrations run without a look at their controllers, against learnt budgets of
+    # attempts and tape steps; one read per step (cnf.PointInterpFlow.check_train_logs) - which is what lets the step be captured
     if model not in MODELS:
         raise ValueError(f"model is one of {MODELS}, not {model!r}")
     cfg = dict(net="UpsamplingFlow", model=model, learning_rate=1e-3, sched_patience=10, sched_factor=0.5, seed=2021, sync_batchnorm=False,
-               fused_optimizer=True, emd_workgroups=0, persistent_kernels=None, deterministic=False, dw_stream=False)
+               fused_optimizer=True, emd_workgroups=0, persistent_kernels=None, deterministic=False, dw_stream=False,
+               cnf_deferred=False)
     cfg.update(kw)
     return SimpleNamespace(**cfg)
 
@@ -59,6 +63,7 @@ class TrainerModule(_Base):
         if self.continuous:
             from .cnf import PointInterpFlow as ContinuousInterpFlow
             self.network = ContinuousInterpFlow(pc_channel=3)
+            self.network.train_deferred = bool(getattr(self.cfg, "cnf_deferred", False))
         else:
             self.network = PointInterpFlow(pc_channel=3)
         self.network.sync_batchnorm = bool(getattr(self.cfg, "sync_batchnorm", False))     # an argument of its train-mode forward
@@ -252,13 +257,34 @@ class TrainerModule(_Base):
     def graphed_train_step(self, batch, optimizer: torch.optim.Optimizer, clip: float = 1e-2, warmup: int = 2):
         """`train_step` for a fixed batch shape captured in hipGraphs (puflow_amd/train_graph.py): returns
         `step(batch) -> loss` that replays forward + backward (+ clip + Adam) with one launch instead of ~3 500."""
-        if self.continuous:
+        if self.continuous and not getattr(self.network, "train_deferred", False):
             raise RuntimeError(GRAPH_ERROR)
+        if self.continuous:
+            from .dist import multi_rank
+            if multi_rank():
+                raise RuntimeError("the continuous model's captured training step is single-process: multi-rank capture (and "
+                                   "SyncBN) of the CNF step is untested - train it eagerly under torchrun")
         from .optim import FusedClipAdam
         from .train_graph import GraphedTrainStep
         if isinstance(optimizer, FusedClipAdam):
             self._fused_opt = optimizer                         # check_device_status reports its skipped updates
         return GraphedTrainStep(self, optimizer, batch, clip, warmup)
+
+    def deferred_short(self, final: bool = False) -> int:
+        """The continuous model's deferred controller after an eager forward + backward: the step's one read of the twelve
+        controller rows (cnf.PointInterpFlow.check_train_logs) -> integrations that fell short of their budgets (already doubled).
+        final: the repeated step fell short too - those budgets are dropped, so the next step runs these integrations through the
+        host-read loop and learns them anew; this step's loss is NaN and the optimizer skips it."""
+        net = self.network
+        if not (self.continuous and getattr(net, "train_deferred", False)) or torch.cuda.is_current_stream_capturing():
+            return 0
+        before = dict(net.tape_budget)
+        short = net.check_train_logs()
+        if short and final:
+            for k, v in before.items():
+                if net.tape_budget.get(k) != v:
+                    del net.tape_budget[k]
+        return short
 
     def backward_seed(self, loss: Tensor) -> Tensor:
         """d loss / d loss = 1 as a tensor that exists already: `loss.backward()` would fill a new one each step (a launch)."""
@@ -278,6 +304,11 @@ class TrainerModule(_Base):
         self._bucket.drop_grads()                               # = optimizer.zero_grad(set_to_none=True): no fill, no accumulate
         loss = self.training_step(batch, 0)
         loss.backward(self.backward_seed(loss))
+        if self.deferred_short():                               # an integration outgrew its budget: once more with the grown ones
+            self._bucket.drop_grads()
+            loss = self.training_step(batch, 0)
+            loss.backward(self.backward_seed(loss))
+            self.deferred_short(final=True)
         from .optim import FusedClipAdam
         if isinstance(optimizer, FusedClipAdam):
             self._fused_opt = optimizer

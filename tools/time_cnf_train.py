@@ -9,6 +9,17 @@ points, with the bench workload's weights (weights.CNF_PU1K_DYNAMICS / CNF_PU1K_
 
   python tools/time_cnf_train.py --out profiles/cnf_train/time_cnf_train.json
 
+--legs: the deferred controller and the captured step against that eager step, three legs on one box, alternated:
+  (a) the eager step as above (thirteen host reads per step), (b) the eager step with cfg.cnf_deferred (one read), (c) the captured
+  step (TrainerModule.graphed_train_step with cfg.cnf_deferred: one replay, a read every CHECK_EVERY replays).
+Five rounds a, b, c, a, b, c, ...; a run is --steps steps, each timed by the host clock around the step and a device synchronise;
+per run the median step time and the spread (max - min) of its steps; the three modules start from the same weights and take the
+same number of optimisation steps (--lr 0, the default, holds the weights: the step then costs the same in every run).  Between
+the runs the captured step is checked and, when stale, captured anew, as train.fit does (untimed, counted).  For (b) and (c) also the step attempts enqueued per step that returned at once because their
+integration was done (budget - the largest count of attempts the sticky table saw; cnf.PointInterpFlow.train_log_stats).
+
+  python tools/time_cnf_train.py --legs --out profiles/cnf_graph/legs.json
+
 Every case is warmed up; host clock around work that ends in a device synchronise; median (min .. max) of the repeats.  The
 trainer runs with emd_workgroups = 1 (no grid-barrier kernels: safe on a device other processes use).  Recorded, not gated."""
 from __future__ import annotations
@@ -119,6 +130,91 @@ def run(a):
     return res
 
 
+def run_legs(a):
+    import torch
+    from puflow_amd.trainer import TrainerModule, default_cfg
+    from puflow_amd.weights import CNF_PU1K_DYNAMICS, CNF_PU1K_END_TIMES, synth_cnf_state_dict, synth_patches
+
+    dev = "cuda:0"
+    sd = synth_cnf_state_dict(2021, dynamics=CNF_PU1K_DYNAMICS, end_times=CNF_PU1K_END_TIMES)
+    dense = synth_patches(B, N * R, seed=2021).to(dev)
+    sparse = dense[:, ::R].contiguous()
+    batch = (sparse, dense)
+
+    def module(deferred):
+        torch.manual_seed(0)
+        m = TrainerModule(default_cfg(model="continuous", emd_workgroups=1, cnf_deferred=deferred, learning_rate=a.lr))
+        m.network.load_state_dict(sd, strict=True)
+        m = m.to(dev)
+        return m, m.configure_optimizers()["optimizer"]
+
+    ma, oa = module(False)
+    mb, ob = module(True)
+    mc, oc = module(True)
+    for _ in range(2):                                                # the warm-up steps the capture takes, for all three
+        ma.train_step(batch, oa)
+        mb.train_step(batch, ob)
+    graph = mc.graphed_train_step(batch, oc, warmup=2)
+    cap = {"graph": graph, "captures": 1, "void": 0, "nan": 0}
+    legs = {"a_eager": lambda: ma.train_step(batch, oa), "b_eager_deferred": lambda: mb.train_step(batch, ob),
+            "c_captured": lambda: cap["graph"](batch)}
+    res = {"device": torch.cuda.get_device_name(0), "shape": [B, N, R], "steps_per_run": a.steps, "rounds": 5, "learning_rate": a.lr,
+           "runs": {k: [] for k in legs}}
+    for _ in range(5):
+        for name, fn in legs.items():
+            if name == "c_captured":                                  # between runs, untimed: what train.fit does with a stale graph
+                nan, void = cap["graph"].check()
+                cap["nan"] += nan
+                cap["void"] += void
+                if cap["graph"].stale:
+                    cap["graph"] = mc.graphed_train_step(batch, oc, warmup=1)
+                    cap["captures"] += 1
+            torch.cuda.synchronize()
+            ts = []
+            for _ in range(a.steps):
+                t = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                ts.append((time.perf_counter() - t) * 1e3)
+            res["runs"][name].append({"ms_median": float(np.median(ts)), "ms_spread": float(np.max(ts) - np.min(ts))})
+    nan, void = cap["graph"].check()
+    mb.network.check_train_logs()
+    res["c_nan_losses"], res["c_void_replays"], res["c_captures"] = int(cap["nan"] + nan), int(cap["void"] + void), cap["captures"]
+    for name, m in (("b_eager_deferred", mb), ("c_captured", mc)):
+        st = m.network.train_log_stats()
+        res[name + "_attempts"] = {"enqueued_per_step": sum(r["attempts"] for r in st["rows"]),
+                                   "largest_taken_per_step": sum(r["max_took"] for r in st["rows"]),
+                                   "noop_launches_per_step": st["noop"], "not_clean_runs": sum(r["not_clean"] for r in st["rows"]),
+                                   "budgets": [[r["attempts"], r["cap"]] for r in st["rows"]]}
+    res["a_steps_per_integration"] = [len(s) for s in ma.network.last_train_steps]
+    return res
+
+
+def text_legs(res):
+    B_, N_, R_ = res["shape"]
+    lines = [f"continuous training step, {B_} x {N_} -> {N_ * R_} points; {res['device']}; three legs alternated on one box, {res['rounds']} rounds of "
+             f"{res['steps_per_run']} steps each; per run: median step ms (spread = max - min of its steps)"]
+    med = {}
+    for name, runs in res["runs"].items():
+        lines.append(f"{name:18s} " + "   ".join(f"{r['ms_median']:.3f} ({r['ms_spread']:.3f})" for r in runs))
+        ms = [r["ms_median"] for r in runs]
+        med[name] = (float(np.median(ms)), float(np.max(ms) - np.min(ms)))
+    for name, (m, sp) in med.items():
+        lines.append(f"{name:18s} median of the run medians {m:.3f} ms, spread of the run medians {sp:.3f} ms")
+    a_m, a_sp = med["a_eager"]
+    for name in ("b_eager_deferred", "c_captured"):
+        d = med[name][0] - a_m
+        lines.append(f"{name} - a_eager = {d:+.3f} ms ({100 * d / a_m:+.1f} %) against a_eager's spread of {a_sp:.3f} ms: "
+                     f"{'more' if abs(d) >= 3 * a_sp else 'LESS'} than three spreads")
+        at = res[name + "_attempts"]
+        lines.append(f"   attempts enqueued per step {at['enqueued_per_step']}, largest taken {at['largest_taken_per_step']}, no-op attempt launches "
+                     f"per step {at['noop_launches_per_step']}, runs not clean {at['not_clean_runs']}")
+    lines.append(f"learning rate {res['learning_rate']:g}; captured leg: NaN losses {res['c_nan_losses']}, void replays {res['c_void_replays']} "
+                 f"(an integration outgrew its captured budget; checked between the runs), captures {res['c_captures']}; accepted steps per "
+                 f"integration (leg a, last step) {res['a_steps_per_integration']}")
+    return "\n".join(lines) + "\n"
+
+
 def text(res):
     f = lambda t: f"{t['ms_median']:10.3f} ({t['ms_min']:.3f} .. {t['ms_max']:.3f}) x{t['repeats']}"
     B_, N_, R_ = res["shape"]
@@ -139,7 +235,21 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", required=True)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--legs", action="store_true", help="eager / eager deferred / captured, alternated (DESIGN 9b)")
+    ap.add_argument("--steps", type=int, default=20, help="--legs: steps per run")
+    ap.add_argument("--lr", type=float, default=0.0, help="--legs: learning rate.  0 (default) holds the weights, so that every run of "
+                    "every leg does the same work; with a real rate the integrations' step counts drift from run to run and a captured "
+                    "step's budgets are outgrown (void replays until the next check, then a new capture)")
     a = ap.parse_args()
+    if a.legs:
+        res = run_legs(a)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as fh:
+            json.dump(res, fh, indent=1)
+        with open(os.path.splitext(a.out)[0] + ".txt", "w") as fh:
+            fh.write(text_legs(res))
+        print(text_legs(res))
+        return
     res = run(a)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as fh:
