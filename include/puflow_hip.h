@@ -734,6 +734,29 @@ long long pf_cnf_tape_vjp_workspace_bytes(int rows, int R);
 int pf_cnf_tape_vjp(const float* states, const float* steps, int n_steps, float sgn, const float* ctx, const float* e,
                     const float* rec, float* ybar, float* ctxbar, float* grad, int rows, int R, void* ws, void* stream);
 
+/* The forward counterpart of pf_cnf_tape_vjp: n_steps Dormand-Prince steps on a step list given IN ADVANCE (a frozen schedule)
+ * in ONE launch, no controller.  On a fixed list nothing couples the rows, so a lane carries its row's state, its seven stage
+ * derivatives and its Hutchinson vector through all steps in registers: k_1 = f(s_0, y_0) is evaluated here, after that FSAL.
+ * The arithmetic is pf_cnf_init's f0 and pf_cnf_steps_taped's attempts (plain gates): on the list those recorded, the same bits.
+ *   x       [rows, x_stride]        points, row stride 3 or 4 floats (a previous block's state is read in place); y_0 = (x, 0)
+ *   steps   [n_steps, 2]            DEVICE floats (s, h) in solver time; reverse != 0: torchdiffeq's decreasing-time convention
+ *                                   (net time = -s, f negated), as pf_cnf_steps_taped
+ *   states  [n_steps + 1, rows, 4]  nullable: the state at the start of each step, then the result - the tape pf_cnf_tape_vjp reads
+ *   y_out   [rows, 4]               the result
+ *   f_start, f_end [rows, 4]        nullable: the derivative at the start of the first and at the end of the last step
+ *   errsq   [n_steps]               nullable DEVICE doubles: per step sum_i (err_i / (atol + rtol max(|y0_i|, |y1_i|)))^2 of the
+ *                                   embedded error estimate, the sum an adaptive attempt hands its controller.  Every wave
+ *                                   keeps its share per step in ws and a second small launch adds the shares in a fixed order:
+ *                                   no float atomics, the same bits from run to run.  ws: pf_cnf_replay_workspace_bytes(rows,
+ *                                   n_steps) bytes (negative: bad shape); not read when errsq is NULL.
+ * n_steps >= 1, x_stride 3 or 4, R >= 1, rows a multiple of R, else PF_ERR_SHAPE before anything is launched.  At most 1024
+ * workgroups, grid-striding over 64-row tiles; for R >= 4 dividing 64 a tile's context rows are in LDS for all 6 n_steps + 1
+ * evaluations.  No grid barrier, no controller word, no residency requirement. */
+long long pf_cnf_replay_workspace_bytes(int rows, int n_steps);
+int pf_cnf_replay(const float* x, int x_stride, const float* steps, int n_steps, int reverse, const float* ctx, const float* e,
+                  const float* rec, float* states, float* y_out, float* f_start, float* f_end, double* errsq, float rtol,
+                  float atol, int rows, int R, void* ws, void* stream);
+
 /* One whole Dormand-Prince 5(4) step attempt per launch (the six stage evaluations fused, stage derivatives in
  * registers): y1 = y0 + h sum b_j k_j with k_1 = f0 (FSAL), f1 = k_7, ymid (nullable) = dense-output mid-point,
  * out[0] (double, device) = sum_i (err_i / (atol + rtol max(|y0_i|, |y1_i|)))^2 of the embedded error estimate.

@@ -6,7 +6,10 @@ gradients (`forward_train`: the discrete training step's extractor and interpola
 integrations, backward by `pf_cnf_tape_vjp`, csrc/cnf_bwd.hip, weights packed from the live parameters on the device by
 `pf_cnf_pack_blocks`, csrc/cnf_pack.hip); `PointInterpFlow.flow_block` is ONE such block as an autograd function.  With
 `net.train_deferred` (off by default) the taped integrations run against learnt budgets without a host read -
-`pf_cnf_tape_close`, `pf_cnf_tape_vjp_dev`, `check_train_logs` - which is what a captured training step needs.
+`pf_cnf_tape_close`, `pf_cnf_tape_vjp_dev`, `check_train_logs` - which is what a captured training step needs.  With
+`net.step_schedule` (None by default) eval and train mode integrate on a FROZEN step schedule instead - per integration
+a grid of step boundaries chosen in advance, e.g. the adaptive solver's own accepted steps on a calibration input
+(`record_schedule`) - one `pf_cnf_replay` launch each (csrc/cnf_replay.hip), no controller at all.
 
 What runs where:
   * kNN, the six EdgeConv units, the merge units and the interpolation module are the discrete model's kernels
@@ -59,6 +62,167 @@ DP_C_ERR = [35 / 384 - 1951 / 21600, 0, 500 / 1113 - 22642 / 50085, 125 / 192 - 
             -2187 / 6784 - -12231 / 42400, 11 / 84 - 649 / 6300, -1. / 60.]
 DP_C_MID = [6025192743 / 30085553152 / 2, 0, 51252292925 / 65400821598 / 2, -2691868925 / 45128329728 / 2,
             187940372067 / 1594534317056 / 2, -1776094331 / 19743644256 / 2, 11237099 / 235043384 / 2]
+
+
+# ---- frozen step schedules: pure Python, no GPU ---------------------------------------------------------------
+# A schedule is a dict: for each of the twelve integrations (block, reverse) a strictly increasing float64 grid of FRACTIONS of the
+# integration's interval, from 0.0 to 1.0.  Step k of integration (i, r) spans [t0 + T g_k, t0 + T g_{k+1}] in solver time
+# (T = the block's end time, t0 = 0 going forward and -T reversed).  A uniform grid is one special case; the usual source is the
+# adaptive solver's own accepted steps on a calibration input (`PointInterpFlow.record_schedule`).
+SCHEDULE_FORMAT = "puflow-cnf-step-schedule"
+
+
+def schedule_keys(num_blocks: int = NUM_BLOCKS):
+    """The integrations in the order they run: f's blocks 0 .. n - 1, then g's n - 1 .. 0."""
+    return [(i, False) for i in range(num_blocks)] + [(i, True) for i in reversed(range(num_blocks))]
+
+
+def validate_schedule(schedule, num_blocks: int = NUM_BLOCKS) -> dict:
+    """-> the schedule as {(block, reverse): tuple of floats}; ValueError says what is wrong with it."""
+    if not isinstance(schedule, dict):
+        raise ValueError("a step schedule is a dict {(block, reverse): grid of fractions from 0.0 to 1.0}")
+    keys = schedule_keys(num_blocks)
+    extra = [k for k in schedule if k not in keys]
+    if extra:
+        raise ValueError(f"step schedule: unknown integration {extra[0]!r} (keys are (block 0..{num_blocks - 1}, reverse False/True))")
+    out = {}
+    for key in keys:
+        if key not in schedule:
+            raise ValueError(f"step schedule: no grid for integration (block {key[0]}, reverse {key[1]})")
+        try:
+            grid = tuple(float(v) for v in schedule[key])
+        except (TypeError, ValueError):
+            raise ValueError(f"step schedule {key}: the grid is a sequence of numbers") from None
+        if len(grid) < 2:
+            raise ValueError(f"step schedule {key}: a grid has at least the two ends 0.0 and 1.0")
+        if len(grid) - 1 > MAX_NUM_STEPS:
+            raise ValueError(f"step schedule {key}: more than {MAX_NUM_STEPS} steps")
+        if any(not math.isfinite(v) for v in grid):
+            raise ValueError(f"step schedule {key}: non-finite grid value")
+        if grid[0] != 0.0 or grid[-1] != 1.0:
+            raise ValueError(f"step schedule {key}: the grid starts at 0.0 and ends at 1.0 (got {grid[0]!r} .. {grid[-1]!r})")
+        if any(not b > a for a, b in zip(grid, grid[1:])):
+            raise ValueError(f"step schedule {key}: the grid must be strictly increasing")
+        out[key] = grid
+    return out
+
+
+def uniform_schedule(k: int, num_blocks: int = NUM_BLOCKS) -> dict:
+    """k equal steps for every integration."""
+    if int(k) != k or k < 1:
+        raise ValueError("uniform_schedule: k >= 1 steps")
+    k = int(k)
+    grid = tuple([j / k for j in range(k)] + [1.0])
+    return {key: grid for key in schedule_keys(num_blocks)}
+
+
+def refine_schedule(schedule, m: int) -> dict:
+    """Every step cut into m equal parts (m = 1: the schedule itself, validated)."""
+    if int(m) != m or m < 1:
+        raise ValueError("refine_schedule: m >= 1")
+    m = int(m)
+    nb = 1 + max((k[0] for k in schedule if isinstance(k, tuple) and len(k) == 2 and isinstance(k[0], int)), default=NUM_BLOCKS - 1)
+    out = {}
+    for key, grid in validate_schedule(schedule, nb).items():
+        fine = []
+        for a, b in zip(grid, grid[1:]):
+            fine += [a + (b - a) * (j / m) for j in range(m)]
+        out[key] = tuple(fine + [1.0])
+    return validate_schedule(out, nb)
+
+
+def save_schedule(schedule, path) -> None:
+    """JSON: {"format", "version", "integrations": [{"block", "reverse", "grid"}]}, in running order.  float64 round-trips."""
+    import json
+    nb = 1 + max(k[0] for k in schedule)
+    sched = validate_schedule(schedule, nb)
+    doc = dict(format=SCHEDULE_FORMAT, version=1,
+               integrations=[dict(block=i, reverse=r, grid=list(sched[(i, r)])) for i, r in schedule_keys(nb)])
+    with open(path, "w") as fh:
+        json.dump(doc, fh, indent=1)
+        fh.write("\n")
+
+
+def load_schedule(path) -> dict:
+    import json
+    with open(path) as fh:
+        try:
+            doc = json.load(fh)
+        except json.JSONDecodeError as err:
+            raise ValueError(f"{path}: not a step-schedule file ({err})") from None
+    if not isinstance(doc, dict) or doc.get("format") != SCHEDULE_FORMAT or not isinstance(doc.get("integrations"), list):
+        raise ValueError(f"{path}: not a step-schedule file (format {SCHEDULE_FORMAT!r})")
+    sched = {}
+    for ent in doc["integrations"]:
+        if not isinstance(ent, dict) or not {"block", "reverse", "grid"} <= set(ent):
+            raise ValueError(f"{path}: an integration entry holds block, reverse and grid")
+        key = (int(ent["block"]), bool(ent["reverse"]))
+        if key in sched:
+            raise ValueError(f"{path}: integration {key} is listed twice")
+        sched[key] = ent["grid"]
+    return validate_schedule(sched, 1 + max((k[0] for k in sched), default=0))
+
+
+def schedule_from_steps(step_lists, T_ends) -> dict:
+    """The grids of recorded (s, h) lists (`last_train_steps` order: `schedule_keys`) of integrations over T_ends[block]:
+    g_k = (h_0 + .. + h_{k-1}) / T, the last one 1.0 - so that fl32(T (g_{k+1} - g_k)) gives back the fp32 h_k of every step but
+    the last, which is cut to end on t1 (`schedule_step_lists`)."""
+    nb = len(T_ends)
+    out = {}
+    for key, steps in zip(schedule_keys(nb), step_lists):
+        T = float(T_ends[key[0]])
+        if not steps:
+            raise ValueError(f"schedule_from_steps: integration {key} recorded no step")
+        grid, acc = [0.0], 0.0
+        for _, h in steps[:-1]:
+            acc += float(h)
+            grid.append(acc / T)
+        out[key] = tuple(grid + [1.0])
+    return validate_schedule(out, nb)
+
+
+def schedule_step_lists(deltas: Tensor, last: Tensor, rev: Tensor, T: Tensor) -> Tensor:
+    """The (s, h) lists of n integrations from their grids, in fp32, by the contiguity rule of the taped controller
+    (csrc/cnf.hip: cnf_ctl_update_taped): s_0 = t0, h_k = fl(T d_k), s_{k+1} = s_k + h_k in fp32, and the last step cut to end on
+    t1: h = fl(t1 - s).  Works on any device, without a host read.
+    deltas [n, m] float64: g_{k+1} - g_k per row, zero-padded; last [n] int64: index of each row's last step; rev [n] bool;
+    T [n] float64: the end times.  -> [n, m, 2] float32; row j's list is its first last[j] + 1 entries."""
+    n, m = deltas.shape
+    t0 = torch.where(rev, -T, torch.zeros_like(T))
+    t1 = torch.where(rev, torch.zeros_like(T), T)
+    out = torch.empty((n, m, 2), dtype=torch.float32, device=deltas.device)
+    S, H = out[:, :, 0], out[:, :, 1]
+    H.copy_((T[:, None] * deltas).to(torch.float32))
+    S[:, 0] = t0.to(torch.float32)
+    for k in range(m - 1):                                   # a sequential fp32 sum: one add over all rows per step
+        torch.add(S[:, k], H[:, k], out=S[:, k + 1])
+    li = last[:, None]
+    H.scatter_(1, li, (t1[:, None] - S.gather(1, li).to(torch.float64)).to(torch.float32))
+    return out
+
+
+class _ScheduleDev:
+    """A schedule's constants on the device (made once, outside any capture): the grid differences of the twelve integrations in
+    running order, padded to the longest, and what `schedule_step_lists` needs beside the end times."""
+
+    def __init__(self, schedule: dict, device: torch.device, num_blocks: int = NUM_BLOCKS):
+        self.schedule = schedule
+        self.keys = schedule_keys(num_blocks)
+        self.n = [len(schedule[k]) - 1 for k in self.keys]
+        m = max(self.n)
+        d = torch.zeros((len(self.keys), m), dtype=torch.float64)
+        for j, k in enumerate(self.keys):
+            g = torch.tensor(schedule[k], dtype=torch.float64)
+            d[j, :self.n[j]] = g[1:] - g[:-1]
+        self.deltas = d.to(device)
+        self.last = torch.tensor([n - 1 for n in self.n], dtype=torch.int64).to(device)
+        self.rev = torch.tensor([r for _, r in self.keys]).to(device)
+        self.block = torch.tensor([i for i, _ in self.keys], dtype=torch.int64).to(device)
+        self.device = device
+
+    def lists(self, T_blocks: Tensor) -> Tensor:
+        """T_blocks [num_blocks] float64 on the device -> steps [12, m, 2] float32."""
+        return schedule_step_lists(self.deltas, self.last, self.rev, T_blocks.index_select(0, self.block))
 
 
 # ---- parameter holders (key names of the reference) ------------------------------------------------
@@ -298,6 +462,91 @@ class _CnfKernels:
                                                self.rec[i].data_ptr(), RTOL, ATOL, rows, R, int(attempts), self.ws1k.data_ptr(),
                                                self._stream()), "pf_cnf_steps_taped")
 
+    def tape_forward(self, i: int, x: Tensor, c: Tensor, e: Tensor, R: int, reverse: bool, cap: int = 32, ctx: Optional[Tensor] = None,
+                     d0c: Optional[Tensor] = None):
+        """dopri5 on block i with the control on the DEVICE (pf_cnf_init, then batches of pf_cnf_steps_taped attempts with one read
+        of the controller per batch, as `_CnfEngine.integrate`), the step that would cover the end time cut to END there: the
+        result is the last accepted step's solution, so the forward is exactly the recorded steps.  cap: steps the tape is
+        allocated for; a tape that fills up (status 3) is allocated anew at twice the size and the integration starts again.
+        -> (state [rows,4], tape): (s, h) per accepted step on the device (`steps_dev` [n,2], the fp32 values the kernels
+        computed with) and as host floats (`steps`, one read when done), the state at the start of each step (`states` [n,rows,4]),
+        the context rows and the derivatives at both ends.
+        ctx, d0c: block i's context rows and the context's norm word where the caller has them already (the train-mode forward
+        computes both once per block for f and g)."""
+        rows = x.shape[0]
+        dev = x.device
+        T = self.T_end[i]
+        t0, t1 = (0.0, T) if not reverse else (-T, 0.0)
+        if ctx is None:
+            ctx = self.context(i, c)
+        n_tot = float(rows * 4 + c.numel() * R)                 # the context is a state of the reference's ODE: it enters the norms
+        if d0c is None:
+            d0c = torch.empty(1, dtype=torch.float64, device=dev)
+            self.context_norm(c, d0c)
+        fbuf =torch.empty((2, rows, 4), dtype=torch.float32, device=dev)
+        cap = max(1, int(cap))
+        while True:
+            states = torch.empty((cap + 1, rows, 4), dtype=torch.float32, device=dev)
+            steps = torch.empty((cap, 2), dtype=torch.float32, device=dev)
+            self._cnf_init(i, self.ctl, x, states[0], fbuf[0], ctx, e, t0, t1, n_tot, d0c, float(R), reverse, rows, R)
+            f_start = fbuf[0].clone()                           # needed for dT when reversed; fbuf ping-pongs from here on
+            attempts, batch = 0, self.first_batch
+            while True:
+                self._cnf_steps_taped(i, self.ctl, states, steps, fbuf, ctx, e, rows, R, batch)
+                attempts += batch
+                st = self.ctl.cpu()                             # the one device->host read per batch of attempts
+                if st[5] != 0:
+                    break
+                if attempts > MAX_NUM_STEPS:
+                    raise _lib.PuflowHipError(f"dopri5: more than {MAX_NUM_STEPS} step attempts in block {i}")
+                batch = self.next_batch
+            self.nfe += int(st[8])
+            if st[9] != 3:
+                break
+            if cap > MAX_NUM_STEPS:
+                raise _lib.PuflowHipError(f"dopri5: more than {MAX_NUM_STEPS} accepted steps in block {i}")
+            cap *= 2
+        t, dt = float(st[0]), float(st[1])
+        if st[9] == 1:
+            raise _lib.PuflowHipError(f"dopri5: non-finite error norm in block {i} at t = {t:g}")
+        if st[9] == 2:
+            raise _lib.PuflowHipError(f"dopri5: underflow in dt ({dt:g}) at t = {t:g}, block {i}")
+        n = int(st[6])
+        host = [(float(s), float(h)) for s, h in steps[:n].cpu().tolist()]
+        return states[n], dict(steps=host, steps_dev=steps[:n], states=states[:n], ctx=ctx, f_start=f_start, f_end=fbuf[int(st[4])],
+                               took=int(st[6]) + int(st[7]))
+
+    def replay(self, i: int, x: Tensor, steps_dev: Tensor, reverse: bool, ctx: Tensor, e: Tensor, R: int, tape: bool = False,
+               errsq: Optional[Tensor] = None):
+        """pf_cnf_replay (csrc/cnf_replay.hip): block i integrated on the step list steps_dev [n, 2] (device floats (s, h)) in ONE
+        launch, no controller.  x [rows, >= 3], row stride 3 or 4 floats.  tape: also write the states [n + 1, rows, 4] and the
+        derivatives at both ends - the tape `tape_vjp` sweeps.  errsq [n] (device doubles): the per-step error sums.
+        -> (state [rows,4], tape dict | None)"""
+        rows, n = x.shape[0], int(steps_dev.shape[0])
+        dev = x.device
+        if x.dtype != torch.float32 or x.stride(1) != 1 or x.stride(0) not in (3, 4):
+            x = x.float().contiguous()[:, :3].contiguous()
+        if steps_dev.dtype != torch.float32 or not steps_dev.is_contiguous():
+            steps_dev = steps_dev.float().contiguous()
+        y = torch.empty((rows, 4), dtype=torch.float32, device=dev)
+        states = torch.empty((n + 1, rows, 4), dtype=torch.float32, device=dev) if tape else None
+        ends = torch.empty((2, rows, 4), dtype=torch.float32, device=dev) if tape else None
+        ws = None
+        if errsq is not None:
+            need = self.lib.pf_cnf_replay_workspace_bytes(rows, n)
+            if need < 0:
+                raise _lib.PuflowHipError(f"pf_cnf_replay: rows = {rows}, n_steps = {n}")
+            ws = torch.empty(need // 8, dtype=torch.float64, device=dev)
+        ptr = lambda t_: t_.data_ptr() if t_ is not None else None
+        _lib.check(self.lib.pf_cnf_replay(x.data_ptr(), int(x.stride(0)), steps_dev.data_ptr(), n, 1 if reverse else 0,
+                                          ctx.data_ptr(), e.data_ptr(), self.rec[i].data_ptr(), ptr(states), y.data_ptr(),
+                                          ptr(ends[0]) if tape else None, ptr(ends[1]) if tape else None, ptr(errsq), RTOL, ATOL,
+                                          rows, R, ptr(ws), self._stream()), "pf_cnf_replay")
+        self.nfe += 1 + 6 * n
+        if not tape:
+            return y, None
+        return y, dict(schedule=True, states=states, steps_dev=steps_dev, ctx=ctx, f_start=ends[0], f_end=ends[1])
+
     def context_norm(self, c: Tensor, out: Tensor) -> None:
         """out[0] (device double) = sum (c / (atol + rtol |c|))^2: the context's share of the solver's initial-step norm."""
         _lib.check(self.lib.pf_scaled_sumsq(c.data_ptr(), None, c.data_ptr(), None, None, (ctypes.c_float * 1)(0.0), 0, 0.0,
@@ -454,60 +703,6 @@ class _BlockTapeEngine(_CnfKernels):
                                         rows, R, self.ws1k.data_ptr(), self.red.data_ptr(), self._stream()), "pf_cnf_step")
         self.nfe += 6
         return float(self.red.item())
-
-    def tape_forward(self, i: int, x: Tensor, c: Tensor, e: Tensor, R: int, reverse: bool, cap: int = 32, ctx: Optional[Tensor] = None,
-                     d0c: Optional[Tensor] = None):
-        """dopri5 on block i with the control on the DEVICE (pf_cnf_init, then batches of pf_cnf_steps_taped attempts with one read
-        of the controller per batch, as `_CnfEngine.integrate`), the step that would cover the end time cut to END there: the
-        result is the last accepted step's solution, so the forward is exactly the recorded steps.  cap: steps the tape is
-        allocated for; a tape that fills up (status 3) is allocated anew at twice the size and the integration starts again.
-        -> (state [rows,4], tape): (s, h) per accepted step on the device (`steps_dev` [n,2], the fp32 values the kernels
-        computed with) and as host floats (`steps`, one read when done), the state at the start of each step (`states` [n,rows,4]),
-        the context rows and the derivatives at both ends.
-        ctx, d0c: block i's context rows and the context's norm word where the caller has them already (the train-mode forward
-        computes both once per block for f and g)."""
-        rows = x.shape[0]
-        dev = x.device
-        T = self.T_end[i]
-        t0, t1 = (0.0, T) if not reverse else (-T, 0.0)
-        if ctx is None:
-            ctx = self.context(i, c)
-        n_tot = float(rows * 4 + c.numel() * R)                 # the context is a state of the reference's ODE: it enters the norms
-        if d0c is None:
-            d0c = torch.empty(1, dtype=torch.float64, device=dev)
-            self.context_norm(c, d0c)
-        fbuf =torch.empty((2, rows, 4), dtype=torch.float32, device=dev)
-        cap = max(1, int(cap))
-        while True:
-            states = torch.empty((cap + 1, rows, 4), dtype=torch.float32, device=dev)
-            steps = torch.empty((cap, 2), dtype=torch.float32, device=dev)
-            self._cnf_init(i, self.ctl, x, states[0], fbuf[0], ctx, e, t0, t1, n_tot, d0c, float(R), reverse, rows, R)
-            f_start = fbuf[0].clone()                           # needed for dT when reversed; fbuf ping-pongs from here on
-            attempts, batch = 0, self.first_batch
-            while True:
-                self._cnf_steps_taped(i, self.ctl, states, steps, fbuf, ctx, e, rows, R, batch)
-                attempts += batch
-                st = self.ctl.cpu()                             # the one device->host read per batch of attempts
-                if st[5] != 0:
-                    break
-                if attempts > MAX_NUM_STEPS:
-                    raise _lib.PuflowHipError(f"dopri5: more than {MAX_NUM_STEPS} step attempts in block {i}")
-                batch = self.next_batch
-            self.nfe += int(st[8])
-            if st[9] != 3:
-                break
-            if cap > MAX_NUM_STEPS:
-                raise _lib.PuflowHipError(f"dopri5: more than {MAX_NUM_STEPS} accepted steps in block {i}")
-            cap *= 2
-        t, dt = float(st[0]), float(st[1])
-        if st[9] == 1:
-            raise _lib.PuflowHipError(f"dopri5: non-finite error norm in block {i} at t = {t:g}")
-        if st[9] == 2:
-            raise _lib.PuflowHipError(f"dopri5: underflow in dt ({dt:g}) at t = {t:g}, block {i}")
-        n = int(st[6])
-        host = [(float(s), float(h)) for s, h in steps[:n].cpu().tolist()]
-        return states[n], dict(steps=host, steps_dev=steps[:n], states=states[:n], ctx=ctx, f_start=f_start, f_end=fbuf[int(st[4])],
-                               took=int(st[6]) + int(st[7]))
 
     def tape_forward_deferred(self, i: int, x: Tensor, c: Tensor, e: Tensor, R: int, reverse: bool, attempts: int, cap: int,
                               log: Tensor, sticky: Tensor, ctx: Optional[Tensor] = None, d0c: Optional[Tensor] = None):
@@ -703,12 +898,31 @@ class _DeferredPlan:
         self.learning = any((i, r) not in self.budget for i in range(net.num_blocks) for r in (False, True))
 
 
+class _SchedulePlan:
+    """What a train-mode forward on a frozen step schedule hands its nodes: the sticky table (the weight pack's status
+    stays on the device, as under the deferred controller) and, once the weights are packed, the twelve step lists made on the
+    device from the pack's end times.  No budgets, no log rows: a replay cannot fall short."""
+    learning = False                                             # `_CnfPackFn`: never read the pack's meta row
+
+    def __init__(self, net: "PointInterpFlow", dev: torch.device):
+        self.logs, self.sticky = net._train_tables(dev)
+        self.sdev = net._schedule_dev(dev)
+        self.steps: Optional[Tensor] = None
+
+    def bind(self, pack: "_DevicePack") -> None:
+        self.steps = self.sdev.lists(pack.meta[:, 0])
+
+    def list_of(self, i: int, reverse: bool) -> Tensor:
+        k = _log_row(i, reverse)
+        return self.steps[k, :self.sdev.n[k]]
+
+
 class _FlowBlockFn(torch.autograd.Function):
     """(x, c, parameters of block i) -> (x', delta logp): `PointInterpFlow.flow_block`."""
 
     @staticmethod
     def forward(fctx, x, c, e, i, R, reverse, keys, record, opts, *params):
-        if opts["controller"] == "deferred":                     # the same launch, its meta row stays on the device
+        if opts["controller"] in ("deferred", "schedule"):       # the same launch, its meta row stays on the device
             by_key = dict(zip(keys, params))
             pack = _DevicePack([[by_key[k] for k in _pack_keys(i)]], x.device, sticky=opts["sticky"][PACK_ROW], read_meta=False)
             eng = _BlockTapeEngine(None, i, x.device, pack=(pack, 0))
@@ -718,7 +932,13 @@ class _FlowBlockFn(torch.autograd.Function):
         else:                                                    # the numpy packers on a host copy: ~70 small uploads
             eng = _BlockTapeEngine({k: p.detach().cpu() for k, p in zip(keys, params)}, i, x.device)
         x32, c32, e32 = x.detach().float().contiguous(), c.detach().float().contiguous(), e.detach().float().contiguous()
-        if opts["controller"] == "deferred":
+        if opts["controller"] == "schedule":                     # one launch on a list made from the pack's end time, no read
+            g = torch.tensor(opts["grid"], dtype=torch.float64)
+            steps = schedule_step_lists((g[1:] - g[:-1])[None].to(x.device), torch.tensor([g.numel() - 2], device=x.device),
+                                        torch.tensor([reverse], device=x.device), pack.meta[:1, 0])[0]
+            y, tape = eng.replay(i, x32, steps, reverse, eng.context(i, c32), e32, R, tape=True)
+            opts["tape"] = tape
+        elif opts["controller"] == "deferred":
             k = _log_row(i, reverse)
             y, tape = eng.tape_forward_deferred(i, x32, c32, e32, R, reverse, opts["attempts"], opts["cap"], opts["logs"][k],
                                                 opts["sticky"][k])
@@ -785,6 +1005,8 @@ class _CnfPackFn(torch.autograd.Function):
                             read_meta=plan.learning))
         for j in range(nb):
             engs.append(_BlockTapeEngine(None, j, dev, pack=(pack, j), scratch=engs[0] if engs else None))
+        if isinstance(plan, _SchedulePlan):
+            plan.bind(pack)
         fctx.meta = [(p.shape, p.dtype) for p in params]
         fctx.set_materialize_grads(False)
         outs = [torch.empty(CNF_GRAD, dtype=torch.float32, device=dev) for _ in range(nb)]
@@ -847,7 +1069,10 @@ class _CnfIntegrateFn(torch.autograd.Function):
         x32 = x.detach().float().contiguous()
         plan = caps if isinstance(caps, _DeferredPlan) else None
         budget = plan.budget.get((i, reverse)) if plan is not None else None
-        if budget is not None:                                   # no look at the controller: `check_train_logs` reads it later
+        if isinstance(caps, _SchedulePlan):                      # a frozen schedule: ONE launch, nothing to look at
+            y, tape = eng.replay(i, x32, caps.list_of(i, reverse), reverse, ctx.detach(), e, R, tape=True)
+            steps_out.append(tape)
+        elif budget is not None:                                   # no look at the controller: `check_train_logs` reads it later
             k = _log_row(i, reverse)
             y, tape = eng.tape_forward_deferred(i, x32, c, e, R, reverse, budget[0], budget[1], plan.logs[k], plan.sticky[k],
                                                 ctx=ctx.detach(), d0c=d0c)
@@ -911,14 +1136,16 @@ def flow_train(net: "PointInterpFlow", xyz: Tensor, R: int, cs: List[Tensor], br
     es = [n.detach().reshape(T, 3).contiguous().float() for n in noise]
     engs: List[_BlockTapeEngine] = []
     params = [p for blk in net.flow_blocks for p in _pack_params(blk)]
-    plan = _DeferredPlan(net, dev) if getattr(net, "train_deferred", False) else None
+    scheduled = getattr(net, "step_schedule", None) is not None
+    plan = (_SchedulePlan(net, dev) if scheduled else _DeferredPlan(net, dev) if getattr(net, "train_deferred", False) else None)
     stand = _CnfPackFn.apply(engs, plan, *params)
     cflat, ctx, d0c = [], [], torch.empty(nb, dtype=torch.float64, device=dev)
     for i in range(nb):
         ci = cs[i].reshape(T, -1)
         cflat.append(ci.detach().float().contiguous())
         ctx.append(_CnfContextFn.apply(engs[i], i, ci, stand[nb + i]))
-        engs[i].context_norm(cflat[i], d0c[i:i + 1])         # the context is a state of the reference's ODE: it enters the norms
+        if not scheduled:                                    # (a replay takes no norm)
+            engs[i].context_norm(cflat[i], d0c[i:i + 1])         # the context is a state of the reference's ODE: it enters the norms
     steps: list = []
     caps = net.tape_capacity if plan is None else plan
     # ---- f + log-likelihood (oracle/cnf_ref.py::forward)
@@ -1004,6 +1231,136 @@ class PointInterpFlow(nn.Module):
         self._logs_host = None
         self._last_steps = None
         self.last_skipped_steps = 0
+        # ---- a frozen step schedule: None (the default) leaves every path on the adaptive solver
+        self._step_schedule: Optional[dict] = None
+        self._sched_dev: Optional[_ScheduleDev] = None
+        self._sched_err = None                    # (errsq [12, m] device doubles, n_tot per integration) of the last scheduled eval forward
+        self.last_record: dict = {}               # what `record_schedule` computed on the way: x, logp, the recorded step lists
+        # (file, refine) | None: the first eval forward records its input's schedule, saves it there and switches it on
+        self.record_first: Optional[tuple] = None
+
+    # -- the frozen step schedule
+    @property
+    def step_schedule(self) -> Optional[dict]:
+        """None: adaptive Dormand-Prince everywhere (the default).  A schedule (`uniform_schedule`, `record_schedule`,
+        `load_schedule`): the eval forward and the train-mode forward integrate on its step grids, one `pf_cnf_replay` launch per
+        integration, no controller.  Assigning validates (ValueError)."""
+        return self._step_schedule
+
+    @step_schedule.setter
+    def step_schedule(self, schedule) -> None:
+        self._step_schedule = None if schedule is None else validate_schedule(schedule, self.num_blocks)
+        self._sched_dev = None
+        self._sched_err = None
+        if self._engine_cache is not None:
+            self._engine_cache.sched_lists = None
+
+    def _schedule_dev(self, dev: torch.device) -> _ScheduleDev:
+        """The schedule's constants on the device, uploaded once per schedule (before any capture)."""
+        if self._step_schedule is None:
+            raise ValueError("no step schedule is set")
+        if self._sched_dev is None or self._sched_dev.device != dev:
+            self._sched_dev = _ScheduleDev(self._step_schedule, dev, self.num_blocks)
+        return self._sched_dev
+
+    def schedule_error_ratios(self) -> dict:
+        """After an eval forward on a schedule: per integration (block, reverse) the embedded error estimate's ratio of every
+        step, sqrt(errsq / n_tot) - the number the adaptive controller accepts a step on when it is <= 1 (n_tot counts the
+        context's elements too, as there).  A schedule whose ratios are far above 1 is too coarse for this input:
+        `refine_schedule`.  The one device -> host read of a scheduled forward, made here."""
+        if self._sched_err is None:
+            raise ValueError("schedule_error_ratios: no eval forward has run on the current step schedule")
+        errsq, n_tot, keys, ns = self._sched_err
+        host = errsq.cpu()
+        return {k: [math.sqrt(float(v) / n_tot[j]) for v in host[j, :ns[j]]] for j, k in enumerate(keys)}
+
+    @torch.no_grad()
+    def record_schedule(self, xyz: Tensor, upratio: int = 4, noise: Optional[List[Tensor]] = None, refine: int = 1) -> dict:
+        """The schedule of the adaptive solver's own accepted steps on the calibration input xyz [B,N,3]: the twelve integrations
+        run with the taped device controller (`tape_forward`: the last step cut to end on the end time, so the result IS the
+        recorded steps) on the eval plan's features, no gradients.  -> the schedule, every step cut into `refine` parts; with
+        refine = 1 and the same input and noise, a scheduled eval forward replays these integrations bit for bit.
+        `last_record`: x [B, N upratio, 3] and logp of this taped forward, the recorded (s, h) lists, accepted / rejected counts.
+        Does not touch `step_schedule`: assign the result to switch it on."""
+        if not xyz.is_cuda:
+            raise _lib.PuflowHipError("input must be a GPU tensor (no CPU fallback)")
+        if self.training:
+            self.invalidate_plan()                               # the eval plan packs the weights as they are NOW
+        xyz = xyz.detach().contiguous().float()
+        B, N, _ = xyz.shape
+        T = B * N
+        eng = self._engine(upratio)
+        base = eng.base
+        idx16 = base.knn(xyz)
+        cs, _, _ = base.features(xyz, idx16, want_cs=True, cs_only=True)
+        if noise is None:
+            noise = [torch.randn(B, N, 3, device=xyz.device) for _ in range(NUM_BLOCKS)]
+        es = [n.reshape(T, 3).contiguous().float() for n in noise]
+        cflat = [c.reshape(T, -1).contiguous() for c in cs]
+        ctx = [eng.context(i, cflat[i]) for i in range(NUM_BLOCKS)]
+        d0c = torch.empty(NUM_BLOCKS, dtype=torch.float64, device=xyz.device)
+        for i in range(NUM_BLOCKS):
+            eng.context_norm(cflat[i], d0c[i:i + 1])
+        lists, took, outs = [], 0, []
+        p = xyz.reshape(T, 3)
+        for i in range(NUM_BLOCKS):
+            p, tape = eng.tape_forward(i, p, cflat[i], es[i], 1, False, ctx=ctx[i], d0c=d0c[i:i + 1])
+            outs.append(p)
+            lists.append(tape["steps"]); took += tape["took"]
+        ldj = torch.stack([s_[:, 3] for s_ in outs]).view(NUM_BLOCKS, B, N).sum(dim=(0, 2))
+        z = outs[-1][:, :3].reshape(B, N, 3)
+        logp = -torch.mean(torch.sum(-0.5 * (z ** 2 + math.log(2 * math.pi)), dim=(1, 2)) - ldj)
+        u = base.interp(xyz, z.contiguous(), idx16, upratio).reshape(T * upratio, 3)
+        for i in reversed(range(NUM_BLOCKS)):
+            u, tape = eng.tape_forward(i, u, cflat[i], es[i], upratio, True, ctx=ctx[i], d0c=d0c[i:i + 1])
+            lists.append(tape["steps"]); took += tape["took"]
+        accepted = sum(len(s) for s in lists)
+        self.last_record = dict(x=u[:, :3].contiguous().view(B, N * upratio, 3), logp=logp, steps=lists, accepted=accepted,
+                                rejected=took - accepted)
+        if self.training:
+            self.invalidate_plan()
+        return refine_schedule(schedule_from_steps(lists, [eng.T_end[i] for i in range(NUM_BLOCKS)]), refine)
+
+    def _forward_eval_schedule(self, xyz: Tensor, upratio: int, noise: Optional[List[Tensor]], stages: bool):
+        """The eval forward on `step_schedule`: twelve pf_cnf_replay launches, no controllers, no hints, no host read."""
+        B, N, _ = xyz.shape
+        T = B * N
+        dev = xyz.device
+        eng = self._engine(upratio)
+        eng.nfe = eng.accepted = eng.rejected = 0
+        base = eng.base
+        sdev = self._schedule_dev(dev)
+        if getattr(eng, "sched_lists", None) is None or eng.sched_lists[0] is not sdev:
+            T_blocks = torch.tensor([eng.T_end[i] for i in range(NUM_BLOCKS)], dtype=torch.float64).to(dev)
+            eng.sched_lists = (sdev, sdev.lists(T_blocks))       # the end times are fixed in eval mode: made once per plan
+        steps = eng.sched_lists[1]
+        idx16 = base.knn(xyz)
+        cs, _, _ = base.features(xyz, idx16, want_cs=True, cs_only=True)
+        if noise is None:
+            noise = [torch.randn(B, N, 3, device=dev) for _ in range(NUM_BLOCKS)]
+        es = [n.reshape(T, 3).contiguous().float() for n in noise]
+        cflat = [c.reshape(T, -1).contiguous() for c in cs]
+        ctx = [eng.context(i, cflat[i]) for i in range(NUM_BLOCKS)]
+        errsq = torch.zeros((2 * NUM_BLOCKS, steps.shape[1]), dtype=torch.float64, device=dev)
+        n_tot, outs = [], []
+        p = xyz.reshape(T, 3)
+        for k, (i, reverse) in enumerate(sdev.keys):
+            R = upratio if reverse else 1
+            if k == NUM_BLOCKS:
+                ldj = torch.stack([s_[:, 3] for s_ in outs]).view(NUM_BLOCKS, B, N).sum(dim=(0, 2))
+                z = p[:, :3].reshape(B, N, 3)
+                logp = -torch.mean(torch.sum(-0.5 * (z ** 2 + math.log(2 * math.pi)), dim=(1, 2)) - ldj)
+                p = base.interp(xyz, z.contiguous(), idx16, upratio).reshape(T * upratio, 3)
+            n = sdev.n[k]
+            p, _ = eng.replay(i, p, steps[k, :n], reverse, ctx[i], es[i], R, errsq=errsq[k, :n])
+            outs.append(p)
+            n_tot.append(float(p.shape[0] * 4 + cflat[i].numel() * R))
+        x = p[:, :3].contiguous().view(B, N * upratio, 3)
+        self._sched_err = (errsq, n_tot, list(sdev.keys), list(sdev.n))
+        self.last_stats = dict(nfe=sum(1 + 6 * n for n in sdev.n), accepted=sum(sdev.n), rejected=0, schedule=True)
+        if stages:
+            return dict(idx16=idx16, cs=cs, z=z, ldj=ldj, logp=logp, x=x, **self.last_stats)
+        return x, logp
 
     # -- the deferred controller's tables
     def _train_tables(self, dev: torch.device):
@@ -1083,7 +1440,9 @@ class PointInterpFlow(nn.Module):
         if st is not None and any(isinstance(t, dict) for t in st):
             out = []
             for t in st:
-                if isinstance(t, dict):
+                if isinstance(t, dict) and t.get("schedule"):
+                    t = [(float(s), float(h)) for s, h in t["steps_dev"].cpu().tolist()]
+                elif isinstance(t, dict):
                     ctl = t["log"].cpu()
                     n = int(ctl[6]) if (ctl[5] != 0 and ctl[9] == 0) else 0
                     t = [(float(s), float(h)) for s, h in t["steps_dev"][:n].cpu().tolist()]
@@ -1141,6 +1500,15 @@ class PointInterpFlow(nn.Module):
     @torch.no_grad()
     def _forward_eval(self, xyz: Tensor, upratio: int, noise: Optional[List[Tensor]], stages: bool):
         xyz = xyz.detach().contiguous().float()
+        if self.record_first is not None:
+            path, refine = self.record_first
+            self.record_first = None
+            if noise is None:                                    # one draw for the recording and the forward behind it
+                noise = [torch.randn(xyz.shape[0], xyz.shape[1], 3, device=xyz.device) for _ in range(NUM_BLOCKS)]
+            self.step_schedule = self.record_schedule(xyz, upratio, noise, refine)
+            save_schedule(self.step_schedule, path)
+        if self._step_schedule is not None:
+            return self._forward_eval_schedule(xyz, upratio, noise, stages)
         B, N, _ = xyz.shape
         T = B * N
         eng = self._engine(upratio)
@@ -1223,7 +1591,8 @@ class PointInterpFlow(nn.Module):
         return x, logp
 
     def flow_block(self, i: int, x: Tensor, c: Tensor, e: Tensor, R: int = 1, reverse: bool = False, sweep: str = "fused",
-                   controller: str = "device", pack: str = "device", attempts: Optional[int] = None, cap: Optional[int] = None):
+                   controller: str = "device", pack: str = "device", attempts: Optional[int] = None, cap: Optional[int] = None,
+                   schedule=None):
         """One CNF flow block, differentiable: x [rows,3] (rows = T R, the R rows of a point adjacent), c [T,cd] context,
         e [T,3] Hutchinson vector -> (x' [rows,3], delta logp [rows]).  An autograd function over x, c and the parameters of
         `self.flow_blocks[i]` (e gets no gradient), whatever `self.training` says; the weight record is packed from the live
@@ -1235,12 +1604,17 @@ class PointInterpFlow(nn.Module):
         attempt (pf_cnf_step); "deferred" (DESIGN 9b): NO host read - `attempts` attempts are enqueued on a tape of `cap` steps
         (default: `self.tape_budget[(i, reverse)]`), the weights' pack status stays on the device too, the same tensors come back
         when the integration ends inside that budget and NaN when it does not; `self.check_train_logs()` reads what happened
-        and `self.last_block_tape` holds the tape (the step list is on the device).  sweep = "fused": the whole tape in one launch (pf_cnf_tape_vjp); "per_eval": pf_cnf_rhs_vjp per
+        and `self.last_block_tape` holds the tape (the step list is on the device); "schedule" (DESIGN 9c): no controller at all -
+        `schedule` is this integration's grid of fractions from 0.0 to 1.0, the (s, h) list is made on the device from the packed
+        end time and ONE pf_cnf_replay launch writes the tape (`last_block_tape`: `steps_dev` [n, 2], `states` [n + 1, rows, 4]);
+        no host read in the forward either.  sweep = "fused": the whole tape in one launch (pf_cnf_tape_vjp); "per_eval": pf_cnf_rhs_vjp per
         evaluation with pf_cnf_rhs / pf_lincomb between them.  "host" and "per_eval" are the in-library A/B references.
         pack = "device": the weight record is made from the live parameters on the device (pf_cnf_pack_blocks, one launch and one
         read of its meta row); "host", its A/B reference: the numpy packers on a host copy of the parameters.  The same bits.
         `sqrt_end_time` gets the CONTINUOUS formula dL/dT = sum(ybar(T) . k(T)) (reversed: -sum(xbar_in . k(T))
         at the start) x 2 sqrt_end_time - NOT the derivative of the discrete scheme, whose step sizes do not depend on T here.
+        Under controller="schedule" the step sizes DO scale with T (h_k = T (g_{k+1} - g_k)); that dependence is ignored, as the
+        adaptive controller's dependence on T is: the continuous formula stays.
         `self.last_block_steps`: the (s, h) of the accepted steps in solver time (s = -t when reversed)."""
         if not (x.is_cuda and c.is_cuda and e.is_cuda):
             raise _lib.PuflowHipError("inputs must be GPU tensors (no CPU fallback)")
@@ -1248,13 +1622,25 @@ class PointInterpFlow(nn.Module):
             raise ValueError("flow_block: x [T R,3], c [T,cd], e [T,3]")
         if not 1 <= R <= 16:
             raise ValueError("flow_block: 1 <= R <= 16 (pf_cnf_rhs_vjp keeps a point's R rows inside one 16-row MFMA tile)")
-        if sweep not in ("fused", "per_eval") or controller not in ("device", "host", "deferred") or pack not in ("device", "host"):
-            raise ValueError('flow_block: sweep is "fused" or "per_eval", controller "device", "host" or "deferred", pack "device" or "host"')
+        if sweep not in ("fused", "per_eval") or controller not in ("device", "host", "deferred", "schedule") or pack not in ("device", "host"):
+            raise ValueError('flow_block: sweep is "fused" or "per_eval", controller "device", "host", "deferred" or "schedule", '
+                             'pack "device" or "host"')
+        if (schedule is not None) != (controller == "schedule"):
+            raise ValueError('flow_block: `schedule` (a grid of fractions from 0.0 to 1.0) goes with controller="schedule"')
         pfx = f"flow_blocks.{i}."
         named = list(self.flow_blocks[i].named_parameters())
         keys = tuple(pfx + n for n, _ in named)
         steps: list = []
         opts = dict(sweep=sweep, controller=controller, pack=pack, cap=self.tape_capacity.get((int(i), bool(reverse)), 32))
+        if controller == "schedule":
+            if sweep != "fused" or pack != "device":
+                raise ValueError('flow_block: controller="schedule" goes with sweep="fused" and pack="device"')
+            key = (int(i), bool(reverse))
+            full = {k: (0.0, 1.0) for k in schedule_keys(self.num_blocks)}     # (validated as one grid of a whole schedule)
+            full[key] = schedule
+            grid = validate_schedule(full, self.num_blocks)[key]
+            logs, sticky = self._train_tables(x.device)
+            opts.update(grid=grid, logs=logs, sticky=sticky)
         if controller == "deferred":
             if sweep != "fused" or pack != "device":
                 raise ValueError('flow_block: controller="deferred" goes with sweep="fused" and pack="device"')

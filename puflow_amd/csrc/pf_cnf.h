@@ -1,6 +1,6 @@
 // What the continuous (CNF) kernels share: the layouts of the weight record, the context row and the gradient record, the
 // hardware-exp activations, the record's LDS staging, the Dormand-Prince tableau and the tile -> row mapping.  Included by
-// csrc/cnf.hip, csrc/cnf_bwd.hip and csrc/cnf_pack.hip (which WRITES the record and the context matrices on the device, bit for
+// csrc/cnf.hip, csrc/cnf_replay.hip, csrc/cnf_bwd.hip and csrc/cnf_pack.hip (which WRITES the record and the context matrices on the device, bit for
 // bit what packing.py makes on the host); packing.py carries the same names with the same values (tests/test_cnf_layout.py).
 // Device and host, everything inline.  All offsets in floats.
 #pragma once

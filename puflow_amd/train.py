@@ -37,6 +37,9 @@ def model_specific_args() -> argparse.ArgumentParser:
                    "modules/continuous/train_interp.py); eager steps only, no --graph, unless --cnf_deferred")
     p.add_argument("--cnf_deferred", action="store_true", help="continuous model: run the taped integrations without reading their "
                    "controllers, against learnt budgets, one read per step (cfg.cnf_deferred); with it --graph captures the step")
+    p.add_argument("--cnf_schedule", default=None, metavar="K|FILE", help="continuous model: integrate on a frozen step schedule, one "
+                   "launch per integration and no step-size controller (cfg.cnf_schedule) - K: K uniform steps per integration, "
+                   "FILE: a schedule written by upsample_cnf --record_schedule; with it --graph captures the step")
     p.add_argument("--learning_rate", default=1e-3, type=float)
     p.add_argument("--sched_patience", default=10, type=int)
     p.add_argument("--sched_factor", default=0.5, type=float)
@@ -81,7 +84,7 @@ def fit(module: TrainerModule, train_data: Iterable, val_data: Optional[Iterable
     rank, _ = _dist()
     graphs = {}
     use_graph = graph and next(module.parameters()).is_cuda
-    deferred = use_graph and bool(getattr(getattr(module, "network", None), "train_deferred", False))
+    deferred = use_graph and bool(getattr(module, "continuous", False))      # the device tables are read once per epoch at least
     try:
         for epoch in range(max_epochs):
             module.train()
@@ -143,7 +146,7 @@ def train(phase: str = "Train", checkpoint_path: Optional[str] = None, begin_che
     torch.manual_seed(int(getattr(cfg, "seed", 2021)))
     dev = device or (f"cuda:{int(os.environ.get('LOCAL_RANK', 0))}" if torch.cuda.is_available() else "cpu")
     module = (module or TrainerModule(cfg, loss_mix=LOSS_MIX[dataset])).to(dev)
-    if graph and getattr(module, "continuous", False) and not getattr(module.network, "train_deferred", False):
+    if graph and getattr(module, "continuous", False) and not module.capturable():
         raise RuntimeError(GRAPH_ERROR)
     hist = None
     if phase == "Train":
@@ -176,7 +179,7 @@ def main(argv=None):
     if dev.startswith("cuda"):
         torch.cuda.set_device(dev)
     cfg = default_cfg(model=a.model, learning_rate=a.learning_rate, sched_patience=a.sched_patience, sched_factor=a.sched_factor,
-                      seed=a.seed, sync_batchnorm=a.sync_batchnorm, cnf_deferred=a.cnf_deferred)
+                      seed=a.seed, sync_batchnorm=a.sync_batchnorm, cnf_deferred=a.cnf_deferred, cnf_schedule=a.cnf_schedule)
     kw = dict(batch_size=a.batch_size, num_point_patch=256, device=dev, seed=a.seed, rank=rank, world=world,
               is_augment=True, jitter_sigma=0.01, jitter_max=0.03)            # train_pu1k.py:132-141
     tkw = {**kw, "use_random_input": True} if a.random_input else kw          # the validation set: no subsample, no augmentation

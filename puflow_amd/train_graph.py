@@ -113,6 +113,22 @@ class GraphedTrainStep:
                 self._reduce()
                 self._update()
         torch.cuda.current_stream(dev).wait_stream(side)
+        self.recaptures = 0           # captures made anew because the continuous model's step schedule was replaced
+        self._capture()
+
+    def _net_schedule(self):
+        return getattr(getattr(self.module, "network", None), "step_schedule", None)
+
+    def _capture(self) -> None:
+        """Forward + backward (+ update) into the graph(s), on the capture stream, with the module as it stands."""
+        module, optimizer = self.module, self.optimizer
+        dev, side = next(module.parameters()).device, self.capture_stream
+        self._schedule = self._net_schedule()         # the continuous model's frozen step schedule this capture was made on
+        if self._schedule is not None:
+            with torch.cuda.stream(side):
+                module.network._schedule_dev(dev)     # its device constants are uploads: they happen before the capture
+        self._gtab = self._gtab_zeros = None
+        self._gtab_used = False
         torch.cuda.synchronize(dev)
         drain_collective_watchdog(dev)
         self.graph_a = torch.cuda.CUDAGraph()
@@ -216,6 +232,9 @@ class GraphedTrainStep:
     def __call__(self, batch) -> Tensor:
         if self.fused:
             self.optimizer.sync_lr()                      # a scheduler may have edited param_groups[0]["lr"] since the last call
+        if self._net_schedule() is not self._schedule:     # the step lists' lengths are part of the graph: capture anew
+            self._capture()
+            self.recaptures += 1
         self._copy_in(batch)
         self.graph_a.replay()
         if self.graph_b is not None:
@@ -242,7 +261,7 @@ class GraphedTrainStep:
         fn = getattr(self.module, "check_device_status", None)
         n = fn() if fn is not None else 0
         net = getattr(self.module, "network", None)
-        if getattr(net, "train_deferred", False) and hasattr(net, "check_train_logs"):
+        if (getattr(net, "train_deferred", False) or getattr(net, "step_schedule", None) is not None) and hasattr(net, "check_train_logs"):
             if net.check_train_logs():
                 self.stale = True
             self.skipped += net.last_skipped_steps

@@ -28,7 +28,7 @@ except Exception:                        # pragma: no cover - not installed in t
 MODELS = ("discrete", "continuous")
 GRAPH_ERROR = ("the continuous model's training step cannot be captured in a graph: its taped integrations read their "
                "step-size controllers on the host (train it eagerly, without --graph, or switch the deferred controller on: "
-               "cfg.cnf_deferred=True / --cnf_deferred)")
+               "cfg.cnf_deferred=True / --cnf_deferred, or integrate on a frozen step schedule: cfg.cnf_schedule / --cnf_schedule)")
 
 
 def default_cfg(model: str = "discrete", **kw):
@@ -42,11 +42,13 @@ def default_cfg(model: str = "discrete", **kw):
     # emd_workgroups == 1 says the device is shared with other processes (grid barriers need every workgroup resident)
     # cnf_deferred (continuous model): the taped integrations run without a look at their controllers, against learnt budgets of
     # attempts and tape steps; one read per step (cnf.PointInterpFlow.check_train_logs) - which is what lets the step be captured
+    # cnf_schedule (continuous model): None, or a frozen step schedule every integration of the training forward runs on, one
+    # launch each, no controller - an integer K (K uniform steps), a file of cnf.save_schedule, or a schedule dict
     if model not in MODELS:
         raise ValueError(f"model is one of {MODELS}, not {model!r}")
     cfg = dict(net="UpsamplingFlow", model=model, learning_rate=1e-3, sched_patience=10, sched_factor=0.5, seed=2021, sync_batchnorm=False,
                fused_optimizer=True, emd_workgroups=0, persistent_kernels=None, deterministic=False, dw_stream=False,
-               cnf_deferred=False)
+               cnf_deferred=False, cnf_schedule=None)
     cfg.update(kw)
     return SimpleNamespace(**cfg)
 
@@ -64,6 +66,7 @@ class TrainerModule(_Base):
             from .cnf import PointInterpFlow as ContinuousInterpFlow
             self.network = ContinuousInterpFlow(pc_channel=3)
             self.network.train_deferred = bool(getattr(self.cfg, "cnf_deferred", False))
+            self.network.step_schedule = self._cfg_schedule(getattr(self.cfg, "cnf_schedule", None))
         else:
             self.network = PointInterpFlow(pc_channel=3)
         self.network.sync_batchnorm = bool(getattr(self.cfg, "sync_batchnorm", False))     # an argument of its train-mode forward
@@ -254,10 +257,38 @@ class TrainerModule(_Base):
                     raise RuntimeError(f"{n} training step(s) produced a NaN loss")
         return n
 
+    @staticmethod
+    def _cfg_schedule(spec):
+        """cfg.cnf_schedule -> a schedule dict or None: an integer (or its string) K = K uniform steps, a path = a saved schedule."""
+        from . import cnf
+        if spec is None or isinstance(spec, dict):
+            return spec
+        if isinstance(spec, int) or (isinstance(spec, str) and spec.strip().isdigit()):
+            return cnf.uniform_schedule(int(spec))
+        return cnf.load_schedule(spec)
+
+    def capturable(self) -> bool:
+        """Can `graphed_train_step` capture this module's step: the continuous model only with nothing to read inside it - the
+        deferred controller, or a frozen step schedule."""
+        net = self.network
+        return not self.continuous or bool(getattr(net, "train_deferred", False)) or getattr(net, "step_schedule", None) is not None
+
+    @torch.no_grad()
+    def record_schedule(self, batch, refine: int = 1, noise=None) -> dict:
+        """Continuous model: the adaptive solver's accepted steps on this batch's sparse input as a schedule
+        (cnf.PointInterpFlow.record_schedule, with the weights as they are now), SET as the network's `step_schedule` and
+        returned - a run refreshes its schedule between steps with this; a captured step captures anew at its next call."""
+        if not self.continuous:
+            raise RuntimeError("record_schedule: the continuous model's (cfg.model='continuous')")
+        sparse, dense, _ = self._unpack(batch)
+        sched = self.network.record_schedule(sparse, upratio=int(dense.shape[1] / sparse.shape[1]), noise=noise, refine=refine)
+        self.network.step_schedule = sched
+        return sched
+
     def graphed_train_step(self, batch, optimizer: torch.optim.Optimizer, clip: float = 1e-2, warmup: int = 2):
         """`train_step` for a fixed batch shape captured in hipGraphs (puflow_amd/train_graph.py): returns
         `step(batch) -> loss` that replays forward + backward (+ clip + Adam) with one launch instead of ~3 500."""
-        if self.continuous and not getattr(self.network, "train_deferred", False):
+        if not self.capturable():
             raise RuntimeError(GRAPH_ERROR)
         if self.continuous:
             from .dist import multi_rank
@@ -276,6 +307,9 @@ class TrainerModule(_Base):
         final: the repeated step fell short too - those budgets are dropped, so the next step runs these integrations through the
         host-read loop and learns them anew; this step's loss is NaN and the optimizer skips it."""
         net = self.network
+        if self.continuous and getattr(net, "step_schedule", None) is not None and not torch.cuda.is_current_stream_capturing():
+            net.check_train_logs()                              # a replay cannot fall short; the read is for the weight pack's status
+            return 0
         if not (self.continuous and getattr(net, "train_deferred", False)) or torch.cuda.is_current_stream_capturing():
             return 0
         before = dict(net.tape_budget)

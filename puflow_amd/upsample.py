@@ -91,7 +91,8 @@ def load_xyz(path) -> np.ndarray:
 @torch.no_grad()
 def upsampling(data_paths: List[str], target_path: str, checkpoint_path: str, up_ratio: int, num_outlier: int,
                num_patch: int, num_upsampling: int = None, seed=None, state_dict=None, network_cls=PointInterpFlow,
-               cloud_batch: int = None, pass_points: int = None):
+               cloud_batch: int = None, pass_points: int = None, network_setup=None):
+    # network_setup(network): called once on the loaded eval-mode network before the first pass (upsample_cnf's schedule options)
     # The continuous model integrates all patches of a pass with ONE adaptive step sequence (the error norm is taken over the
     # whole batch, cnf.py:97-113), so a cloud's result depends on what shares its pass: it keeps the reference's one file at a
     # time unless asked otherwise.  The discrete model's patches never interact.
@@ -106,13 +107,13 @@ def upsampling(data_paths: List[str], target_path: str, checkpoint_path: str, up
     torch.set_num_threads(1)
     try:
         return _upsampling(data_paths, target_path, checkpoint_path, up_ratio, num_outlier, num_patch, num_upsampling, seed,
-                           state_dict, network_cls, cloud_batch, pass_points)
+                           state_dict, network_cls, cloud_batch, pass_points, network_setup)
     finally:
         torch.set_num_threads(host_threads)
 
 
 def _upsampling(data_paths, target_path, checkpoint_path, up_ratio, num_outlier, num_patch, num_upsampling, seed, state_dict,
-                network_cls, cloud_batch, pass_points=None):
+                network_cls, cloud_batch, pass_points=None, network_setup=None):
     if seed is not None:
         np.random.seed(seed)
         torch.random.manual_seed(seed)
@@ -132,6 +133,8 @@ def _upsampling(data_paths, target_path, checkpoint_path, up_ratio, num_outlier,
     network.load_state_dict(state_dict if state_dict is not None else torch.load(checkpoint_path, map_location="cpu"))
     network.set_to_initialized_state()
     network = network.to(device).eval()
+    if network_setup is not None:
+        network_setup(network)
     patch_helper = PatchHelper(num_patch, patch_expand_ratio=4)
     # The reference takes one file at a time (upsample.py:42-57).  Here up to `cloud_batch` consecutive files go through the
     # pipeline together, whatever their point counts: the FPS merge, which is sequential in its 4N output points and 95 % of a
@@ -183,7 +186,8 @@ def _upsampling(data_paths, target_path, checkpoint_path, up_ratio, num_outlier,
             w.result()                                             # re-raises a failed write
 
 
-def main(argv=None, network_cls=PointInterpFlow):
+def main(argv=None, network_cls=PointInterpFlow, add_arguments=None, network_setup=None):
+    """add_arguments(parser), network_setup(network, args): a model's own options (upsample_cnf)."""
     parser = ArgumentParser()
     parser.add_argument("--source", type=str, help="Path of input directory")
     parser.add_argument("--target", type=str, help="Path of output directory")
@@ -198,6 +202,8 @@ def main(argv=None, network_cls=PointInterpFlow):
     parser.add_argument("--pass_points", type=int, default=None,
                         help="(not in the reference) a pass is also closed before its input points would exceed this "
                              "(default: no limit); a larger file is a pass of its own")
+    if add_arguments is not None:
+        add_arguments(parser)
     args = parser.parse_args(argv)
     os.makedirs(args.target, exist_ok=True)            # exist_ok: several ranks may race to create it
     data_paths = []
@@ -205,7 +211,8 @@ def main(argv=None, network_cls=PointInterpFlow):
         data_paths.extend([os.path.join(root, f) for f in files if ".xyz" in f])
     upsampling(data_paths, args.target, args.checkpoint, up_ratio=args.up_ratio, num_outlier=24, num_patch=args.num_patch,
                num_upsampling=args.num_out, seed=args.seed, network_cls=network_cls, cloud_batch=args.cloud_batch,
-               pass_points=args.pass_points)
+               pass_points=args.pass_points,
+               network_setup=(lambda net: network_setup(net, args)) if network_setup is not None else None)
 
 
 if __name__ == "__main__":
