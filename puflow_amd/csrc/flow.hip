@@ -12,6 +12,8 @@
 // 64 -> 64 -> (1|2): split-fp16 products with a natural-scale low half on the fp16 MFMA (pf_mfma.h "f16n", fp32-class
 // accuracy; W2 / W4 arrive scaled by a power of two each, their biases pre-multiplied, the kernel multiplies by the
 // inverses), 16 rows per column tile, 30 MFMAs per tile and block.
+// exp(+-s) of the injector is pf_mfma.h pf_exp: v_exp_f32 of s log2(e), in f and g alike ((-s) log2e rounds to -(s log2e), so g
+// still inverts f to 2 ulp per block); the log-det sum takes s itself.
 //
 // The chain of 6 blocks is latency-bound, not throughput-bound (per tile: 6 x [gather cp/st -> 64 VALU ->
 // 24 MFMA -> split -> 6 MFMA -> exp/affine]), so the kernel is built for occupancy and short latencies:
@@ -177,14 +179,14 @@ __global__ __launch_bounds__(NW * 64) void flow_kernel(FlowArgs a) {
                 coupling_net<TD>(rec, lane, q, c, h1, o);
                 if (TD == 1) { v[1] -= o[0]; v[2] -= o[1]; } else { v[2] -= o[0]; }
                 const float y0 = v[2], y1 = v[1], y2 = v[0];                   // reverse channels
-                v[0] = (y0 - t[0]) * expf(-s[0]);
-                v[1] = (y1 - t[1]) * expf(-s[1]);
-                v[2] = (y2 - t[2]) * expf(-s[2]);
+                v[0] = (y0 - t[0]) * pf_exp(-s[0]);
+                v[1] = (y1 - t[1]) * pf_exp(-s[1]);
+                v[2] = (y2 - t[2]) * pf_exp(-s[2]);
                 ld -= (s[0] + s[1]) + s[2];
             } else {
-                const float y0 = fmaf(v[0], expf(s[0]), t[0]);
-                const float y1 = fmaf(v[1], expf(s[1]), t[1]);
-                const float y2 = fmaf(v[2], expf(s[2]), t[2]);
+                const float y0 = fmaf(v[0], pf_exp(s[0]), t[0]);
+                const float y1 = fmaf(v[1], pf_exp(s[1]), t[1]);
+                const float y2 = fmaf(v[2], pf_exp(s[2]), t[2]);
                 v[0] = y2; v[1] = y1; v[2] = y0;                               // reverse^-1 (self-inverse)
                 h1[0] = v[0]; h1[1] = v[1];
                 coupling_net<TD>(rec, lane, q, c, h1, o);

@@ -13,12 +13,16 @@
 // of the split product share the 32 k-slots (pf_mfma.h pf_edge_operand / pf_mm1, packing._etab_frag1).  Only the first R
 // rows of the last weight conv are computed (interpflow.py:180).
 // Arithmetic: split-fp16 products with a natural-scale low half (pf_mfma.h "f16n": one accumulator, no fold), fp32-class
-// accuracy; 20 table fragments + 71 fragment pairs = 233 fp16 MFMAs per tile where the unfolded f32 formulation needs 1216.  Matrices that
-// share an accumulator share a power-of-two scale (packing.INTERP_SCALES); the kernel multiplies by its inverse.
+// accuracy; 20 table fragments + 71 fragment pairs = 233 fp16 MFMAs per tile where the unfolded f32 formulation needs 1216.
+// Scale plan (packing.interp_scaled): every activation is stored times a power of two 2^a (growth block t: 2^t) and every
+// matrix times 2^(a_out - a_in), so an accumulator already holds the scaled pre-activation and the layer epilogues are
+// LeakyReLU + split with no rescale; only the logits are multiplied by 2^-A in front of the softmax (scales[5]).  Range:
+// |activation| < 65504 / 2^a, 255 for the most scaled one (packing.py states the rule); beyond it the output is inf / NaN.
+// The softmax and the edge norm use the one-instruction exp, rcp and sqrt of pf_mfma.h.
 //
 // Weight blob (float offsets in `off[]`, see puflow_amd/packing.py::INTERP_SLOTS); matrices are f16n fragment-pair images,
 // the three edge tables (slots 0, 5, 8) one-MFMA images of 256 floats per 16 rows:
-//   0 dtab [64 x e]        1 d_W3 [64 x 64]     2 d_b3 [64] f32      3 (W0a W6) [128 x 64]    4 scales [6] f32
+//   0 dtab [64 x e]        1 d_W3 [64 x 64]     2 d_b3 [64] f32      3 (W0a W6) [128 x 64]    4 scales [6] f32 (1 x 5, 2^-A)
 //   5 ectab [128 x e]      6 ec G1..G7 (16 pair fragments; layer t starts at fragment floor(t/2) * ceil(t/2))
 //   7 (W0b Gout) [128 x 128]   8 w1tab [128 x e] (bracket above)   9 w_W3 [64 x 128]  10 w_b3 [64] f32
 //   11 w_W6 [16 x 64] (rows 0..3 replicated per q group: the R <= 4 fast path)   12 w_b6 [16] f32
@@ -81,7 +85,7 @@ __global__ __launch_bounds__(NW * 64) void interp_kernel(InterpArgs a) {
     const PfW2BufD<2> wsW6(a.w + a.off[BIG ? 13 : 11], lane);
 
     const float* sc = a.w + a.off[4];
-    const float iDT = sc[0], iD3 = sc[1], iW1 = sc[2], iEC = sc[3], iW3 = sc[4], iW6 = sc[5];
+    const float iW6 = sc[5];         // 2^-A of the logits; the other five slots are 1: nothing is left to undo inside the chains
 
     // a workgroup owns `per` consecutive WAVE tiles (2 P points each), its waves take them round-robin: every CU gets the same
     // number of wave tiles (4 x 2048 points: 16 per CU = one full round + four waves, instead of two full rounds on a third
@@ -105,7 +109,7 @@ __global__ __launch_bounds__(NW * 64) void interp_kernel(InterpArgs a) {
                 xj[c] = a.xyz[(size_t)gj[p] * 3 + c];
             }
             const float v0 = xi[0] - xj[0], v1 = xi[1] - xj[1], v2 = xi[2] - xj[2];
-            const float nrm = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(v0, v0), __fmul_rn(v1, v1)), __fmul_rn(v2, v2)));
+            const float nrm = pf_sqrt(__fadd_rn(__fadd_rn(__fmul_rn(v0, v0), __fmul_rn(v1, v1)), __fmul_rn(v2, v2)));
             const f4 e0 = {xi[0], xi[1], xi[2], xj[0]}, e1 = {xj[1], xj[2], nrm, 1.f};
             e[p] = pf_edge_operand(e0, e1, q);
         }
@@ -123,7 +127,7 @@ __global__ __launch_bounds__(NW * 64) void interp_kernel(InterpArgs a) {
                 pf_mm1<false, 1>(wsET, 0, e, acc);                       // pre-activation from the raw inputs (edge table)
 #pragma unroll
                 for (int p = 0; p < P; ++p) {
-                    last[p] = pf_act_halfn(acc[p][0], iEC, 0.05f);
+                    last[p] = pf_act_halfn(acc[p][0], 0.05f);
                     fp[p][0] = pf_join_halfn(last[p], PfHalfN{});
                 }
             }
@@ -138,7 +142,7 @@ __global__ __launch_bounds__(NW * 64) void interp_kernel(InterpArgs a) {
                 pf_mmn<false, 1, CPT, CPT>(wsEC, F0, fp, acc);
 #pragma unroll
                 for (int p = 0; p < P; ++p) {
-                    const PfHalfN f = pf_act_halfn(acc[p][0], iEC, 0.05f);
+                    const PfHalfN f = pf_act_halfn(acc[p][0], 0.05f);
                     if constexpr (t % 2 == 1) fp[p][t / 2] = pf_join_halfn(last[p], f);
                     else fp[p][t / 2] = pf_join_halfn(f, PfHalfN{});
                     last[p] = f;
@@ -166,8 +170,8 @@ __global__ __launch_bounds__(NW * 64) void interp_kernel(InterpArgs a) {
             PfPairN dp[P][2];
 #pragma unroll
             for (int p = 0; p < P; ++p) {
-                dp[p][0] = pf_act_pairn(d[p][0], d[p][1], iDT, 0.01f);
-                dp[p][1] = pf_act_pairn(d[p][2], d[p][3], iDT, 0.01f);
+                dp[p][0] = pf_act_pairn(d[p][0], d[p][1], 0.01f);
+                dp[p][1] = pf_act_pairn(d[p][2], d[p][3], 0.01f);
             }
 #pragma unroll
             for (int cb = 0; cb < 4; ++cb)
@@ -176,8 +180,8 @@ __global__ __launch_bounds__(NW * 64) void interp_kernel(InterpArgs a) {
             pf_mmn<false, 4, 2, 2>(wsD3, 0, dp, d);
 #pragma unroll
             for (int p = 0; p < P; ++p) {
-                dp[p][0] = pf_act_pairn(d[p][0], d[p][1], iD3, 0.01f);
-                dp[p][1] = pf_act_pairn(d[p][2], d[p][3], iD3, 0.01f);
+                dp[p][0] = pf_act_pairn(d[p][0], d[p][1], 0.01f);
+                dp[p][1] = pf_act_pairn(d[p][2], d[p][3], 0.01f);
             }
             // w1 += (W0a W6) d2
             pf_mmn<false, 4, 2, 2>(wsD6, 0, dp, w1, 0, 0);
@@ -192,7 +196,7 @@ __global__ __launch_bounds__(NW * 64) void interp_kernel(InterpArgs a) {
             for (int c = 0; c < 4; ++c)
 #pragma unroll
                 for (int p = 0; p < P; ++p)
-                    w1p[p][c] = pf_act_pairn(w1[p][2 * c], w1[p][2 * c + 1], iW1, 0.01f);
+                    w1p[p][c] = pf_act_pairn(w1[p][2 * c], w1[p][2 * c + 1], 0.01f);
             f4 w2[P][4];
 #pragma unroll
             for (int ob = 0; ob < 4; ++ob)
@@ -202,8 +206,8 @@ __global__ __launch_bounds__(NW * 64) void interp_kernel(InterpArgs a) {
             PfPairN w2p[P][2];
 #pragma unroll
             for (int p = 0; p < P; ++p) {
-                w2p[p][0] = pf_act_pairn(w2[p][0], w2[p][1], iW3, 0.01f);
-                w2p[p][1] = pf_act_pairn(w2[p][2], w2[p][3], iW3, 0.01f);
+                w2p[p][0] = pf_act_pairn(w2[p][0], w2[p][1], 0.01f);
+                w2p[p][1] = pf_act_pairn(w2[p][2], w2[p][3], 0.01f);
             }
 #pragma unroll
             for (int p = 0; p < P; ++p)
@@ -232,10 +236,10 @@ __global__ __launch_bounds__(NW * 64) void interp_kernel(InterpArgs a) {
                         const float x = w3[p][ob][r];
                         float m = x;
                         m = pf_xor_max<1, 4>(m);
-                        const float ex = expf(x - m);
+                        const float ex = pf_exp(x - m);
                         float sm = ex;
                         sm = pf_xor_sum<1, 4>(sm);
-                        const float av = ex / sm;
+                        const float av = ex * pf_rcp(sm);
 #pragma unroll
                         for (int c = 0; c < 3; ++c) {
                             float s = av * zj[c];
@@ -250,10 +254,10 @@ __global__ __launch_bounds__(NW * 64) void interp_kernel(InterpArgs a) {
                     const float x = w3[p][0][r];
                     float m = x;
                     m = pf_xor_max<1, 4>(m);
-                    const float ex = expf(x - m);
+                    const float ex = pf_exp(x - m);
                     float s = ex;
                     s = pf_xor_sum<1, 4>(s);
-                    av[r] = ex / s;
+                    av[r] = ex * pf_rcp(s);
                 }
                 if (a.aw) {                                                      // weights only (uniform branch)
                     if (ok[p] && q == 0) {

@@ -36,6 +36,17 @@ __device__ __forceinline__ f4 pf_lrelu(f4 v, float slope) {
     return r;
 }
 
+// ---- hardware transcendentals of the inference kernels (flow f / g, the interpolation softmax) -------------------------------
+// One instruction each (v_exp_f32 after one multiply, v_rcp_f32, v_sqrt_f32; 1 ulp) where expf, an IEEE division and sqrtf are
+// sequences of 8 - 12 around the same instruction.  exp: x log2(e) is rounded once, an absolute error of half an ulp of the
+// product, i.e. a relative error of ln2 ulp(x log2e) / 2 + |x| 2^-25 in the result: 3e-7 at |x| = 5.3 (the largest injector
+// log-scale s of the pretrained checkpoint), 6e-8 at |x| < 1; for the softmax terms e^(x - max), whose error weighs |x| e^-|x|,
+// below 3e-8 of the sum at any spread.  Results below 2^-126 flush to zero and there is no overflow handling: s and the logits
+// are O(10).  v_sqrt_f32 / v_rcp_f32 treat subnormal inputs as zero (a neighbour closer than 1e-19, a softmax sum is >= 1).
+__device__ __forceinline__ float pf_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896341f); }
+__device__ __forceinline__ float pf_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
+__device__ __forceinline__ float pf_sqrt(float x) { return __builtin_amdgcn_sqrtf(x); }
+
 // ---- weight fragment sources -----------------------------------------------------------
 // Every lane-address of a weight fragment is (wave-uniform base) + lane*16.  hipcc otherwise
 // hoists one 64-bit VGPR address pair PER FRAGMENT out of the persistent tile loop (hundreds of

@@ -279,6 +279,102 @@ def ec4_weights(u: Dict[str, np.ndarray], nconv: int = 4, g: int = 32) -> np.nda
     return np.concatenate(parts)
 
 
+# ---- scale plan of interp_kernel's chains (csrc/interp.hip) -----------------------------------------------------------
+# The same idea as ec4_scales: an activation that only feeds layers of its own kernel is stored as 2^a x, the accumulator that
+# produces it holds 2^a v (LeakyReLU and ReLU commute with a positive factor, exactly), and every matrix between two such
+# activations is stored as W 2^(a_out - a_in) - the kernel's epilogue is activation + split, no rescale multiply.  Biases that
+# initialise an accumulator carry its 2^a.  The chain ends in the softmax logits, whose scale stays: their accumulator's
+# exponent A is free, it brings w_W6 to f16n_scale's [2^13, 2^14) and the kernel multiplies by 2^-A (the last `scales` slot;
+# the slots of the five multiplies that are gone hold 1).
+#
+# Range rule (the one edgeconv4_kernel lives by):
+#   hi   every stored activation must stay below fp16's 65504: |x| < 65504 / 2^a.  The wanted exponents below give
+#            growth block t of interp_kernel   2^t     |x| < 511 at the deepest block (t = 7)
+#            distance encoder                  2^4, 2^6                |x| < 1023
+#            weight unit w1, w2                2^7, 2^8                |x| < 511, 255
+#        against activations of at most 5.6 on unit-sphere patches with the pretrained PU1K weights and 1.9 with the synthetic
+#        ones (tests/test_scale_plan.py asserts a factor 16 of head-room; the chains see nothing but the patch's coordinates).
+#        Past the limit the fp16 conversion gives inf and the output is inf / NaN (PF_CHECK_FINITE=1 raises) - never a finite
+#        wrong number.
+#        cond_body (csrc/pointwise.hip) keeps its rescale multiplies: with the pretrained weights its activations reach 1950 in
+#        unit 5 (33 times under 65504 unscaled), so nothing there can be stored scaled up, and at exponent 0 its matrices
+#        (largest entries 0.3 .. 2.4) would put their low halves on the subnormal floor.  flow_kernel's coupling net keeps
+#        them as well: its input cp comes from another kernel at its natural scale and 2^s2 h2 with W2 at [2^13, 2^14)
+#        (tests/test_host_abi.py pins that image) overflows at |h2| > 4; unit 0's table is pinned at its scale likewise.
+#   lo   a low half has an absolute floor of 2^-25 in STORED units.  In a product W' x' with x' = 2^a_in x, W' = 2^(A - a_in) W
+#        the two floors cost 2^-25 (2^(a_in - A) |x| + 2^-a_in |W|) per term in natural units.  No exponent is negative and no
+#        matrix is scaled down (A >= a_in; `_scaled` refuses anything else), so this is at most 2^-25 (|x| + |W|), i.e. half an
+#        fp32 ulp of a product of O(1) operands: what the unscaled activations (a_in = 0) cost before this plan.  The
+#        wanted exponents rise along a chain so that most matrices are stored times 2 .. 2^7 and stay well under that.
+#   A wanted exponent is lowered where the weights ask for it (`_fit`: no stored matrix above f16n_scale's [2^13, 2^14)).
+def _f16n_exp(W: np.ndarray) -> int:
+    return int(round(np.log2(f16n_scale(W))))
+
+
+def _fit(want: int, *terms) -> int:
+    """Largest exponent <= want that keeps every matrix W of terms (a_in, W), stored as W 2^(a - a_in), inside f16n_scale's range."""
+    return int(min([want] + [a_in + _f16n_exp(W) for a_in, W in terms]))
+
+
+def _scaled(W: np.ndarray, rows, cols=0) -> np.ndarray:
+    """W[r][c] 2^(rows[r] - cols[c]) in fp32 (exact: powers of two); rows / cols: one exponent or one per row / column."""
+    e = np.broadcast_to(np.asarray(rows, np.int64).reshape(-1, 1), W.shape) - np.broadcast_to(np.asarray(cols, np.int64).reshape(1, -1), W.shape)
+    if e.min() < 0:
+        raise ValueError("scale plan: a matrix would be scaled down (range rule, packing.py)")
+    return np.ldexp(W.astype(np.float32), e.astype(np.int32)).astype(np.float32)
+
+
+def _scaled_vec(v: np.ndarray, a: int) -> np.ndarray:
+    """A bias that initialises an accumulator of exponent a."""
+    return np.ldexp(v.astype(np.float32), int(a)).astype(np.float32)
+
+
+INTERP_WANT = {"g": list(range(8)), "d1": 4, "d2": 6, "w1": 7, "w2": 8}
+
+
+def interp_exps(ip: Dict[str, np.ndarray]) -> Dict[str, object]:
+    """Exponents of interp_kernel's plan: g[t] growth block t, d1 / d2 the distance encoder's activations, w1 / w2 the weight
+    unit's, w3 its logits' accumulator (multiplied by 2^-w3 in front of the softmax)."""
+    ec = ip["ec"]
+    tab = lambda t: np.concatenate([ec["PA"][16 * t:16 * t + 16], ec["QB"][16 * t:16 * t + 16], ec["pb"][16 * t:16 * t + 16, None]], axis=1)
+    g: List[int] = []
+    for t in range(8):
+        g.append(_fit(INTERP_WANT["g"][t], (0, tab(t)), *[(g[c], ec[f"G{t}"][:, 16 * c:16 * c + 16]) for c in range(t)]))
+    ft = ip["f_tab"]
+    d1 = _fit(INTERP_WANT["d1"], (0, np.concatenate([ip["d_PA"], ip["d_QB"], ip["d_wn"][:, None], ip["d_b0"][:, None]], axis=1)))
+    d2 = _fit(INTERP_WANT["d2"], (d1, ip["d_W3"]))
+    w1 = _fit(INTERP_WANT["w1"], (0, np.concatenate([ft[:, :7], ip["f_b0"][:, None]], axis=1)), (d2, ip["f_dW"]),
+              *[(g[c], ip["f_eW"][:, 16 * c:16 * c + 16]) for c in range(8)])
+    w2 = _fit(INTERP_WANT["w2"], (w1, ip["w_W3"]))
+    w3 = w2 + _f16n_exp(ip["w_W6"])                # covers the replicated first four rows as well
+    return {"g": g, "d1": d1, "d2": d2, "w1": w1, "w2": w2, "w3": w3}
+
+
+def interp_scaled(ip: Dict[str, np.ndarray]):
+    """-> (exponents, {name: fp32 matrix / vector as the kernel's images store it}).  Tables are dense [rows, 32] (_etab_dense)."""
+    x = interp_exps(ip)
+    ec, ft, g = ip["ec"], ip["f_tab"], x["g"]
+    gr = np.repeat(g, 16)                                        # per growth channel
+    W6r = np.zeros((16, 64), np.float32)           # R <= 4 fast path: rows 0..3 replicated into every 4-row q group
+    b6r = np.zeros(16, np.float32)
+    for q in range(4):
+        W6r[4 * q:4 * q + 4] = ip["w_W6"][:4]
+        b6r[4 * q:4 * q + 4] = ip["w_b6"][:4]
+    m = {
+        "dtab": _scaled(_etab_dense(ip["d_PA"], ip["d_QB"], ip["d_wn"], ip["d_b0"]), x["d1"]),
+        "d_W3": _scaled(ip["d_W3"], x["d2"], x["d1"]), "d_b3": _scaled_vec(ip["d_b3"], x["d2"]),
+        "ectab": _scaled(_etab_dense(ec["PA"][:128], ec["QB"][:128], None, ec["pb"][:128]), gr),
+        "w1tab": _scaled(_etab_dense(ft[:, 0:3], ft[:, 3:6], None, ft[:, 6] + ip["f_b0"]), x["w1"]),   # W0b.(edge table) + b0 + W0a.b6
+        "f_dW": _scaled(ip["f_dW"], x["w1"], x["d2"]), "f_eW": _scaled(ip["f_eW"], x["w1"], gr),
+        "w_W3": _scaled(ip["w_W3"], x["w2"], x["w1"]), "w_b3": _scaled_vec(ip["w_b3"], x["w2"]),
+        "w_W6": _scaled(W6r, x["w3"], x["w2"]), "w_b6": _scaled_vec(b6r, x["w3"]),
+        "w_W6full": _scaled(ip["w_W6"], x["w3"], x["w2"]), "w_b6full": _scaled_vec(ip["w_b6"], x["w3"]),
+    }
+    for t in range(1, 8):
+        m[f"G{t}"] = _scaled(ec[f"G{t}"], g[t], gr[:16 * t])
+    return x, m
+
+
 def frag_unpack_f16x2(F: np.ndarray, out: int, inn: int) -> np.ndarray:
     """Inverse of frag_pack_f16x2 (tests): float64 hi + lo' / 2^11 of the [out, inn] matrix."""
     OB, CP = (out + 15) // 16, (inn + 31) // 32
@@ -320,7 +416,7 @@ POST_SLOTS = ["M1", "b1", "M2", "H1", "S2", "bS2", "T2", "bT2", "ST4", "bST4", "
 POST_SCALES = ["M1", "M2", "H1", "S2", "T2", "ST4", "PQ"]      # order of the 2^-sw factors in the "scales" slot
 INTERP_SLOTS = ["dtab", "d_W3", "d_b3", "d_W6", "scales", "ectab", "ec_w", "w_W0", "w_b0", "w_W3", "w_b3", "w_W6", "w_b6",
                 "w_W6full", "w_b6full"]
-INTERP_SCALES = ["dtab", "d_W3", "w1", "ec", "w_W3", "w_W6"]     # 2^-sw factors in the "scales" slot (csrc/interp.hip)
+INTERP_SCALES = ["dtab", "d_W3", "w1", "ec", "w_W3", "w_W6"]     # the "scales" slot (csrc/interp.hip): 1 where the scale plan left no multiply, 2^-A for w_W6
 FLOW_REC = 5360
 
 
@@ -529,46 +625,29 @@ def pack_plan(plan: Dict[str, object], ec_mode: str = "f16n") -> Dict[str, objec
     out["flow"] = B.add(np.concatenate([pack_flow_record(f) for f in plan["flows"]]))
     out["ld_const"] = float(sum(f["ld_const"] for f in plan["flows"]))
     ip = plan["interp"]
-    W6r = np.zeros((16, 64), np.float32)           # R <= 4 fast path: rows 0..3 replicated into every 4-row q group
-    b6r = np.zeros(16, np.float32)
-    for q in range(4):
-        W6r[4 * q:4 * q + 4] = ip["w_W6"][:4]
-        b6r[4 * q:4 * q + 4] = ip["w_b6"][:4]
-    ec = ip["ec"]
-    ft = ip["f_tab"]
-    # matrices: f16n fragment images (natural-scale low half) scaled by a power of two per GROUP of matrices that share
-    # an accumulator; biases that initialise accumulators are pre-multiplied by the group's 2^sw; "scales" = the 2^-sw
-    # factors in INTERP_SCALES order (csrc/interp.hip header lists the slots)
-    def grp(*mats, tables=0):                      # the first `tables` matrices are edge tables: one-MFMA images
-        sc = min(f16n_scale(m) for m in mats)
-        return sc, [(_etab_frag1 if i < tables else frag_pack_f16n)((m.astype(np.float64) * sc).astype(np.float32))
-                    for i, m in enumerate(mats)]
-    dtab_d = _etab_dense(ip["d_PA"], ip["d_QB"], ip["d_wn"], ip["d_b0"])
-    ectab_d = _etab_dense(ec["PA"][:128], ec["QB"][:128], None, ec["pb"][:128])
-    w1tab_d = _etab_dense(ft[:, 0:3], ft[:, 3:6], None, ft[:, 6] + ip["f_b0"])     # W0b.(edge table) + b0 + W0a.b6
-    s_dt, (i_dt,) = grp(dtab_d, tables=1)
-    s_d3, (i_d3,) = grp(ip["d_W3"])
-    s_w1, (i_w1t, i_d6, i_w0) = grp(w1tab_d, ip["f_dW"], ip["f_eW"], tables=1)
-    ecG = [ec[f"G{t}"] for t in range(1, 8)]
-    s_ec, ec_imgs = grp(ectab_d, *ecG, tables=1)
-    s_w3, (i_w3,) = grp(ip["w_W3"])
-    s_w6, (i_w6r, i_w6f) = grp(W6r, ip["w_W6"])
+    # matrices: f16n fragment images (natural-scale low half; the three edge tables one-MFMA images) at the exponents of
+    # interp_kernel's scale plan (interp_scaled); biases that initialise accumulators carry their exponent; "scales", in
+    # INTERP_SCALES order, holds what the kernel still multiplies by: 1 five times and 2^-A of the logits (csrc/interp.hip)
+    ix, im = interp_scaled(ip)
+    i_dt, i_et, i_w1t = _etab_frag1(im["dtab"]), _etab_frag1(im["ectab"]), _etab_frag1(im["w1tab"])
+    i_d3, i_d6, i_w0, i_w3 = (frag_pack_f16n(im[k]) for k in ("d_W3", "f_dW", "f_eW", "w_W3"))
+    i_ec = np.concatenate([frag_pack_f16n(im[f"G{t}"]) for t in range(1, 8)])
     io = {}
     # the LDS image of interp_kernel, back to back in its order (2 + 4 + 4 + 8 + 16 + 16 + 16 = 66 slots of 2 KiB): edge tables
     # (distance encoder, growth pre-activations, w1 bracket: 4 + 8 + 8 one-MFMA fragments of 1 KiB), d_W3, the growth chain,
     # (W0a W6), w_W3 (fragment pairs) - ONE copy
-    for k, im in (("dtab", i_dt), ("ectab", ec_imgs[0]), ("w_b0", i_w1t), ("d_W3", i_d3), ("ec_w", np.concatenate(ec_imgs[1:])),
-                  ("d_W6", i_d6), ("w_W3", i_w3)):
-        io[k] = B.add(im)
+    for k, image in (("dtab", i_dt), ("ectab", i_et), ("w_b0", i_w1t), ("d_W3", i_d3), ("ec_w", i_ec), ("d_W6", i_d6), ("w_W3", i_w3)):
+        io[k] = B.add(image)
     assert B.n - io["dtab"] == 66 * 512
     io.update({
-        "d_b3": B.add(ip["d_b3"] * s_d3),
-        "scales": B.add(_pad_vec(np.array([1 / s_dt, 1 / s_d3, 1 / s_w1, 1 / s_ec, 1 / s_w3, 1 / s_w6], np.float32), 16)),
+        "d_b3": B.add(im["d_b3"]),
+        "scales": B.add(_pad_vec(np.array([1, 1, 1, 1, 1, 2.0 ** -ix["w3"]], np.float32), 16)),
         "w_W0": B.add(i_w0),                                                        # folded: W0b.Gout
-        "w_b3": B.add(ip["w_b3"] * s_w3),
-        "w_W6": B.add(i_w6r), "w_b6": B.add(b6r * s_w6),
-        "w_W6full": B.add(i_w6f), "w_b6full": B.add(ip["w_b6"] * s_w6),
+        "w_b3": B.add(im["w_b3"]),
+        "w_W6": B.add(frag_pack_f16n(im["w_W6"])), "w_b6": B.add(im["w_b6"]),
+        "w_W6full": B.add(frag_pack_f16n(im["w_W6full"])), "w_b6full": B.add(im["w_b6full"]),
     })
+    out["exps"] = {"interp": ix}          # the scale plan's exponents (tests)
     out["interp"] = [io[k] for k in INTERP_SLOTS]
     out["blob"] = B.data()
     return out
