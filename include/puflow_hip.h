@@ -651,6 +651,15 @@ int pf_fps_ragged_layout(const int* n, int B, int group, long long* scratch_off,
  * for the others - with one points-per-thread shape per pass (chosen for the largest cloud; it changes no index). */
 int pf_fps_ragged(const float* xyz, const int* n, const int* npoint, int B, int group, float* scratch, int* idx_out,
                   void* stream);
+/* pf_fps_ragged with a fixed context (no reference counterpart; the merge of a tiled pass): ctx [sum n_ctx, 3]
+ * holds, cloud after cloud, points that are already taken (n_ctx: HOST array of B ints >= 0; ctx may be null when all are 0).
+ * Every candidate's running min-distance of cloud i starts as the smallest squared distance to its n_ctx[i] context points (the
+ * same unfused arithmetic as the update); every sample, the first included, is then the arg-max (first maximum wins ties).
+ * Context points are never output.  r2_out [B] (nullable): the min-distance cloud i's last sample had when it was taken (1e10
+ * for a single sample without a context).  A cloud with n_ctx[i] = 0 gets pf_fps_ragged's samples bit for bit, starting at its
+ * index 0, whatever the other clouds of the pass have.  Scratch, status words, group hint and launches as pf_fps_ragged. */
+int pf_fps_ragged_ctx(const float* xyz, const int* n, const int* npoint, const float* ctx, const int* n_ctx, int B, int group,
+                      float* scratch, int* idx_out, float* r2_out, void* stream);
 /* pf_knn_large per cloud: ref [sum n, 3], query [sum m, 3] (m[i] queries against cloud i) -> idx_out [sum m, K] (indices
  * inside the cloud), dist_out [sum m, K] (nullable).  K <= every n[i]; clouds beyond 16384 points stream as in pf_knn_large. */
 int pf_knn_large_ragged(const float* ref, const float* query, const int* n, const int* m, int B, int K, int* idx_out,
@@ -1087,6 +1096,20 @@ int pf_poisson_eliminate_wg(const PfPoissonPool* pools, int B, const long long* 
 int pf_poisson_rounds(const PfPoissonPool* pools, int B, int max_s, long long total, const long long* offsets, const int* nbr,
                       const int* q, unsigned* w, int* state, PfPoissonState* st, int* keep, int round0, int n_rounds,
                       int* unfinished, void* stream);
+
+/* ---- Tiled passes over large clouds (csrc/tiles.hip, puflow_amd/tiles.py; the reference has no counterpart) ------------------
+ * Boxes: the points of pts [M,3] with lo <= p <= hi on every axis, boxes [T,6] = lo xyz, hi xyz (+-inf allowed, faces belong
+ * to the box; a box with lo > hi is empty).
+ *   pf_box_count: counts [T] int32.
+ *   pf_box_fill:  row t of the CSR, member [offsets[t], offsets[t+1]) (offsets [T+1] int64 on the device, sized by the caller
+ *                 from counts): the members in ascending index order.  A row shorter than its box is filled and not overrun.
+ * One workgroup per box sweeps all M points; order comes from wave ballots and prefix counts, not from atomics. */
+int pf_box_count(const float* pts, int M, const float* boxes, int T, int* counts, void* stream);
+int pf_box_fill(const float* pts, int M, const float* boxes, int T, const long long* offsets, int* member, void* stream);
+/* Cells: leaf [M] int32 = the leaf (0 .. 2^L - 1, left to right) every point of pts [M,3] reaches in a complete k-d tree of
+ * depth L (0 <= L <= 24) given in heap order - inner node k splits axis[k] (0, 1, 2) at split[k], children 2k + 1 and 2k + 2,
+ * 2^L - 1 inner nodes; a point goes right iff p[axis] >= split.  L = 0: every point is in leaf 0, axis / split are not read. */
+int pf_kd_assign(const float* pts, int M, const int* axis, const float* split, int L, int* leaf, void* stream);
 
 #ifdef __cplusplus
 }

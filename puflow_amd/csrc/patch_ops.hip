@@ -22,24 +22,44 @@ __device__ __forceinline__ float sqd(float ax, float ay, float az, float bx, flo
 // sequential in npoint by nature: per step = one strided sweep + one workgroup arg-max.
 constexpr int FPS_T = 1024;
 
-// one cloud: p [N,3], md [N] scratch, o [npoint] (the dense and the ragged kernel differ only in where these come from)
+// one cloud: p [N,3], md [N] scratch, o [npoint] (the dense and the ragged kernel differ only in where these come from).
+// CTX (pf_fps_ragged_ctx): cx [nctx,3] are points already taken - with nctx > 0 every min-distance starts as the distance to
+// the nearest of them and EVERY sample, the first included, is the arg-max; r2 (nullable) receives the min-distance the last
+// sample had when it was taken.  CTX = false compiles to the kernel this was before the context existed.
+template <bool CTX = false>
 __device__ __forceinline__ void fps_body(const float* __restrict__ p, int N, int npoint, float* __restrict__ md,
-                                         int* __restrict__ o) {
+                                         int* __restrict__ o, const float* __restrict__ cx = nullptr, int nctx = 0,
+                                         float* __restrict__ r2 = nullptr) {
     __shared__ float sv[FPS_T / 64];
     __shared__ int si[FPS_T / 64];
     __shared__ int cur;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (int k = tid; k < N; k += FPS_T) md[k] = 1e10f;
-    if (tid == 0) { cur = 0; o[0] = 0; }
+    const bool seeded = CTX && nctx > 0;                    // uniform over the workgroup
+    if (seeded) {
+        for (int k = tid; k < N; k += FPS_T) {
+            const float x = p[k * 3 + 0], y = p[k * 3 + 1], z = p[k * 3 + 2];
+            float d = 1e10f;
+            for (int c = 0; c < nctx; ++c) d = fminf(d, sqd(x, y, z, cx[c * 3 + 0], cx[c * 3 + 1], cx[c * 3 + 2]));
+            md[k] = d;
+        }
+    } else {
+        for (int k = tid; k < N; k += FPS_T) md[k] = 1e10f;
+    }
+    if (tid == 0 && !seeded) { cur = 0; o[0] = 0; }
+    float lastd = 1e10f;                                    // thread 0: the min-distance of the sample taken last
     __syncthreads();
-    for (int j = 1; j < npoint; ++j) {
-        const int last = cur;
+    for (int j = seeded ? 0 : 1; j < npoint; ++j) {
+        const bool upd = !CTX || !seeded || j > 0;          // the first step after a context only looks for the arg-max
+        const int last = upd ? cur : 0;
         const float lx = p[last * 3 + 0], ly = p[last * 3 + 1], lz = p[last * 3 + 2];
         float best = -1.f;
         int besti = 0;
         for (int k = tid; k < N; k += FPS_T) {
-            const float d = fminf(md[k], sqd(p[k * 3 + 0], p[k * 3 + 1], p[k * 3 + 2], lx, ly, lz));
-            md[k] = d;
+            float d = md[k];
+            if (upd) {
+                d = fminf(d, sqd(p[k * 3 + 0], p[k * 3 + 1], p[k * 3 + 2], lx, ly, lz));
+                md[k] = d;
+            }
             if (d > best) { best = d; besti = k; }          // increasing k: first maximum kept
         }
         pf_xor_argmax<1, 32>(best, besti);
@@ -52,9 +72,11 @@ __device__ __forceinline__ void fps_body(const float* __restrict__ p, int N, int
                 if (sv[w] > bv || (sv[w] == bv && si[w] < bi)) { bv = sv[w]; bi = si[w]; }
             cur = bi;
             o[j] = bi;
+            if (CTX) lastd = bv;
         }
         __syncthreads();
     }
+    if (CTX && r2 && tid == 0) *r2 = lastd;
 }
 
 __global__ __launch_bounds__(FPS_T) void fps_kernel(const float* __restrict__ xyz, int N, int npoint,
@@ -177,10 +199,18 @@ __device__ __forceinline__ fps_f2 sqd2(fps_f2 ax, fps_f2 ay, fps_f2 az, float bx
 // Workgroup g of the G that share one cloud: p [N,3], ring [4][FPSC_SLOTSM], abort_w = the cloud's status word (+ 1: rounds),
 // o [npoint].  fps_coopm_kernel (dense batch) and fps_coopm_ragged_kernel (clouds of different sizes) differ only in where
 // these come from.
-template <int PPT>
+// CTX (pf_fps_ragged_ctx): cx [nctx,3] are points already taken.  With nctx > 0 a prologue lowers every min-distance to the
+// distance to the nearest of them (64 context points at a time, culled by the round update's exact bounding-box test against
+// the wave's current largest min-distance), and the rounds start with NOTHING emitted: round 0 only publishes, its chain takes
+// sample 0.  Nothing else of a round changes - the chain's first sample is the arg-max whatever lowered the min-distances
+// before, and a candidate a context point coincides with has distance 0 like one a sample coincides with.  r2 (nullable): the
+// min-distance of the last sample when it was taken (the distance bits of its key).  A cloud with nctx = 0 runs the code of
+// CTX = false, which in turn compiles to the kernel this was before the context existed.
+template <int PPT, bool CTX = false>
 __device__ __forceinline__ void fps_coopm_body(const float* __restrict__ p, int N, int npoint, int G, int g,
                                                unsigned long long* __restrict__ ring, unsigned long long* __restrict__ abort_w,
-                                               int* __restrict__ o) {
+                                               int* __restrict__ o, const float* __restrict__ cx = nullptr, int nctx = 0,
+                                               float* __restrict__ r2 = nullptr) {
     constexpr int NW = FPSC_T / 64, KW = FPSM_KW, MS = FPSM_MS, NT = FPSM_NT, PH = (PPT + 1) / 2, NC = FPSM_NC, CAP = 64 * NC;
     __shared__ unsigned long long s_ck[CAP];                            // wave 0: the round's compacted candidates
     __shared__ float s_l[2][3 * MS + 4];                                // samples of a round, [3 MS] = count, [3 MS + 1] = alive
@@ -209,18 +239,49 @@ __device__ __forceinline__ void fps_coopm_body(const float* __restrict__ p, int 
         lox = fminf(lox, __shfl_xor(lox, off)); loy = fminf(loy, __shfl_xor(loy, off)); loz = fminf(loz, __shfl_xor(loz, off));
         hix = fmaxf(hix, __shfl_xor(hix, off)); hiy = fmaxf(hiy, __shfl_xor(hiy, off)); hiz = fmaxf(hiz, __shfl_xor(hiz, off));
     }
+    const bool seeded = CTX && nctx > 0;                                // uniform over the cloud's workgroups
     if (tid == 0) {
-        if (g == 0) o[0] = 0;
-        s_l[1][0] = p[0]; s_l[1][1] = p[1]; s_l[1][2] = p[2];           // "round -1" emitted point 0
-        s_l[1][3 * MS] = 1.f; s_l[1][3 * MS + 1] = 1.f;
+        if (!seeded) {
+            if (g == 0) o[0] = 0;
+            s_l[1][0] = p[0]; s_l[1][1] = p[1]; s_l[1][2] = p[2];       // "round -1" emitted point 0
+            s_l[1][3 * MS] = 1.f; s_l[1][3 * MS + 1] = 1.f;
+            if (CTX && r2 && g == 0) *r2 = 1e10f;                       // point 0's min-distance (stands when npoint = 1)
+        } else {
+            s_l[1][3 * MS] = 0.f; s_l[1][3 * MS + 1] = 1.f;             // "round -1" emitted nothing
+        }
     }
     __syncthreads();
     float Dw = 1e10f;                                                   // >= every min-distance of this wave (its last published best)
+    if (CTX && seeded) {
+        // lane s looks at context point c0 + s; the skip is the round update's: sqd(nearest point of the box, c) >= Dw >= md
+        for (int c0 = 0; c0 < nctx; c0 += 64) {
+            const int ci = c0 + lane < nctx ? c0 + lane : nctx - 1;
+            const float ccx = cx[ci * 3 + 0], ccy = cx[ci * 3 + 1], ccz = cx[ci * 3 + 2];
+            const float bd = sqd(fminf(fmaxf(ccx, lox), hix), fminf(fmaxf(ccy, loy), hiy), fminf(fmaxf(ccz, loz), hiz), ccx, ccy, ccz);
+            unsigned long long need = __ballot(c0 + lane < nctx && bd < Dw);
+            if (need == 0ull) continue;                                 // uniform over the wave
+            while (need) {
+                const int s = __builtin_ctzll(need);
+                need &= need - 1ull;
+                auto rl = [](float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); };
+                const float lx = rl(ccx, s), ly = rl(ccy, s), lz = rl(ccz, s);
+#pragma unroll
+                for (int h = 0; h < PH; ++h) {
+                    const fps_f2 d = sqd2(px[h], py[h], pz[h], lx, ly, lz);
+                    md[h][0] = fminf(md[h][0], d[0]); md[h][1] = fminf(md[h][1], d[1]);
+                }
+            }
+            float mx = -1.f;                                            // the wave's largest min-distance bounds the next 64
+#pragma unroll
+            for (int h = 0; h < PH; ++h) mx = fmaxf(mx, fmaxf(md[h][0], md[h][1]));
+            Dw = __int_as_float(wave_max_i32(__float_as_int(mx)));
+        }
+    }
     int pv[KW];                                                         // the wave's last published keys (distance bits, index)
     unsigned pidx[KW];
 #pragma unroll
     for (int e = 0; e < KW; ++e) { pv[e] = -1; pidx[e] = 0u; }
-    int j = 1, rounds = 0;
+    int j = seeded ? 0 : 1, rounds = 0;
     for (int r = 0; j < npoint; ++r) {
         // update with the samples of the previous round - those that can reach this wave.  Lane s looks at sample s: the
         // nearest point q of the wave's box to it is at least as close as every point of the wave, in fp32 as computed by
@@ -235,7 +296,7 @@ __device__ __forceinline__ void fps_coopm_body(const float* __restrict__ p, int 
             const float cx = sp[3 * ls], cy = sp[3 * ls + 1], cz = sp[3 * ls + 2];
             const float bd = sqd(fminf(fmaxf(cx, lox), hix), fminf(fmaxf(cy, loy), hiy), fminf(fmaxf(cz, loz), hiz), cx, cy, cz);
             unsigned long long need = __ballot(lane < m && bd < Dw);
-            touched = need != 0ull;
+            touched = need != 0ull || (CTX && seeded && r == 0);       // after the context prologue no key is published yet
             while (need) {
                 const int s = __builtin_ctzll(need);
                 need &= need - 1ull;
@@ -335,6 +396,7 @@ __device__ __forceinline__ void fps_coopm_body(const float* __restrict__ p, int 
                 // pipeline's clouds: ~20 qualify), NC otherwise
                 int m = 0;
                 int kx = 0, ky = 0, kz = 0, ki = 0;
+                unsigned kd = 0u;                                           // CTX: lane m keeps sample m's min-distance bits
                 auto chain = [&](auto ncc_) {
                     constexpr int NCC = decltype(ncc_)::value;
                     unsigned long long ck[NCC];
@@ -379,6 +441,7 @@ __device__ __forceinline__ void fps_coopm_body(const float* __restrict__ p, int 
                             const bool me = lane == m;
                             kx = me ? __float_as_int(sx) : kx; ky = me ? __float_as_int(sy) : ky;
                             kz = me ? __float_as_int(sz) : kz; ki = me ? (int)idx : ki;
+                            if (CTX) kd = me ? hmax : kd;
                         }
                         ++m;
                         if (m == MS || j + m >= npoint || idx >= (unsigned)N) break;
@@ -395,6 +458,7 @@ __device__ __forceinline__ void fps_coopm_body(const float* __restrict__ p, int 
                 if (lane < m) {
                     sl[3 * lane] = __int_as_float(kx); sl[3 * lane + 1] = __int_as_float(ky); sl[3 * lane + 2] = __int_as_float(kz);
                     if (g == 0) o[j + lane] = ki;
+                    if (CTX && r2 && g == 0 && lane == m - 1 && j + m >= npoint) *r2 = __uint_as_float(kd);
                 }
                 if (lane == 0) { sl[3 * MS] = (float)m; sl[3 * MS + 1] = 1.f; }
             }
@@ -456,6 +520,37 @@ __global__ __launch_bounds__(FPS_T) void fps_ragged_kernel(const float* __restri
                                                            int* __restrict__ out) {
     const int c = blockIdx.x;
     fps_body(xyz + (size_t)t.off[c] * 3, t.n[c], t.npoint[c], scratch + t.soff[c], out + t.ooff[c]);
+    if (threadIdx.x == 0) PF_ST(status + 2 * t.cloud[c], FPSC_ST_DONE);
+}
+
+// ---- the same two launches with a fixed context per cloud (pf_fps_ragged_ctx) ---------------------------------------------
+// Instantiations of their own: the context costs the kernels above neither an argument nor a register.  Both per-cloud
+// tables of the context travel as kernel arguments next to FpsRaggedTab (2.6 KB of the 4 KB an argument block may have).
+struct FpsCtxTab {
+    int coff[PF_RAGGED_MAXB];         // first context point of the cloud in ctx
+    int nctx[PF_RAGGED_MAXB];         // its context points (0: the cloud is sampled as by pf_fps_ragged)
+};
+static_assert(sizeof(FpsRaggedTab) + sizeof(FpsCtxTab) + 64 <= 4096, "the kernel argument block");
+
+template <int PPT>
+__global__ __launch_bounds__(FPSC_T, (PPT <= 16 ? 4 : (PPT <= 24 ? 3 : 2))) void fps_coopm_ragged_ctx_kernel(
+    const float* __restrict__ xyz, const FpsRaggedTab t, const FpsCtxTab ct, int nc, const float* __restrict__ ctx,
+    float* __restrict__ scratch, unsigned long long* __restrict__ status, int* __restrict__ out, float* __restrict__ r2_out) {
+    int c = 0;
+    while (c + 1 < nc && (int)blockIdx.x >= t.wg0[c + 1]) ++c;         // uniform: nc <= 64 table entries
+    const int g = (int)blockIdx.x - t.wg0[c], G = t.wg0[c + 1] - t.wg0[c];
+    unsigned long long* ring = reinterpret_cast<unsigned long long*>(scratch + t.soff[c]);
+    fps_coopm_body<PPT, true>(xyz + (size_t)t.off[c] * 3, t.n[c], t.npoint[c], G, g, ring, status + 2 * t.cloud[c], out + t.ooff[c],
+                              ctx + (size_t)ct.coff[c] * 3, ct.nctx[c], r2_out ? r2_out + t.cloud[c] : nullptr);
+}
+
+__global__ __launch_bounds__(FPS_T) void fps_ragged_ctx_kernel(const float* __restrict__ xyz, const FpsRaggedTab t,
+                                                               const FpsCtxTab ct, const float* __restrict__ ctx,
+                                                               float* __restrict__ scratch, unsigned long long* __restrict__ status,
+                                                               int* __restrict__ out, float* __restrict__ r2_out) {
+    const int c = blockIdx.x;
+    fps_body<true>(xyz + (size_t)t.off[c] * 3, t.n[c], t.npoint[c], scratch + t.soff[c], out + t.ooff[c],
+                   ctx + (size_t)ct.coff[c] * 3, ct.nctx[c], r2_out ? r2_out + t.cloud[c] : nullptr);
     if (threadIdx.x == 0) PF_ST(status + 2 * t.cloud[c], FPSC_ST_DONE);
 }
 
@@ -813,28 +908,44 @@ extern "C" int pf_fps_ragged_layout(const int* n, int B, int group, long long* s
     return ppt;
 }
 
-extern "C" int pf_fps_ragged(const float* xyz, const int* n, const int* npoint, int B, int group, float* scratch, int* idx_out,
-                             void* stream) {
-    if (!xyz || !n || !npoint || !scratch || !idx_out) return PF_ERR_NULL;
+namespace {
+// pf_fps_ragged (n_ctx = nullptr: the kernels without a context) and pf_fps_ragged_ctx (n_ctx: the context kernels, for every
+// cloud of the pass - one with n_ctx[i] = 0 takes the other kernels' path inside them)
+int fps_ragged_run(const float* xyz, const int* n, const int* npoint, const float* ctx, const int* n_ctx, int B, int group,
+                   float* scratch, int* idx_out, float* r2_out, hipStream_t s) {
     long long total = 0, sw = 0;
     const int ppt = pf_fps_ragged_layout(n, B, group, nullptr, nullptr, &total, &sw, nullptr);
     if (ppt < 0) return ppt;
     if (((size_t)scratch & 7) != 0) return PF_ERR_SHAPE;
     for (int i = 0; i < B; ++i)
         if (npoint[i] <= 0 || npoint[i] > n[i]) return PF_ERR_SHAPE;
-    hipStream_t s = (hipStream_t)stream;
+    if (n_ctx) {
+        long long ctot = 0;
+        for (int i = 0; i < B; ++i) {
+            if (n_ctx[i] < 0) return PF_ERR_SHAPE;
+            ctot += n_ctx[i];
+        }
+        if (ctot * 3 > 0x7fffffffll) return PF_ERR_SHAPE;
+        if (ctot > 0 && !ctx) return PF_ERR_NULL;
+    }
     unsigned long long* status = reinterpret_cast<unsigned long long*>(scratch) + sw;
     hipLaunchKernelGGL(fps_ragged_init_kernel, dim3(256), dim3(256), 0, s, scratch, total, sw);
     // two kernel families, each in launches of up to PF_RAGGED_MAXB clouds in batch order: cooperative, then single-workgroup
     for (int fam = 0; fam < 2; ++fam) {
         FpsRaggedTab t;
+        FpsCtxTab ct;
         int nc = 0;
-        long long poff = 0, ooff = 0, soff = 0;
+        long long poff = 0, ooff = 0, soff = 0, coff = 0;
         auto launch = [&]() {
             if (!nc) return;
             if (fam == 0) {
                 const dim3 grid(t.wg0[nc]), block(FPSC_T);
-#define PF_FPS_LAUNCH(PPT) hipLaunchKernelGGL(fps_coopm_ragged_kernel<PPT>, grid, block, 0, s, xyz, t, nc, scratch, status, idx_out)
+#define PF_FPS_LAUNCH(PPT)                                                                                                        \
+    do {                                                                                                                          \
+        if (n_ctx) hipLaunchKernelGGL(fps_coopm_ragged_ctx_kernel<PPT>, grid, block, 0, s, xyz, t, ct, nc, ctx, scratch, status,  \
+                                      idx_out, r2_out);                                                                           \
+        else hipLaunchKernelGGL(fps_coopm_ragged_kernel<PPT>, grid, block, 0, s, xyz, t, nc, scratch, status, idx_out);           \
+    } while (0)
                 switch (ppt) {
                     case 1: PF_FPS_LAUNCH(1); break;
                     case 4: PF_FPS_LAUNCH(4); break;
@@ -846,6 +957,9 @@ extern "C" int pf_fps_ragged(const float* xyz, const int* n, const int* npoint, 
                     default: PF_FPS_LAUNCH(32); break;
                 }
 #undef PF_FPS_LAUNCH
+            } else if (n_ctx) {
+                hipLaunchKernelGGL(fps_ragged_ctx_kernel, dim3(nc), dim3(FPS_T), 0, s, xyz, t, ct, ctx, scratch, status, idx_out,
+                                   r2_out);
             } else {
                 hipLaunchKernelGGL(fps_ragged_kernel, dim3(nc), dim3(FPS_T), 0, s, xyz, t, scratch, status, idx_out);
             }
@@ -857,14 +971,28 @@ extern "C" int pf_fps_ragged(const float* xyz, const int* n, const int* npoint, 
                 if (nc == 0) t.wg0[0] = 0;
                 t.off[nc] = (int)poff; t.n[nc] = n[i]; t.npoint[nc] = npoint[i]; t.ooff[nc] = (int)ooff; t.cloud[nc] = i;
                 t.soff[nc] = soff;
+                ct.coff[nc] = (int)coff; ct.nctx[nc] = n_ctx ? n_ctx[i] : 0;
                 t.wg0[nc + 1] = t.wg0[nc] + (fam == 0 ? (n[i] + FPSC_T * ppt - 1) / (FPSC_T * ppt) : 1);
                 if (++nc == PF_RAGGED_MAXB) launch();
             }
-            poff += n[i]; ooff += npoint[i]; soff += fps_ragged_row(n[i]);
+            poff += n[i]; ooff += npoint[i]; soff += fps_ragged_row(n[i]); coff += n_ctx ? n_ctx[i] : 0;
         }
         launch();
     }
     return pf_last_launch_status();
+}
+}  // namespace
+
+extern "C" int pf_fps_ragged(const float* xyz, const int* n, const int* npoint, int B, int group, float* scratch, int* idx_out,
+                             void* stream) {
+    if (!xyz || !n || !npoint || !scratch || !idx_out) return PF_ERR_NULL;
+    return fps_ragged_run(xyz, n, npoint, nullptr, nullptr, B, group, scratch, idx_out, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int pf_fps_ragged_ctx(const float* xyz, const int* n, const int* npoint, const float* ctx, const int* n_ctx, int B,
+                                 int group, float* scratch, int* idx_out, float* r2_out, void* stream) {
+    if (!xyz || !n || !npoint || !n_ctx || !scratch || !idx_out) return PF_ERR_NULL;
+    return fps_ragged_run(xyz, n, npoint, ctx, n_ctx, B, group, scratch, idx_out, r2_out, (hipStream_t)stream);
 }
 
 extern "C" int pf_knn_large_ragged(const float* ref, const float* query, const int* n, const int* m, int B, int K, int* idx_out,

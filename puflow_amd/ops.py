@@ -274,34 +274,127 @@ def fps_ragged_layout(lengths, group: int = 0):
             "status_words": [word.value + i * stride.value for i in range(B)]}
 
 
-def furthest_point_sample_ragged(xyz: torch.Tensor, lengths, npoints, group: int = 0) -> torch.Tensor:
+def furthest_point_sample_ragged(xyz: torch.Tensor, lengths, npoints, group: int = 0, context=None, context_lengths=None,
+                                 return_radius: bool = False, radius_limit=None):
     """furthest_point_sample per cloud of a packed tensor: xyz [sum, 3], npoints[i] samples of cloud i -> int32 [sum npoints],
-    indices inside each cloud (every cloud starts at its index 0).  `group`: the layout hint of furthest_point_sample."""
+    indices inside each cloud (every cloud starts at its index 0).  `group`: the layout hint of furthest_point_sample.
+    context [sum context_lengths, 3] (pf_fps_ragged_ctx; no reference counterpart): points that are already taken, cloud after
+    cloud - cloud i's min-distances start at the distance to its context and every sample, the first included, is the
+    arg-max; a cloud with context_lengths[i] = 0 gets the samples it gets without the argument.  return_radius: also return
+    float32 [B], the min-distance (squared) every cloud's last sample had when it was taken.  radius_limit: raise when a
+    cloud's radius exceeds it - checked on the device and read back with the status words, in the same host read."""
     lib = _lib.load()
     xyz = _packed(xyz, "furthest_point_sample_ragged")
     lengths = _lengths(lengths, xyz.shape[0], "furthest_point_sample_ragged")
     npoints = [int(v) for v in npoints]
     if len(npoints) != len(lengths):
         raise _lib.PuflowHipError("furthest_point_sample_ragged: one sample count per cloud")
+    B = len(lengths)
     lay = fps_ragged_layout(lengths, group)
     idx = torch.zeros((max(sum(npoints), 0),), dtype=torch.int32, device=xyz.device)
     scratch = torch.empty((lay["total_floats"],), dtype=torch.float32, device=xyz.device)
-    _lib.check(lib.pf_fps_ragged(xyz.data_ptr(), _lib.counts(lengths), _lib.counts(npoints), len(lengths), int(group),
-                                 scratch.data_ptr(), idx.data_ptr(), _stream()), "pf_fps_ragged")
-    _check_fps_abort_ragged(scratch, lay["status_words"])
-    return idx
+    if context is None and context_lengths is None and not return_radius and radius_limit is None:
+        _lib.check(lib.pf_fps_ragged(xyz.data_ptr(), _lib.counts(lengths), _lib.counts(npoints), B, int(group),
+                                     scratch.data_ptr(), idx.data_ptr(), _stream()), "pf_fps_ragged")
+        _check_fps_abort_ragged(scratch, lay["status_words"])
+        return idx
+    cl = [0] * B if context_lengths is None else [int(v) for v in context_lengths]
+    if len(cl) != B or min(cl) < 0:
+        raise _lib.PuflowHipError("furthest_point_sample_ragged: one context length >= 0 per cloud")
+    if sum(cl) > 0:
+        context = _packed(context, "furthest_point_sample_ragged (context)") if context is not None else None
+        if context is None or context.shape[0] != sum(cl) or context.device != xyz.device:
+            raise _lib.PuflowHipError(f"furthest_point_sample_ragged: context lengths {cl} do not describe the context tensor")
+    r2 = torch.empty((B,), dtype=torch.float32, device=xyz.device)
+    _lib.check(lib.pf_fps_ragged_ctx(xyz.data_ptr(), _lib.counts(lengths), _lib.counts(npoints),
+                                     context.data_ptr() if sum(cl) > 0 else None, _lib.counts(cl), B, int(group),
+                                     scratch.data_ptr(), idx.data_ptr(), r2.data_ptr(), _stream()), "pf_fps_ragged_ctx")
+    _check_fps_abort_ragged(scratch, lay["status_words"], None if radius_limit is None else (r2, float(radius_limit)))
+    return (idx, r2) if return_radius else idx
 
 
-def _check_fps_abort_ragged(scratch: torch.Tensor, status_words) -> None:
+def _check_fps_abort_ragged(scratch: torch.Tensor, status_words, radius=None) -> None:
     """_check_fps_abort for a ragged pass: one status word per cloud (whichever kernel ran it), all read in ONE device -> host
-    read; anything but 0 means that cloud's index row is invalid."""
+    read; anything but 0 means that cloud's index row is invalid.  radius = (r2 [B], limit): the comparison r2 <= limit is made
+    on the device and travels in the same read."""
     words = scratch.view(-1)[: scratch.numel() // 2 * 2].view(torch.int64)
     pos = torch.tensor(list(status_words), dtype=torch.int64).to(scratch.device, non_blocking=True)
-    bad = (words[pos] != 0).cpu()
-    if bool(bad.any()):
-        which = [i for i, b in enumerate(bad.tolist()) if b]
+    bad = words[pos] != 0
+    if radius is not None:
+        bad = torch.cat([bad, ~(radius[0] <= radius[1])])
+    bad = bad.cpu()
+    B = len(status_words)
+    if bool(bad[:B].any()):
+        which = [i for i, b in enumerate(bad[:B].tolist()) if b]
         raise _lib.PuflowHipError(f"pf_fps_ragged: clouds {which} of the pass did not complete (the cooperative kernel's workgroups "
                                   "timed out waiting for each other or were never co-resident); the sampled indices are invalid")
+    if bool(bad[B:].any()):
+        which = [i for i, b in enumerate(bad[B:].tolist()) if b]
+        raise FpsRadiusError(which, f"pf_fps_ragged_ctx: the last sample of clouds {which} of the pass lies farther than "
+                                    f"sqrt({radius[1]:g}) from every sample and context point")
+
+
+class FpsRadiusError(_lib.PuflowHipError):
+    """furthest_point_sample_ragged(radius_limit=...): .clouds are the clouds of the pass whose radius exceeds the limit."""
+
+    def __init__(self, clouds, msg):
+        super().__init__(msg)
+        self.clouds = clouds
+
+
+def box_query(pts: torch.Tensor, boxes: torch.Tensor):
+    """pf_box_count / pf_box_fill: pts [M,3], boxes [T,6] (lo xyz, hi xyz; +-inf allowed, faces inside) -> (counts [T] int64 on
+    the device, offsets [T+1] int64 on the device, member [sum counts] int32: per box the ascending indices of its points).
+    One host read (the total) between the two passes."""
+    counts = box_count(pts, boxes)
+    host = counts.tolist()
+    offsets, member = box_fill(pts, boxes, host)
+    return counts.long(), offsets, member
+
+
+def box_count(pts: torch.Tensor, boxes: torch.Tensor) -> torch.Tensor:
+    """pf_box_count: int32 [T] on the device (the first pass of box_query; a caller with other values to read reads them along)"""
+    lib = _lib.load()
+    pts, boxes = _packed(pts, "box_count"), _f32c(boxes)
+    if boxes.dim() != 2 or boxes.shape[1] != 6 or boxes.shape[0] == 0:
+        raise _lib.PuflowHipError(f"box_count: boxes are [T,6], got {tuple(boxes.shape)}")
+    counts = torch.empty((boxes.shape[0],), dtype=torch.int32, device=pts.device)
+    _lib.check(lib.pf_box_count(pts.data_ptr(), pts.shape[0], boxes.data_ptr(), boxes.shape[0], counts.data_ptr(), _stream()),
+               "pf_box_count")
+    return counts
+
+
+def box_fill(pts: torch.Tensor, boxes: torch.Tensor, counts):
+    """pf_box_fill for the HOST counts of box_count -> (offsets int64 [T+1] on the device, member int32 [sum counts])"""
+    lib = _lib.load()
+    pts, boxes = _packed(pts, "box_fill"), _f32c(boxes)
+    counts = [int(c) for c in counts]
+    if boxes.dim() != 2 or boxes.shape[1] != 6 or boxes.shape[0] != len(counts) or min(counts) < 0:
+        raise _lib.PuflowHipError(f"box_fill: one count >= 0 per box of [T,6], got {tuple(boxes.shape)} and {len(counts)} counts")
+    off = [0]
+    for c in counts:
+        off.append(off[-1] + c)
+    offsets = torch.tensor(off, dtype=torch.int64).to(pts.device)
+    member = torch.empty((max(off[-1], 1),), dtype=torch.int32, device=pts.device)
+    _lib.check(lib.pf_box_fill(pts.data_ptr(), pts.shape[0], boxes.data_ptr(), len(counts), offsets.data_ptr(), member.data_ptr(),
+                               _stream()), "pf_box_fill")
+    return offsets, member[: off[-1]]
+
+
+def kd_assign(pts: torch.Tensor, axis: torch.Tensor, split: torch.Tensor, depth: int) -> torch.Tensor:
+    """pf_kd_assign: the leaf (int32 [M]) of every point of pts [M,3] in the complete k-d tree of this depth, axis int32 /
+    split float32 [2^depth - 1] in heap order; a point goes right iff p[axis] >= split."""
+    lib = _lib.load()
+    pts = _packed(pts, "kd_assign")
+    depth = int(depth)
+    axis = axis.to(device=pts.device, dtype=torch.int32).contiguous()
+    split = split.to(device=pts.device, dtype=torch.float32).contiguous()
+    if axis.numel() != (1 << depth) - 1 or split.numel() != axis.numel():
+        raise _lib.PuflowHipError(f"kd_assign: a tree of depth {depth} has {(1 << depth) - 1} inner nodes")
+    leaf = torch.empty((pts.shape[0],), dtype=torch.int32, device=pts.device)
+    _lib.check(lib.pf_kd_assign(pts.data_ptr(), pts.shape[0], axis.data_ptr() if depth else None,
+                                split.data_ptr() if depth else None, depth, leaf.data_ptr(), _stream()), "pf_kd_assign")
+    return leaf
 
 
 def knn_ragged(ref: torch.Tensor, ref_lengths, query: torch.Tensor, query_lengths, k: int):

@@ -149,17 +149,37 @@ class PatchHelper(object):
         for i, n in enumerate(lengths):
             if n < k:       # the dense path fails in its kNN (K > N): the same exception, before anything is launched
                 raise ops._lib.PuflowHipError(f"{names[i] if names else 'cloud %d' % i}: {n} points, fewer than one patch ({k})")
-        n_patch = [int(n / k * self._patch_expand_ratio) for n in lengths]
         dev = clouds[0].device
         # every index helper depends on the sizes alone: built (and uploaded) before the first kernel of the pass is queued
-        c_first, _, _ = PatchHelper._rows(lengths, dev)
-        _, p_cloud, _ = PatchHelper._rows(n_patch, dev)
-        per_patch = k * ((upratio or 4) + 1)                                                   # sampled points + the patch itself
-        cand_lengths = [p * per_patch for p in n_patch]
+        index = self._ragged_index(lengths, upratio, dev)
+        cand_lengths, per_patch = index[3], index[4]
         m_first, _, _ = PatchHelper._rows(cand_lengths, dev)
         _, o_cloud, _ = PatchHelper._rows(npoints, dev)
         pc = torch.cat([c.reshape(-1, 3) for c in clouds], dim=0)
         pc, g_centroid, g_furthest_distance = ops.normalize_pc_ragged(pc, lengths)
+        cand = self._ragged_candidates(upsampler, pc, lengths, upratio, index, **kwargs)
+        idx = PatchHelper._ragged_merge(cand, cand_lengths, npoints, per_patch, m_first[o_cloud])
+        out = cand[idx] * g_furthest_distance.view(B, 1)[o_cloud] + g_centroid.view(B, 3)[o_cloud]
+        return list(torch.split(out, npoints))
+
+    # The two halves of a ragged pass (upsample_ragged runs them back to back; upsample_tiled, tiles.py, puts the tiles'
+    # ownership between them and merges with a context)
+    def _ragged_index(self, lengths, upratio, dev):
+        """What the candidate half needs of the sizes alone: (first row of every cloud, cloud of every patch, patches per cloud,
+        candidates per cloud, candidates per patch)."""
+        k = self._npoint_patch
+        n_patch = [int(n / k * self._patch_expand_ratio) for n in lengths]
+        c_first, _, _ = PatchHelper._rows(lengths, dev)
+        _, p_cloud, _ = PatchHelper._rows(n_patch, dev)
+        per_patch = k * ((upratio or 4) + 1)                                                   # sampled points + the patch itself
+        return c_first, p_cloud, n_patch, [p * per_patch for p in n_patch], per_patch
+
+    def _ragged_candidates(self, upsampler, pc: Tensor, lengths, upratio, index=None, **kwargs) -> Tensor:
+        """Candidates of the clouds of a packed, already normalised tensor pc [sum lengths, 3]: FPS seeds, K-nearest patches,
+        per-patch normalisation, network, concatenation with the patch -> [sum n_patch x per_patch, 3], cloud after cloud,
+        patch after patch."""
+        k = self._npoint_patch
+        c_first, p_cloud, n_patch, _, per_patch = index if index is not None else self._ragged_index(lengths, upratio, pc.device)
         seeds = ops.furthest_point_sample_ragged(pc, lengths, n_patch).long() + c_first[p_cloud]
         _, idx_patches = ops.knn_ragged(pc, lengths, pc[seeds], n_patch, k)                    # [sum n_patch, k] inside the cloud
         patches = pc[idx_patches + c_first[p_cloud].view(-1, 1)]                               # [sum n_patch, k, 3]
@@ -169,10 +189,21 @@ class PatchHelper(object):
         predict = predict * furthest_distance + centroids                                      # [sum n_patch, per_patch, 3]
         if predict.shape[1] != per_patch:
             raise ValueError(f"the upsampler returned {predict.shape[1] - k} points per patch, expected {per_patch - k}")
-        cand = predict.reshape(-1, 3).contiguous()
-        idx = ops.furthest_point_sample_ragged(cand, cand_lengths, npoints, group=per_patch).long() + m_first[o_cloud]
-        out = cand[idx] * g_furthest_distance.view(B, 1)[o_cloud] + g_centroid.view(B, 3)[o_cloud]
-        return list(torch.split(out, npoints))
+        return predict.reshape(-1, 3).contiguous()
+
+    @staticmethod
+    def _ragged_merge(cand: Tensor, cand_lengths, npoints, group: int, first: Tensor) -> Tensor:
+        """FPS merge of every cloud's candidates -> rows of cand, int64 [sum npoints] (first: the first candidate row of every
+        output row's cloud)."""
+        return ops.furthest_point_sample_ragged(cand, cand_lengths, npoints, group=group).long() + first
+
+    def upsample_tiled(self, upsampler, pc: Tensor, npoint: int, upratio=None, tile_points: int = 4096, halo: float = 1.0,
+                       tiles_per_pass: int = 64, return_stats: bool = False, **kwargs):
+        """`upsample` for ONE large cloud pc [N, 3] -> [npoint, 3] in k-d tiles merged by FPS with a fixed context (tiles.py; no
+        reference counterpart).  tile_points >= N: one tile, `upsample`'s tensor bit for bit."""
+        from . import tiles
+        return tiles.upsample_tiled(self, upsampler, pc, npoint, upratio=upratio, tile_points=tile_points, halo=halo,
+                                    tiles_per_pass=tiles_per_pass, return_stats=return_stats, **kwargs)
 
     @staticmethod
     def remove_outliers_ragged(srs, lrs, num_outliers: int):

@@ -91,7 +91,9 @@ def load_xyz(path) -> np.ndarray:
 @torch.no_grad()
 def upsampling(data_paths: List[str], target_path: str, checkpoint_path: str, up_ratio: int, num_outlier: int,
                num_patch: int, num_upsampling: int = None, seed=None, state_dict=None, network_cls=PointInterpFlow,
-               cloud_batch: int = None, pass_points: int = None, network_setup=None):
+               cloud_batch: int = None, pass_points: int = None, network_setup=None, tile_points: int = None):
+    # tile_points (not in the reference): a file with more points than this is upsampled in k-d tiles of about that many points
+    # (PatchHelper.upsample_tiled), as a pass of its own; None = off, every file takes the passes below
     # network_setup(network): called once on the loaded eval-mode network before the first pass (upsample_cnf's schedule options)
     # The continuous model integrates all patches of a pass with ONE adaptive step sequence (the error norm is taken over the
     # whole batch, cnf.py:97-113), so a cloud's result depends on what shares its pass: it keeps the reference's one file at a
@@ -107,13 +109,13 @@ def upsampling(data_paths: List[str], target_path: str, checkpoint_path: str, up
     torch.set_num_threads(1)
     try:
         return _upsampling(data_paths, target_path, checkpoint_path, up_ratio, num_outlier, num_patch, num_upsampling, seed,
-                           state_dict, network_cls, cloud_batch, pass_points, network_setup)
+                           state_dict, network_cls, cloud_batch, pass_points, network_setup, tile_points)
     finally:
         torch.set_num_threads(host_threads)
 
 
 def _upsampling(data_paths, target_path, checkpoint_path, up_ratio, num_outlier, num_patch, num_upsampling, seed, state_dict,
-                network_cls, cloud_batch, pass_points=None, network_setup=None):
+                network_cls, cloud_batch, pass_points=None, network_setup=None, tile_points=None):
     if seed is not None:
         np.random.seed(seed)
         torch.random.manual_seed(seed)
@@ -178,6 +180,15 @@ def _upsampling(data_paths, target_path, checkpoint_path, up_ratio, num_outlier,
             if path not in mine:
                 continue                                            # another rank's file: only the RNG draw is replayed
             pt_input = pt_input[:, perm].contiguous()
+            if tile_points is not None and pt_input.shape[1] > int(tile_points):
+                flush(pool)                                         # a pass of its own, in file order
+                cloud = pt_input.to(device)
+                pred = patch_helper.upsample_tiled(network, cloud[0], npoint_of(cloud.shape[1]), upratio=up_ratio,
+                                                   tile_points=int(tile_points))[None]
+                if num_outlier is not None and num_outlier > 0:
+                    pred = PatchHelper.remove_outliers(pred, cloud, num_outlier)
+                writes.append(pool.submit(save_xyz, Path(target_path) / file_name, pred[0].cpu().numpy()))
+                continue
             if pass_is_full(len(pending), sum(c.shape[1] for _, c in pending), pt_input.shape[1], cloud_batch, pass_points):
                 flush(pool)
             pending.append((file_name, pt_input))
@@ -202,6 +213,9 @@ def main(argv=None, network_cls=PointInterpFlow, add_arguments=None, network_set
     parser.add_argument("--pass_points", type=int, default=None,
                         help="(not in the reference) a pass is also closed before its input points would exceed this "
                              "(default: no limit); a larger file is a pass of its own")
+    parser.add_argument("--tile_points", type=int, default=None,
+                        help="(not in the reference) a file with more points than this is upsampled in k-d tiles of about this many "
+                             "points, merged by FPS with a fixed context, as a pass of its own (default: off)")
     if add_arguments is not None:
         add_arguments(parser)
     args = parser.parse_args(argv)
@@ -211,7 +225,7 @@ def main(argv=None, network_cls=PointInterpFlow, add_arguments=None, network_set
         data_paths.extend([os.path.join(root, f) for f in files if ".xyz" in f])
     upsampling(data_paths, args.target, args.checkpoint, up_ratio=args.up_ratio, num_outlier=24, num_patch=args.num_patch,
                num_upsampling=args.num_out, seed=args.seed, network_cls=network_cls, cloud_batch=args.cloud_batch,
-               pass_points=args.pass_points,
+               pass_points=args.pass_points, tile_points=args.tile_points,
                network_setup=(lambda net: network_setup(net, args)) if network_setup is not None else None)
 
 
