@@ -1111,6 +1111,50 @@ int pf_box_fill(const float* pts, int M, const float* boxes, int T, const long l
  * 2^L - 1 inner nodes; a point goes right iff p[axis] >= split.  L = 0: every point is in leaf 0, axis / split are not read. */
 int pf_kd_assign(const float* pts, int M, const int* axis, const float* split, int L, int* leaf, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Per-point attributes on the upsampled cloud (puflow_amd/attributes.py), csrc/attr.hip.  No reference
+ * counterpart: the reference writes bare xyz.
+ * ------------------------------------------------------------------------------------------- */
+#define PF_ATTR_LIN 0           /* segment kind: weighted sum of the neighbours' values                    */
+#define PF_ATTR_UNIT 1          /* 3 columns, a direction up to sign: sign-aligned, blended, normalised    */
+#define PF_ATTR_NEAR 2          /* the nearest neighbour's values verbatim (labels)                        */
+#define PF_ATTR_MAX_K 8
+#define PF_ATTR_MAX_C 16
+#define PF_NORMALS_MIN_K 8
+#define PF_NORMALS_MAX_K 64
+
+/* The columns a cloud carries beside xyz, moved to new points.  idx, d2 [B,M,K]: the K nearest of the cloud's N input points
+ * of every output point, as pf_knn_large(ref = input, query = output) writes them (ordered by distance); attr [B,N,C] the input
+ * points' rows; out [B,M,C].  The C columns are nseg consecutive segments, seg_kind[g] one of PF_ATTR_* over seg_cols[g]
+ * columns (HOST arrays; the columns must add up to C, a UNIT segment has 3).  Weights w_k = (1 / d2_k) / sum_j (1 / d2_j), float32,
+ * k = 0 .. K-1 in order, IEEE division.
+ *   LIN   sum_k w_k attr_k
+ *   UNIT  every neighbour's vector is negated when its dot product with neighbour 0's is negative, then blended as LIN and
+ *         divided by its length; a length that is 0 or not finite writes neighbour 0's vector unchanged
+ *   NEAR  neighbour 0's values
+ * An output point with d2_0 == 0 (it IS an input point) gets neighbour 0's whole row bit for bit, whatever the plan.
+ * 1 <= K <= PF_ATTR_MAX_K, 1 <= C <= PF_ATTR_MAX_C and a known kind, else PF_ERR_UNSUPPORTED; K <= N.  One launch. */
+int pf_attr_blend(const int* idx, const float* d2, const float* attr, int B, int N, int M, int K, int C, const int* seg_kind,
+                  const int* seg_cols, int nseg, float* out, void* stream);
+/* pf_attr_blend per cloud of a ragged pass: attr [sum n, C], idx / d2 [sum m, K] (indices inside the cloud, as
+ * pf_knn_large_ragged writes them), out [sum m, C]; n, m: HOST arrays of B ints.  Every cloud gets, bit for bit, what
+ * pf_attr_blend gives it alone.  One launch per 64 clouds. */
+int pf_attr_blend_ragged(const int* idx, const float* d2, const float* attr, const int* n, const int* m, int B, int K, int C,
+                         const int* seg_kind, const int* seg_cols, int nseg, float* out, void* stream);
+/* A normal per point from its own neighbourhood: pts [B,M,3], idx [B,M,K] from pf_knn_large(ref = query = pts) -> normal
+ * [B,M,3] unit length, variation [B,M] = l0 / (l0 + l1 + l2) in [0, 1/3] (l0 <= l1 <= l2: eigenvalues of the neighbourhood's
+ * covariance).  Centroid and centred second moments of the K neighbours in double, eigenvectors by 8 cyclic Jacobi sweeps in
+ * double, the smallest eigenvalue's vector rounded to float32 once.  Sign: with viewpoint (HOST float[3], nullable)
+ * dot(n, viewpoint - p) >= 0; without, dot(n, p - c) >= 0 for the cloud's centroid c, which this call writes to centroid [B,3]
+ * (double, on the device; required without a viewpoint, not touched with one).  A neighbourhood whose moments are all 0 gets
+ * (0, 0, 1) and variation 0.  PF_NORMALS_MIN_K <= K <= PF_NORMALS_MAX_K, else PF_ERR_UNSUPPORTED; K <= M. */
+int pf_normals_pca(const float* pts, const int* idx, int B, int M, int K, const float* viewpoint, double* centroid,
+                   float* normal, float* variation, void* stream);
+/* pf_normals_pca per cloud of a ragged pass: pts [sum m, 3], idx [sum m, K] (pf_knn_large_ragged, indices inside the cloud),
+ * m: HOST array of B ints.  Every cloud gets, bit for bit, what pf_normals_pca gives it alone. */
+int pf_normals_pca_ragged(const float* pts, const int* idx, const int* m, int B, int K, const float* viewpoint, double* centroid,
+                          float* normal, float* variation, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

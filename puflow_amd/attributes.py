@@ -1,0 +1,120 @@
+"""Per-point attributes on the upsampled cloud (the reference writes bare xyz).
+
+A scan's columns after x y z - normals, colour, intensity, labels - are carried to the new points: every output point takes
+the `k` nearest INPUT points (pf_knn_large, exact) and blends their rows by inverse squared distance, column segment by column
+segment as a plan says (`parse_plan`).  `estimate_normals` fits a plane to every output point's own neighbourhood instead
+(PCA in double on the device).  Both are HIP kernels (csrc/attr.hip); there is no CPU path.
+
+  plan = parse_plan("normal,lin3,near1", columns=10)         # a 10-column file: xyz | normal | 3 blended | 1 label
+  out_attr = transfer(pred, cloud_xyz, cloud_attr, plan)     # [M,3], [N,3], [N,7] -> [M,7]
+  normals, variation = estimate_normals(pred, 16)            # [M,3] -> [M,3], [M]
+"""
+from __future__ import annotations
+
+from typing import List, NamedTuple, Optional, Sequence
+
+import torch
+
+from . import _lib, ops
+
+MAX_COLUMNS = _lib.PF_ATTR_MAX_C
+MAX_K = _lib.PF_ATTR_MAX_K
+NORMALS_MIN_K, NORMALS_MAX_K = _lib.PF_NORMALS_MIN_K, _lib.PF_NORMALS_MAX_K
+KINDS = {"lin": _lib.PF_ATTR_LIN, "unit": _lib.PF_ATTR_UNIT, "near": _lib.PF_ATTR_NEAR}
+
+
+class Segment(NamedTuple):
+    kind: str            # "lin": weighted sum | "unit": a direction (3 columns) | "near": the nearest input point's values
+    cols: int
+
+
+def parse_plan(text: str, columns: Optional[int] = None) -> List[Segment]:
+    """"normal,lin3,near1" -> [Segment("unit", 3), Segment("lin", 3), Segment("near", 1)].  `normal` is 3 columns of kind unit
+    (at most once), lin<C> / near<C> are C >= 1 columns each, at most MAX_COLUMNS in all.  columns: the file's column count - the
+    plan must cover exactly its columns 4 ... .  Raises ValueError."""
+    import re
+    plan: List[Segment] = []
+    for tok in (t.strip() for t in str(text).split(",")):
+        m = re.fullmatch(r"(lin|near)(\d+)", tok)
+        if tok == "normal":
+            if any(s.kind == "unit" for s in plan):
+                raise ValueError(f"attribute plan {text!r}: `normal` appears twice")
+            plan.append(Segment("unit", 3))
+        elif m and int(m.group(2)) >= 1:
+            plan.append(Segment(m.group(1), int(m.group(2))))
+        else:
+            raise ValueError(f"attribute plan {text!r}: {tok!r} is not `normal`, `lin<C>` or `near<C>` with C >= 1")
+    total = sum(s.cols for s in plan)
+    if total > MAX_COLUMNS:
+        raise ValueError(f"attribute plan {text!r} covers {total} columns; at most {MAX_COLUMNS} are carried")
+    if columns is not None and total != int(columns) - 3:
+        raise ValueError(f"attribute plan {text!r} covers {total} columns, the file has {int(columns) - 3} after x y z")
+    return plan
+
+
+def has_normal(plan: Sequence[Segment]) -> bool:
+    return any(s.kind == "unit" for s in plan)
+
+
+def _segments(plan):
+    if isinstance(plan, str):
+        plan = parse_plan(plan)
+    return [(KINDS[kind], int(cols)) for kind, cols in plan]
+
+
+def _k(k: int, n: int) -> int:
+    k = int(k)
+    if not 1 <= k <= MAX_K or k > int(n):
+        raise _lib.PuflowHipError(f"attributes: k = {k} neighbours in a cloud of {int(n)} points; 1 .. {MAX_K} (and at most the "
+                                  "cloud) are supported")
+    return k
+
+
+def transfer(pred: torch.Tensor, cloud_xyz: torch.Tensor, cloud_attr: torch.Tensor, plan, k: int = 8) -> torch.Tensor:
+    """The input cloud's attribute rows on the output points: pred [M,3] (or [B,M,3]), cloud_xyz [N,3] ([B,N,3]), cloud_attr
+    [N,C] ([B,N,C]) -> [M,C] ([B,M,C]).  An output point that IS an input point gets that point's row bit for bit.  One search
+    and one blend launch for the whole batch."""
+    single = pred.dim() == 2
+    if single:
+        pred, cloud_xyz, cloud_attr = pred[None], cloud_xyz[None], cloud_attr[None]
+    idx, d2 = ops.knn_large(cloud_xyz, pred, _k(k, cloud_xyz.shape[1]))
+    out = ops.attr_blend(idx, d2, cloud_attr, _segments(plan))
+    return out[0] if single else out
+
+
+def transfer_ragged(preds, clouds_xyz, clouds_attr, plan, k: int = 8) -> List[torch.Tensor]:
+    """transfer for clouds of different sizes (lists of [M_i,3], [N_i,3], [N_i,C]) in one search and one blend launch; every
+    cloud gets what transfer gives it alone."""
+    nl, ml = [int(c.shape[0]) for c in clouds_xyz], [int(p.shape[0]) for p in preds]
+    idx, d2 = ops.knn_large_ragged(torch.cat(list(clouds_xyz), dim=0), nl, torch.cat(list(preds), dim=0), ml, _k(k, min(nl)))
+    out = ops.attr_blend_ragged(idx, d2, torch.cat(list(clouds_attr), dim=0), nl, ml, _segments(plan))
+    return list(torch.split(out, ml))
+
+
+def _normals_k(k: int, m: int) -> int:
+    k = int(k)
+    if not _lib.PF_NORMALS_MIN_K <= k <= _lib.PF_NORMALS_MAX_K or k > m:
+        raise _lib.PuflowHipError(f"estimate_normals: k = {k} neighbours on a cloud of {m} points; "
+                                  f"{_lib.PF_NORMALS_MIN_K} .. {_lib.PF_NORMALS_MAX_K} (and at most the cloud) are supported")
+    return k
+
+
+def estimate_normals(pred: torch.Tensor, k: int, viewpoint=None):
+    """A unit normal and the surface variation l0 / (l0 + l1 + l2) per point of pred [M,3] (or [B,M,3]) from the PCA of its k
+    nearest points (itself included).  Sign: towards `viewpoint` (three numbers) when given; else away from the cloud's centroid,
+    a heuristic that is right for star-shaped objects seen from their centroid and wrong in cavities and on inner walls."""
+    single = pred.dim() == 2
+    if single:
+        pred = pred[None]
+    idx, _ = ops.knn_large(pred, pred, _normals_k(k, pred.shape[1]))
+    normal, var = ops.normals_pca(pred, idx, viewpoint)
+    return (normal[0], var[0]) if single else (normal, var)
+
+
+def estimate_normals_ragged(preds, k: int, viewpoint=None):
+    """estimate_normals for clouds of different sizes in one search and one launch: ([normals_i], [variation_i])"""
+    ml = [int(p.shape[0]) for p in preds]
+    pts = torch.cat(list(preds), dim=0)
+    idx, _ = ops.knn_large_ragged(pts, ml, pts, ml, _normals_k(k, min(ml)))
+    normal, var = ops.normals_pca_ragged(pts, idx, ml, viewpoint)
+    return list(torch.split(normal, ml)), list(torch.split(var, ml))

@@ -426,3 +426,134 @@ def nearest_distance_ragged(x: torch.Tensor, x_lengths, y: torch.Tensor, y_lengt
     _lib.check(lib.pf_nn1_ragged(x.data_ptr(), y.data_ptr(), _lib.counts(xl), _lib.counts(yl), len(xl), d1.data_ptr(), None,
                                  _stream()), "pf_nn1_ragged")
     return d1
+
+
+# ----------------------------------------------------------------------------------------
+# Per-point attributes on the upsampled cloud (csrc/attr.hip; puflow_amd/attributes.py is the caller): the search is
+# pf_knn_large / pf_knn_large_ragged in its device format (int32 indices), the kernels take exactly what it writes.
+# ----------------------------------------------------------------------------------------
+def knn_large(ref: torch.Tensor, query: torch.Tensor, k: int):
+    """pf_knn_large: ref [B,N,3], query [B,M,3] -> (idx int32 [B,M,k], squared distances [B,M,k]), ordered by (distance, index)"""
+    lib = _lib.load()
+    ref, query = _f32c(ref), _f32c(query)
+    if ref.dim() != 3 or query.dim() != 3 or ref.shape[2] != 3 or query.shape[2] != 3 or ref.shape[0] != query.shape[0]:
+        raise _lib.PuflowHipError(f"knn_large: ref [B,N,3] and query [B,M,3], got {tuple(ref.shape)} and {tuple(query.shape)}")
+    B, N, _ = ref.shape
+    M = query.shape[1]
+    idx = torch.empty((B, M, int(k)), dtype=torch.int32, device=ref.device)
+    dist = torch.empty((B, M, int(k)), dtype=torch.float32, device=ref.device)
+    _lib.check(lib.pf_knn_large(ref.data_ptr(), query.data_ptr(), B, N, M, int(k), idx.data_ptr(), dist.data_ptr(), _stream()),
+               "pf_knn_large")
+    return idx, dist
+
+
+def knn_large_ragged(ref: torch.Tensor, ref_lengths, query: torch.Tensor, query_lengths, k: int):
+    """pf_knn_large_ragged in the device format: (idx int32 [sum queries, k] inside each cloud, squared distances)"""
+    lib = _lib.load()
+    ref, query = _packed(ref, "knn_large_ragged"), _packed(query, "knn_large_ragged")
+    rl = _lengths(ref_lengths, ref.shape[0], "knn_large_ragged")
+    ql = _lengths(query_lengths, query.shape[0], "knn_large_ragged")
+    if len(rl) != len(ql):
+        raise _lib.PuflowHipError("knn_large_ragged: one query count per cloud")
+    idx = torch.empty((query.shape[0], int(k)), dtype=torch.int32, device=ref.device)
+    dist = torch.empty((query.shape[0], int(k)), dtype=torch.float32, device=ref.device)
+    _lib.check(lib.pf_knn_large_ragged(ref.data_ptr(), query.data_ptr(), _lib.counts(rl), _lib.counts(ql), len(rl), int(k),
+                                       idx.data_ptr(), dist.data_ptr(), _stream()), "pf_knn_large_ragged")
+    return idx, dist
+
+
+def _segments(segments):
+    """[(kind, columns), ...] with kind a PF_ATTR_* value -> the two host arrays of the entry points and the column total"""
+    segments = [(int(kind), int(cols)) for kind, cols in segments]
+    return _lib.counts([s[0] for s in segments]), _lib.counts([s[1] for s in segments]), len(segments), sum(s[1] for s in segments)
+
+
+def _i32c(t: torch.Tensor, what: str) -> torch.Tensor:
+    if not t.is_cuda:
+        raise _lib.PuflowHipError("puflow_amd ops need GPU tensors (no CPU fallback)")
+    if t.dtype != torch.int32:
+        raise _lib.PuflowHipError(f"{what}: neighbour indices are int32 (the search's device format), got {t.dtype}")
+    return t.contiguous()
+
+
+def attr_blend(idx: torch.Tensor, d2: torch.Tensor, attr: torch.Tensor, segments) -> torch.Tensor:
+    """pf_attr_blend: idx int32 / d2 [B,M,K] from knn_large(ref = input cloud, query = output points), attr [B,N,C] the input
+    points' rows, segments [(PF_ATTR_LIN | PF_ATTR_UNIT | PF_ATTR_NEAR, columns), ...] covering the C columns -> [B,M,C]"""
+    lib = _lib.load()
+    idx, d2, attr = _i32c(idx, "attr_blend"), _f32c(d2), _f32c(attr)
+    if idx.dim() != 3 or attr.dim() != 3 or d2.shape != idx.shape or attr.shape[0] != idx.shape[0]:
+        raise _lib.PuflowHipError(f"attr_blend: idx / d2 [B,M,K] and attr [B,N,C], got {tuple(idx.shape)}, {tuple(d2.shape)} and "
+                                  f"{tuple(attr.shape)}")
+    kind, cols, nseg, total = _segments(segments)
+    B, M, K = idx.shape
+    N, C = attr.shape[1], attr.shape[2]
+    if total != C:
+        raise _lib.PuflowHipError(f"attr_blend: the plan covers {total} columns, the attributes have {C}")
+    out = torch.empty((B, M, C), dtype=torch.float32, device=attr.device)
+    _lib.check(lib.pf_attr_blend(idx.data_ptr(), d2.data_ptr(), attr.data_ptr(), B, N, M, K, C, kind, cols, nseg, out.data_ptr(),
+                                 _stream()), "pf_attr_blend")
+    return out
+
+
+def attr_blend_ragged(idx: torch.Tensor, d2: torch.Tensor, attr: torch.Tensor, lengths, out_lengths, segments) -> torch.Tensor:
+    """pf_attr_blend_ragged: attr [sum lengths, C], idx int32 / d2 [sum out_lengths, K] from knn_large_ragged -> [sum
+    out_lengths, C]; every cloud gets what attr_blend gives it alone"""
+    lib = _lib.load()
+    idx, d2, attr = _i32c(idx, "attr_blend_ragged"), _f32c(d2), _f32c(attr)
+    if idx.dim() != 2 or attr.dim() != 2 or d2.shape != idx.shape:
+        raise _lib.PuflowHipError(f"attr_blend_ragged: idx / d2 [sum m, K] and attr [sum n, C], got {tuple(idx.shape)}, "
+                                  f"{tuple(d2.shape)} and {tuple(attr.shape)}")
+    nl = _lengths(lengths, attr.shape[0], "attr_blend_ragged")
+    ml = _lengths(out_lengths, idx.shape[0], "attr_blend_ragged")
+    kind, cols, nseg, total = _segments(segments)
+    if len(nl) != len(ml) or total != attr.shape[1]:
+        raise _lib.PuflowHipError("attr_blend_ragged: one output count per cloud and a plan that covers the attribute columns")
+    out = torch.empty((idx.shape[0], attr.shape[1]), dtype=torch.float32, device=attr.device)
+    _lib.check(lib.pf_attr_blend_ragged(idx.data_ptr(), d2.data_ptr(), attr.data_ptr(), _lib.counts(nl), _lib.counts(ml), len(nl),
+                                        idx.shape[1], attr.shape[1], kind, cols, nseg, out.data_ptr(), _stream()),
+               "pf_attr_blend_ragged")
+    return out
+
+
+def _viewpoint(viewpoint):
+    if viewpoint is None:
+        return None
+    import ctypes
+    v = [float(x) for x in viewpoint]
+    if len(v) != 3:
+        raise _lib.PuflowHipError("a viewpoint is three numbers")
+    return (ctypes.c_float * 3)(*v)
+
+
+def normals_pca(pts: torch.Tensor, idx: torch.Tensor, viewpoint=None):
+    """pf_normals_pca: pts [B,M,3], idx int32 [B,M,K] from knn_large(pts, pts, K) -> (unit normals [B,M,3], surface variation
+    [B,M]).  viewpoint (three numbers): the normals look at it; None: they look away from the cloud's centroid."""
+    lib = _lib.load()
+    pts, idx = _f32c(pts), _i32c(idx, "normals_pca")
+    if pts.dim() != 3 or pts.shape[2] != 3 or idx.dim() != 3 or idx.shape[:2] != pts.shape[:2]:
+        raise _lib.PuflowHipError(f"normals_pca: pts [B,M,3] and idx [B,M,K], got {tuple(pts.shape)} and {tuple(idx.shape)}")
+    B, M, K = idx.shape
+    normal = torch.empty((B, M, 3), dtype=torch.float32, device=pts.device)
+    var = torch.empty((B, M), dtype=torch.float32, device=pts.device)
+    cen = torch.empty((B, 3), dtype=torch.float64, device=pts.device) if viewpoint is None else None
+    _lib.check(lib.pf_normals_pca(pts.data_ptr(), idx.data_ptr(), B, M, K, _viewpoint(viewpoint),
+                                  cen.data_ptr() if cen is not None else None, normal.data_ptr(), var.data_ptr(), _stream()),
+               "pf_normals_pca")
+    return normal, var
+
+
+def normals_pca_ragged(pts: torch.Tensor, idx: torch.Tensor, lengths, viewpoint=None):
+    """pf_normals_pca_ragged: pts [sum lengths, 3], idx int32 [sum lengths, K] from knn_large_ragged(pts, lengths, pts, lengths,
+    K) -> (normals [sum lengths, 3], variation [sum lengths]); every cloud gets what normals_pca gives it alone"""
+    lib = _lib.load()
+    pts, idx = _packed(pts, "normals_pca_ragged"), _i32c(idx, "normals_pca_ragged")
+    if idx.dim() != 2 or idx.shape[0] != pts.shape[0]:
+        raise _lib.PuflowHipError(f"normals_pca_ragged: idx [sum lengths, K], got {tuple(idx.shape)}")
+    ml = _lengths(lengths, pts.shape[0], "normals_pca_ragged")
+    normal = torch.empty_like(pts)
+    var = torch.empty((pts.shape[0],), dtype=torch.float32, device=pts.device)
+    cen = torch.empty((len(ml), 3), dtype=torch.float64, device=pts.device) if viewpoint is None else None
+    _lib.check(lib.pf_normals_pca_ragged(pts.data_ptr(), idx.data_ptr(), _lib.counts(ml), len(ml), idx.shape[1],
+                                         _viewpoint(viewpoint), cen.data_ptr() if cen is not None else None, normal.data_ptr(),
+                                         var.data_ptr(), _stream()), "pf_normals_pca_ragged")
+    return normal, var

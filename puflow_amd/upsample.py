@@ -91,7 +91,11 @@ def load_xyz(path) -> np.ndarray:
 @torch.no_grad()
 def upsampling(data_paths: List[str], target_path: str, checkpoint_path: str, up_ratio: int, num_outlier: int,
                num_patch: int, num_upsampling: int = None, seed=None, state_dict=None, network_cls=PointInterpFlow,
-               cloud_batch: int = None, pass_points: int = None, network_setup=None, tile_points: int = None):
+               cloud_batch: int = None, pass_points: int = None, network_setup=None, tile_points: int = None,
+               attributes: str = None, attr_k: int = 8, estimate_normals: int = None, normals_viewpoint=None):
+    # attributes / attr_k / estimate_normals / normals_viewpoint (not in the reference; puflow_amd/attributes.py): the
+    # files' columns after x y z are carried to the output points as the plan says, and / or a PCA normal is appended to every
+    # output row.  All None: bare xyz in, bare xyz out, as the reference.
     # tile_points (not in the reference): a file with more points than this is upsampled in k-d tiles of about that many points
     # (PatchHelper.upsample_tiled), as a pass of its own; None = off, every file takes the passes below
     # network_setup(network): called once on the loaded eval-mode network before the first pass (upsample_cnf's schedule options)
@@ -109,13 +113,36 @@ def upsampling(data_paths: List[str], target_path: str, checkpoint_path: str, up
     torch.set_num_threads(1)
     try:
         return _upsampling(data_paths, target_path, checkpoint_path, up_ratio, num_outlier, num_patch, num_upsampling, seed,
-                           state_dict, network_cls, cloud_batch, pass_points, network_setup, tile_points)
+                           state_dict, network_cls, cloud_batch, pass_points, network_setup, tile_points, attributes, attr_k,
+                           estimate_normals, normals_viewpoint)
     finally:
         torch.set_num_threads(host_threads)
 
 
 def _upsampling(data_paths, target_path, checkpoint_path, up_ratio, num_outlier, num_patch, num_upsampling, seed, state_dict,
-                network_cls, cloud_batch, pass_points=None, network_setup=None, tile_points=None):
+                network_cls, cloud_batch, pass_points=None, network_setup=None, tile_points=None, attributes=None, attr_k=8,
+                estimate_normals=None, normals_viewpoint=None):
+    from . import attributes as A
+    plan = None
+    try:
+        if attributes is not None:
+            plan = A.parse_plan(attributes)
+    except ValueError as e:
+        raise SystemExit(f"--attributes: {e}")
+    if estimate_normals is not None and plan is not None and A.has_normal(plan):
+        raise SystemExit("--estimate_normals: the --attributes plan already carries the files' normals (`normal`); "
+                         "drop one of the two")
+    if plan is not None and not 1 <= int(attr_k) <= A.MAX_K:
+        raise SystemExit(f"--attr_k: 1 .. {A.MAX_K} input points are blended per output point, got {attr_k}")
+    if estimate_normals is not None and not A.NORMALS_MIN_K <= int(estimate_normals) <= A.NORMALS_MAX_K:
+        raise SystemExit(f"--estimate_normals: a neighbourhood of {A.NORMALS_MIN_K} .. {A.NORMALS_MAX_K} points, got {estimate_normals}")
+    if isinstance(normals_viewpoint, str):
+        try:
+            normals_viewpoint = [float(v) for v in normals_viewpoint.split(",")]
+        except ValueError:
+            normals_viewpoint = []
+    if normals_viewpoint is not None and (estimate_normals is None or len(normals_viewpoint) != 3):
+        raise SystemExit("--normals_viewpoint takes x,y,z and goes with --estimate_normals")
     if seed is not None:
         np.random.seed(seed)
         torch.random.manual_seed(seed)
@@ -146,7 +173,27 @@ def _upsampling(data_paths, target_path, checkpoint_path, up_ratio, num_outlier,
     # order as before), and finished clouds are written by a worker thread while the GPU works on the next pass.
     from concurrent.futures import ThreadPoolExecutor
     writes = []
-    pending = []                                                   # (file name, shuffled cloud [1,N,3] on the host)
+    pending = []                                                   # (file name, shuffled cloud [1,N,3] on the host, its
+                                                                   # attribute rows [1,N,C] in the same order or None)
+
+    # The extra columns of the output rows, on the final (de-normalised, outlier-free) points: the input's attribute rows blended
+    # from every output point's attr_k nearest input points, then the estimated normals.  One search and one kernel launch each
+    # per pass; a cloud's columns are the ones it gets alone.  Without the options: the points as they are.
+    def with_columns(pred, cloud, attr):                           # a dense pass: [B,M,3], [B,N,3], [B,N,C] or None
+        cols = [pred]
+        if plan is not None:
+            cols.append(A.transfer(pred, cloud, attr, plan, attr_k))
+        if estimate_normals is not None:
+            cols.append(A.estimate_normals(pred, estimate_normals, normals_viewpoint)[0])
+        return torch.cat(cols, dim=-1) if len(cols) > 1 else pred
+
+    def with_columns_ragged(pred, clouds, attrs):                  # a ragged pass: lists of [M_i,3], [N_i,3], [N_i,C]
+        cols = [pred]
+        if plan is not None:
+            cols.append(A.transfer_ragged(pred, clouds, attrs, plan, attr_k))
+        if estimate_normals is not None:
+            cols.append(A.estimate_normals_ragged(pred, estimate_normals, normals_viewpoint)[0])
+        return [torch.cat(c, dim=-1) for c in zip(*cols)] if len(cols) > 1 else pred
 
     def npoint_of(n):
         return (n * up_ratio if num_upsampling is None else num_upsampling) + (num_outlier or 0)
@@ -154,21 +201,24 @@ def _upsampling(data_paths, target_path, checkpoint_path, up_ratio, num_outlier,
     def flush(pool):
         if not pending:
             return
-        sizes = [c.shape[1] for _, c in pending]
+        sizes = [c.shape[1] for _, c, _ in pending]
         if len(set(sizes)) == 1:
-            pt_input = torch.cat([c for _, c in pending], dim=0).to(device)
+            pt_input = torch.cat([c for _, c, _ in pending], dim=0).to(device)
             pred = patch_helper.upsample(network, pt_input, npoint=npoint_of(sizes[0]), upratio=up_ratio, jitter=False)
             if num_outlier is not None and num_outlier > 0:
                 pred = PatchHelper.remove_outliers(pred, pt_input, num_outlier)
+            pred = with_columns(pred, pt_input, torch.cat([a for _, _, a in pending], dim=0).to(device) if plan is not None else None)
             pred = list(pred.cpu().numpy())
         else:
-            clouds = list(torch.split(torch.cat([c[0] for _, c in pending], dim=0).to(device), sizes))
+            clouds = list(torch.split(torch.cat([c[0] for _, c, _ in pending], dim=0).to(device), sizes))
             pred = patch_helper.upsample_ragged(network, clouds, [npoint_of(n) for n in sizes], upratio=up_ratio,
-                                                names=[name for name, _ in pending])
+                                                names=[name for name, _, _ in pending])
             if num_outlier is not None and num_outlier > 0:
                 pred = PatchHelper.remove_outliers_ragged(pred, clouds, num_outlier)
+            pred = with_columns_ragged(pred, clouds, list(torch.split(torch.cat([a[0] for _, _, a in pending], dim=0).to(device), sizes))
+                                       if plan is not None else None)
             pred = [p.numpy() for p in torch.split(torch.cat(pred, dim=0).cpu(), [p.shape[0] for p in pred])]
-        for (file_name, _), cloud in zip(pending, pred):
+        for (file_name, _, _), cloud in zip(pending, pred):
             writes.append(pool.submit(save_xyz, Path(target_path) / file_name, cloud))
         pending.clear()
 
@@ -180,6 +230,16 @@ def _upsampling(data_paths, target_path, checkpoint_path, up_ratio, num_outlier,
             if path not in mine:
                 continue                                            # another rank's file: only the RNG draw is replayed
             pt_input = pt_input[:, perm].contiguous()
+            attr = None
+            if plan is not None:                                    # columns 4 ...: beside the cloud, in the cloud's order
+                try:
+                    A.parse_plan(attributes, columns=pt_input.shape[-1] if pt_input.dim() == 3 else 0)
+                except ValueError as e:
+                    raise SystemExit(f"{path}: --attributes: {e}")
+                pt_input, attr = pt_input[..., :3].contiguous(), pt_input[..., 3:].contiguous()
+            elif pt_input.dim() == 3 and pt_input.shape[-1] > 3:
+                raise SystemExit(f"{path}: {pt_input.shape[-1]} columns; the network takes x y z - name the others with "
+                                 f"--attributes (for instance --attributes lin{pt_input.shape[-1] - 3})")
             if tile_points is not None and pt_input.shape[1] > int(tile_points):
                 flush(pool)                                         # a pass of its own, in file order
                 cloud = pt_input.to(device)
@@ -187,11 +247,12 @@ def _upsampling(data_paths, target_path, checkpoint_path, up_ratio, num_outlier,
                                                    tile_points=int(tile_points))[None]
                 if num_outlier is not None and num_outlier > 0:
                     pred = PatchHelper.remove_outliers(pred, cloud, num_outlier)
+                pred = with_columns(pred, cloud, attr.to(device) if attr is not None else None)      # against the whole input cloud
                 writes.append(pool.submit(save_xyz, Path(target_path) / file_name, pred[0].cpu().numpy()))
                 continue
-            if pass_is_full(len(pending), sum(c.shape[1] for _, c in pending), pt_input.shape[1], cloud_batch, pass_points):
+            if pass_is_full(len(pending), sum(c.shape[1] for _, c, _ in pending), pt_input.shape[1], cloud_batch, pass_points):
                 flush(pool)
-            pending.append((file_name, pt_input))
+            pending.append((file_name, pt_input, attr))
         flush(pool)
         for w in writes:
             w.result()                                             # re-raises a failed write
@@ -216,6 +277,17 @@ def main(argv=None, network_cls=PointInterpFlow, add_arguments=None, network_set
     parser.add_argument("--tile_points", type=int, default=None,
                         help="(not in the reference) a file with more points than this is upsampled in k-d tiles of about this many "
                              "points, merged by FPS with a fixed context, as a pass of its own (default: off)")
+    parser.add_argument("--attributes", type=str, default=None, metavar="PLAN",
+                        help="(not in the reference) carry the files' columns after x y z to the output points: PLAN names them in "
+                             "order, e.g. normal,lin3,near1 = a normal (3 columns, sign-aligned, blended, normalised), 3 columns "
+                             "blended by inverse squared distance, 1 column copied from the nearest input point (labels); at most "
+                             "16 columns (default: files hold x y z only)")
+    parser.add_argument("--attr_k", type=int, default=8, help="(not in the reference) input points blended per output point, 1..8")
+    parser.add_argument("--estimate_normals", type=int, default=None, metavar="K",
+                        help="(not in the reference) append nx ny nz to every output row: the PCA normal of the output point's K "
+                             "nearest output points (8..64), pointing away from the cloud's centroid (default: off)")
+    parser.add_argument("--normals_viewpoint", type=str, default=None, metavar="X,Y,Z",
+                        help="(not in the reference) estimated normals point towards this position instead")
     if add_arguments is not None:
         add_arguments(parser)
     args = parser.parse_args(argv)
@@ -225,7 +297,8 @@ def main(argv=None, network_cls=PointInterpFlow, add_arguments=None, network_set
         data_paths.extend([os.path.join(root, f) for f in files if ".xyz" in f])
     upsampling(data_paths, args.target, args.checkpoint, up_ratio=args.up_ratio, num_outlier=24, num_patch=args.num_patch,
                num_upsampling=args.num_out, seed=args.seed, network_cls=network_cls, cloud_batch=args.cloud_batch,
-               pass_points=args.pass_points, tile_points=args.tile_points,
+               pass_points=args.pass_points, tile_points=args.tile_points, attributes=args.attributes, attr_k=args.attr_k,
+               estimate_normals=args.estimate_normals, normals_viewpoint=args.normals_viewpoint,
                network_setup=(lambda net: network_setup(net, args)) if network_setup is not None else None)
 
 
