@@ -601,8 +601,11 @@ __global__ __launch_bounds__(64 * MLP_DW_WAVES, PF_DW_OCC) void mlp_dw_kernel(Ml
         }
         rowB += MLP_EB;
         {
-            const float x = *pY;
-            yv = (ycol && rb + yel < r_hi) ? x : 0.f;
+            // (a block's rows past r_hi lie past the END of y when the chunk is the last one: up to 31 rows x ldy floats beyond
+            // the tensor - like the units above, the load goes through an address that is valid when the row is not)
+            const bool yok = ycol && rb + yel < r_hi;
+            const float x = *(yok ? pY : bsrc);
+            yv = yok ? x : 0.f;
             pY += stepY;
         }
     };

@@ -292,8 +292,10 @@ __global__ __launch_bounds__(256) void group_sum_kernel(const float* __restrict_
     }
 }
 
-// ---- softmax over K of R logit channels + weighted latent sum; one thread per point (K = 8, R <= 8)
-constexpr int SW_K = 8, SW_RMAX = 8;
+// ---- softmax over K of R logit channels + weighted latent sum; one thread per point (K = 8; R: any up-ratio the weight unit's
+// 32 logit channels allow - the kernels loop over r and hold nothing sized by R; the g chain takes R = 16, and train_ops sends
+// R > 8 here)
+constexpr int SW_K = 8, SW_RMAX = 32;
 __global__ __launch_bounds__(256) void softmax_wsum_fwd_kernel(const float* __restrict__ w /*[T,K,ldw] first R used*/,
                                                               int ldw, const float* __restrict__ zj /*[T,K,3]*/, int R,
                                                               long long T, float* __restrict__ a /*[T,K,R]*/,

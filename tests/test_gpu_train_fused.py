@@ -357,10 +357,12 @@ def test_training_forward_backward_on_an_odd_patch_size():
     assert np.median(v) < 1e-3 and v[int(0.9 * len(v))] < 2e-2 and v[-1] < 0.5, (float(np.median(v)), float(v[int(0.9 * len(v))]), worst, errs[worst])
 
 
-@pytest.mark.parametrize("R", [2, 3])
+@pytest.mark.parametrize("R", [1, 2, 3, 8, 16])
 def test_training_forward_backward_other_up_ratios(R):
     """Up-ratios other than 4 in train mode (the reference's interpolation supports any R <= r_max): a power of two shares the
-    conditioning row in the kernel, any other ratio goes through a materialised repeat - fused path against per-op path."""
+    conditioning row in the kernel, any other ratio goes through a materialised repeat - fused path against per-op path, the
+    output, the loss and the gradient of every flow-block parameter.  (The per-op tier is itself held to float64 by
+    tests/test_gpu_flow_train.py.)"""
     from puflow_amd import train_ops
     from puflow_amd.interpflow import PointInterpFlow
     from puflow_amd.weights import synth_patches, synth_state_dict
@@ -375,14 +377,19 @@ def test_training_forward_backward_other_up_ratios(R):
             (u.square().mean() + 1e-4 * logp).backward()
         finally:
             train_ops._FUSED = old
-        g = net.flow_blocks[3].coupling1.bias_net.layers[2].weight.grad.clone()
+        g = {n: q.grad.clone() for n, q in net.named_parameters() if n.startswith("flow_blocks.")}
         return u.detach(), float(logp), g
 
     u_f, l_f, g_f = run(True)
     u_u, l_u, g_u = run(False)
     assert u_f.shape == (2, 128 * R, 3)
     assert (u_f - u_u).abs().max() < 2e-5 and abs(l_f - l_u) < 1e-5 * abs(l_u)
-    assert float((g_f - g_u).abs().max()) < 2e-2 * float(g_u.abs().max())
+    assert g_f.keys() == g_u.keys() and len(g_u) == 6 * 18              # ActNorm 2, W 1, three conditioner nets of 5
+    worst = max(g_u, key=lambda n: float((g_f[n] - g_u[n]).abs().max()) / float(g_u[n].abs().max()))
+    print(f"\nup-ratio {R}: worst flow-block gradient {worst} "
+          f"{float((g_f[worst] - g_u[worst]).abs().max()) / float(g_u[worst].abs().max()):.2e} of its maximum", end="")
+    for n in g_u:
+        assert float((g_f[n] - g_u[n]).abs().max()) < 2e-2 * float(g_u[n].abs().max()), n
 
 
 def test_fused_batchnorm_statistics_with_a_large_mean():
