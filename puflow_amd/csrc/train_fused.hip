@@ -198,15 +198,24 @@ __global__ __launch_bounds__(256) void ec_bwdg_kernel(EcBwdgArgs a) {
 // the f32 kernel (the 16x16 accumulator layout does not depend on the input type).
 typedef __bf16 gbf8 __attribute__((ext_vector_type(8)));
 struct GBf2 { gbf8 hi, mid; };
+// Two floats rounded to bf16 (nearest, ties to even: the hardware's packed conversion), a in the low half of the word.  Both
+// parts of a split are ROUNDED: with hi and mid truncated (a mask and a shift) every product came out short by ~4e-5 of itself,
+// always towards zero, and through the six chained units of the extractor that bias added up to 2.8e-4 of the first unit's
+// gradients against float64 (tests/test_gpu_extract_train.py); rounded, x - hi has either sign, what is left after mid is at
+// most 2^-16 of x with mean zero, and so is the dropped mid mid product.  One v_cvt_pk_bf16_f32 per pair and part replaces the
+// masks, shifts and ors of the truncating form (integer rounding by hand, add 0x7fff + lsb and mask, cost 2 % of the step).
+typedef float gf2v __attribute__((ext_vector_type(2)));
+typedef __bf16 gb2v __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ unsigned bf16_pair(float a, float b) {
+    const gf2v v = {a, b};
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, gb2v));
+}
 __device__ __forceinline__ GBf2 g_split(const float (&x)[8]) {
     unsigned hw[4], mw[4];
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
-        const unsigned b0 = __float_as_uint(x[2 * p]), b1 = __float_as_uint(x[2 * p + 1]);
-        const unsigned h0 = b0 & 0xffff0000u, h1 = b1 & 0xffff0000u;
-        const unsigned m0 = __float_as_uint(x[2 * p] - __uint_as_float(h0)), m1 = __float_as_uint(x[2 * p + 1] - __uint_as_float(h1));
-        hw[p] = (h0 >> 16) | h1;
-        mw[p] = (m0 >> 16) | (m1 & 0xffff0000u);
+        hw[p] = bf16_pair(x[2 * p], x[2 * p + 1]);
+        mw[p] = bf16_pair(x[2 * p] - __uint_as_float(hw[p] << 16), x[2 * p + 1] - __uint_as_float(hw[p] & 0xffff0000u));
     }
     GBf2 r;
     r.hi = __builtin_bit_cast(gbf8, *reinterpret_cast<const uint4*>(hw));
@@ -1049,8 +1058,8 @@ __global__ __launch_bounds__(512) void ec_dw2_kernel(EcDw2Args g2) {
 }
 #endif
 
-// The same jobs on the bf16 matrix pipe: x = hi + mid with hi = the top 16 bits of x and mid = bf16(x - hi) (16 mantissa bits
-// together, fp32 exponent range - gradients of 1e-7 keep their digits, which fp16 halves would not), three
+// The same jobs on the bf16 matrix pipe: x = hi + mid with hi = bf16(x) and mid = bf16(x - hi), both rounded to nearest (bf16_pair
+// above; 16 significant bits together, fp32 exponent range - gradients of 1e-7 keep their digits, which fp16 halves would not), three
 // v_mfma_f32_32x32x16_bf16 per tile and 16 edges (hi hi + hi mid + mid hi, fp32 accumulate) instead of eight f32 MFMAs: 96 against
 // 512 matrix-pipe cycles.  Lane l holds its channel for the 8 edges 8 (l >> 5) + j of a 16-edge step.  In the no-LDS structure
 // the f32 pipe WAS the limit (the busiest SIMD of a workgroup owns 7 of its 22 tiles: 448 cycles per two edges); in the staged
@@ -1061,11 +1070,8 @@ __device__ __forceinline__ Bf2 dw3_split(const float (&x)[8]) {
     unsigned hw[4], mw[4];
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
-        const unsigned b0 = __float_as_uint(x[2 * p]), b1 = __float_as_uint(x[2 * p + 1]);
-        const unsigned h0 = b0 & 0xffff0000u, h1 = b1 & 0xffff0000u;
-        const unsigned m0 = __float_as_uint(x[2 * p] - __uint_as_float(h0)), m1 = __float_as_uint(x[2 * p + 1] - __uint_as_float(h1));
-        hw[p] = (h0 >> 16) | h1;
-        mw[p] = (m0 >> 16) | (m1 & 0xffff0000u);
+        hw[p] = bf16_pair(x[2 * p], x[2 * p + 1]);
+        mw[p] = bf16_pair(x[2 * p] - __uint_as_float(hw[p] << 16), x[2 * p + 1] - __uint_as_float(hw[p] & 0xffff0000u));
     }
     Bf2 r;
     r.hi = __builtin_bit_cast(bf8, *reinterpret_cast<const uint4*>(hw));

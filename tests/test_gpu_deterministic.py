@@ -5,7 +5,8 @@ the four-launch loss-head backward.  Run-to-run equality alone passes a gradient
 kernel the switch changes is held to the bar the project applies to the same quantity in the default mode.  The default mode
 runs on the same inputs against the same reference and bar: where it meets the bar, that shows the bar is one the fp32
 kernels meet; where it misses, the miss is reported (DefaultModeMiss), not asserted - a finding about the default kernels.
-Every test prints a `ROW` line: the worst max err / max |ref| of each mode and the masked shares."""
+Every test prints a `ROW` line: the worst max err / max |ref| of each mode and the masked shares.
+(The default mode of the fused unit and of the BatchNorm MLPs is asserted against float64 in tests/test_gpu_extract_train.py.)"""
 import copy
 import warnings
 from contextlib import contextmanager

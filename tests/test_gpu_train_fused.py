@@ -1,7 +1,8 @@
 """GPU: the fused training kernels of one EdgeConv unit (csrc/train_ec_fwd.hip, csrc/train_fused.hip) against the un-fused composition
 (train_ops.edgeconv_train with PF_TRAIN_FUSED semantics off), which is itself pinned to the oracle's train step in
 tests/test_gpu_train.py.  Output, input gradient and every parameter gradient, all unit shapes of the network
-(interpflow.py:190-248: growth 8/16/32, pooled K = 16 and the interpolation's un-pooled K = 8 unit with 8 layers)."""
+(interpflow.py:190-248: growth 8/16/32, pooled K = 16 and the interpolation's un-pooled K = 8 unit with 8 layers).
+Both tiers are held to a float64 restatement, at small and odd sizes and in every variant, by tests/test_gpu_extract_train.py."""
 import numpy as np
 import pytest
 import torch
