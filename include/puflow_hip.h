@@ -1155,6 +1155,24 @@ int pf_normals_pca(const float* pts, const int* idx, int B, int M, int K, const 
 int pf_normals_pca_ragged(const float* pts, const int* idx, const int* m, int B, int K, const float* viewpoint, double* centroid,
                           float* normal, float* variation, void* stream);
 
+/* ---- exact small-K nearest neighbours over a uniform grid (csrc/knn_grid.hip) -------------------------------
+ * The same results as pf_knn_large / pf_knn_large_ragged, bit for bit - the K smallest keys (squared distance, index), the
+ * squared distance the unfused fp32 ((dx*dx)+(dy*dy))+(dz*dz) - for 1 <= K <= PF_KNN_GRID_MAX_K, found by visiting
+ * the cells of growing Chebyshev rings around the query's cell of a per-cloud uniform grid instead of sorting the whole cloud.
+ * Shapes, index convention (indices inside the cloud), ordering and the nullable dist_out are pf_knn_large's.  Coordinates are
+ * assumed finite.  ws: pf_knn_grid_ws_bytes(n, B) bytes of device memory, 16-byte aligned, rebuilt by every call (box, cells
+ * and the cell-sorted references of each cloud); n / m: HOST arrays of B ints.  Before any device work: PF_ERR_NULL (ws too),
+ * PF_ERR_SHAPE (B, N, M, n[i] or m[i] <= 0, K > N or K > any n[i], more than 2^31 / 3 points, misaligned ws),
+ * PF_ERR_UNSUPPORTED (K outside 1 .. PF_KNN_GRID_MAX_K), PF_ERR_WORKSPACE (ws_bytes too small).  Five launches per 64 clouds,
+ * integer atomics only, the same bits from run to run. */
+#define PF_KNN_GRID_MAX_K 64
+/* bytes of workspace for B clouds of n[i] references (pf_knn_grid: n[i] = N for all); negative PF_ERR_* on a bad argument */
+long long pf_knn_grid_ws_bytes(const int* n, int B);
+int pf_knn_grid(const float* ref, const float* query, int B, int N, int M, int K, void* ws, long long ws_bytes, int* idx_out,
+                float* dist_out, void* stream);
+int pf_knn_grid_ragged(const float* ref, const float* query, const int* n, const int* m, int B, int K, void* ws,
+                       long long ws_bytes, int* idx_out, float* dist_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,8 +1,9 @@
 """Per-point attributes on the upsampled cloud (the reference writes bare xyz).
 
 A scan's columns after x y z - normals, colour, intensity, labels - are carried to the new points: every output point takes
-the `k` nearest INPUT points (pf_knn_large, exact) and blends their rows by inverse squared distance, column segment by column
-segment as a plan says (`parse_plan`).  `estimate_normals` fits a plane to every output point's own neighbourhood instead
+the `k` nearest INPUT points (pf_knn_large, exact; `search="grid"`: pf_knn_grid, the same neighbours bit for bit from a uniform
+grid of the cloud) and blends their rows by inverse squared distance, column segment by column segment as a plan says
+(`parse_plan`).  `estimate_normals` fits a plane to every output point's own neighbourhood instead
 (PCA in double on the device).  Both are HIP kernels (csrc/attr.hip); there is no CPU path.
 
   plan = parse_plan("normal,lin3,near1", columns=10)         # a 10-column file: xyz | normal | 3 blended | 1 label
@@ -70,23 +71,40 @@ def _k(k: int, n: int) -> int:
     return k
 
 
-def transfer(pred: torch.Tensor, cloud_xyz: torch.Tensor, cloud_attr: torch.Tensor, plan, k: int = 8) -> torch.Tensor:
+SEARCHES = ("brute", "grid")
+
+
+def _search(search: str, ragged: bool):
+    """the neighbour search of a `search=` argument: "brute" = pf_knn_large (one workgroup sorts the whole cloud per query), "grid"
+    = pf_knn_grid (a uniform grid of the cloud, csrc/knn_grid.hip) - the same indices and distances bit for bit, so everything
+    below produces the same bytes with either"""
+    if search not in SEARCHES:
+        raise ValueError(f"search = {search!r}: one of {', '.join(SEARCHES)}")
+    if search == "grid":
+        return ops.knn_grid_ragged if ragged else ops.knn_grid
+    return ops.knn_large_ragged if ragged else ops.knn_large
+
+
+def transfer(pred: torch.Tensor, cloud_xyz: torch.Tensor, cloud_attr: torch.Tensor, plan, k: int = 8,
+             search: str = "brute") -> torch.Tensor:
     """The input cloud's attribute rows on the output points: pred [M,3] (or [B,M,3]), cloud_xyz [N,3] ([B,N,3]), cloud_attr
     [N,C] ([B,N,C]) -> [M,C] ([B,M,C]).  An output point that IS an input point gets that point's row bit for bit.  One search
     and one blend launch for the whole batch."""
+    knn = _search(search, False)
     single = pred.dim() == 2
     if single:
         pred, cloud_xyz, cloud_attr = pred[None], cloud_xyz[None], cloud_attr[None]
-    idx, d2 = ops.knn_large(cloud_xyz, pred, _k(k, cloud_xyz.shape[1]))
+    idx, d2 = knn(cloud_xyz, pred, _k(k, cloud_xyz.shape[1]))
     out = ops.attr_blend(idx, d2, cloud_attr, _segments(plan))
     return out[0] if single else out
 
 
-def transfer_ragged(preds, clouds_xyz, clouds_attr, plan, k: int = 8) -> List[torch.Tensor]:
+def transfer_ragged(preds, clouds_xyz, clouds_attr, plan, k: int = 8, search: str = "brute") -> List[torch.Tensor]:
     """transfer for clouds of different sizes (lists of [M_i,3], [N_i,3], [N_i,C]) in one search and one blend launch; every
     cloud gets what transfer gives it alone."""
+    knn = _search(search, True)
     nl, ml = [int(c.shape[0]) for c in clouds_xyz], [int(p.shape[0]) for p in preds]
-    idx, d2 = ops.knn_large_ragged(torch.cat(list(clouds_xyz), dim=0), nl, torch.cat(list(preds), dim=0), ml, _k(k, min(nl)))
+    idx, d2 = knn(torch.cat(list(clouds_xyz), dim=0), nl, torch.cat(list(preds), dim=0), ml, _k(k, min(nl)))
     out = ops.attr_blend_ragged(idx, d2, torch.cat(list(clouds_attr), dim=0), nl, ml, _segments(plan))
     return list(torch.split(out, ml))
 
@@ -99,22 +117,24 @@ def _normals_k(k: int, m: int) -> int:
     return k
 
 
-def estimate_normals(pred: torch.Tensor, k: int, viewpoint=None):
+def estimate_normals(pred: torch.Tensor, k: int, viewpoint=None, search: str = "brute"):
     """A unit normal and the surface variation l0 / (l0 + l1 + l2) per point of pred [M,3] (or [B,M,3]) from the PCA of its k
     nearest points (itself included).  Sign: towards `viewpoint` (three numbers) when given; else away from the cloud's centroid,
     a heuristic that is right for star-shaped objects seen from their centroid and wrong in cavities and on inner walls."""
+    knn = _search(search, False)
     single = pred.dim() == 2
     if single:
         pred = pred[None]
-    idx, _ = ops.knn_large(pred, pred, _normals_k(k, pred.shape[1]))
+    idx, _ = knn(pred, pred, _normals_k(k, pred.shape[1]))
     normal, var = ops.normals_pca(pred, idx, viewpoint)
     return (normal[0], var[0]) if single else (normal, var)
 
 
-def estimate_normals_ragged(preds, k: int, viewpoint=None):
+def estimate_normals_ragged(preds, k: int, viewpoint=None, search: str = "brute"):
     """estimate_normals for clouds of different sizes in one search and one launch: ([normals_i], [variation_i])"""
+    knn = _search(search, True)
     ml = [int(p.shape[0]) for p in preds]
     pts = torch.cat(list(preds), dim=0)
-    idx, _ = ops.knn_large_ragged(pts, ml, pts, ml, _normals_k(k, min(ml)))
+    idx, _ = knn(pts, ml, pts, ml, _normals_k(k, min(ml)))
     normal, var = ops.normals_pca_ragged(pts, idx, ml, viewpoint)
     return list(torch.split(normal, ml)), list(torch.split(var, ml))

@@ -462,6 +462,49 @@ def knn_large_ragged(ref: torch.Tensor, ref_lengths, query: torch.Tensor, query_
     return idx, dist
 
 
+def _knn_grid_ws(lib, lengths, device):
+    """the grid search's workspace (box, cells and cell-sorted references per cloud), rebuilt by every call"""
+    nbytes = lib.pf_knn_grid_ws_bytes(_lib.counts(lengths), len(lengths))
+    if nbytes < 0:
+        _lib.check(int(nbytes), "pf_knn_grid_ws_bytes")
+    return torch.empty((int(nbytes),), dtype=torch.uint8, device=device), int(nbytes)
+
+
+def knn_grid(ref: torch.Tensor, query: torch.Tensor, k: int):
+    """pf_knn_grid: what knn_large returns, bit for bit, for k <= PF_KNN_GRID_MAX_K, found over a uniform grid of the cloud
+    (csrc/knn_grid.hip): ref [B,N,3], query [B,M,3] -> (idx int32 [B,M,k], squared distances [B,M,k])"""
+    lib = _lib.load()
+    ref, query = _f32c(ref), _f32c(query)
+    if ref.dim() != 3 or query.dim() != 3 or ref.shape[2] != 3 or query.shape[2] != 3 or ref.shape[0] != query.shape[0]:
+        raise _lib.PuflowHipError(f"knn_grid: ref [B,N,3] and query [B,M,3], got {tuple(ref.shape)} and {tuple(query.shape)}")
+    B, N, _ = ref.shape
+    M = query.shape[1]
+    if B <= 0 or N <= 0:
+        raise _lib.PuflowHipError(f"knn_grid: empty input {tuple(ref.shape)}")
+    ws, nbytes = _knn_grid_ws(lib, [N] * B, ref.device)
+    idx = torch.empty((B, M, int(k)), dtype=torch.int32, device=ref.device)
+    dist = torch.empty((B, M, int(k)), dtype=torch.float32, device=ref.device)
+    _lib.check(lib.pf_knn_grid(ref.data_ptr(), query.data_ptr(), B, N, M, int(k), ws.data_ptr(), nbytes, idx.data_ptr(),
+                               dist.data_ptr(), _stream()), "pf_knn_grid")
+    return idx, dist
+
+
+def knn_grid_ragged(ref: torch.Tensor, ref_lengths, query: torch.Tensor, query_lengths, k: int):
+    """pf_knn_grid_ragged: what knn_large_ragged returns, bit for bit, for k <= PF_KNN_GRID_MAX_K"""
+    lib = _lib.load()
+    ref, query = _packed(ref, "knn_grid_ragged"), _packed(query, "knn_grid_ragged")
+    rl = _lengths(ref_lengths, ref.shape[0], "knn_grid_ragged")
+    ql = _lengths(query_lengths, query.shape[0], "knn_grid_ragged")
+    if len(rl) != len(ql):
+        raise _lib.PuflowHipError("knn_grid_ragged: one query count per cloud")
+    ws, nbytes = _knn_grid_ws(lib, rl, ref.device)
+    idx = torch.empty((query.shape[0], int(k)), dtype=torch.int32, device=ref.device)
+    dist = torch.empty((query.shape[0], int(k)), dtype=torch.float32, device=ref.device)
+    _lib.check(lib.pf_knn_grid_ragged(ref.data_ptr(), query.data_ptr(), _lib.counts(rl), _lib.counts(ql), len(rl), int(k),
+                                      ws.data_ptr(), nbytes, idx.data_ptr(), dist.data_ptr(), _stream()), "pf_knn_grid_ragged")
+    return idx, dist
+
+
 def _segments(segments):
     """[(kind, columns), ...] with kind a PF_ATTR_* value -> the two host arrays of the entry points and the column total"""
     segments = [(int(kind), int(cols)) for kind, cols in segments]

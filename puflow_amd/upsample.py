@@ -92,7 +92,10 @@ def load_xyz(path) -> np.ndarray:
 def upsampling(data_paths: List[str], target_path: str, checkpoint_path: str, up_ratio: int, num_outlier: int,
                num_patch: int, num_upsampling: int = None, seed=None, state_dict=None, network_cls=PointInterpFlow,
                cloud_batch: int = None, pass_points: int = None, network_setup=None, tile_points: int = None,
-               attributes: str = None, attr_k: int = 8, estimate_normals: int = None, normals_viewpoint=None):
+               attributes: str = None, attr_k: int = 8, estimate_normals: int = None, normals_viewpoint=None,
+               attr_search: str = "brute"):
+    # attr_search: the neighbour search behind the two options below - "brute" (pf_knn_large) or "grid" (pf_knn_grid, a uniform
+    # grid of the cloud); the same neighbours bit for bit, hence the same files
     # attributes / attr_k / estimate_normals / normals_viewpoint (not in the reference; puflow_amd/attributes.py): the
     # files' columns after x y z are carried to the output points as the plan says, and / or a PCA normal is appended to every
     # output row.  All None: bare xyz in, bare xyz out, as the reference.
@@ -114,15 +117,17 @@ def upsampling(data_paths: List[str], target_path: str, checkpoint_path: str, up
     try:
         return _upsampling(data_paths, target_path, checkpoint_path, up_ratio, num_outlier, num_patch, num_upsampling, seed,
                            state_dict, network_cls, cloud_batch, pass_points, network_setup, tile_points, attributes, attr_k,
-                           estimate_normals, normals_viewpoint)
+                           estimate_normals, normals_viewpoint, attr_search)
     finally:
         torch.set_num_threads(host_threads)
 
 
 def _upsampling(data_paths, target_path, checkpoint_path, up_ratio, num_outlier, num_patch, num_upsampling, seed, state_dict,
                 network_cls, cloud_batch, pass_points=None, network_setup=None, tile_points=None, attributes=None, attr_k=8,
-                estimate_normals=None, normals_viewpoint=None):
+                estimate_normals=None, normals_viewpoint=None, attr_search="brute"):
     from . import attributes as A
+    if attr_search not in A.SEARCHES:
+        raise SystemExit(f"--attr_search: one of {', '.join(A.SEARCHES)}, got {attr_search!r}")
     plan = None
     try:
         if attributes is not None:
@@ -182,17 +187,17 @@ def _upsampling(data_paths, target_path, checkpoint_path, up_ratio, num_outlier,
     def with_columns(pred, cloud, attr):                           # a dense pass: [B,M,3], [B,N,3], [B,N,C] or None
         cols = [pred]
         if plan is not None:
-            cols.append(A.transfer(pred, cloud, attr, plan, attr_k))
+            cols.append(A.transfer(pred, cloud, attr, plan, attr_k, search=attr_search))
         if estimate_normals is not None:
-            cols.append(A.estimate_normals(pred, estimate_normals, normals_viewpoint)[0])
+            cols.append(A.estimate_normals(pred, estimate_normals, normals_viewpoint, search=attr_search)[0])
         return torch.cat(cols, dim=-1) if len(cols) > 1 else pred
 
     def with_columns_ragged(pred, clouds, attrs):                  # a ragged pass: lists of [M_i,3], [N_i,3], [N_i,C]
         cols = [pred]
         if plan is not None:
-            cols.append(A.transfer_ragged(pred, clouds, attrs, plan, attr_k))
+            cols.append(A.transfer_ragged(pred, clouds, attrs, plan, attr_k, search=attr_search))
         if estimate_normals is not None:
-            cols.append(A.estimate_normals_ragged(pred, estimate_normals, normals_viewpoint)[0])
+            cols.append(A.estimate_normals_ragged(pred, estimate_normals, normals_viewpoint, search=attr_search)[0])
         return [torch.cat(c, dim=-1) for c in zip(*cols)] if len(cols) > 1 else pred
 
     def npoint_of(n):
@@ -288,9 +293,15 @@ def main(argv=None, network_cls=PointInterpFlow, add_arguments=None, network_set
                              "nearest output points (8..64), pointing away from the cloud's centroid (default: off)")
     parser.add_argument("--normals_viewpoint", type=str, default=None, metavar="X,Y,Z",
                         help="(not in the reference) estimated normals point towards this position instead")
+    parser.add_argument("--attr_search", type=str, default=None, choices=("brute", "grid"),
+                        help="(not in the reference) the neighbour search behind --attributes and --estimate_normals: brute = one "
+                             "workgroup sorts the whole cloud per output point, grid = a uniform grid of the cloud, far faster on "
+                             "large clouds; the same files either way (default: brute)")
     if add_arguments is not None:
         add_arguments(parser)
     args = parser.parse_args(argv)
+    if args.attr_search is not None and args.attributes is None and args.estimate_normals is None:
+        raise SystemExit("--attr_search goes with --attributes or --estimate_normals")
     os.makedirs(args.target, exist_ok=True)            # exist_ok: several ranks may race to create it
     data_paths = []
     for root, _dirs, files in os.walk(args.source):
@@ -299,6 +310,7 @@ def main(argv=None, network_cls=PointInterpFlow, add_arguments=None, network_set
                num_upsampling=args.num_out, seed=args.seed, network_cls=network_cls, cloud_batch=args.cloud_batch,
                pass_points=args.pass_points, tile_points=args.tile_points, attributes=args.attributes, attr_k=args.attr_k,
                estimate_normals=args.estimate_normals, normals_viewpoint=args.normals_viewpoint,
+               attr_search=args.attr_search or "brute",
                network_setup=(lambda net: network_setup(net, args)) if network_setup is not None else None)
 
 

@@ -8,15 +8,19 @@ figure.  The comparison leg is the same tree without the flags (on the files' x 
   share:  where the added time goes, per output point, for clouds of 5000 and --tiled-points input points: the neighbour search
           (pf_knn_large, an existing kernel) against the new kernels (pf_attr_blend, pf_normals_pca), timed with events on
           --sample output points (the search's cost per query does not depend on how many queries there are).
+--attr_search grid runs the attribute and normal legs with the uniform-grid search (pf_knn_grid) instead of pf_knn_large and
+writes time_attributes_grid.txt / .json; `share` times pf_knn_large and is left out then (tools/time_knn_grid.py compares the
+two searches).  --skip-dense / --skip-share leave those parts out.
 A leg that fails or runs out of time ends the run: nothing else is started on the GPU after it.
-  python tools/time_attributes.py [--out-dir profiles/attributes] [--commit ID] [--tiled-points N] [--sample Q] [--skip-tiled]"""
+  python tools/time_attributes.py [--out-dir profiles/attributes] [--commit ID] [--tiled-points N] [--sample Q] [--skip-tiled]
+                                  [--attr_search brute|grid] [--skip-dense] [--skip-share]"""
 import json, os, socket, subprocess, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 FLAGS = {"none": {}, "attributes": {"attributes": "normal,lin3"}, "normals": {"estimate_normals": 16}}
 
 if len(sys.argv) > 1 and sys.argv[1] == "--child":
-    src, dst, leg, tile_points = sys.argv[2], sys.argv[3], sys.argv[4], int(sys.argv[5])
+    src, dst, leg, tile_points, search = sys.argv[2], sys.argv[3], sys.argv[4], int(sys.argv[5]), sys.argv[6]
     import torch
     from puflow_amd import upsample as U
     from puflow_amd.weights import synth_state_dict
@@ -26,7 +30,7 @@ if len(sys.argv) > 1 and sys.argv[1] == "--child":
     for tag in ("FIRST", "ELAPSED"):
         t0 = time.perf_counter()
         U.upsampling(paths, dst, None, up_ratio=4, num_outlier=24, num_patch=256, seed=2021, state_dict=sd,
-                     tile_points=tile_points or None, **FLAGS[leg])
+                     tile_points=tile_points or None, **FLAGS[leg], **({} if leg == "none" else {"attr_search": search}))
         print("%s %.6f" % (tag, time.perf_counter() - t0), flush=True)
     print("BOX %s / %s" % (socket.gethostname(), torch.cuda.get_device_name(0)), flush=True)
     sys.exit(0)
@@ -70,7 +74,11 @@ out_dir = args[args.index("--out-dir") + 1] if "--out-dir" in args else os.path.
 commit = args[args.index("--commit") + 1] if "--commit" in args else "unknown"
 tiled_points = int(args[args.index("--tiled-points") + 1]) if "--tiled-points" in args else 262144
 sample = int(args[args.index("--sample") + 1]) if "--sample" in args else 4096
-lines, record = [], {"commit": commit, "legs": [], "share": []}
+attr_search = args[args.index("--attr_search") + 1] if "--attr_search" in args else "brute"
+if attr_search not in ("brute", "grid"):
+    sys.exit("--attr_search: brute or grid")
+stem = "time_attributes" if attr_search == "brute" else "time_attributes_" + attr_search
+lines, record = [], {"commit": commit, "attr_search": attr_search, "legs": [], "share": []}
 
 
 def say(s):
@@ -80,9 +88,9 @@ def say(s):
 
 def finish(ok):
     os.makedirs(out_dir, exist_ok=True)
-    with open(os.path.join(out_dir, "time_attributes.txt"), "w") as f:
+    with open(os.path.join(out_dir, stem + ".txt"), "w") as f:
         f.write("\n".join(lines) + "\n")
-    with open(os.path.join(out_dir, "time_attributes.json"), "w") as f:
+    with open(os.path.join(out_dir, stem + ".json"), "w") as f:
         json.dump(record, f, indent=1)
     sys.exit(0 if ok else 1)
 
@@ -101,7 +109,7 @@ def write_scans(folder, sizes):
 
 box = "?"
 with tempfile.TemporaryDirectory() as tmp:
-    settings = [("dense", [5000] * 32, 0, 240)]
+    settings = [("dense", [5000] * 32, 0, 240)] if "--skip-dense" not in args else []
     if "--skip-tiled" not in args:
         settings.append(("tiled", [tiled_points], 4096, 900))
     for name, sizes, tile_points, limit in settings:
@@ -113,7 +121,7 @@ with tempfile.TemporaryDirectory() as tmp:
                 os.makedirs(dst)
                 src = os.path.join(tmp, name, "xyz9" if leg == "attributes" else "xyz3")
                 try:
-                    out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", src, dst, leg, str(tile_points)],
+                    out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", src, dst, leg, str(tile_points), attr_search],
                                          capture_output=True, text=True, timeout=limit)
                 except subprocess.TimeoutExpired:
                     say(f"{name} / {leg}: TIMED OUT after {limit} s - stopping")
@@ -133,7 +141,7 @@ with tempfile.TemporaryDirectory() as tmp:
         for leg in ("attributes", "normals"):
             say(f"{name:5s} {leg:10s} adds {(min(times[leg]) - base) / len(sizes) * 1e3:9.2f} ms per cloud to {base / len(sizes) * 1e3:.2f} "
                 f"(best of two rounds each; {len(sizes)} clouds of {sizes[0]} points)")
-    for n in (5000, tiled_points):
+    for n in (5000, tiled_points) if attr_search == "brute" and "--skip-share" not in args else ():
         try:
             out = subprocess.run([sys.executable, os.path.abspath(__file__), "--share", str(n), str(sample)], capture_output=True,
                                  text=True, timeout=600)
@@ -152,5 +160,5 @@ with tempfile.TemporaryDirectory() as tmp:
             f"normals = search {u['normals_search']:.2f} us + PCA {u['normals_pca']:.4f} us "
             f"(search {u['normals_search'] / (u['normals_search'] + u['normals_pca']):.2%}); whole cloud at these rates: attributes "
             f"{(u['attributes_search'] + u['attributes_blend']) * r['outputs'] * 1e-6:.2f} s, normals {(u['normals_search'] + u['normals_pca']) * r['outputs'] * 1e-6:.2f} s")
-    say(f"box: {box}   commit: {commit}")
+    say(f"box: {box}   commit: {commit}   attr_search: {attr_search}")
 finish(True)
