@@ -1173,6 +1173,41 @@ int pf_knn_grid(const float* ref, const float* query, int B, int N, int M, int K
 int pf_knn_grid_ragged(const float* ref, const float* query, const int* n, const int* m, int B, int K, void* ws,
                        long long ws_bytes, int* idx_out, float* dist_out, void* stream);
 
+/* ---- consistent signs for normals: propagation along a minimum spanning forest (csrc/normals_orient.hip) ------
+ * pts, normal_in [B,M,3]; idx [B,M,K] as pf_knn_large(ref = query = pts) writes it (indices inside the cloud; an entry outside
+ * the cloud is ignored).  normal_in may have any signs (pf_normals_pca's, a file's).
+ *   Graph    the undirected edges {i, j}, i != j, with j in i's list or i in j's list.
+ *   Weights  d_ij = ((nx_i*nx_j) + (ny_i*ny_j)) + (nz_i*nz_j) in unfused fp32 (bitwise symmetric), w_ij = max(0, 1 - |d_ij|) in
+ *            fp32.  Edges are ordered by the key (w_ij, min(i,j), max(i,j)): a strict order, so the minimum spanning forest is
+ *            unique whatever finds it.
+ *   Signs    normal_out_i = normal_in_i with the sign bit of all three components flipped or not.  Along every forest edge i's
+ *            flip differs from j's exactly when d_ij < 0 (d_ij == 0: no relative flip).  Per connected component the seed is
+ *            the point with the largest z, or with viewpoint v (HOST float[3], nullable) the point with the smallest unfused
+ *            fp32 squared distance ((dx*dx)+(dy*dy))+(dz*dz), d = p - v; the lowest index among equals.  The component as a whole
+ *            is flipped or not so that the seed's output n' has n'_z >= 0, or with a viewpoint the unfused fp32
+ *            ((n'x*(vx-px)) + (n'y*(vy-py))) + (n'z*(vz-pz)) >= 0; with an exact 0 the seed keeps its input sign.  A closed piece
+ *            has its outward normal on the outer side at an extreme point, so closed pieces come out pointing outwards.
+ *   comp_out [B,M] int, nullable: the smallest point index, inside the cloud, of the point's connected component.
+ * The output is bit-determined by the inputs, does not depend on the input signs (apart from dots that are exactly 0) and is
+ * the same from run to run.  Limits: a neighbour graph can fall into several components even on one surface; each is oriented
+ * on its own by the extreme-point rule, which is right for closed pieces and a guess for fragments (components are not joined);
+ * sheets closer together than a neighbourhood can still flip.
+ * Boruvka rounds with a flip bit per vertex; ceil(log2 M) rounds (M: the largest cloud) are enqueued without a host read
+ * between launches, finished rounds return at once; every loop in every kernel has a constant or host-given bound; integer atomics only.
+ * ws: pf_normals_orient_ws_bytes(m, B) bytes of device memory, 16-byte aligned (37 bytes per point), rebuilt by every call.
+ * normal_out may alias normal_in.  2 <= K <= PF_KNN_GRID_MAX_K, else PF_ERR_UNSUPPORTED.  Before any device work: PF_ERR_NULL
+ * (ws too; viewpoint and comp_out may be null), PF_ERR_SHAPE (B, M or m[i] <= 0, K > M or K > any m[i], more than 2^31 / 3
+ * points, misaligned ws), PF_ERR_UNSUPPORTED, PF_ERR_WORKSPACE (ws_bytes too small). */
+/* bytes of workspace for B clouds of m[i] points (pf_normals_orient: m[i] = M for all); negative PF_ERR_* on a bad argument */
+long long pf_normals_orient_ws_bytes(const int* m, int B);
+int pf_normals_orient(const float* pts, const float* normal_in, const int* idx, int B, int M, int K, const float* viewpoint,
+                      void* ws, long long ws_bytes, float* normal_out, int* comp_out, void* stream);
+/* pf_normals_orient per cloud of a ragged pass: pts, normal_in [sum m, 3], idx [sum m, K] (pf_knn_large_ragged, indices inside
+ * the cloud), m: HOST array of B ints.  Edges never cross clouds: one forest over the packed tensor.  Every cloud gets, bit for
+ * bit, what pf_normals_orient gives it alone. */
+int pf_normals_orient_ragged(const float* pts, const float* normal_in, const int* idx, const int* m, int B, int K,
+                             const float* viewpoint, void* ws, long long ws_bytes, float* normal_out, int* comp_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

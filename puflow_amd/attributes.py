@@ -4,11 +4,14 @@ A scan's columns after x y z - normals, colour, intensity, labels - are carried 
 the `k` nearest INPUT points (pf_knn_large, exact; `search="grid"`: pf_knn_grid, the same neighbours bit for bit from a uniform
 grid of the cloud) and blends their rows by inverse squared distance, column segment by column segment as a plan says
 (`parse_plan`).  `estimate_normals` fits a plane to every output point's own neighbourhood instead
-(PCA in double on the device).  Both are HIP kernels (csrc/attr.hip); there is no CPU path.
+(PCA in double on the device) and, asked to, gives the normals consistent signs by propagation along a minimum spanning
+forest of the neighbour graph (csrc/normals_orient.hip).  All are HIP kernels (csrc/attr.hip); there is no CPU path.
 
   plan = parse_plan("normal,lin3,near1", columns=10)         # a 10-column file: xyz | normal | 3 blended | 1 label
   out_attr = transfer(pred, cloud_xyz, cloud_attr, plan)     # [M,3], [N,3], [N,7] -> [M,7]
   normals, variation = estimate_normals(pred, 16)            # [M,3] -> [M,3], [M]
+  normals, variation = estimate_normals(pred, 16, orient="propagate")       # signs consistent over the surface
+  normals, comp = orient_normals(pred, file_normals, 16)     # the same for normals that came from elsewhere
 """
 from __future__ import annotations
 
@@ -117,24 +120,79 @@ def _normals_k(k: int, m: int) -> int:
     return k
 
 
-def estimate_normals(pred: torch.Tensor, k: int, viewpoint=None, search: str = "brute"):
+ORIENTS = ("point", "propagate")
+
+
+def _orient(orient: str) -> bool:
+    if orient not in ORIENTS:
+        raise ValueError(f"orient = {orient!r}: one of {', '.join(ORIENTS)}")
+    return orient == "propagate"
+
+
+def _orient_k(k: int, m: int) -> int:
+    k = int(k)
+    if not 2 <= k <= _lib.PF_KNN_GRID_MAX_K or k > m:
+        raise _lib.PuflowHipError(f"orient_normals: k = {k} neighbours on a cloud of {m} points; 2 .. {_lib.PF_KNN_GRID_MAX_K} "
+                                  "(and at most the cloud) are supported")
+    return k
+
+
+def estimate_normals(pred: torch.Tensor, k: int, viewpoint=None, search: str = "brute", orient: str = "point"):
     """A unit normal and the surface variation l0 / (l0 + l1 + l2) per point of pred [M,3] (or [B,M,3]) from the PCA of its k
-    nearest points (itself included).  Sign: towards `viewpoint` (three numbers) when given; else away from the cloud's centroid,
-    a heuristic that is right for star-shaped objects seen from their centroid and wrong in cavities and on inner walls."""
-    knn = _search(search, False)
+    nearest points (itself included).  Sign, orient="point": every point on its own, towards `viewpoint` (three numbers) when
+    given; else away from the cloud's centroid, a heuristic that is right for star-shaped objects seen from their centroid and
+    wrong in cavities and on inner walls (the whole inner ring of a torus).  orient="propagate": the signs are carried along
+    the minimum spanning forest of the same k-neighbour graph (orient_normals; no second search), which is right on every
+    closed piece the graph holds together."""
+    knn, propagate = _search(search, False), _orient(orient)
     single = pred.dim() == 2
     if single:
         pred = pred[None]
     idx, _ = knn(pred, pred, _normals_k(k, pred.shape[1]))
     normal, var = ops.normals_pca(pred, idx, viewpoint)
+    if propagate:
+        normal, _ = ops.normals_orient(pred, normal, idx, viewpoint, out=normal)
     return (normal[0], var[0]) if single else (normal, var)
 
 
-def estimate_normals_ragged(preds, k: int, viewpoint=None, search: str = "brute"):
+def estimate_normals_ragged(preds, k: int, viewpoint=None, search: str = "brute", orient: str = "point"):
     """estimate_normals for clouds of different sizes in one search and one launch: ([normals_i], [variation_i])"""
-    knn = _search(search, True)
+    knn, propagate = _search(search, True), _orient(orient)
     ml = [int(p.shape[0]) for p in preds]
     pts = torch.cat(list(preds), dim=0)
     idx, _ = knn(pts, ml, pts, ml, _normals_k(k, min(ml)))
     normal, var = ops.normals_pca_ragged(pts, idx, ml, viewpoint)
+    if propagate:
+        normal, _ = ops.normals_orient_ragged(pts, normal, idx, ml, viewpoint)
     return list(torch.split(normal, ml)), list(torch.split(var, ml))
+
+
+def orient_normals(pts: torch.Tensor, normals: torch.Tensor, k: int, viewpoint=None, search: str = "brute", idx=None):
+    """Consistent signs for any normals (estimated, or carried from a file): pts, normals [M,3] (or [B,M,3]) -> (normals with
+    every row kept or negated, comp int32 [M]: the smallest index of the row's connected component).  The graph is the k
+    nearest neighbours of every point (idx int32 [.., M, k] from ops.knn_large / knn_grid skips the search), the signs follow
+    its minimum spanning forest under the weights 1 - |n_i . n_j| (Hoppe et al. 1992), and each component's highest point - with
+    `viewpoint` the one nearest to it - looks up, or at the viewpoint.  The result does not depend on the signs that came in.
+    A graph that falls into several components is oriented piece by piece: right for closed pieces, a guess for fragments;
+    components are not joined, and sheets closer together than a neighbourhood can still flip."""
+    knn = _search(search, False)
+    single = pts.dim() == 2
+    if single:
+        pts, normals = pts[None], normals[None]
+        idx = idx[None] if idx is not None else None
+    if idx is None:
+        idx, _ = knn(pts, pts, _orient_k(k, pts.shape[1]))
+    out, comp = ops.normals_orient(pts, normals, idx, viewpoint)
+    return (out[0], comp[0]) if single else (out, comp)
+
+
+def orient_normals_ragged(pts_list, normals_list, k: int, viewpoint=None, search: str = "brute", idx=None):
+    """orient_normals for clouds of different sizes in one search and one pass: ([normals_i], [comp_i]); idx: the packed
+    [sum M_i, k] int32 lists of ops.knn_large_ragged / knn_grid_ragged"""
+    knn = _search(search, True)
+    ml = [int(p.shape[0]) for p in pts_list]
+    pts, normals = torch.cat(list(pts_list), dim=0), torch.cat(list(normals_list), dim=0)
+    if idx is None:
+        idx, _ = knn(pts, ml, pts, ml, _orient_k(k, min(ml)))
+    out, comp = ops.normals_orient_ragged(pts, normals, idx, ml, viewpoint)
+    return list(torch.split(out, ml)), list(torch.split(comp, ml))

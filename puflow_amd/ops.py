@@ -600,3 +600,54 @@ def normals_pca_ragged(pts: torch.Tensor, idx: torch.Tensor, lengths, viewpoint=
                                          _viewpoint(viewpoint), cen.data_ptr() if cen is not None else None, normal.data_ptr(),
                                          var.data_ptr(), _stream()), "pf_normals_pca_ragged")
     return normal, var
+
+
+def _normals_orient_ws(lib, lengths, device):
+    """the orientation's workspace (component, flip, link and offers per point), rebuilt by every call"""
+    nbytes = lib.pf_normals_orient_ws_bytes(_lib.counts(lengths), len(lengths))
+    if nbytes < 0:
+        _lib.check(int(nbytes), "pf_normals_orient_ws_bytes")
+    return torch.empty((int(nbytes),), dtype=torch.uint8, device=device), int(nbytes)
+
+
+def normals_orient(pts: torch.Tensor, normals: torch.Tensor, idx: torch.Tensor, viewpoint=None, out: torch.Tensor = None):
+    """pf_normals_orient: pts, normals [B,M,3] (any signs), idx int32 [B,M,K] from knn_large(pts, pts, K) -> (the normals with
+    consistent signs [B,M,3], every point's component int32 [B,M]: its smallest point index).  Signs are carried along the
+    minimum spanning forest of the neighbour graph; each component's seed - its highest point, or the one nearest to `viewpoint`
+    (three numbers) - looks up, or at the viewpoint (csrc/normals_orient.hip).  out: where the normals go (float32, contiguous, the shape of
+    `normals`; it may be `normals` itself); default: a new tensor."""
+    lib = _lib.load()
+    pts, normals, idx = _f32c(pts), _f32c(normals), _i32c(idx, "normals_orient")
+    if pts.dim() != 3 or pts.shape[2] != 3 or normals.shape != pts.shape or idx.dim() != 3 or idx.shape[:2] != pts.shape[:2]:
+        raise _lib.PuflowHipError(f"normals_orient: pts / normals [B,M,3] and idx [B,M,K], got {tuple(pts.shape)}, "
+                                  f"{tuple(normals.shape)} and {tuple(idx.shape)}")
+    B, M, K = idx.shape
+    if B <= 0 or M <= 0:
+        raise _lib.PuflowHipError(f"normals_orient: empty input {tuple(pts.shape)}")
+    if out is None:
+        out = torch.empty_like(normals)
+    elif out.dtype != torch.float32 or out.shape != normals.shape or not out.is_contiguous() or out.device != normals.device:
+        raise _lib.PuflowHipError("normals_orient: out is a contiguous float32 tensor of the normals' shape, on their device")
+    ws, nbytes = _normals_orient_ws(lib, [M] * B, pts.device)
+    comp = torch.empty((B, M), dtype=torch.int32, device=pts.device)
+    _lib.check(lib.pf_normals_orient(pts.data_ptr(), normals.data_ptr(), idx.data_ptr(), B, M, K, _viewpoint(viewpoint),
+                                     ws.data_ptr(), nbytes, out.data_ptr(), comp.data_ptr(), _stream()), "pf_normals_orient")
+    return out, comp
+
+
+def normals_orient_ragged(pts: torch.Tensor, normals: torch.Tensor, idx: torch.Tensor, lengths, viewpoint=None):
+    """pf_normals_orient_ragged: pts, normals [sum lengths, 3], idx int32 [sum lengths, K] from knn_large_ragged -> (normals [sum
+    lengths, 3], components int32 [sum lengths], indices inside the cloud); every cloud gets what normals_orient gives it alone"""
+    lib = _lib.load()
+    pts, normals, idx = _packed(pts, "normals_orient_ragged"), _f32c(normals), _i32c(idx, "normals_orient_ragged")
+    if normals.shape != pts.shape or idx.dim() != 2 or idx.shape[0] != pts.shape[0]:
+        raise _lib.PuflowHipError(f"normals_orient_ragged: normals [sum lengths, 3] and idx [sum lengths, K], got "
+                                  f"{tuple(normals.shape)} and {tuple(idx.shape)}")
+    ml = _lengths(lengths, pts.shape[0], "normals_orient_ragged")
+    ws, nbytes = _normals_orient_ws(lib, ml, pts.device)
+    out = torch.empty_like(normals)
+    comp = torch.empty((pts.shape[0],), dtype=torch.int32, device=pts.device)
+    _lib.check(lib.pf_normals_orient_ragged(pts.data_ptr(), normals.data_ptr(), idx.data_ptr(), _lib.counts(ml), len(ml),
+                                            idx.shape[1], _viewpoint(viewpoint), ws.data_ptr(), nbytes, out.data_ptr(),
+                                            comp.data_ptr(), _stream()), "pf_normals_orient_ragged")
+    return out, comp

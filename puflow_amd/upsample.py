@@ -93,7 +93,9 @@ def upsampling(data_paths: List[str], target_path: str, checkpoint_path: str, up
                num_patch: int, num_upsampling: int = None, seed=None, state_dict=None, network_cls=PointInterpFlow,
                cloud_batch: int = None, pass_points: int = None, network_setup=None, tile_points: int = None,
                attributes: str = None, attr_k: int = 8, estimate_normals: int = None, normals_viewpoint=None,
-               attr_search: str = "brute"):
+               attr_search: str = "brute", normals_orient: str = "point"):
+    # normals_orient: the sign of the estimated normals - "point": every point on its own (towards the viewpoint, or away from the
+    # centroid); "propagate": carried along the minimum spanning forest of the neighbour graph (attributes.orient_normals)
     # attr_search: the neighbour search behind the two options below - "brute" (pf_knn_large) or "grid" (pf_knn_grid, a uniform
     # grid of the cloud); the same neighbours bit for bit, hence the same files
     # attributes / attr_k / estimate_normals / normals_viewpoint (not in the reference; puflow_amd/attributes.py): the
@@ -117,15 +119,19 @@ def upsampling(data_paths: List[str], target_path: str, checkpoint_path: str, up
     try:
         return _upsampling(data_paths, target_path, checkpoint_path, up_ratio, num_outlier, num_patch, num_upsampling, seed,
                            state_dict, network_cls, cloud_batch, pass_points, network_setup, tile_points, attributes, attr_k,
-                           estimate_normals, normals_viewpoint, attr_search)
+                           estimate_normals, normals_viewpoint, attr_search, normals_orient)
     finally:
         torch.set_num_threads(host_threads)
 
 
 def _upsampling(data_paths, target_path, checkpoint_path, up_ratio, num_outlier, num_patch, num_upsampling, seed, state_dict,
                 network_cls, cloud_batch, pass_points=None, network_setup=None, tile_points=None, attributes=None, attr_k=8,
-                estimate_normals=None, normals_viewpoint=None, attr_search="brute"):
+                estimate_normals=None, normals_viewpoint=None, attr_search="brute", normals_orient="point"):
     from . import attributes as A
+    if normals_orient not in A.ORIENTS:
+        raise SystemExit(f"--normals_orient: one of {', '.join(A.ORIENTS)}, got {normals_orient!r}")
+    if normals_orient != "point" and estimate_normals is None:
+        raise SystemExit("--normals_orient goes with --estimate_normals")
     if attr_search not in A.SEARCHES:
         raise SystemExit(f"--attr_search: one of {', '.join(A.SEARCHES)}, got {attr_search!r}")
     plan = None
@@ -189,7 +195,7 @@ def _upsampling(data_paths, target_path, checkpoint_path, up_ratio, num_outlier,
         if plan is not None:
             cols.append(A.transfer(pred, cloud, attr, plan, attr_k, search=attr_search))
         if estimate_normals is not None:
-            cols.append(A.estimate_normals(pred, estimate_normals, normals_viewpoint, search=attr_search)[0])
+            cols.append(A.estimate_normals(pred, estimate_normals, normals_viewpoint, search=attr_search, orient=normals_orient)[0])
         return torch.cat(cols, dim=-1) if len(cols) > 1 else pred
 
     def with_columns_ragged(pred, clouds, attrs):                  # a ragged pass: lists of [M_i,3], [N_i,3], [N_i,C]
@@ -197,7 +203,8 @@ def _upsampling(data_paths, target_path, checkpoint_path, up_ratio, num_outlier,
         if plan is not None:
             cols.append(A.transfer_ragged(pred, clouds, attrs, plan, attr_k, search=attr_search))
         if estimate_normals is not None:
-            cols.append(A.estimate_normals_ragged(pred, estimate_normals, normals_viewpoint, search=attr_search)[0])
+            cols.append(A.estimate_normals_ragged(pred, estimate_normals, normals_viewpoint, search=attr_search,
+                                                  orient=normals_orient)[0])
         return [torch.cat(c, dim=-1) for c in zip(*cols)] if len(cols) > 1 else pred
 
     def npoint_of(n):
@@ -297,9 +304,16 @@ def main(argv=None, network_cls=PointInterpFlow, add_arguments=None, network_set
                         help="(not in the reference) the neighbour search behind --attributes and --estimate_normals: brute = one "
                              "workgroup sorts the whole cloud per output point, grid = a uniform grid of the cloud, far faster on "
                              "large clouds; the same files either way (default: brute)")
+    parser.add_argument("--normals_orient", type=str, default=None, choices=("point", "propagate"),
+                        help="(not in the reference) the sign of the --estimate_normals columns: point = every point on its own, "
+                             "away from the centroid or towards --normals_viewpoint; propagate = carried along a minimum spanning "
+                             "tree of the neighbour graph from each piece's highest point (or the one nearest to the viewpoint), "
+                             "consistent in cavities and on inner walls too (default: point)")
     if add_arguments is not None:
         add_arguments(parser)
     args = parser.parse_args(argv)
+    if args.normals_orient is not None and args.estimate_normals is None:
+        raise SystemExit("--normals_orient goes with --estimate_normals")
     if args.attr_search is not None and args.attributes is None and args.estimate_normals is None:
         raise SystemExit("--attr_search goes with --attributes or --estimate_normals")
     os.makedirs(args.target, exist_ok=True)            # exist_ok: several ranks may race to create it
@@ -310,7 +324,7 @@ def main(argv=None, network_cls=PointInterpFlow, add_arguments=None, network_set
                num_upsampling=args.num_out, seed=args.seed, network_cls=network_cls, cloud_batch=args.cloud_batch,
                pass_points=args.pass_points, tile_points=args.tile_points, attributes=args.attributes, attr_k=args.attr_k,
                estimate_normals=args.estimate_normals, normals_viewpoint=args.normals_viewpoint,
-               attr_search=args.attr_search or "brute",
+               attr_search=args.attr_search or "brute", normals_orient=args.normals_orient or "point",
                network_setup=(lambda net: network_setup(net, args)) if network_setup is not None else None)
 
 
