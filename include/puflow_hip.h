@@ -1208,6 +1208,62 @@ int pf_normals_orient(const float* pts, const float* normal_in, const int* idx, 
 int pf_normals_orient_ragged(const float* pts, const float* normal_in, const int* idx, const int* m, int B, int K,
                              const float* viewpoint, void* ws, long long ws_bytes, float* normal_out, int* comp_out, void* stream);
 
+/* ---- surface from an oriented cloud: IMLS and marching tetrahedra (csrc/recon.hip) ---------------------------
+ * Three stages on the device: mark a narrow band of grid corners around the points, compute an implicit value at those corners
+ * from the K nearest oriented points, extract the zero set with marching tetrahedra, vertices welded by grid-edge id.
+ *   Grid      (host) cell size h; with pad = 3, in double, o_a = lo_a - pad h and D_a = ceil((hi_a - lo_a) / h) + 2 pad + 1
+ *             corners per axis, lo / hi the fp32 box of the points.  Corner coordinates are three fp32 tables made on the host,
+ *             g_a[i] = float32(o_a + i h), double rounded once; the kernels read the tables and never recompute a coordinate, so
+ *             no contraction choice can move a corner.  x is the fastest index: corner c = (k D_y + j) D_x + i.  Every D_a >= 2
+ *             (else PF_ERR_SHAPE) and D_x D_y D_z <= PF_RECON_MAX_CORNERS (else PF_ERR_UNSUPPORTED): dense arrays over the box,
+ *             the band only limits where work is done.
+ *   Cell      cell_a(p) = (number of entries of g_a that are <= p_a) - 1, clamped to 0 .. D_a - 2: a binary search in the table
+ *             itself, monotone and exact by construction.
+ *   Band      pf_recon_mark: flags [D_z, D_y, D_x] bytes, cleared, then every point stores 1 at the 4 x 4 x 4 corners
+ *             cell_a - 1 .. cell_a + 2 of its cell (those inside the box; pad = 3 keeps all of them inside).  Plain stores of one
+ *             value, no atomics.  A cell is ACTIVE when all 8 of its corners are flagged.
+ *   Value     pf_imls: query [Q,3], pts / normals [N,3] (unit normals), idx [Q,K] from pf_knn_grid(ref = pts, query), entries
+ *             clamped to the cloud.  Per query x, in double: d2_k = |x - p_k|^2 from the coordinates (not the search's fp32
+ *             value), w_k = exp(-(d2_k - d2_0) / sigma_h^2) - neighbour 0 has weight 1, the denominator cannot underflow -
+ *             f(x) = sum_k w_k (n_k . (x - p_k)) / sum_k w_k, summed for k = 0 .. K - 1 in that order, rounded to fp32 once.
+ *             sigma_h = sigma h > 0 and 1 / sigma_h^2 finite.  One lane per query.
+ *   Tets      INSIDE means f < 0.  Every active cell with lower corner c is cut into 6 tets along its main diagonal: for the
+ *             permutations pi of (x, y, z) in lexicographic order, v0 = c, v1 = v0 + e_pi0, v2 = v1 + e_pi1, v3 = c + (1,1,1).
+ *             The cut is the same in every cell, so tet faces match across cells.
+ *   Edges     7 classes by offset: (1,0,0) (0,1,0) (0,0,1) (1,1,0) (1,0,1) (0,1,1) (1,1,1) = 0 .. 6.  An edge is owned by its
+ *             lower corner: edge id = 7 c + class, as long long.
+ *   Triangles per tet: 1 or 3 corners inside - one triangle on the three edges at the lone corner, the others in tet order;
+ *             2 inside - with the inside pair a < b and the outside pair c < d in tet order, (ac, ad, bd) and (ac, bd, bc).
+ *             The last two edges are swapped where needed so that the triangle's normal points to the positive side
+ *             (counter-clockwise seen from outside), decided in integers as if every vertex sat at its edge's midpoint, from a
+ *             table generated in code: a triangle that an exact 0 in f makes degenerate is oriented like its neighbours.
+ *   Order     triangles go out in the order (cell index c, tet 0 .. 5, triangle 0 .. 1).  pf_mtet_count: count [D_z, D_y, D_x]
+ *             ints, the triangles of cell c (0 where c is no active cell).  pf_mtet_emit: first [D_z, D_y, D_x] long long, the
+ *             exclusive prefix sum of count; T its total; edge_ids [T,3] long long.  Triangles outside 0 .. T - 1 are dropped.
+ *   Vertices  pf_mtet_vertices: edge_ids [V] (the distinct ids, ascending) -> verts [V,3].  Vertex (a, b), a < b by corner index,
+ *             sits at t = f_a / (f_a - f_b), an IEEE fp32 division; per component v = g[a] + t (g[b] - g[a]) with the subtraction,
+ *             the product and the sum as three separately rounded fp32 operations.  An id that names no edge of the box: (0,0,0).
+ * The mesh is bit-determined by the inputs and the same from run to run.  f is read at flagged corners only.
+ * Every loop in every kernel has a constant or host-given bound; no spin-wait, no grid barrier, no cooperative launch, no
+ * atomics.  Before any device work: PF_ERR_NULL; PF_ERR_SHAPE (N, Q, T or V <= 0, a D_a < 2, K > N, more than 2^31 / 3 points or
+ * queries, sigma_h not positive, T > 12 or V > 7 times the corners); PF_ERR_UNSUPPORTED (K outside 1 .. PF_KNN_GRID_MAX_K, a
+ * box over the cap). */
+#define PF_RECON_MAX_CORNERS (1 << 26)
+int pf_recon_mark(const float* pts, int N, const float* gx, const float* gy, const float* gz, int Dx, int Dy, int Dz,
+                  unsigned char* flags, void* stream);
+int pf_imls(const float* query, const float* pts, const float* normals, const int* idx, int Q, int N, int K, double sigma_h,
+            float* f, void* stream);
+/* the generated triangle table as the kernels hold it, copied to HOST memory (no device work): corner[6][4], the cube corner
+ * x | y << 1 | z << 2 of every tet vertex; ntri[6][16], triangles per tet and sign pattern (bit v: vertex v inside);
+ * edge[6][16][2][3], per triangle its three edges as (owner's cube corner) << 3 | class.  Returns PF_MTET_TABLE_BYTES. */
+#define PF_MTET_TABLE_BYTES 696
+int pf_mtet_table(unsigned char* out, int bytes);
+int pf_mtet_count(const float* f, const unsigned char* flags, int Dx, int Dy, int Dz, int* count, void* stream);
+int pf_mtet_emit(const float* f, const unsigned char* flags, int Dx, int Dy, int Dz, const long long* first, long long T,
+                 long long* edge_ids, void* stream);
+int pf_mtet_vertices(const long long* edge_ids, long long V, const float* f, const float* gx, const float* gy, const float* gz,
+                     int Dx, int Dy, int Dz, float* verts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

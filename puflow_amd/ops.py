@@ -651,3 +651,91 @@ def normals_orient_ragged(pts: torch.Tensor, normals: torch.Tensor, idx: torch.T
                                             idx.shape[1], _viewpoint(viewpoint), ws.data_ptr(), nbytes, out.data_ptr(),
                                             comp.data_ptr(), _stream()), "pf_normals_orient_ragged")
     return out, comp
+
+
+# ---- surface from an oriented cloud (csrc/recon.hip; the contract is in puflow_hip.h) -------------------------------------------
+def _recon_box(tables, what: str):
+    """three float32 corner tables on the device -> (contiguous tables, (D_x, D_y, D_z))"""
+    tables = [_f32c(t) for t in tables]
+    if len(tables) != 3 or any(t.dim() != 1 for t in tables):
+        raise _lib.PuflowHipError(f"{what}: three corner tables [D_x], [D_y], [D_z]")
+    return tables, tuple(int(t.shape[0]) for t in tables)
+
+
+def _recon_dense(t: torch.Tensor, dims, dtype, what: str) -> torch.Tensor:
+    if not t.is_cuda:
+        raise _lib.PuflowHipError("puflow_amd ops need GPU tensors (no CPU fallback)")
+    if t.dtype != dtype or tuple(t.shape) != (dims[2], dims[1], dims[0]):
+        raise _lib.PuflowHipError(f"{what}: a {dtype} array [D_z, D_y, D_x] = {(dims[2], dims[1], dims[0])}, got {t.dtype} "
+                                  f"{tuple(t.shape)}")
+    return t.contiguous()
+
+
+def recon_mark(pts: torch.Tensor, tables) -> torch.Tensor:
+    """pf_recon_mark: pts [N,3], the corner tables -> uint8 flags [D_z, D_y, D_x], 1 at the 4 x 4 x 4 corners around every
+    point's cell"""
+    lib = _lib.load()
+    pts = _f32c(pts)
+    if pts.dim() != 2 or pts.shape[1] != 3 or pts.shape[0] <= 0:
+        raise _lib.PuflowHipError(f"recon_mark: pts [N,3], got {tuple(pts.shape)}")
+    (gx, gy, gz), (Dx, Dy, Dz) = _recon_box(tables, "recon_mark")
+    flags = torch.empty((Dz, Dy, Dx), dtype=torch.uint8, device=pts.device)
+    _lib.check(lib.pf_recon_mark(pts.data_ptr(), pts.shape[0], gx.data_ptr(), gy.data_ptr(), gz.data_ptr(), Dx, Dy, Dz,
+                                 flags.data_ptr(), _stream()), "pf_recon_mark")
+    return flags
+
+
+def imls(query: torch.Tensor, pts: torch.Tensor, normals: torch.Tensor, idx: torch.Tensor, sigma_h: float) -> torch.Tensor:
+    """pf_imls: query [Q,3], pts / normals [N,3], idx int32 [Q,K] from knn_grid(ref = pts, query) -> the implicit value [Q]"""
+    lib = _lib.load()
+    query, pts, normals, idx = _f32c(query), _f32c(pts), _f32c(normals), _i32c(idx, "imls")
+    if query.dim() != 2 or query.shape[1] != 3 or pts.dim() != 2 or pts.shape[1] != 3 or normals.shape != pts.shape or \
+            idx.dim() != 2 or idx.shape[0] != query.shape[0] or query.shape[0] <= 0:
+        raise _lib.PuflowHipError(f"imls: query [Q,3], pts / normals [N,3] and idx [Q,K], got {tuple(query.shape)}, {tuple(pts.shape)}, "
+                                  f"{tuple(normals.shape)} and {tuple(idx.shape)}")
+    f = torch.empty((query.shape[0],), dtype=torch.float32, device=query.device)
+    _lib.check(lib.pf_imls(query.data_ptr(), pts.data_ptr(), normals.data_ptr(), idx.data_ptr(), query.shape[0], pts.shape[0],
+                           idx.shape[1], float(sigma_h), f.data_ptr(), _stream()), "pf_imls")
+    return f
+
+
+def mtet_count(f: torch.Tensor, flags: torch.Tensor) -> torch.Tensor:
+    """pf_mtet_count: f float32 / flags uint8 [D_z, D_y, D_x] -> triangles per cell, int32 [D_z, D_y, D_x]"""
+    lib = _lib.load()
+    if flags.dim() != 3:
+        raise _lib.PuflowHipError(f"mtet_count: flags [D_z, D_y, D_x], got {tuple(flags.shape)}")
+    dims = (int(flags.shape[2]), int(flags.shape[1]), int(flags.shape[0]))
+    f, flags = _recon_dense(f, dims, torch.float32, "mtet_count"), _recon_dense(flags, dims, torch.uint8, "mtet_count")
+    count = torch.empty(flags.shape, dtype=torch.int32, device=f.device)
+    _lib.check(lib.pf_mtet_count(f.data_ptr(), flags.data_ptr(), dims[0], dims[1], dims[2], count.data_ptr(), _stream()),
+               "pf_mtet_count")
+    return count
+
+
+def mtet_emit(f: torch.Tensor, flags: torch.Tensor, first: torch.Tensor, total: int) -> torch.Tensor:
+    """pf_mtet_emit: first int64 [D_z, D_y, D_x] (the exclusive prefix sum of mtet_count), total its sum -> the triangles' edge
+    ids, int64 [total, 3], in the order (cell, tet, triangle)"""
+    lib = _lib.load()
+    if flags.dim() != 3:
+        raise _lib.PuflowHipError(f"mtet_emit: flags [D_z, D_y, D_x], got {tuple(flags.shape)}")
+    dims = (int(flags.shape[2]), int(flags.shape[1]), int(flags.shape[0]))
+    f, flags = _recon_dense(f, dims, torch.float32, "mtet_emit"), _recon_dense(flags, dims, torch.uint8, "mtet_emit")
+    first = _recon_dense(first, dims, torch.int64, "mtet_emit")
+    ids = torch.empty((int(total), 3), dtype=torch.int64, device=f.device)
+    _lib.check(lib.pf_mtet_emit(f.data_ptr(), flags.data_ptr(), dims[0], dims[1], dims[2], first.data_ptr(), int(total),
+                                ids.data_ptr(), _stream()), "pf_mtet_emit")
+    return ids
+
+
+def mtet_vertices(edge_ids: torch.Tensor, f: torch.Tensor, tables) -> torch.Tensor:
+    """pf_mtet_vertices: the distinct edge ids int64 [V], f [D_z, D_y, D_x], the corner tables -> float32 [V,3]"""
+    lib = _lib.load()
+    (gx, gy, gz), dims = _recon_box(tables, "mtet_vertices")
+    f = _recon_dense(f, dims, torch.float32, "mtet_vertices")
+    if not edge_ids.is_cuda or edge_ids.dtype != torch.int64 or edge_ids.dim() != 1 or edge_ids.shape[0] <= 0:
+        raise _lib.PuflowHipError(f"mtet_vertices: edge ids int64 [V] on the GPU, got {edge_ids.dtype} {tuple(edge_ids.shape)}")
+    edge_ids = edge_ids.contiguous()
+    verts = torch.empty((edge_ids.shape[0], 3), dtype=torch.float32, device=f.device)
+    _lib.check(lib.pf_mtet_vertices(edge_ids.data_ptr(), edge_ids.shape[0], f.data_ptr(), gx.data_ptr(), gy.data_ptr(),
+                                    gz.data_ptr(), dims[0], dims[1], dims[2], verts.data_ptr(), _stream()), "pf_mtet_vertices")
+    return verts

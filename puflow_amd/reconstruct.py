@@ -1,0 +1,227 @@
+"""A triangle mesh from an oriented cloud (DESIGN.md 8e "Surface from an oriented cloud"; the contract is in puflow_hip.h).
+
+Three stages, all on the device (csrc/recon.hip): a narrow band of grid corners around the points, an IMLS value - a weighted
+mean of signed tangent-plane distances to the `k` nearest oriented points (pf_knn_grid) - at those corners, and its zero set by
+marching tetrahedra.  Vertices are welded by grid-edge id, so a closed surface comes out closed, and the mesh is the same bytes
+from run to run.  There is no CPU path.
+
+  verts, faces, info = mesh_from_cloud(points, normals)       # [N,3], [N,3] -> [V,3] float32, [F,3] int32, {h, dims, open_edges}
+  f = implicit(points, normals, query, h=cell_size(points))   # the implicit value at any points
+  python -m puflow_amd.reconstruct --source DIR --target DIR  # every x y z nx ny nz file of DIR -> <name>.off
+"""
+from __future__ import annotations
+
+import os
+from argparse import ArgumentParser
+
+import numpy as np
+import torch
+
+from . import _lib, ops
+
+PAD = 3                                 # corners of margin on every side of the cloud's box: keeps the band inside
+MAX_CORNERS = _lib.PF_RECON_MAX_CORNERS
+CELL_NEIGHBOUR = 6                      # the cell size follows the distance to this nearest OTHER point
+
+
+def _cloud(points, normals, what: str):
+    for t, name in ((points, "points"), (normals, "normals")):
+        if t is None:
+            continue
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise _lib.PuflowHipError(f"{what}: {name} is a GPU tensor (no CPU path)")
+        if t.dim() != 2 or t.shape[1] != 3 or t.shape[0] <= 0:
+            raise _lib.PuflowHipError(f"{what}: {name} [N,3], got {tuple(t.shape)}")
+    if normals is not None and normals.shape != points.shape:
+        raise _lib.PuflowHipError(f"{what}: one normal per point, got {tuple(points.shape)} and {tuple(normals.shape)}")
+    return ops._f32c(points), (ops._f32c(normals) if normals is not None else None)
+
+
+def _k(k, n: int, what: str) -> int:
+    k = int(k)
+    if not 1 <= k <= _lib.PF_KNN_GRID_MAX_K or k > n:
+        raise _lib.PuflowHipError(f"{what}: k = {k} neighbours in a cloud of {n} points; 1 .. {_lib.PF_KNN_GRID_MAX_K} (and at most "
+                                  "the cloud) are supported")
+    return k
+
+
+def _positive(v, name: str, what: str) -> float:
+    v = float(v)
+    if not (v > 0.0 and np.isfinite(v)):
+        raise _lib.PuflowHipError(f"{what}: {name} = {v} is not a positive number")
+    return v
+
+
+def _stats(points: torch.Tensor, want_median: bool):
+    """(median squared distance to the 6th nearest other point or None, lo [3], hi [3]) of a cloud, float32 values as float64, from
+    ONE host read"""
+    parts = [points.min(dim=0).values, points.max(dim=0).values]
+    if want_median:
+        n = points.shape[0]
+        if n <= CELL_NEIGHBOUR:
+            raise _lib.PuflowHipError(f"cell_size: a cloud of {n} points has no {CELL_NEIGHBOUR}th neighbour; give the cell size")
+        _, d2 = ops.knn_grid(points[None], points[None], CELL_NEIGHBOUR + 1)
+        parts.append(torch.median(d2[0, :, CELL_NEIGHBOUR]).reshape(1))       # the lower median
+    host = torch.cat(parts).cpu().numpy().astype(np.float64)
+    return (float(host[6]) if want_median else None), host[0:3], host[3:6]
+
+
+def cell_size(points: torch.Tensor, scale: float = 1.0) -> float:
+    """scale x sqrt(m), m the lower median over the points of the fp32 squared distance to the 6th nearest other point"""
+    points, _ = _cloud(points, None, "cell_size")
+    m, _lo, _hi = _stats(points, True)
+    return _positive(scale, "scale", "cell_size") * float(np.sqrt(m))
+
+
+def corner_tables(lo, hi, h: float):
+    """the fp32 box and the cell size -> ((D_x, D_y, D_z), three float32 numpy tables g_a[i] = float32(o_a + i h))"""
+    lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
+    o = lo - PAD * h
+    cells = np.ceil((hi - lo) / h)
+    if not (cells < MAX_CORNERS).all() or int(cells[0] + 2 * PAD + 1) * int(cells[1] + 2 * PAD + 1) * int(cells[2] + 2 * PAD + 1) > MAX_CORNERS:
+        raise _lib.PuflowHipError(
+            f"reconstruct: a box of {' x '.join(str(int(c) + 2 * PAD + 1) if np.isfinite(c) else 'inf' for c in cells)} corners at "
+            f"cell size {h:.6g} is over the cap of {MAX_CORNERS} ({_lib.load().pf_error_string(_lib.PF_ERR_UNSUPPORTED).decode()}): "
+            "use a larger --cell (or --cell_scale)")
+    dims = tuple(int(c) + 2 * PAD + 1 for c in cells)
+    return dims, [(o[a] + np.arange(dims[a], dtype=np.float64) * h).astype(np.float32) for a in range(3)]
+
+
+def implicit(points: torch.Tensor, normals: torch.Tensor, query: torch.Tensor, k: int = 8, sigma: float = 1.0, h: float = None):
+    """The IMLS value at query [Q,3]: f = sum_k w_k n_k.(x - p_k) / sum_k w_k over the k nearest points, w_k = exp(-(d2_k - d2_0) /
+    (sigma h)^2), in double on the device, float32 [Q].  h: the cell size (default: cell_size(points))."""
+    points, normals = _cloud(points, normals, "implicit")
+    if not torch.is_tensor(query) or not query.is_cuda or query.dim() != 2 or query.shape[1] != 3 or query.shape[0] <= 0:
+        raise _lib.PuflowHipError("implicit: query is a GPU tensor [Q,3] (no CPU path)")
+    k = _k(k, points.shape[0], "implicit")
+    h = cell_size(points) if h is None else _positive(h, "h", "implicit")
+    query = ops._f32c(query)
+    idx, _ = ops.knn_grid(points[None], query[None], k)
+    return ops.imls(query, points, normals, idx[0], _positive(sigma, "sigma", "implicit") * h)
+
+
+def _open_edges(faces: torch.Tensor, nv: int) -> torch.Tensor:
+    """undirected mesh edges used by exactly one triangle, counted on the device (a 0-dim tensor)"""
+    a = torch.cat([faces[:, 0], faces[:, 1], faces[:, 2]])
+    b = torch.cat([faces[:, 1], faces[:, 2], faces[:, 0]])
+    _, n = torch.unique(torch.minimum(a, b) * nv + torch.maximum(a, b), return_counts=True)
+    return (n == 1).sum()
+
+
+def extract(f: torch.Tensor, flags: torch.Tensor, tables):
+    """marching tetrahedra over the active cells: f float32 / flags uint8 [D_z, D_y, D_x], the corner tables (device) ->
+    (verts float32 [V,3] in ascending edge id, faces int64 [T,3] in the order (cell, tet, triangle))"""
+    count = ops.mtet_count(f, flags)
+    incl = torch.cumsum(count.reshape(-1), dim=0)
+    total = int(incl[-1])                                                   # a size: the triangle array's
+    if total == 0:
+        return torch.zeros((0, 3), dtype=torch.float32, device=f.device), torch.zeros((0, 3), dtype=torch.int64, device=f.device)
+    first = (incl - count.reshape(-1)).reshape(count.shape)
+    ids = ops.mtet_emit(f, flags, first, total)
+    edge, inverse = torch.unique(ids.reshape(-1), sorted=True, return_inverse=True)
+    return ops.mtet_vertices(edge, f, tables), inverse.reshape(-1, 3)
+
+
+def mesh_from_cloud(points: torch.Tensor, normals: torch.Tensor, cell: float = None, cell_scale: float = 1.0, k: int = 8,
+                    sigma: float = 1.0):
+    """points, normals [N,3] on the GPU (unit normals with consistent signs: estimate_normals(..., orient="propagate") or a
+    scanner's) -> (verts [V,3] float32, faces [F,3] int32, info).  cell: the grid's cell size; default cell_scale x the median
+    distance to the 6th nearest other point.  info: h, dims (D_x, D_y, D_z) and open_edges, the number of mesh edges used by one
+    triangle only - 0 for a closed surface; a cell below the sampling spacing tears holes, and a scan's real boundary stays one."""
+    points, normals = _cloud(points, normals, "mesh_from_cloud")
+    k = _k(k, points.shape[0], "mesh_from_cloud")
+    sigma = _positive(sigma, "sigma", "mesh_from_cloud")
+    if cell is not None:
+        h = _positive(cell, "cell", "mesh_from_cloud")
+        _, lo, hi = _stats(points, False)
+    else:
+        scale = _positive(cell_scale, "cell_scale", "mesh_from_cloud")
+        m, lo, hi = _stats(points, True)
+        h = _positive(scale * float(np.sqrt(m)), "the cell size from the cloud's spacing", "mesh_from_cloud")
+    dims, host_tables = corner_tables(lo, hi, h)
+    dev = points.device
+    tables = [torch.from_numpy(t).to(dev) for t in host_tables]
+    flags = ops.recon_mark(points, tables)
+    corner = torch.nonzero(flags.reshape(-1)).reshape(-1)                   # ascending corner index
+    Dx, Dy = dims[0], dims[1]
+    query = torch.stack([tables[0][corner % Dx], tables[1][(corner // Dx) % Dy], tables[2][corner // (Dx * Dy)]], dim=1)
+    idx, _ = ops.knn_grid(points[None], query[None], k)
+    f = torch.empty(flags.shape, dtype=torch.float32, device=dev)           # inactive corners are never read
+    f.reshape(-1)[corner] = ops.imls(query, points, normals, idx[0], sigma * h)
+    verts, faces = extract(f, flags, tables)
+    open_edges = int(_open_edges(faces, verts.shape[0])) if faces.shape[0] else 0
+    return verts, faces.to(torch.int32), {"h": h, "dims": dims, "open_edges": open_edges}
+
+
+def write_off(path, verts, faces) -> None:
+    """an OFF file: vertex rows as save_xyz formats them (%.6f), face rows `3 a b c`"""
+    import ctypes
+    verts = np.ascontiguousarray(verts.detach().cpu().numpy() if torch.is_tensor(verts) else verts, dtype=np.float32).reshape(-1, 3)
+    faces = np.ascontiguousarray(faces.detach().cpu().numpy() if torch.is_tensor(faces) else faces).reshape(-1, 3)
+    with open(path, "wb") as fh:
+        fh.write(b"OFF\n%d %d 0\n" % (len(verts), len(faces)))
+        if len(verts):
+            lib = _lib.load()
+            cap = lib.pf_format_xyz_bound(len(verts), 3)
+            buf = ctypes.create_string_buffer(cap)
+            m = lib.pf_format_xyz(verts.ctypes.data, len(verts), 3, ctypes.addressof(buf), cap)
+            if m < 0:
+                _lib.check(int(m), "pf_format_xyz")
+            fh.write(memoryview(buf)[:m])
+        fh.write((("3 %d %d %d\n" * len(faces)) % tuple(faces.ravel().tolist())).encode())
+
+
+OPEN_EDGES_LINE = ("{name}: {n} open edges - the mesh has a boundary: the cell ({h:.6g}) is below the sampling spacing somewhere "
+                   "(try a larger --cell or --cell_scale), or the scan really ends there")
+
+
+@torch.no_grad()
+def reconstruct_files(paths, target: str, cell=None, cell_scale: float = 1.0, k: int = 8, sigma: float = 1.0,
+                      normal_column: int = 4, device="cuda:0"):
+    from .upsample import load_xyz
+    c0 = int(normal_column) - 1
+    if c0 < 3:
+        raise SystemExit("--normal_column is the 1-based first column of the normal, after x y z: 4 or more")
+    clouds = []
+    for p in sorted(paths):
+        rows = np.atleast_2d(load_xyz(p))
+        if rows.shape[1] < c0 + 3:
+            raise SystemExit(f"{p}: {rows.shape[1]} columns, no normal in columns {c0 + 1} .. {c0 + 3}; write oriented normals with "
+                             "--estimate_normals K --normals_orient propagate (upsample / upsample_cnf)")
+        clouds.append((p, rows))
+    os.makedirs(target, exist_ok=True)
+    out = []
+    for p, rows in clouds:
+        xyz = torch.from_numpy(np.ascontiguousarray(rows[:, :3])).to(device)
+        nrm = torch.from_numpy(np.ascontiguousarray(rows[:, c0:c0 + 3])).to(device)
+        nrm = nrm / nrm.norm(dim=1, keepdim=True).clamp_min(1e-30)          # six printed decimals are not unit length
+        verts, faces, info = mesh_from_cloud(xyz, nrm, cell=cell, cell_scale=cell_scale, k=k, sigma=sigma)
+        name = os.path.splitext(os.path.basename(p))[0] + ".off"
+        write_off(os.path.join(target, name), verts, faces)
+        if info["open_edges"] > 0:
+            print(OPEN_EDGES_LINE.format(name=name, n=info["open_edges"], h=info["h"]), flush=True)
+        out.append((os.path.join(target, name), info))
+    return out
+
+
+def main(argv=None):
+    parser = ArgumentParser(description="x y z nx ny nz clouds of a directory -> <name>.off triangle meshes")
+    parser.add_argument("--source", type=str, required=True, help="Path of input directory")
+    parser.add_argument("--target", type=str, required=True, help="Path of output directory")
+    size = parser.add_mutually_exclusive_group()
+    size.add_argument("--cell", type=float, default=None, help="the grid's cell size")
+    size.add_argument("--cell_scale", type=float, default=1.0,
+                      help="cell size as a multiple of the median distance to the 6th nearest other point")
+    parser.add_argument("--k", type=int, default=8, help="oriented points per implicit value")
+    parser.add_argument("--sigma", type=float, default=1.0, help="width of the weights, in cells")
+    parser.add_argument("--normal_column", type=int, default=4, help="1-based first column of the normal")
+    args = parser.parse_args(argv)
+    paths = []
+    for root, _dirs, files in os.walk(args.source):
+        paths.extend([os.path.join(root, f) for f in files if ".xyz" in f])
+    reconstruct_files(paths, args.target, cell=args.cell, cell_scale=args.cell_scale, k=args.k, sigma=args.sigma,
+                      normal_column=args.normal_column)
+
+
+if __name__ == "__main__":
+    main()
