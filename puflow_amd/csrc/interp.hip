@@ -8,10 +8,13 @@
 // last conv, the EdgeConv's conv_out) that feeds the weight unit's first conv with no nonlinearity in
 // between (interpflow.py:134,144), so the host composes them (packing.fold_state_dict):
 //     w1 = (W0a W6) d2 + (W0b Gout) feat + [W0b (PA x_i + QB x_j + pb) + b0 + W0a b6]
-// Every term that is affine in the edge's raw inputs e = (x_i, x_j, |x_i - x_j|, 1) - the distance encoder's first
+// Every term that is affine in the edge's raw inputs e = (x_i, 16 (x_i - x_j), |x_i - x_j|, 1) - the distance encoder's first
 // layer, the EdgeConv pre-activations, the bracket above - is ONE MFMA against an 8-column "edge table": the three terms
-// of the split product share the 32 k-slots (pf_mfma.h pf_edge_operand / pf_mm1, packing._etab_frag1).  Only the first R
-// rows of the last weight conv are computed (interpflow.py:180).
+// of the split product share the 32 k-slots (pf_mfma.h pf_edge_operand / pf_mm1, packing._etab_frag1).  The neighbour enters
+// as the fp32 DIFFERENCE x_i - x_j (PA x_i + QB x_j = (PA + QB) x_i - QB (x_i - x_j), packing._etab_rel), times 2^4 to keep
+// its low half off fp16's subnormal floor: trained weights make PA and QB large and nearly opposite, and the split images of
+// two absolute coordinates would cost the edge vector 2^-22 |x| / |x_i - x_j| of its value.  Only the first R rows of the
+// last weight conv are computed (interpflow.py:180).
 // Arithmetic: split-fp16 products with a natural-scale low half (pf_mfma.h "f16n": one accumulator, no fold), fp32-class
 // accuracy; 20 table fragments + 71 fragment pairs = 233 fp16 MFMAs per tile where the unfolded f32 formulation needs 1216.
 // Scale plan (packing.interp_scaled): every activation is stored times a power of two 2^a (growth block t: 2^t) and every
@@ -95,7 +98,7 @@ __global__ __launch_bounds__(NW * 64) void interp_kernel(InterpArgs a) {
         const int pt0 = wt * P * 2;
         int gi[P], gj[P];
         bool ok[P];
-        h8 e[P];                         // raw edge inputs (x_i, x_j, |x_i - x_j|, 1): hi | lo | hi | 0 over the lanes q = 0..3
+        h8 e[P];                         // raw edge inputs (x_i, 16 (x_i - x_j), |x_i - x_j|, 1): hi | lo | hi | 0 over the lanes q = 0..3
 #pragma unroll
         for (int p = 0; p < P; ++p) {
             const int g = pt0 + p * 2 + ps;
@@ -110,7 +113,7 @@ __global__ __launch_bounds__(NW * 64) void interp_kernel(InterpArgs a) {
             }
             const float v0 = xi[0] - xj[0], v1 = xi[1] - xj[1], v2 = xi[2] - xj[2];
             const float nrm = pf_sqrt(__fadd_rn(__fadd_rn(__fmul_rn(v0, v0), __fmul_rn(v1, v1)), __fmul_rn(v2, v2)));
-            const f4 e0 = {xi[0], xi[1], xi[2], xj[0]}, e1 = {xj[1], xj[2], nrm, 1.f};
+            const f4 e0 = {xi[0], xi[1], xi[2], 16.f * v0}, e1 = {16.f * v1, 16.f * v2, nrm, 1.f};     // 16 = 2^packing.ETAB_VSHIFT
             e[p] = pf_edge_operand(e0, e1, q);
         }
 

@@ -331,19 +331,43 @@ def _scaled_vec(v: np.ndarray, a: int) -> np.ndarray:
 
 INTERP_WANT = {"g": list(range(8)), "d1": 4, "d2": 6, "w1": 7, "w2": 8}
 
+# interp_kernel's edge operand is (x_i, 2^ETAB_VSHIFT (x_i - x_j), |x_i - x_j|, 1), not (x_i, x_j, ...): a trained network weighs the
+# edge vector heavily, so the coefficients of x_i and x_j are large and nearly opposite, and the split-fp16 images of two
+# ABSOLUTE coordinates (2^-23 |x| each) cost up to 2^-22 |x| / |x_i - x_j| of the edge vector - with the pretrained PU1K weights
+# 5 times the rounding error of a whole fp32 evaluation of the module (profiles/infer_anchor/accuracy.txt).  The fp32 difference
+# is exact to half an ulp of ITSELF; times 2^4 (exact; |v| <= 2 on normalised patches, 32 stored) its low half stays off fp16's
+# subnormal floor.
+ETAB_VSHIFT = 4
+
+
+def _etab_rel(PA: np.ndarray, QB: np.ndarray):
+    """Coefficients of (x_i, x_j) -> of (x_i, 2^ETAB_VSHIFT (x_i - x_j)):  PA x_i + QB x_j = (PA + QB) x_i - QB (x_i - x_j)."""
+    A, B = PA.astype(np.float64), QB.astype(np.float64)
+    return (A + B).astype(np.float32), np.ldexp(-B, -ETAB_VSHIFT).astype(np.float32)
+
+
+def _interp_tables(ip: Dict[str, np.ndarray]):
+    """The three edge tables of interp_kernel as (x_i columns, v columns, norm column or None, constant column), unscaled:
+    the distance encoder's first layer, the EdgeConv pre-activations, the weight unit's bracket (csrc/interp.hip header)."""
+    ec, ft = ip["ec"], ip["f_tab"]
+    return {"dtab": (*_etab_rel(ip["d_PA"], ip["d_QB"]), ip["d_wn"], ip["d_b0"]),
+            "ectab": (*_etab_rel(ec["PA"][:128], ec["QB"][:128]), None, ec["pb"][:128]),
+            "w1tab": (*_etab_rel(ft[:, 0:3], ft[:, 3:6]), None, ft[:, 6] + ip["f_b0"])}       # W0b.(edge table) + b0 + W0a.b6
+
 
 def interp_exps(ip: Dict[str, np.ndarray]) -> Dict[str, object]:
     """Exponents of interp_kernel's plan: g[t] growth block t, d1 / d2 the distance encoder's activations, w1 / w2 the weight
     unit's, w3 its logits' accumulator (multiplied by 2^-w3 in front of the softmax)."""
     ec = ip["ec"]
-    tab = lambda t: np.concatenate([ec["PA"][16 * t:16 * t + 16], ec["QB"][16 * t:16 * t + 16], ec["pb"][16 * t:16 * t + 16, None]], axis=1)
+    tabs = {k: np.concatenate([xi, v, np.zeros_like(c)[:, None] if n is None else n[:, None], c[:, None]], axis=1)
+            for k, (xi, v, n, c) in _interp_tables(ip).items()}
+    tab = lambda t: tabs["ectab"][16 * t:16 * t + 16]
     g: List[int] = []
     for t in range(8):
         g.append(_fit(INTERP_WANT["g"][t], (0, tab(t)), *[(g[c], ec[f"G{t}"][:, 16 * c:16 * c + 16]) for c in range(t)]))
-    ft = ip["f_tab"]
-    d1 = _fit(INTERP_WANT["d1"], (0, np.concatenate([ip["d_PA"], ip["d_QB"], ip["d_wn"][:, None], ip["d_b0"][:, None]], axis=1)))
+    d1 = _fit(INTERP_WANT["d1"], (0, tabs["dtab"]))
     d2 = _fit(INTERP_WANT["d2"], (d1, ip["d_W3"]))
-    w1 = _fit(INTERP_WANT["w1"], (0, np.concatenate([ft[:, :7], ip["f_b0"][:, None]], axis=1)), (d2, ip["f_dW"]),
+    w1 = _fit(INTERP_WANT["w1"], (0, tabs["w1tab"]), (d2, ip["f_dW"]),
               *[(g[c], ip["f_eW"][:, 16 * c:16 * c + 16]) for c in range(8)])
     w2 = _fit(INTERP_WANT["w2"], (w1, ip["w_W3"]))
     w3 = w2 + _f16n_exp(ip["w_W6"])                # covers the replicated first four rows as well
@@ -353,7 +377,8 @@ def interp_exps(ip: Dict[str, np.ndarray]) -> Dict[str, object]:
 def interp_scaled(ip: Dict[str, np.ndarray]):
     """-> (exponents, {name: fp32 matrix / vector as the kernel's images store it}).  Tables are dense [rows, 32] (_etab_dense)."""
     x = interp_exps(ip)
-    ec, ft, g = ip["ec"], ip["f_tab"], x["g"]
+    ec, g = ip["ec"], x["g"]
+    tabs = _interp_tables(ip)
     gr = np.repeat(g, 16)                                        # per growth channel
     W6r = np.zeros((16, 64), np.float32)           # R <= 4 fast path: rows 0..3 replicated into every 4-row q group
     b6r = np.zeros(16, np.float32)
@@ -361,10 +386,10 @@ def interp_scaled(ip: Dict[str, np.ndarray]):
         W6r[4 * q:4 * q + 4] = ip["w_W6"][:4]
         b6r[4 * q:4 * q + 4] = ip["w_b6"][:4]
     m = {
-        "dtab": _scaled(_etab_dense(ip["d_PA"], ip["d_QB"], ip["d_wn"], ip["d_b0"]), x["d1"]),
+        "dtab": _scaled(_etab_dense(*tabs["dtab"]), x["d1"]),
         "d_W3": _scaled(ip["d_W3"], x["d2"], x["d1"]), "d_b3": _scaled_vec(ip["d_b3"], x["d2"]),
-        "ectab": _scaled(_etab_dense(ec["PA"][:128], ec["QB"][:128], None, ec["pb"][:128]), gr),
-        "w1tab": _scaled(_etab_dense(ft[:, 0:3], ft[:, 3:6], None, ft[:, 6] + ip["f_b0"]), x["w1"]),   # W0b.(edge table) + b0 + W0a.b6
+        "ectab": _scaled(_etab_dense(*tabs["ectab"]), gr),
+        "w1tab": _scaled(_etab_dense(*tabs["w1tab"]), x["w1"]),
         "f_dW": _scaled(ip["f_dW"], x["w1"], x["d2"]), "f_eW": _scaled(ip["f_eW"], x["w1"], gr),
         "w_W3": _scaled(ip["w_W3"], x["w2"], x["w1"]), "w_b3": _scaled_vec(ip["w_b3"], x["w2"]),
         "w_W6": _scaled(W6r, x["w3"], x["w2"]), "w_b6": _scaled_vec(b6r, x["w3"]),

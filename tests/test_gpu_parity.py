@@ -195,9 +195,12 @@ def test_forward_matches_reference_with_pretrained_weights(lib, pretrained_pu1k,
     tools/make_golden_pretrained.py): trained-scale activations (|cs| up to 480) through the split-fp16 kernels.
     The contract quantities hold their bars: kNN indices bit-exact, x within 1e-5, log-det / log-likelihood within 1e-5
     relative, the conditioning features within 2e-6 of their scale.  The LATENT z is a different matter with trained weights:
-    the map cs -> z is ill-conditioned (measured on the CPU oracle: a RELATIVE perturbation of 1e-7 of cs - below fp32
-    epsilon - moves z by 9e-5, 1e-6 by 4e-4), so any fp32 evaluation in another summation order, including the f32-MFMA
-    mode here, differs from the reference's z by a few 1e-4; g inverts f with the same cs, which is why x does not."""
+    the reference's own fp32 z is 2.5e-4 (case a) and 3.2e-4 (case b) from a float64 evaluation of the same network, 1.1e-4 and
+    1.7e-4 of it from the flow's own arithmetic on exact features, while x, which g computes back with the same cs, is within
+    4e-6 (tests/test_infer_ref.py::test_trained_checkpoint_conditioning_figures pins these figures and that the golden z is as
+    far from float64 as the oracle's).  So any fp32 evaluation in another summation order, the f32-MFMA mode included, differs
+    from the reference's z by a few 1e-4 and this test can only bound it at 2e-3; the bar that means something for the latent is
+    the one against float64 in tests/test_gpu_infer_anchor.py::test_forward_end_to_end."""
     g = pretrained_pu1k
     sd = {k[3:]: torch.from_numpy(g[k]) for k in g if k.startswith("sd/")}
     B, N, seed = (int(v) for v in g[f"{case}/meta"])

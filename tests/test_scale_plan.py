@@ -51,9 +51,12 @@ def test_interp_matrices_are_the_parents_times_powers_of_two(case):
     assert 0 <= x["d1"] <= x["d2"] <= x["w1"] and max(g) <= x["w1"] <= x["w2"] <= x["w3"]
     gr = np.repeat(g, 16)
     ec, ft = ip["ec"], ip["f_tab"]
-    np.testing.assert_array_equal(_undo(m["dtab"], x["d1"]), P._etab_dense(ip["d_PA"], ip["d_QB"], ip["d_wn"], ip["d_b0"]))
-    np.testing.assert_array_equal(_undo(m["ectab"], gr), P._etab_dense(ec["PA"][:128], ec["QB"][:128], None, ec["pb"][:128]))
-    np.testing.assert_array_equal(_undo(m["w1tab"], x["w1"]), P._etab_dense(ft[:, 0:3], ft[:, 3:6], None, ft[:, 6] + ip["f_b0"]))
+    # the edge tables multiply (x_i, 2^ETAB_VSHIFT (x_i - x_j), |x_i - x_j|, 1): PA x_i + QB x_j = (PA + QB) x_i - QB (x_i - x_j)
+    rel = lambda PA, QB: ((PA.astype(np.float64) + QB).astype(np.float32), np.ldexp(-QB.astype(np.float64), -P.ETAB_VSHIFT).astype(np.float32))
+    assert P.ETAB_VSHIFT == 4                                     # csrc/interp.hip multiplies the difference by 16
+    np.testing.assert_array_equal(_undo(m["dtab"], x["d1"]), P._etab_dense(*rel(ip["d_PA"], ip["d_QB"]), ip["d_wn"], ip["d_b0"]))
+    np.testing.assert_array_equal(_undo(m["ectab"], gr), P._etab_dense(*rel(ec["PA"][:128], ec["QB"][:128]), None, ec["pb"][:128]))
+    np.testing.assert_array_equal(_undo(m["w1tab"], x["w1"]), P._etab_dense(*rel(ft[:, 0:3], ft[:, 3:6]), None, ft[:, 6] + ip["f_b0"]))
     for t in range(1, 8):
         np.testing.assert_array_equal(_undo(m[f"G{t}"], g[t], gr[:16 * t]), ec[f"G{t}"])
     np.testing.assert_array_equal(_undo(m["d_W3"], x["d2"], x["d1"]), ip["d_W3"])
