@@ -1264,6 +1264,60 @@ int pf_mtet_emit(const float* f, const unsigned char* flags, int Dx, int Dy, int
 int pf_mtet_vertices(const long long* edge_ids, long long V, const float* f, const float* gx, const float* gy, const float* gz,
                      int Dx, int Dy, int Dz, float* verts, void* stream);
 
+/* ---- the same surface in a block-sparse layout (csrc/recon_sparse.hip; DESIGN.md 8e "Block-sparse band") -------------------
+ * A second layout of the stages above whose memory and work follow the band, not the box.  It returns the dense layout's mesh
+ * bit for bit (vertices, faces and their order) wherever that one runs, and the same contract's mesh beyond its cap.
+ *   Grid      virtual: the host rule, the tables and the cell rule are the dense ones; corner c = (k D_y + j) D_x + i is a long
+ *             long and no array has D_x D_y D_z entries.  Every D_a >= 2 (else PF_ERR_SHAPE) and D_a <= PF_RECON_SPARSE_MAX_AXIS
+ *             = 2^20 (else PF_ERR_UNSUPPORTED): 7 c + 6 < 2^63, a table is at most 4 MB.
+ *   Blocks    PF_RECON_BLOCK = 8 corners per axis.  Corner (i, j, k) lies in block (i >> 3, j >> 3, k >> 3) at slot
+ *             (k & 7) << 6 | (j & 7) << 3 | (i & 7).  Block key = (bk NB_y + bj) NB_x + bi as long long, NB_a = ceil(D_a / 8).
+ *             A block array is [NB, 512]; slot number = 512 b + slot, b the block's position in the list.
+ *   List      pf_recon_block_keys: keys [N, 8] long long, per point the blocks that its 4 x 4 x 4 corners (clipped to the grid as
+ *             in pf_recon_mark) touch: entry o = ox | oy << 1 | oz << 2 is the block of the FIRST (o_a = 0) or LAST (o_a = 1) of
+ *             its corners along each axis - four corners span at most two blocks, and the same key comes twice where one block
+ *             holds all four.  The host's ascending list of the distinct keys, blocks [NB], IS the layout: 1 <= NB <=
+ *             PF_RECON_SPARSE_MAX_BLOCKS = 2^21 (else PF_ERR_UNSUPPORTED), so a slot number fits an int, and NB <= NB_x NB_y NB_z
+ *             (else PF_ERR_SHAPE).  A block is found by a binary search in the list, 32 halvings; there is no hash table.
+ *   Links     pf_recon_block_links: links [NB, 8] ints, entry o the list position of the block at offset (o & 1, o >> 1 & 1,
+ *             o >> 2 & 1), -1 where the list (or the grid) has none; entry 0 is the block itself.  A cell's corners and an
+ *             edge's upper corner are at +0 / +1, so the links are all that cells and edges need.
+ *   Band      pf_recon_mark_sparse: flags [NB, 512] bytes, cleared, then every point stores 1 at its 4 x 4 x 4 corners, after
+ *             finding its at most 8 blocks once.  Slots beyond D_a in a last block are never flagged.  A corner whose block is
+ *             not listed is skipped (the list of pf_recon_block_keys misses none).
+ *   Value     pf_knn_grid and pf_imls as above on the flagged slots in ascending slot number, scattered into f [NB, 512]; one
+ *             lane per query, so the order of the queries changes no bit.
+ *   Count     pf_mtet_count_sparse: count [NB, 512] ints, per slot the triangles of the cell whose lower corner it is, by the
+ *             dense rules; the cell's 8 corners are reached through the links, and it is active when all are flagged.
+ *   Order     triangles go out in ascending GLOBAL cell index c, then tet, then triangle: the dense order.  The host lists the
+ *             slot numbers with a non-zero count sorted by their c (distinct keys) - cells [M] long long - with first [M] long
+ *             long, the exclusive prefix sum of their counts in that order, T its total.  pf_mtet_emit_sparse: edge_ids [T,3],
+ *             7 (owner's global c) + class.  Entries of cells outside 0 .. 512 NB - 1, cells that are not active, and triangles
+ *             outside 0 .. T - 1 are dropped.
+ *   Vertices  pf_mtet_vertices_sparse: id -> (i, j, k) by 64-bit division -> the block by a search -> f_a; the upper corner
+ *             through the block's link -> f_b; then the dense arithmetic.  An id that names no edge of the grid, or whose
+ *             corners lie in no listed block: (0,0,0).
+ * Every index that comes from a list (keys, links, slots, first, ids) is clamped or checked; every loop has a constant or
+ * host-given bound; no atomics, no grid barrier, no cooperative launch.  Before any device work: PF_ERR_NULL; PF_ERR_SHAPE
+ * (N, NB, M, T or V <= 0, a D_a < 2, more than 2^31 / 3 points, NB over the grid's blocks, M > 512 NB, T > 12 M, V > 7 x 512
+ * NB); PF_ERR_UNSUPPORTED (an axis or a block list over its cap). */
+#define PF_RECON_BLOCK 8
+#define PF_RECON_SPARSE_MAX_AXIS (1 << 20)
+#define PF_RECON_SPARSE_MAX_BLOCKS (1 << 21)
+int pf_recon_block_keys(const float* pts, int N, const float* gx, const float* gy, const float* gz, int Dx, int Dy, int Dz,
+                        long long* keys, void* stream);
+int pf_recon_block_links(const long long* blocks, int NB, int Dx, int Dy, int Dz, int* links, void* stream);
+int pf_recon_mark_sparse(const float* pts, int N, const float* gx, const float* gy, const float* gz, int Dx, int Dy, int Dz,
+                         const long long* blocks, int NB, unsigned char* flags, void* stream);
+int pf_mtet_count_sparse(const float* f, const unsigned char* flags, const long long* blocks, const int* links, int NB, int Dx,
+                         int Dy, int Dz, int* count, void* stream);
+int pf_mtet_emit_sparse(const float* f, const unsigned char* flags, const long long* blocks, const int* links, int NB, int Dx,
+                        int Dy, int Dz, const long long* cells, const long long* first, long long M, long long T,
+                        long long* edge_ids, void* stream);
+int pf_mtet_vertices_sparse(const long long* edge_ids, long long V, const float* f, const long long* blocks, const int* links,
+                            int NB, const float* gx, const float* gy, const float* gz, int Dx, int Dy, int Dz, float* verts,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -739,3 +739,126 @@ def mtet_vertices(edge_ids: torch.Tensor, f: torch.Tensor, tables) -> torch.Tens
     _lib.check(lib.pf_mtet_vertices(edge_ids.data_ptr(), edge_ids.shape[0], f.data_ptr(), gx.data_ptr(), gy.data_ptr(),
                                     gz.data_ptr(), dims[0], dims[1], dims[2], verts.data_ptr(), _stream()), "pf_mtet_vertices")
     return verts
+
+
+# ---- the same surface in a block-sparse layout (csrc/recon_sparse.hip; the contract is in puflow_hip.h) -------------------------
+RECON_BLOCK = _lib.PF_RECON_BLOCK
+RECON_SLOTS = RECON_BLOCK ** 3
+
+
+def _recon_dims(dims, what: str):
+    dims = tuple(int(d) for d in dims)
+    if len(dims) != 3:
+        raise _lib.PuflowHipError(f"{what}: dims (D_x, D_y, D_z), got {dims}")
+    return dims
+
+
+def _recon_list(blocks: torch.Tensor, what: str) -> torch.Tensor:
+    """the ascending list of block keys, int64 [NB] on the device"""
+    if not torch.is_tensor(blocks) or not blocks.is_cuda:
+        raise _lib.PuflowHipError("puflow_amd ops need GPU tensors (no CPU fallback)")
+    if blocks.dtype != torch.int64 or blocks.dim() != 1 or blocks.shape[0] <= 0:
+        raise _lib.PuflowHipError(f"{what}: block keys int64 [NB], got {blocks.dtype} {tuple(blocks.shape)}")
+    return blocks.contiguous()
+
+
+def _recon_block(t: torch.Tensor, nb: int, width: int, dtype, what: str) -> torch.Tensor:
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise _lib.PuflowHipError("puflow_amd ops need GPU tensors (no CPU fallback)")
+    if t.dtype != dtype or tuple(t.shape) != (nb, width):
+        raise _lib.PuflowHipError(f"{what}: a {dtype} block array [NB, {width}] = {(nb, width)}, got {t.dtype} {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def recon_block_keys(pts: torch.Tensor, tables) -> torch.Tensor:
+    """pf_recon_block_keys: pts [N,3], the corner tables -> int64 [N, 8], the keys of the blocks every point's 4 x 4 x 4 corners
+    touch; torch.unique of it is the block list"""
+    lib = _lib.load()
+    pts = _f32c(pts)
+    if pts.dim() != 2 or pts.shape[1] != 3 or pts.shape[0] <= 0:
+        raise _lib.PuflowHipError(f"recon_block_keys: pts [N,3], got {tuple(pts.shape)}")
+    (gx, gy, gz), (Dx, Dy, Dz) = _recon_box(tables, "recon_block_keys")
+    keys = torch.empty((pts.shape[0], 8), dtype=torch.int64, device=pts.device)
+    _lib.check(lib.pf_recon_block_keys(pts.data_ptr(), pts.shape[0], gx.data_ptr(), gy.data_ptr(), gz.data_ptr(), Dx, Dy, Dz,
+                                       keys.data_ptr(), _stream()), "pf_recon_block_keys")
+    return keys
+
+
+def recon_block_links(blocks: torch.Tensor, dims) -> torch.Tensor:
+    """pf_recon_block_links: the block list, (D_x, D_y, D_z) -> int32 [NB, 8], the list positions of the blocks at offsets {0,1}^3
+    (-1: absent)"""
+    lib = _lib.load()
+    blocks, (Dx, Dy, Dz) = _recon_list(blocks, "recon_block_links"), _recon_dims(dims, "recon_block_links")
+    links = torch.empty((blocks.shape[0], 8), dtype=torch.int32, device=blocks.device)
+    _lib.check(lib.pf_recon_block_links(blocks.data_ptr(), blocks.shape[0], Dx, Dy, Dz, links.data_ptr(), _stream()),
+               "pf_recon_block_links")
+    return links
+
+
+def recon_mark_sparse(pts: torch.Tensor, tables, blocks: torch.Tensor) -> torch.Tensor:
+    """pf_recon_mark_sparse: pts [N,3], the corner tables, the block list -> uint8 flags [NB, 512]"""
+    lib = _lib.load()
+    pts = _f32c(pts)
+    if pts.dim() != 2 or pts.shape[1] != 3 or pts.shape[0] <= 0:
+        raise _lib.PuflowHipError(f"recon_mark_sparse: pts [N,3], got {tuple(pts.shape)}")
+    (gx, gy, gz), (Dx, Dy, Dz) = _recon_box(tables, "recon_mark_sparse")
+    blocks = _recon_list(blocks, "recon_mark_sparse")
+    flags = torch.empty((blocks.shape[0], RECON_SLOTS), dtype=torch.uint8, device=pts.device)
+    _lib.check(lib.pf_recon_mark_sparse(pts.data_ptr(), pts.shape[0], gx.data_ptr(), gy.data_ptr(), gz.data_ptr(), Dx, Dy, Dz,
+                                        blocks.data_ptr(), blocks.shape[0], flags.data_ptr(), _stream()), "pf_recon_mark_sparse")
+    return flags
+
+
+def _recon_sparse_field(f, flags, blocks, links, dims, what: str):
+    blocks, dims = _recon_list(blocks, what), _recon_dims(dims, what)
+    nb = int(blocks.shape[0])
+    return (_recon_block(f, nb, RECON_SLOTS, torch.float32, what), _recon_block(flags, nb, RECON_SLOTS, torch.uint8, what), blocks,
+            _recon_block(links, nb, 8, torch.int32, what), nb, dims)
+
+
+def mtet_count_sparse(f: torch.Tensor, flags: torch.Tensor, blocks: torch.Tensor, links: torch.Tensor, dims) -> torch.Tensor:
+    """pf_mtet_count_sparse: f float32 / flags uint8 [NB, 512], the block list and its links -> triangles per slot (the cell whose
+    lower corner it is), int32 [NB, 512]"""
+    lib = _lib.load()
+    f, flags, blocks, links, nb, (Dx, Dy, Dz) = _recon_sparse_field(f, flags, blocks, links, dims, "mtet_count_sparse")
+    count = torch.empty((nb, RECON_SLOTS), dtype=torch.int32, device=f.device)
+    _lib.check(lib.pf_mtet_count_sparse(f.data_ptr(), flags.data_ptr(), blocks.data_ptr(), links.data_ptr(), nb, Dx, Dy, Dz,
+                                        count.data_ptr(), _stream()), "pf_mtet_count_sparse")
+    return count
+
+
+def mtet_emit_sparse(f: torch.Tensor, flags: torch.Tensor, blocks: torch.Tensor, links: torch.Tensor, dims, cells: torch.Tensor,
+                     first: torch.Tensor, total: int) -> torch.Tensor:
+    """pf_mtet_emit_sparse: cells int64 [M], the slot numbers with triangles sorted by global cell index; first int64 [M], the
+    exclusive prefix sum of their counts; total its sum -> the triangles' edge ids, int64 [total, 3]"""
+    lib = _lib.load()
+    f, flags, blocks, links, nb, (Dx, Dy, Dz) = _recon_sparse_field(f, flags, blocks, links, dims, "mtet_emit_sparse")
+    for t, name in ((cells, "cells"), (first, "first")):
+        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.int64 or t.dim() != 1 or t.shape != cells.shape or t.shape[0] <= 0:
+            raise _lib.PuflowHipError(f"mtet_emit_sparse: {name} int64 [M] on the GPU, got {getattr(t, 'dtype', type(t))} "
+                                      f"{tuple(getattr(t, 'shape', ()))}")
+    cells, first = cells.contiguous(), first.contiguous()
+    ids = torch.empty((int(total), 3), dtype=torch.int64, device=f.device)
+    _lib.check(lib.pf_mtet_emit_sparse(f.data_ptr(), flags.data_ptr(), blocks.data_ptr(), links.data_ptr(), nb, Dx, Dy, Dz,
+                                       cells.data_ptr(), first.data_ptr(), cells.shape[0], int(total), ids.data_ptr(), _stream()),
+               "pf_mtet_emit_sparse")
+    return ids
+
+
+def mtet_vertices_sparse(edge_ids: torch.Tensor, f: torch.Tensor, blocks: torch.Tensor, links: torch.Tensor, tables) -> torch.Tensor:
+    """pf_mtet_vertices_sparse: the distinct edge ids int64 [V], f [NB, 512], the block list and its links, the corner tables ->
+    float32 [V,3]"""
+    lib = _lib.load()
+    (gx, gy, gz), dims = _recon_box(tables, "mtet_vertices_sparse")
+    blocks = _recon_list(blocks, "mtet_vertices_sparse")
+    nb = int(blocks.shape[0])
+    f = _recon_block(f, nb, RECON_SLOTS, torch.float32, "mtet_vertices_sparse")
+    links = _recon_block(links, nb, 8, torch.int32, "mtet_vertices_sparse")
+    if not edge_ids.is_cuda or edge_ids.dtype != torch.int64 or edge_ids.dim() != 1 or edge_ids.shape[0] <= 0:
+        raise _lib.PuflowHipError(f"mtet_vertices_sparse: edge ids int64 [V] on the GPU, got {edge_ids.dtype} {tuple(edge_ids.shape)}")
+    edge_ids = edge_ids.contiguous()
+    verts = torch.empty((edge_ids.shape[0], 3), dtype=torch.float32, device=f.device)
+    _lib.check(lib.pf_mtet_vertices_sparse(edge_ids.data_ptr(), edge_ids.shape[0], f.data_ptr(), blocks.data_ptr(), links.data_ptr(), nb,
+                                           gx.data_ptr(), gy.data_ptr(), gz.data_ptr(), dims[0], dims[1], dims[2], verts.data_ptr(),
+                                           _stream()), "pf_mtet_vertices_sparse")
+    return verts

@@ -5,7 +5,10 @@ mean of signed tangent-plane distances to the `k` nearest oriented points (pf_kn
 marching tetrahedra.  Vertices are welded by grid-edge id, so a closed surface comes out closed, and the mesh is the same bytes
 from run to run.  There is no CPU path.
 
-  verts, faces, info = mesh_from_cloud(points, normals)       # [N,3], [N,3] -> [V,3] float32, [F,3] int32, {h, dims, open_edges}
+  verts, faces, info = mesh_from_cloud(points, normals)       # [N,3], [N,3] -> [V,3] float32, [F,3] int32, {h, dims, open_edges, ..}
+  mesh_from_cloud(points, normals, layout="sparse")           # the same mesh from 8 x 8 x 8 blocks around the band (csrc/
+                                                              # recon_sparse.hip): nothing is as large as the box; "auto": dense
+                                                              # while the box is within the dense cap, else sparse
   f = implicit(points, normals, query, h=cell_size(points))   # the implicit value at any points
   python -m puflow_amd.reconstruct --source DIR --target DIR  # every x y z nx ny nz file of DIR -> <name>.off
 """
@@ -22,6 +25,11 @@ from . import _lib, ops
 PAD = 3                                 # corners of margin on every side of the cloud's box: keeps the band inside
 MAX_CORNERS = _lib.PF_RECON_MAX_CORNERS
 CELL_NEIGHBOUR = 6                      # the cell size follows the distance to this nearest OTHER point
+BLOCK = _lib.PF_RECON_BLOCK             # the sparse layout: corners per axis of a block, ...
+SLOTS = BLOCK ** 3                      # ... corners of a block, ...
+MAX_AXIS = _lib.PF_RECON_SPARSE_MAX_AXIS        # ... corners per axis of its virtual grid ...
+MAX_BLOCKS = _lib.PF_RECON_SPARSE_MAX_BLOCKS    # ... and listed blocks
+LAYOUTS = ("dense", "sparse", "auto")
 
 
 def _cloud(points, normals, what: str):
@@ -73,16 +81,39 @@ def cell_size(points: torch.Tensor, scale: float = 1.0) -> float:
     return _positive(scale, "scale", "cell_size") * float(np.sqrt(m))
 
 
-def corner_tables(lo, hi, h: float):
-    """the fp32 box and the cell size -> ((D_x, D_y, D_z), three float32 numpy tables g_a[i] = float32(o_a + i h))"""
+def _layout(layout, what: str) -> str:
+    if layout not in LAYOUTS:
+        raise _lib.PuflowHipError(f"{what}: layout is one of {', '.join(LAYOUTS)}, got {layout!r}")
+    return layout
+
+
+def _box(cells) -> str:
+    return " x ".join(str(int(c) + 2 * PAD + 1) if np.isfinite(c) else "inf" for c in cells)
+
+
+def _within_dense_cap(cells) -> bool:
+    return bool((cells < MAX_CORNERS).all()) and \
+        int(cells[0] + 2 * PAD + 1) * int(cells[1] + 2 * PAD + 1) * int(cells[2] + 2 * PAD + 1) <= MAX_CORNERS
+
+
+def corner_tables(lo, hi, h: float, layout: str = "dense"):
+    """the fp32 box and the cell size -> ((D_x, D_y, D_z), three float32 numpy tables g_a[i] = float32(o_a + i h)).  layout "dense":
+    at most PF_RECON_MAX_CORNERS corners in the box; "sparse": at most PF_RECON_SPARSE_MAX_AXIS per axis; "auto": either"""
+    layout = _layout(layout, "corner_tables")
     lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
     o = lo - PAD * h
     cells = np.ceil((hi - lo) / h)
-    if not (cells < MAX_CORNERS).all() or int(cells[0] + 2 * PAD + 1) * int(cells[1] + 2 * PAD + 1) * int(cells[2] + 2 * PAD + 1) > MAX_CORNERS:
+    unsupported = _lib.load().pf_error_string(_lib.PF_ERR_UNSUPPORTED).decode()
+    dense = _within_dense_cap(cells)
+    if layout == "dense" and not dense:
         raise _lib.PuflowHipError(
-            f"reconstruct: a box of {' x '.join(str(int(c) + 2 * PAD + 1) if np.isfinite(c) else 'inf' for c in cells)} corners at "
-            f"cell size {h:.6g} is over the cap of {MAX_CORNERS} ({_lib.load().pf_error_string(_lib.PF_ERR_UNSUPPORTED).decode()}): "
-            "use a larger --cell (or --cell_scale)")
+            f"reconstruct: a box of {_box(cells)} corners at "
+            f"cell size {h:.6g} is over the cap of {MAX_CORNERS} ({unsupported}): "
+            "use a larger --cell (or --cell_scale) or --layout sparse")
+    if not (layout == "dense" or (layout == "auto" and dense) or (cells + 2 * PAD + 1 <= MAX_AXIS).all()):      # inf, nan: over
+        raise _lib.PuflowHipError(
+            f"reconstruct: a grid of {_box(cells)} corners at cell size {h:.6g} is over the sparse layout's cap of {MAX_AXIS} per "
+            f"axis ({unsupported}): use a larger --cell (or --cell_scale)")
     dims = tuple(int(c) + 2 * PAD + 1 for c in cells)
     return dims, [(o[a] + np.arange(dims[a], dtype=np.float64) * h).astype(np.float32) for a in range(3)]
 
@@ -122,15 +153,83 @@ def extract(f: torch.Tensor, flags: torch.Tensor, tables):
     return ops.mtet_vertices(edge, f, tables), inverse.reshape(-1, 3)
 
 
+# ---- the block-sparse layout (the contract is in puflow_hip.h) ---------------------------------------------------------------
+def block_dims(dims):
+    """(D_x, D_y, D_z) -> blocks per axis (NB_x, NB_y, NB_z)"""
+    return tuple((int(d) + BLOCK - 1) // BLOCK for d in dims)
+
+
+def slot_corners(slots: torch.Tensor, blocks: torch.Tensor, dims):
+    """slot numbers int64 [Q] (512 b + slot), the block list -> the corners' (i, j, k), three int64 [Q]"""
+    nbx, nby, _ = block_dims(dims)
+    key, s = blocks[slots >> 9], slots & (SLOTS - 1)
+    return ((key % nbx) * BLOCK + (s & 7), ((key // nbx) % nby) * BLOCK + ((s >> 3) & 7), (key // (nbx * nby)) * BLOCK + (s >> 6))
+
+
+def dense_to_blocks(dense: torch.Tensor, blocks: torch.Tensor) -> torch.Tensor:
+    """a dense [D_z, D_y, D_x] array -> its block form [NB, 512] over this block list; slots beyond the grid are 0"""
+    dims = (int(dense.shape[2]), int(dense.shape[1]), int(dense.shape[0]))
+    slots = torch.arange(blocks.shape[0] * SLOTS, dtype=torch.int64, device=dense.device)
+    i, j, k = slot_corners(slots, blocks, dims)
+    inside = (i < dims[0]) & (j < dims[1]) & (k < dims[2])
+    out = torch.zeros((blocks.shape[0] * SLOTS,), dtype=dense.dtype, device=dense.device)
+    out[inside] = dense.reshape(-1)[((k * dims[1] + j) * dims[0] + i)[inside]]
+    return out.reshape(-1, SLOTS)
+
+
+def blocks_to_dense(block_array: torch.Tensor, blocks: torch.Tensor, dims) -> torch.Tensor:
+    """a block array [NB, 512] -> the dense [D_z, D_y, D_x] array, 0 outside the listed blocks (tests and small grids: this one
+    IS as large as the box)"""
+    slots = torch.arange(blocks.shape[0] * SLOTS, dtype=torch.int64, device=block_array.device)
+    i, j, k = slot_corners(slots, blocks, dims)
+    inside = (i < dims[0]) & (j < dims[1]) & (k < dims[2])
+    out = torch.zeros((dims[2] * dims[1] * dims[0],), dtype=block_array.dtype, device=block_array.device)
+    out[((k * dims[1] + j) * dims[0] + i)[inside]] = block_array.reshape(-1)[inside]
+    return out.reshape(dims[2], dims[1], dims[0])
+
+
+def block_list(points: torch.Tensor, tables):
+    """the layout of a cloud: (blocks int64 [NB], the ascending distinct keys of the blocks its band touches; links int32 [NB, 8])"""
+    blocks = torch.unique(ops.recon_block_keys(points, tables).reshape(-1))          # sorted
+    if blocks.shape[0] > MAX_BLOCKS:
+        raise _lib.PuflowHipError(
+            f"reconstruct: the band touches {blocks.shape[0]} blocks of {BLOCK}^3 corners, over the cap of {MAX_BLOCKS} "
+            f"({_lib.load().pf_error_string(_lib.PF_ERR_UNSUPPORTED).decode()}): use a larger --cell (or --cell_scale)")
+    return blocks, ops.recon_block_links(blocks, tuple(int(t.shape[0]) for t in tables))
+
+
+def extract_sparse(f: torch.Tensor, flags: torch.Tensor, blocks: torch.Tensor, links: torch.Tensor, tables):
+    """extract() over the block layout: f float32 / flags uint8 [NB, 512], the block list and its links, the corner tables
+    (device) -> the same (verts, faces): triangles in ascending GLOBAL cell index, then tet, then triangle"""
+    dims = tuple(int(t.shape[0]) for t in tables)
+    empty = lambda: (torch.zeros((0, 3), dtype=torch.float32, device=f.device), torch.zeros((0, 3), dtype=torch.int64, device=f.device))
+    count = ops.mtet_count_sparse(f, flags, blocks, links, dims).reshape(-1)
+    slots = torch.nonzero(count).reshape(-1)                                # block-major: not the order of the mesh
+    if slots.shape[0] == 0:                                                 # a size
+        return empty()
+    i, j, k = slot_corners(slots, blocks, dims)
+    _, order = torch.sort((k * dims[1] + j) * dims[0] + i)                  # distinct keys: the order is determined
+    cells = slots[order]
+    n = count[cells].to(torch.int64)
+    incl = torch.cumsum(n, dim=0)
+    ids = ops.mtet_emit_sparse(f, flags, blocks, links, dims, cells, incl - n, int(incl[-1]))       # a size: the triangle array's
+    edge, inverse = torch.unique(ids.reshape(-1), sorted=True, return_inverse=True)
+    return ops.mtet_vertices_sparse(edge, f, blocks, links, tables), inverse.reshape(-1, 3)
+
+
 def mesh_from_cloud(points: torch.Tensor, normals: torch.Tensor, cell: float = None, cell_scale: float = 1.0, k: int = 8,
-                    sigma: float = 1.0):
+                    sigma: float = 1.0, layout: str = "dense"):
     """points, normals [N,3] on the GPU (unit normals with consistent signs: estimate_normals(..., orient="propagate") or a
     scanner's) -> (verts [V,3] float32, faces [F,3] int32, info).  cell: the grid's cell size; default cell_scale x the median
-    distance to the 6th nearest other point.  info: h, dims (D_x, D_y, D_z) and open_edges, the number of mesh edges used by one
-    triangle only - 0 for a closed surface; a cell below the sampling spacing tears holes, and a scan's real boundary stays one."""
+    distance to the 6th nearest other point.  layout: "dense" - arrays over the cloud's box, refused over PF_RECON_MAX_CORNERS;
+    "sparse" - 8 x 8 x 8 blocks around the band, the same mesh bit for bit, nothing allocated by the size of the box; "auto" -
+    dense while the box is within the dense cap, else sparse.  info: h, dims (D_x, D_y, D_z), layout (the one used), blocks (0
+    for dense) and open_edges, the number of mesh edges used by one triangle only - 0 for a closed surface; a cell below the
+    sampling spacing tears holes, and a scan's real boundary stays one."""
     points, normals = _cloud(points, normals, "mesh_from_cloud")
     k = _k(k, points.shape[0], "mesh_from_cloud")
     sigma = _positive(sigma, "sigma", "mesh_from_cloud")
+    layout = _layout(layout, "mesh_from_cloud")
     if cell is not None:
         h = _positive(cell, "cell", "mesh_from_cloud")
         _, lo, hi = _stats(points, False)
@@ -138,19 +237,34 @@ def mesh_from_cloud(points: torch.Tensor, normals: torch.Tensor, cell: float = N
         scale = _positive(cell_scale, "cell_scale", "mesh_from_cloud")
         m, lo, hi = _stats(points, True)
         h = _positive(scale * float(np.sqrt(m)), "the cell size from the cloud's spacing", "mesh_from_cloud")
-    dims, host_tables = corner_tables(lo, hi, h)
+    if layout == "auto":
+        layout = "dense" if _within_dense_cap(np.ceil((hi - lo) / h)) else "sparse"
+    dims, host_tables = corner_tables(lo, hi, h, layout)
     dev = points.device
     tables = [torch.from_numpy(t).to(dev) for t in host_tables]
-    flags = ops.recon_mark(points, tables)
-    corner = torch.nonzero(flags.reshape(-1)).reshape(-1)                   # ascending corner index
-    Dx, Dy = dims[0], dims[1]
-    query = torch.stack([tables[0][corner % Dx], tables[1][(corner // Dx) % Dy], tables[2][corner // (Dx * Dy)]], dim=1)
-    idx, _ = ops.knn_grid(points[None], query[None], k)
-    f = torch.empty(flags.shape, dtype=torch.float32, device=dev)           # inactive corners are never read
-    f.reshape(-1)[corner] = ops.imls(query, points, normals, idx[0], sigma * h)
-    verts, faces = extract(f, flags, tables)
+    if layout == "sparse":
+        blocks, links = block_list(points, tables)
+        flags = ops.recon_mark_sparse(points, tables, blocks)
+        slot = torch.nonzero(flags.reshape(-1)).reshape(-1)                 # ascending slot number
+        i, j, kk = slot_corners(slot, blocks, dims)
+        query = torch.stack([tables[0][i], tables[1][j], tables[2][kk]], dim=1)
+        idx, _ = ops.knn_grid(points[None], query[None], k)
+        f = torch.empty(flags.shape, dtype=torch.float32, device=dev)       # unflagged slots are never read
+        f.reshape(-1)[slot] = ops.imls(query, points, normals, idx[0], sigma * h)
+        verts, faces = extract_sparse(f, flags, blocks, links, tables)
+        nblocks = int(blocks.shape[0])
+    else:
+        flags = ops.recon_mark(points, tables)
+        corner = torch.nonzero(flags.reshape(-1)).reshape(-1)               # ascending corner index
+        Dx, Dy = dims[0], dims[1]
+        query = torch.stack([tables[0][corner % Dx], tables[1][(corner // Dx) % Dy], tables[2][corner // (Dx * Dy)]], dim=1)
+        idx, _ = ops.knn_grid(points[None], query[None], k)
+        f = torch.empty(flags.shape, dtype=torch.float32, device=dev)       # inactive corners are never read
+        f.reshape(-1)[corner] = ops.imls(query, points, normals, idx[0], sigma * h)
+        verts, faces = extract(f, flags, tables)
+        nblocks = 0
     open_edges = int(_open_edges(faces, verts.shape[0])) if faces.shape[0] else 0
-    return verts, faces.to(torch.int32), {"h": h, "dims": dims, "open_edges": open_edges}
+    return verts, faces.to(torch.int32), {"h": h, "dims": dims, "open_edges": open_edges, "layout": layout, "blocks": nblocks}
 
 
 def write_off(path, verts, faces) -> None:
@@ -177,7 +291,7 @@ OPEN_EDGES_LINE = ("{name}: {n} open edges - the mesh has a boundary: the cell (
 
 @torch.no_grad()
 def reconstruct_files(paths, target: str, cell=None, cell_scale: float = 1.0, k: int = 8, sigma: float = 1.0,
-                      normal_column: int = 4, device="cuda:0"):
+                      normal_column: int = 4, device="cuda:0", layout: str = "dense"):
     from .upsample import load_xyz
     c0 = int(normal_column) - 1
     if c0 < 3:
@@ -195,7 +309,7 @@ def reconstruct_files(paths, target: str, cell=None, cell_scale: float = 1.0, k:
         xyz = torch.from_numpy(np.ascontiguousarray(rows[:, :3])).to(device)
         nrm = torch.from_numpy(np.ascontiguousarray(rows[:, c0:c0 + 3])).to(device)
         nrm = nrm / nrm.norm(dim=1, keepdim=True).clamp_min(1e-30)          # six printed decimals are not unit length
-        verts, faces, info = mesh_from_cloud(xyz, nrm, cell=cell, cell_scale=cell_scale, k=k, sigma=sigma)
+        verts, faces, info = mesh_from_cloud(xyz, nrm, cell=cell, cell_scale=cell_scale, k=k, sigma=sigma, layout=layout)
         name = os.path.splitext(os.path.basename(p))[0] + ".off"
         write_off(os.path.join(target, name), verts, faces)
         if info["open_edges"] > 0:
@@ -215,12 +329,15 @@ def main(argv=None):
     parser.add_argument("--k", type=int, default=8, help="oriented points per implicit value")
     parser.add_argument("--sigma", type=float, default=1.0, help="width of the weights, in cells")
     parser.add_argument("--normal_column", type=int, default=4, help="1-based first column of the normal")
+    parser.add_argument("--layout", type=str, default="dense", choices=LAYOUTS,
+                        help="dense: arrays over the cloud's box; sparse: blocks around the band, for a box that is mostly empty; "
+                             "auto: dense while the box is within the dense cap")
     args = parser.parse_args(argv)
     paths = []
     for root, _dirs, files in os.walk(args.source):
         paths.extend([os.path.join(root, f) for f in files if ".xyz" in f])
     reconstruct_files(paths, args.target, cell=args.cell, cell_scale=args.cell_scale, k=args.k, sigma=args.sigma,
-                      normal_column=args.normal_column)
+                      normal_column=args.normal_column, layout=args.layout)
 
 
 if __name__ == "__main__":
