@@ -897,6 +897,40 @@ long long pf_point_mesh_ws_floats(int P, int F);
 int pf_point_mesh_dist(const float* pts, int P, const float* tris, int F, const int* seed, int brute, float* dist, int* face,
                        float* ws, long long ws_floats, void* stream);
 
+/* The same closest triangle over a uniform grid of the triangles (csrc/tri_grid.hip): for the same
+ * pts [P,3], tris [F,9] and seed (nullable, same meaning and same default), dist[P] and face[P] (nullable) equal, BIT FOR BIT,
+ * what pf_point_mesh_dist(..., brute = 1, ...) returns - including its tie rule: if the 64-triangle seed window attains the
+ * minimal fp32 squared distance the winner is the window's first minimiser, otherwise the lowest triangle index attaining that
+ * distance; dist is the winner's distance again in double, sqrt, cast to float.  The arithmetic is shared (csrc/pf_tri.h).
+ *   Grid      the fp32 box of all triangle vertices; g = the smallest integer with g^3 >= 2 F, at most 256, cells along the
+ *             longest extent, the same edge h on every axis (h >= 2^-19 of the largest |coordinate|, > 0), G_a = cell_a(hi_a) + 1
+ *             cells on axis a (a zero-extent axis: one; all vertices coincident: G = (1, 1, 1)); cell_a(x) =
+ *             clamp((int)floorf((x - lo_a) * (1 / h)), 0, G_a - 1) in unfused fp32, monotone in x.  A triangle is registered in
+ *             EVERY cell its bounding box touches (conservative: no triangle-box test); one whose box touches more than 64
+ *             cells goes to the oversize list instead, which every query tests after the seed window (a mesh of huge faces
+ *             only degenerates to brute force; exactness is never affected).
+ *   Search    one wave per query: the seed window, the oversize list, then the Chebyshev rings r = 0, 1, .. of cells around the
+ *             query's (clamped) cell - queries outside the box are legal.  After ring r every unseen triangle lies wholly beyond
+ *             a face of the visited block; the search stops when the squared gap to the nearest such face exceeds
+ *             best (1 + 2^-12) + sc^2, sc = 2^-19 x the largest coordinate magnitude of query and box (pf_point_mesh_dist's
+ *             margin for its boxes: the fp32 triangle distance is not correctly rounded), never on equality, and at the latest
+ *             when the block covers the grid.  A query D cells from the surface visits on the order of D^3 cells: the search is
+ *             meant for points near the surface; far queries are slow, never wrong.
+ *   Calls     pf_point_mesh_grid_count builds the grid's histogram in ws (>= pf_point_mesh_grid_ws_bytes(P, F, 0) bytes) and
+ *             writes info [8] (DEVICE, 64-bit): the (cell, triangle) pairs, the oversize triangles, G_x, G_y, G_z, and the byte
+ *             offsets in ws of the cells' first pair positions (int [cells + 1], x fastest), of the oversize list and of the
+ *             pair list.  The caller reads the pair count, sizes ws by pf_point_mesh_grid_ws_bytes(P, F, pairs) and calls
+ *             pf_point_mesh_grid with that `pairs`, which builds the grid again and searches.  A ws sized for fewer pairs than
+ *             the mesh has is safe: the pair list is not used then and every query scans all triangles.  More pairs than an
+ *             int holds: PF_ERR_UNSUPPORTED from the size call.  P <= 2^26, F <= 2^28; ws 16-byte aligned.
+ *   cand      (nullable) [P]: triangle evaluations per query - seed window, oversize list and rings.
+ * No float atomics; integer atomics in the grid build only (the order inside a cell cannot show); every loop bounded by a
+ * constant or a host-given size; every index read from a list is clamped before it addresses memory. */
+long long pf_point_mesh_grid_ws_bytes(int P, int F, long long pairs);
+int pf_point_mesh_grid_count(const float* tris, int F, void* ws, long long ws_bytes, long long* info, void* stream);
+int pf_point_mesh_grid(const float* pts, int P, const float* tris, int F, const int* seed, float* dist, int* face, int* cand,
+                       void* ws, long long ws_bytes, long long pairs, void* stream);
+
 /* ---- training batches on the device (csrc/data_aug.hip; the reference's dataset/pu1k/fetcher.py:69-101) ---------------------
  * One launch assembles and augments rows [0, b) of a batch from a device-resident dataset: one workgroup per patch, no grid
  * barrier, no float atomics, no host synchronisation, no global state.

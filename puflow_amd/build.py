@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpuflow_hip.so")
 EXPORTS = os.path.join(CSRC, "exports.map")             # linker version script: only pf_* enters the dynamic symbol table
-SOURCES = ["api.hip", "knn.hip", "edgeconv.hip", "pointwise.hip", "flow.hip", "interp.hip", "chamfer.hip", "emd.hip", "train_ops.hip", "train_gemm.hip", "train_fused.hip", "train_ec_fwd.hip", "train_csr.hip", "train_bnmlp.hip", "train_mlp.hip", "train_flow.hip", "train_flowchain.hip", "train_glue.hip", "optim.hip", "patch_ops.hip", "cnf.hip", "cnf_replay.hip", "cnf_bwd.hip", "cnf_pack.hip", "xyz_io.hip", "eval_metrics.hip", "data_aug.hip", "eval_uniform.hip", "poisson.hip", "surface_reach.hip", "tiles.hip", "attr.hip", "knn_grid.hip", "normals_orient.hip", "recon.hip", "recon_sparse.hip"]
+SOURCES = ["api.hip", "knn.hip", "edgeconv.hip", "pointwise.hip", "flow.hip", "interp.hip", "chamfer.hip", "emd.hip", "train_ops.hip", "train_gemm.hip", "train_fused.hip", "train_ec_fwd.hip", "train_csr.hip", "train_bnmlp.hip", "train_mlp.hip", "train_flow.hip", "train_flowchain.hip", "train_glue.hip", "optim.hip", "patch_ops.hip", "cnf.hip", "cnf_replay.hip", "cnf_bwd.hip", "cnf_pack.hip", "xyz_io.hip", "eval_metrics.hip", "data_aug.hip", "eval_uniform.hip", "poisson.hip", "surface_reach.hip", "tiles.hip", "attr.hip", "knn_grid.hip", "normals_orient.hip", "recon.hip", "recon_sparse.hip", "tri_grid.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=on", "-Wno-unused-result"]
 # The fused MFMA kernels never see NaNs; without the flag every fmaxf() is preceded by a canonicalising v_max x,x and
 # the DPP row-max steps stay as v_mov_dpp + v_max instead of one v_max_f32_dpp (3x the instructions of a max-pool).

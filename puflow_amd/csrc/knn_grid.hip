@@ -8,9 +8,11 @@
 // made it and cannot show, because the output is ordered by key.
 //
 // cell_a(x) = clamp((int)floorf((x - lo_a) * inv_h), 0, G_a - 1), unfused fp32, is MONOTONE in x (subtraction, multiplication by
-// a positive constant, floor and clamp all are).  The stopping rule rests on that and on nothing else - kg_face_bound below.
+// a positive constant, floor and clamp all are).  The stopping rule rests on that and on nothing else - kg_cell and kg_face_bound
+// of pf_cells.h, which the grid of triangles (tri_grid.hip) shares.
 #include <hip/hip_runtime.h>
 #include "pf_api_internal.h"
+#include "pf_cells.h"
 #include "pf_wave.h"
 
 namespace {
@@ -55,12 +57,6 @@ __device__ __forceinline__ const KgHeader* kg_header(const char* w) { return rei
 __device__ __forceinline__ float4* kg_pts(char* w) { return reinterpret_cast<float4*>(w + KG_HEADER); }
 __device__ __forceinline__ int* kg_cstart(char* w, int n) { return reinterpret_cast<int*>(w + KG_HEADER + 16ll * n); }
 __device__ __forceinline__ int* kg_cursor(char* w, int n, int g) { return kg_cstart(w, n) + (g * g * g + 1); }
-
-__device__ __forceinline__ int kg_cell(float x, float lo, float inv_h, int G) {
-#pragma clang fp contract(off)
-    const float t = floorf(__fmul_rn(__fsub_rn(x, lo), inv_h));
-    return (int)fminf(fmaxf(t, 0.f), (float)(G - 1));                   // clamped as a float: a far query cannot overflow the int
-}
 
 __device__ __forceinline__ float kg_sqd(float ax, float ay, float az, float bx, float by, float bz) {      // sqd() of patch_ops.hip
 #pragma clang fp contract(off)
@@ -181,38 +177,7 @@ __global__ __launch_bounds__(256) void kg_scatter_kernel(const float* __restrict
     if ((unsigned)pos < (unsigned)n) kg_pts(w)[pos] = make_float4(x, y, z, __int_as_float(i));
 }
 
-// ---- 5. search
-// What the cells NOT yet visited can still hold, along one axis.  The visited block spans the cells c - r .. c + r of the axis
-// (clipped to 0 .. G - 1).  Returns a lower bound of the COMPUTED d2 of every reference beyond the block's two faces of this
-// axis (+inf when both faces are the grid's ends) and sets `face` when at least one face is interior.
-//   low face (c - r > 0): unvisited references have cell(x) < c - r.  Take any float E with cell(E) >= c - r: by monotony
-//   x >= E would give cell(x) >= c - r, so x < E.  With q >= E: q - x > q - E >= 0, rounding is monotone, so the kernel's
-//   dx = fl(q - x) >= fl(q - E) =: gap, fl(dx dx) >= fl(gap gap), and adding the other two non-negative squares cannot go below
-//   it (fl(a + b) >= a for b >= 0).  Hence d2 >= fl(gap gap) EXACTLY, no relative allowance.  E is the edge lo + (c - r) h moved
-//   up by 2^-20 of the magnitudes involved (about 8 ulps: the roundings of x - lo, of (.) inv_h, of inv_h = fl(1 / h) and of the
-//   edge itself are under 5), and cell(E) >= c - r is CHECKED here: if it ever failed the face would give 0 and the search go on.
-//   The high face is the mirror image.  Exactness therefore never depends on the size of the slack, only speed does.
-__device__ __forceinline__ float kg_face_bound(float q, float lo, float h, float inv_h, int G, int c, int r, bool& face) {
-#pragma clang fp contract(off)
-    float b = INFINITY;
-    const int lc = c - r, hc = c + r;
-    if (lc > 0) {
-        face = true;
-        float E = __fadd_rn(lo, __fmul_rn((float)lc, h));
-        E = __fadd_rn(E, __fmul_rn(fmaxf(fabsf(lo), fabsf(E)), 0x1p-20f));
-        const float gap = __fsub_rn(q, E);
-        b = fminf(b, (kg_cell(E, lo, inv_h, G) >= lc && gap > 0.f) ? __fmul_rn(gap, gap) : 0.f);
-    }
-    if (hc < G - 1) {
-        face = true;
-        float E = __fadd_rn(lo, __fmul_rn((float)(hc + 1), h));
-        E = __fsub_rn(E, __fmul_rn(fmaxf(fabsf(lo), fabsf(E)), 0x1p-20f));
-        const float gap = __fsub_rn(E, q);
-        b = fminf(b, (kg_cell(E, lo, inv_h, G) <= hc && gap > 0.f) ? __fmul_rn(gap, gap) : 0.f);
-    }
-    return b;
-}
-
+// ---- 5. search (the stopping bound: kg_face_bound of pf_cells.h)
 __device__ __forceinline__ unsigned long long kg_min(unsigned long long a, unsigned long long b) { return a < b ? a : b; }
 __device__ __forceinline__ unsigned long long kg_max(unsigned long long a, unsigned long long b) { return a < b ? b : a; }
 

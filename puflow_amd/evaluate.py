@@ -86,8 +86,11 @@ def _batches(items, key, size):
 
 def evaluate(pred_dir: str, gt_dir: str, save_path: str, mesh_dir: str = None, write_p2m: bool = False,
              cloud_batch: int = 16, emd_levels_top: int = 7, device=None, uniform: bool = False, uniform_seeds: int = 1000,
-             uniform_seed: int = 0, write_disks: bool = False, uniform_disks: str = "ball"):
-    """Score the directory; returns (per-file rows, summary row) as written to evaluation.csv."""
+             uniform_seed: int = 0, write_disks: bool = False, uniform_disks: str = "ball", p2f_search: str = "tiles"):
+    """Score the directory; returns (per-file rows, summary row) as written to evaluation.csv.  p2f_search: the closest-triangle
+    search of P2F, "tiles" or "grid" (metrics.point_to_mesh_distance) - the same numbers and files either way."""
+    if p2f_search not in metrics.P2F_SEARCHES:
+        raise ValueError(f"p2f_search is one of {metrics.P2F_SEARCHES}, got {p2f_search!r}")
     if uniform_disks not in ("ball", "surface"):
         raise ValueError(f"uniform_disks is 'ball' or 'surface', got {uniform_disks!r}")
     uni = dict(seeds=int(uniform_seeds), seed=int(uniform_seed), write=bool(write_disks),
@@ -113,7 +116,7 @@ def evaluate(pred_dir: str, gt_dir: str, save_path: str, mesh_dir: str = None, w
             g_hd.append(hd[i])
             g_emd.append(emd[i])
             g_jsd.append(float(jsd[i]))
-            p2f, u = _p2f(pp, pred, i, name, mesh_dir, write_p2m, uni)
+            p2f, u = _p2f(pp, pred, i, name, mesh_dir, write_p2m, uni, p2f_search)
             if p2f is not None and p2f.size > 0:
                 row["p2f avg"] = np.nanmean(p2f)
                 row["p2f std"] = np.nanstd(p2f)
@@ -146,7 +149,7 @@ def evaluate(pred_dir: str, gt_dir: str, save_path: str, mesh_dir: str = None, w
     return rows, summary
 
 
-def _p2f(pred_path, pred_gpu, i, name, mesh_dir, write_p2m, uni=None):
+def _p2f(pred_path, pred_gpu, i, name, mesh_dir, write_p2m, uni=None, search="tiles"):
     """(the file's point-to-surface distances (float32 [N]) or None, its uniformity [5] or None).  uni: None, or the
     --uniform settings dict(seeds, seed, write, surface)."""
     out_path = pred_path[:-4] + "_point2mesh_distance.xyz"
@@ -169,9 +172,9 @@ def _p2f(pred_path, pred_gpu, i, name, mesh_dir, write_p2m, uni=None):
     verts, faces = metrics.read_off(off)
     vt, ft = torch.from_numpy(verts).to(dev), torch.from_numpy(faces).to(dev)
     if uni is None:
-        dist, face = metrics.point_to_mesh_distance(pred_gpu[i], vt, ft), None
+        dist, face = metrics.point_to_mesh_distance(pred_gpu[i], vt, ft, search=search), None
     else:
-        dist, face = metrics.point_to_mesh_distance(pred_gpu[i], vt, ft, return_face=True)
+        dist, face = metrics.point_to_mesh_distance(pred_gpu[i], vt, ft, return_face=True, search=search)
     dist = dist.cpu().numpy()
     if write_p2m:
         tokens = np.atleast_2d(np.loadtxt(pred_path, dtype=np.float64))[:, :3]
@@ -218,10 +221,13 @@ def main(argv=None):
     ap.add_argument("--uniform_seed", type=int, default=0, help="key of the seeds' random numbers")
     ap.add_argument("--write_disks", action="store_true",
                     help="with --uniform --mesh: write <pred>_disk_idx.txt, _radius.txt and _point2mesh_distance.txt")
+    ap.add_argument("--p2f_search", choices=metrics.P2F_SEARCHES, default="tiles",
+                    help="closest-triangle search of P2F: tiles of 64 triangles and their boxes, or a uniform grid of the "
+                         "triangles (for many points near a large mesh); the same numbers and files either way")
     a = ap.parse_args(argv)
     _, summary = evaluate(os.path.abspath(a.pred), os.path.abspath(a.gt), a.save_path, a.mesh, a.write_p2m, a.cloud_batch,
                           a.emd_levels_top, uniform=a.uniform, uniform_seeds=a.uniform_seeds, uniform_seed=a.uniform_seed,
-                          write_disks=a.write_disks, uniform_disks=a.uniform_disks)
+                          write_disks=a.write_disks, uniform_disks=a.uniform_disks, p2f_search=a.p2f_search)
     print(f"Evaluation: {a.save_path}")
     print(summary_line(summary))
 

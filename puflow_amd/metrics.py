@@ -128,12 +128,65 @@ def _morton(x: torch.Tensor, lo: torch.Tensor, ext: torch.Tensor) -> torch.Tenso
     return code
 
 
+P2F_SEARCHES = ("tiles", "grid")
+
+
+def tri_grid_search(pts: torch.Tensor, tris: torch.Tensor, seed: torch.Tensor = None, return_cand: bool = False,
+                    return_info: bool = False):
+    """pf_point_mesh_grid as it is: pts [P,3], tris [F,9] float32 on the GPU in the caller's order, seed int32 [P] or None ->
+    (dist float32 [P], face int32 [P]) - what pf_point_mesh_dist(brute = 1) returns for the same arguments, bit for bit, from
+    a uniform grid of the triangles (csrc/tri_grid.hip).  return_cand: also the triangle evaluations per query (int32 [P]).
+    return_info: also {"pairs", "oversize", "G", "cstart", "over", "pair_list", "ws"}: the grid's sizes, the byte offsets of
+    its lists in the workspace and the workspace itself (uint8).  One host read (the pair count sizes the workspace)."""
+    lib = _lib.load()
+    if not (pts.is_cuda and tris.is_cuda):
+        raise _lib.PuflowHipError("tri_grid_search needs GPU tensors (no CPU fallback)")
+    pts, tris = ops._f32c(pts), ops._f32c(tris)
+    P, F = pts.shape[0], tris.shape[0]
+    if pts.dim() != 2 or pts.shape[1] != 3 or tris.dim() != 2 or tris.shape[1] != 9:
+        raise _lib.PuflowHipError(f"tri_grid_search: pts [P,3] and tris [F,9], got {tuple(pts.shape)} and {tuple(tris.shape)}")
+    if seed is not None:
+        seed = seed.to(device=pts.device, dtype=torch.int32).contiguous()
+        if seed.shape[0] != P:
+            raise _lib.PuflowHipError(f"tri_grid_search: {seed.shape[0]} seeds for {P} points")
+    n0 = lib.pf_point_mesh_grid_ws_bytes(P, F, 0)
+    if n0 < 0:
+        _lib.check(int(n0), "pf_point_mesh_grid_ws_bytes")
+    ws = torch.empty(int(n0), dtype=torch.uint8, device=pts.device)
+    info = torch.zeros(8, dtype=torch.int64, device=pts.device)
+    _lib.check(lib.pf_point_mesh_grid_count(tris.data_ptr(), F, ws.data_ptr(), int(n0), info.data_ptr(), ops._stream()),
+               "pf_point_mesh_grid_count")
+    info = info.cpu().tolist()                                                   # the host sizes the pair list
+    pairs = int(info[0])
+    nb = lib.pf_point_mesh_grid_ws_bytes(P, F, pairs)
+    if nb < 0:
+        _lib.check(int(nb), "pf_point_mesh_grid_ws_bytes")
+    ws = torch.empty(int(nb), dtype=torch.uint8, device=pts.device)
+    dist = torch.empty(P, dtype=torch.float32, device=pts.device)
+    face = torch.empty(P, dtype=torch.int32, device=pts.device)
+    cand = torch.empty(P, dtype=torch.int32, device=pts.device) if return_cand else None
+    _lib.check(lib.pf_point_mesh_grid(pts.data_ptr(), P, tris.data_ptr(), F, None if seed is None else seed.data_ptr(),
+                                      dist.data_ptr(), face.data_ptr(), None if cand is None else cand.data_ptr(), ws.data_ptr(),
+                                      int(nb), pairs, ops._stream()), "pf_point_mesh_grid")
+    out = (dist, face) + ((cand,) if return_cand else ())
+    if return_info:
+        out += ({"pairs": pairs, "oversize": int(info[1]), "G": tuple(int(g) for g in info[2:5]), "cstart": int(info[5]),
+                 "over": int(info[6]), "pair_list": int(info[7]), "ws": ws},)
+    return out
+
+
 def point_to_mesh_distance(points: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, return_face: bool = False,
-                           brute: bool = False):
+                           brute: bool = False, search: str = "tiles"):
     """Distance [P] of every point of points [P,3] to the closest point of the triangle mesh (verts [V,3], faces [F,3]):
     what evaluation.cpp:224-232 gets from CGAL's AABB tree.  return_face: also the index of the closest face [P] (int64;
     the first of equally near faces in the search's order).  Points and faces go to pf_point_mesh_dist in Morton order
-    (the order makes its box pruning effective, not the result); brute = True disables the pruning."""
+    (the order makes its box pruning effective, not the result); brute = True disables the pruning.  search = "grid": the
+    same sort and seeds, then pf_point_mesh_grid (a uniform grid of the triangles, `tri_grid_search`) - the same dist and face,
+    bit for bit; meant for many points near a large mesh.  It has no unpruned form: brute = True with it is refused."""
+    if search not in P2F_SEARCHES:
+        raise ValueError(f"search is one of {P2F_SEARCHES}, got {search!r}")
+    if brute and search == "grid":
+        raise ValueError("brute=True goes with search='tiles': the grid search has no unpruned form")
     lib = _lib.load()
     pts = ops._f32c(points)
     v = ops._f32c(verts)
@@ -151,15 +204,18 @@ def point_to_mesh_distance(points: torch.Tensor, verts: torch.Tensor, faces: tor
     seed = torch.searchsorted(ct_sorted, cp_sorted).clamp_(max=F - 1).int()
     tris_s = tris[ot].reshape(F, 9).contiguous()
     pts_s = pts[op].contiguous()
-    nws = lib.pf_point_mesh_ws_floats(P, F)
-    if nws < 0:
-        _lib.check(int(nws), "pf_point_mesh_dist")
-    ws = torch.empty(int(nws), dtype=torch.float32, device=pts.device)
-    d_s = torch.empty(P, dtype=torch.float32, device=pts.device)
-    f_s = torch.empty(P, dtype=torch.int32, device=pts.device)
-    _lib.check(lib.pf_point_mesh_dist(pts_s.data_ptr(), P, tris_s.data_ptr(), F, seed.data_ptr(), 1 if brute else 0,
-                                      d_s.data_ptr(), f_s.data_ptr(), ws.data_ptr(), int(nws), ops._stream()),
-               "pf_point_mesh_dist")
+    if search == "grid":
+        d_s, f_s = tri_grid_search(pts_s, tris_s, seed)
+    else:
+        nws = lib.pf_point_mesh_ws_floats(P, F)
+        if nws < 0:
+            _lib.check(int(nws), "pf_point_mesh_dist")
+        ws = torch.empty(int(nws), dtype=torch.float32, device=pts.device)
+        d_s = torch.empty(P, dtype=torch.float32, device=pts.device)
+        f_s = torch.empty(P, dtype=torch.int32, device=pts.device)
+        _lib.check(lib.pf_point_mesh_dist(pts_s.data_ptr(), P, tris_s.data_ptr(), F, seed.data_ptr(), 1 if brute else 0,
+                                          d_s.data_ptr(), f_s.data_ptr(), ws.data_ptr(), int(nws), ops._stream()),
+                   "pf_point_mesh_dist")
     dist = torch.empty_like(d_s)
     dist[op] = d_s
     if not return_face:
