@@ -1298,6 +1298,34 @@ int pf_mtet_emit(const float* f, const unsigned char* flags, int Dx, int Dy, int
 int pf_mtet_vertices(const long long* edge_ids, long long V, const float* f, const float* gx, const float* gy, const float* gz,
                      int Dx, int Dy, int Dz, float* verts, void* stream);
 
+/* ---- closing holes: the band grows at its exits (csrc/recon.hip; DESIGN.md 8e "Closing holes") ------------------------------
+ * Where the samples leave a gap wider than the band, the zero set of f runs out of the active cells and the mesh ends there.
+ * f is defined everywhere (pf_imls takes the K nearest points wherever the query lies), so the host extends the band exactly
+ * where the surface leaves it, for up to R <= PF_RECON_GROW_MAX_ROUNDS rounds (a host-given bound), one pf_recon_grow per round,
+ * in the dense layout only.  Band, value and extraction are the entry points above, unchanged.
+ *   Grid      (host) pad = 3 + R corners per side: D_a = ceil((hi_a - lo_a) / h) + 7 + 2 R, and the tables are the old ones
+ *             shifted, g_a[i] = float32(o_a + (i - R) h) with the unchanged o_a = lo_a - 3 h, in double.  R = 0 is the expression
+ *             above.  The shift is monotone in the corner index, so edge ids keep their order and, on a cloud where nothing
+ *             grows, the mesh is the R = 0 mesh bit for bit.  PF_RECON_MAX_CORNERS applies to the padded box.
+ *   Exit      an inactive cell c (not on the last index of any axis) with one of its six face neighbours inside the grid, for
+ *             which both hold: the neighbour is ACTIVE (all 8 of its corners flagged), and the shared face's four corners do
+ *             not all agree in f < 0.  Those four corners belong to the active neighbour, so they are flagged and their f is
+ *             valid.  -0.0 and +0.0 are both "not inside", as in the extraction.
+ *   Round     pf_recon_grow: added [D_z, D_y, D_x] bytes, cleared, then every exit stores 1 at its own 8 corners.  Plain stores
+ *             of one value, no atomics; reads go to flags and f only, so nothing depends on the order of lanes.  The host takes
+ *             new = added & ~flags, compacts it in ascending corner index, evaluates pf_knn_grid and pf_imls at the new corners
+ *             only, scatters the values into f and sets flags |= added.
+ *   Stop      after R rounds, or earlier when a round finds no exit (an exit is inactive, so one of its corners is new: no new
+ *             corner, no exit).  The mesh is extracted once, after the last round.
+ * Marching tetrahedra cut every cell the same way, so a mesh edge used by one triangle lies on a face between an active and an
+ * inactive cell that the zero set crosses - an exit's face: "no exit left" and "no open edge" coincide, up to exact zeros of f.
+ * A hole shrinks from all sides by at most a cell per round.  A real boundary grows outward by at most R cells along the tangent
+ * planes and stays a boundary.  One lane per cell, every index checked, constant loop bounds, no atomics, no spin-wait, no grid
+ * barrier, no cooperative launch.  Before any device work: PF_ERR_NULL; PF_ERR_SHAPE (a D_a < 2); PF_ERR_UNSUPPORTED (a box over
+ * the cap). */
+#define PF_RECON_GROW_MAX_ROUNDS 64
+int pf_recon_grow(const float* f, const unsigned char* flags, int Dx, int Dy, int Dz, unsigned char* added, void* stream);
+
 /* ---- the same surface in a block-sparse layout (csrc/recon_sparse.hip; DESIGN.md 8e "Block-sparse band") -------------------
  * A second layout of the stages above whose memory and work follow the band, not the box.  It returns the dense layout's mesh
  * bit for bit (vertices, faces and their order) wherever that one runs, and the same contract's mesh beyond its cap.

@@ -1,6 +1,7 @@
 // A triangle mesh from an oriented cloud (DESIGN.md 8e "Surface from an oriented cloud"; the contract is in puflow_hip.h):
 // a band of grid corners around the points (pf_recon_mark), an IMLS value at those corners from the K nearest oriented points
 // (pf_imls), and the zero set by marching tetrahedra with vertices named by grid-edge id (pf_mtet_count / _emit / _vertices).
+// Between the value and the extraction the host may grow the band where the zero set leaves it (pf_recon_grow, "closing holes").
 //
 // Corner coordinates come from three fp32 tables the host made and are never recomputed here.  One lane per point, query, cell
 // or vertex; no LDS, no atomics, no lane-to-lane traffic; every loop has a constant or host-given bound.  All writers of the band
@@ -127,6 +128,47 @@ __global__ __launch_bounds__(RC_T) void mtet_vertices_kernel(const long long* __
     verts[v * 3 + 0] = x; verts[v * 3 + 1] = y; verts[v * 3 + 2] = z;
 }
 
+// ---- band growth at the exits (the rule: puflow_hip.h "closing holes") --------------------------------------------------------
+// One lane per cell.  A face can only be shared with an active neighbour when its four corners - corners of this cell - are
+// flagged, so a cell far from the band leaves after its own 8 flag bytes; the neighbour's other four flags and the face's four
+// values are read for the faces that pass.  Every index is a corner of this cell or of a neighbour checked to be a cell.
+__global__ __launch_bounds__(RC_T) void recon_grow_kernel(const float* __restrict__ f, const unsigned char* __restrict__ flags, int Dx,
+                                                          int Dy, int Dz, unsigned char* __restrict__ added) {
+    const int c = blockIdx.x * RC_T + threadIdx.x;
+    if (c >= Dx * Dy * Dz) return;
+    const int pos[3] = {c % Dx, (c / Dx) % Dy, c / (Dx * Dy)}, dim[3] = {Dx, Dy, Dz}, step[3] = {1, Dx, Dx * Dy};
+    if (pos[0] >= Dx - 1 || pos[1] >= Dy - 1 || pos[2] >= Dz - 1) return;
+    int own = 0;                                                            // bit x | y << 1 | z << 2: that corner is flagged
+#pragma unroll
+    for (int b = 0; b < 8; ++b) own |= (flags[c + (b & 1) + ((b >> 1) & 1) * Dx + ((b >> 2) & 1) * Dx * Dy] != 0 ? 1 : 0) << b;
+    if (own == 255) return;                                                 // active: no exit
+    bool exit = false;
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {                                       // the neighbour below (s = 0) / above (s = 1) along axis a
+            int face = 0;
+#pragma unroll
+            for (int b = 0; b < 8; ++b)
+                if (((b >> a) & 1) == s) face |= 1 << b;
+            const int n = pos[a] + (s ? 1 : -1), far = s ? step[a] : -step[a];
+            if ((own & face) != face || n < 0 || n > dim[a] - 2) continue;
+            bool all = true;
+            int inside = 0;
+#pragma unroll
+            for (int b = 0; b < 8; ++b)
+                if (((b >> a) & 1) == s) all = all && flags[c + (b & 1) + ((b >> 1) & 1) * Dx + ((b >> 2) & 1) * Dx * Dy + far] != 0;
+            if (!all) continue;                                             // f is read at the corners of an active cell only
+#pragma unroll
+            for (int b = 0; b < 8; ++b)
+                if (((b >> a) & 1) == s) inside += f[c + (b & 1) + ((b >> 1) & 1) * Dx + ((b >> 2) & 1) * Dx * Dy] < 0.f ? 1 : 0;
+            exit = exit || (inside != 0 && inside != 4);
+        }
+    if (!exit) return;
+#pragma unroll
+    for (int b = 0; b < 8; ++b) added[c + (b & 1) + ((b >> 1) & 1) * Dx + ((b >> 2) & 1) * Dx * Dy] = 1;
+}
+
 // PF_OK, or what the entry points return for a box that is no box / over the cap
 int rc_box(int Dx, int Dy, int Dz) {
     if (Dx < 2 || Dy < 2 || Dz < 2) return PF_ERR_SHAPE;
@@ -156,6 +198,16 @@ extern "C" int pf_imls(const float* query, const float* pts, const float* normal
         return PF_ERR_SHAPE;
     hipLaunchKernelGGL(imls_kernel, dim3(rc_blocks(Q)), dim3(RC_T), 0, (hipStream_t)stream, query, pts, normals, idx, Q, N, K,
                        1.0 / (sigma_h * sigma_h), f);
+    return pf_last_launch_status();
+}
+
+extern "C" int pf_recon_grow(const float* f, const unsigned char* flags, int Dx, int Dy, int Dz, unsigned char* added, void* stream) {
+    if (!f || !flags || !added) return PF_ERR_NULL;
+    const int rc = rc_box(Dx, Dy, Dz);
+    if (rc != PF_OK) return rc;
+    if (hipMemsetAsync(added, 0, (size_t)Dx * Dy * Dz, (hipStream_t)stream) != hipSuccess) return PF_ERR_LAUNCH;
+    hipLaunchKernelGGL(recon_grow_kernel, dim3(rc_blocks((long long)Dx * Dy * Dz)), dim3(RC_T), 0, (hipStream_t)stream, f, flags, Dx, Dy,
+                       Dz, added);
     return pf_last_launch_status();
 }
 

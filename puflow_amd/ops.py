@@ -699,6 +699,20 @@ def imls(query: torch.Tensor, pts: torch.Tensor, normals: torch.Tensor, idx: tor
     return f
 
 
+def recon_grow(f: torch.Tensor, flags: torch.Tensor) -> torch.Tensor:
+    """pf_recon_grow: f float32 / flags uint8 [D_z, D_y, D_x] -> uint8 added [D_z, D_y, D_x], 1 at the 8 corners of every exit (an
+    inactive cell that shares a face the zero set crosses with an active one)"""
+    lib = _lib.load()
+    if flags.dim() != 3:
+        raise _lib.PuflowHipError(f"recon_grow: flags [D_z, D_y, D_x], got {tuple(flags.shape)}")
+    dims = (int(flags.shape[2]), int(flags.shape[1]), int(flags.shape[0]))
+    f, flags = _recon_dense(f, dims, torch.float32, "recon_grow"), _recon_dense(flags, dims, torch.uint8, "recon_grow")
+    added = torch.empty(flags.shape, dtype=torch.uint8, device=f.device)
+    _lib.check(lib.pf_recon_grow(f.data_ptr(), flags.data_ptr(), dims[0], dims[1], dims[2], added.data_ptr(), _stream()),
+               "pf_recon_grow")
+    return added
+
+
 def mtet_count(f: torch.Tensor, flags: torch.Tensor) -> torch.Tensor:
     """pf_mtet_count: f float32 / flags uint8 [D_z, D_y, D_x] -> triangles per cell, int32 [D_z, D_y, D_x]"""
     lib = _lib.load()

@@ -9,6 +9,8 @@ from run to run.  There is no CPU path.
   mesh_from_cloud(points, normals, layout="sparse")           # the same mesh from 8 x 8 x 8 blocks around the band (csrc/
                                                               # recon_sparse.hip): nothing is as large as the box; "auto": dense
                                                               # while the box is within the dense cap, else sparse
+  mesh_from_cloud(points, normals, close_holes=4)             # up to 4 rounds of band growth where the zero set leaves the band
+                                                              # (pf_recon_grow): holes up to about 8 cells wider than the band close
   f = implicit(points, normals, query, h=cell_size(points))   # the implicit value at any points
   python -m puflow_amd.reconstruct --source DIR --target DIR  # every x y z nx ny nz file of DIR -> <name>.off
 """
@@ -30,6 +32,7 @@ SLOTS = BLOCK ** 3                      # ... corners of a block, ...
 MAX_AXIS = _lib.PF_RECON_SPARSE_MAX_AXIS        # ... corners per axis of its virtual grid ...
 MAX_BLOCKS = _lib.PF_RECON_SPARSE_MAX_BLOCKS    # ... and listed blocks
 LAYOUTS = ("dense", "sparse", "auto")
+GROW_MAX_ROUNDS = _lib.PF_RECON_GROW_MAX_ROUNDS  # band growth: rounds, each with one more corner of padding per side
 
 
 def _cloud(points, normals, what: str):
@@ -87,24 +90,37 @@ def _layout(layout, what: str) -> str:
     return layout
 
 
-def _box(cells) -> str:
-    return " x ".join(str(int(c) + 2 * PAD + 1) if np.isfinite(c) else "inf" for c in cells)
+def _rounds(close_holes, what: str) -> int:
+    if isinstance(close_holes, bool) or not isinstance(close_holes, (int, np.integer)) or not 0 <= close_holes <= GROW_MAX_ROUNDS:
+        raise _lib.PuflowHipError(f"{what}: close_holes = {close_holes!r} is no whole number of rounds in 0 .. {GROW_MAX_ROUNDS}")
+    return int(close_holes)
 
 
-def _within_dense_cap(cells) -> bool:
-    return bool((cells < MAX_CORNERS).all()) and \
-        int(cells[0] + 2 * PAD + 1) * int(cells[1] + 2 * PAD + 1) * int(cells[2] + 2 * PAD + 1) <= MAX_CORNERS
+def _box(cells, rounds: int = 0) -> str:
+    return " x ".join(str(int(c) + 2 * (PAD + rounds) + 1) if np.isfinite(c) else "inf" for c in cells)
 
 
-def corner_tables(lo, hi, h: float, layout: str = "dense"):
-    """the fp32 box and the cell size -> ((D_x, D_y, D_z), three float32 numpy tables g_a[i] = float32(o_a + i h)).  layout "dense":
-    at most PF_RECON_MAX_CORNERS corners in the box; "sparse": at most PF_RECON_SPARSE_MAX_AXIS per axis; "auto": either"""
-    layout = _layout(layout, "corner_tables")
+def _within_dense_cap(cells, rounds: int = 0) -> bool:
+    pad = 2 * (PAD + rounds) + 1
+    return bool((cells < MAX_CORNERS).all()) and int(cells[0] + pad) * int(cells[1] + pad) * int(cells[2] + pad) <= MAX_CORNERS
+
+
+def corner_tables(lo, hi, h: float, layout: str = "dense", rounds: int = 0):
+    """the fp32 box and the cell size -> ((D_x, D_y, D_z), three float32 numpy tables g_a[i] = float32(o_a + (i - rounds) h)).
+    layout "dense": at most PF_RECON_MAX_CORNERS corners in the box; "sparse": at most PF_RECON_SPARSE_MAX_AXIS per axis; "auto":
+    either.  rounds: that many more corners of padding per side for band growth (close_holes), dense only."""
+    layout, rounds = _layout(layout, "corner_tables"), _rounds(rounds, "corner_tables")
     lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
     o = lo - PAD * h
     cells = np.ceil((hi - lo) / h)
     unsupported = _lib.load().pf_error_string(_lib.PF_ERR_UNSUPPORTED).decode()
-    dense = _within_dense_cap(cells)
+    dense = _within_dense_cap(cells, rounds)
+    if rounds and (layout == "sparse" or not dense):
+        raise _lib.PuflowHipError(
+            f"reconstruct: close_holes = {rounds}: growth needs the dense layout" + (
+                " (--layout dense, or auto); a grown block list is not built" if layout == "sparse" else
+                f", and the padded box of {_box(cells, rounds)} corners at cell size {h:.6g} is over its cap of {MAX_CORNERS} "
+                f"({unsupported}): use a larger --cell (or --cell_scale) or fewer rounds"))
     if layout == "dense" and not dense:
         raise _lib.PuflowHipError(
             f"reconstruct: a box of {_box(cells)} corners at "
@@ -114,8 +130,8 @@ def corner_tables(lo, hi, h: float, layout: str = "dense"):
         raise _lib.PuflowHipError(
             f"reconstruct: a grid of {_box(cells)} corners at cell size {h:.6g} is over the sparse layout's cap of {MAX_AXIS} per "
             f"axis ({unsupported}): use a larger --cell (or --cell_scale)")
-    dims = tuple(int(c) + 2 * PAD + 1 for c in cells)
-    return dims, [(o[a] + np.arange(dims[a], dtype=np.float64) * h).astype(np.float32) for a in range(3)]
+    dims = tuple(int(c) + 2 * (PAD + rounds) + 1 for c in cells)
+    return dims, [(o[a] + (np.arange(dims[a], dtype=np.float64) - rounds) * h).astype(np.float32) for a in range(3)]
 
 
 def implicit(points: torch.Tensor, normals: torch.Tensor, query: torch.Tensor, k: int = 8, sigma: float = 1.0, h: float = None):
@@ -217,19 +233,68 @@ def extract_sparse(f: torch.Tensor, flags: torch.Tensor, blocks: torch.Tensor, l
     return ops.mtet_vertices_sparse(edge, f, blocks, links, tables), inverse.reshape(-1, 3)
 
 
+# ---- closing holes: the band grows at its exits (the rule is in puflow_hip.h) ---------------------------------------------------
+EXITS_CHUNK = 1 << 17                   # new corners per pass of the exit count: its index tensors are [chunk, 8, 8] int64
+
+
+def _exits(f: torch.Tensor, born: torch.Tensor, corners) -> list:
+    """the exits of every round, counted ONCE after the last round, for info["grown_cells"] only (what grows is pf_recon_grow's
+    business).  born int8 [D_z, D_y, D_x]: the round that flagged a corner (0: the band of the points, 127: never), so the flags
+    round r saw are born < r; f: the final values - a round reads f at the corners of cells active by then, and those never
+    change.  corners: per round r = 1, 2, .. the indices of its new corners.  Every exit has a new corner, so the candidates are
+    the 8 cells around each new corner - torch gathers over [Q, 8], nothing over the box - and a cell counts at its first new
+    corner.  One host read."""
+    Dz, Dy, Dx = born.shape
+    dev = born.device
+    bits = torch.arange(8, device=dev)
+    off = torch.stack([bits & 1, (bits >> 1) & 1, bits >> 2], dim=1)                           # [8, 3]: x, y, z of corner b
+    stride = torch.tensor([1, Dx, Dx * Dy], device=dev)
+    last = torch.tensor([Dx - 2, Dy - 2, Dz - 2], device=dev)                                  # the last cell of an axis
+    flat, values, size = born.reshape(-1), f.reshape(-1), born.numel()
+    count = torch.zeros(len(corners) + 1, dtype=torch.int64, device=dev)
+    every = torch.cat(corners)
+    rounds = torch.cat([torch.full((c.shape[0],), r, dtype=torch.int64, device=dev) for r, c in enumerate(corners, 1)])
+    for corner, r in zip(every.split(EXITS_CHUNK), rounds.split(EXITS_CHUNK)):
+        cell = torch.stack([corner % Dx, (corner // Dx) % Dy, corner // (Dx * Dy)], dim=1)[:, None] - off       # [Q, 8, 3]
+        is_cell = ((cell >= 0) & (cell <= last)).all(dim=2)
+        cell = torch.minimum(cell.clamp(min=0), last)                                          # clamped: every gather stays inside
+        at = (cell[:, :, None] + off).mul(stride).sum(dim=3)                                   # [Q, 8, 8]: the cell's corners
+        when = flat[at]
+        own = when < r[:, None, None]
+        first = ~((when == r[:, None, None]) & (bits[None, :] < bits[:, None])).any(dim=2)     # no new corner before corner b
+        crossed = torch.zeros_like(is_cell)
+        for a in range(3):
+            for s in (0, 1):
+                face = [b for b in range(8) if (b >> a) & 1 == s]                              # the four corners on that side
+                n = cell[:, :, a] + (2 * s - 1)
+                far = (at[:, :, face] + (2 * s - 1) * stride[a]).clamp(0, size - 1)            # the neighbour's other four
+                active = own[:, :, face].all(dim=2) & (flat[far] < r[:, None, None]).all(dim=2) & (n >= 0) & (n <= last[a])
+                inside = (values[at[:, :, face]] < 0).sum(dim=2)
+                crossed |= active & (inside != 0) & (inside != 4)
+        count.index_add_(0, r, (is_cell & ~own.all(dim=2) & crossed & first).sum(dim=1))
+    return count[1:].tolist()
+
+
 def mesh_from_cloud(points: torch.Tensor, normals: torch.Tensor, cell: float = None, cell_scale: float = 1.0, k: int = 8,
-                    sigma: float = 1.0, layout: str = "dense"):
+                    sigma: float = 1.0, layout: str = "dense", close_holes: int = 0):
     """points, normals [N,3] on the GPU (unit normals with consistent signs: estimate_normals(..., orient="propagate") or a
     scanner's) -> (verts [V,3] float32, faces [F,3] int32, info).  cell: the grid's cell size; default cell_scale x the median
     distance to the 6th nearest other point.  layout: "dense" - arrays over the cloud's box, refused over PF_RECON_MAX_CORNERS;
     "sparse" - 8 x 8 x 8 blocks around the band, the same mesh bit for bit, nothing allocated by the size of the box; "auto" -
     dense while the box is within the dense cap, else sparse.  info: h, dims (D_x, D_y, D_z), layout (the one used), blocks (0
     for dense) and open_edges, the number of mesh edges used by one triangle only - 0 for a closed surface; a cell below the
-    sampling spacing tears holes, and a scan's real boundary stays one."""
+    sampling spacing tears holes, and a scan's real boundary stays one.  close_holes = R (0 .. PF_RECON_GROW_MAX_ROUNDS, dense
+    layout): up to R rounds in which the band grows by the cells into which the zero set leaves it (pf_recon_grow) - a hole
+    shrinks from all sides by at most a cell per round, a real boundary moves outward by at most R cells and stays one; the
+    filled patch follows the nearest points' tangent planes.  info then has grow_rounds, the rounds that added something, and
+    grown_cells, the exits of each.  R = 0 is the call without it, byte for byte."""
     points, normals = _cloud(points, normals, "mesh_from_cloud")
     k = _k(k, points.shape[0], "mesh_from_cloud")
     sigma = _positive(sigma, "sigma", "mesh_from_cloud")
-    layout = _layout(layout, "mesh_from_cloud")
+    layout, rounds = _layout(layout, "mesh_from_cloud"), _rounds(close_holes, "mesh_from_cloud")
+    if rounds and layout == "sparse":
+        raise _lib.PuflowHipError(f"mesh_from_cloud: close_holes = {rounds}: growth needs the dense layout (layout=\"dense\", or "
+                                  "\"auto\" while the padded box is within the dense cap); a grown block list is not built")
     if cell is not None:
         h = _positive(cell, "cell", "mesh_from_cloud")
         _, lo, hi = _stats(points, False)
@@ -238,8 +303,9 @@ def mesh_from_cloud(points: torch.Tensor, normals: torch.Tensor, cell: float = N
         m, lo, hi = _stats(points, True)
         h = _positive(scale * float(np.sqrt(m)), "the cell size from the cloud's spacing", "mesh_from_cloud")
     if layout == "auto":
-        layout = "dense" if _within_dense_cap(np.ceil((hi - lo) / h)) else "sparse"
-    dims, host_tables = corner_tables(lo, hi, h, layout)
+        layout = "dense" if rounds or _within_dense_cap(np.ceil((hi - lo) / h)) else "sparse"      # growth: dense, or refused
+    dims, host_tables = corner_tables(lo, hi, h, layout, rounds)
+    grown = []
     dev = points.device
     tables = [torch.from_numpy(t).to(dev) for t in host_tables]
     if layout == "sparse":
@@ -254,17 +320,34 @@ def mesh_from_cloud(points: torch.Tensor, normals: torch.Tensor, cell: float = N
         verts, faces = extract_sparse(f, flags, blocks, links, tables)
         nblocks = int(blocks.shape[0])
     else:
+        Dx, Dy = dims[0], dims[1]
+
+        def value(corner):
+            query = torch.stack([tables[0][corner % Dx], tables[1][(corner // Dx) % Dy], tables[2][corner // (Dx * Dy)]], dim=1)
+            idx, _ = ops.knn_grid(points[None], query[None], k)
+            return ops.imls(query, points, normals, idx[0], sigma * h)
         flags = ops.recon_mark(points, tables)
         corner = torch.nonzero(flags.reshape(-1)).reshape(-1)               # ascending corner index
-        Dx, Dy = dims[0], dims[1]
-        query = torch.stack([tables[0][corner % Dx], tables[1][(corner // Dx) % Dy], tables[2][corner // (Dx * Dy)]], dim=1)
-        idx, _ = ops.knn_grid(points[None], query[None], k)
         f = torch.empty(flags.shape, dtype=torch.float32, device=dev)       # inactive corners are never read
-        f.reshape(-1)[corner] = ops.imls(query, points, normals, idx[0], sigma * h)
+        f.reshape(-1)[corner] = value(corner)
+        born = None
+        for r in range(1, rounds + 1):
+            added = ops.recon_grow(f, flags)
+            corner = torch.nonzero((added & ~flags).reshape(-1)).reshape(-1)            # its size: the one host read of a round
+            if corner.shape[0] == 0:                                        # no new corner, no exit
+                break
+            if born is None:
+                born = (flags == 0).to(torch.int8) * 127
+            born.reshape(-1)[corner] = r
+            grown.append(corner)
+            f.reshape(-1)[corner] = value(corner)
+            flags |= added
+        grown = _exits(f, born, grown) if grown else []
         verts, faces = extract(f, flags, tables)
         nblocks = 0
     open_edges = int(_open_edges(faces, verts.shape[0])) if faces.shape[0] else 0
-    return verts, faces.to(torch.int32), {"h": h, "dims": dims, "open_edges": open_edges, "layout": layout, "blocks": nblocks}
+    return verts, faces.to(torch.int32), {"h": h, "dims": dims, "open_edges": open_edges, "layout": layout, "blocks": nblocks,
+                                          "grow_rounds": len(grown), "grown_cells": grown}
 
 
 def write_off(path, verts, faces) -> None:
@@ -291,7 +374,7 @@ OPEN_EDGES_LINE = ("{name}: {n} open edges - the mesh has a boundary: the cell (
 
 @torch.no_grad()
 def reconstruct_files(paths, target: str, cell=None, cell_scale: float = 1.0, k: int = 8, sigma: float = 1.0,
-                      normal_column: int = 4, device="cuda:0", layout: str = "dense"):
+                      normal_column: int = 4, device="cuda:0", layout: str = "dense", close_holes: int = 0):
     from .upsample import load_xyz
     c0 = int(normal_column) - 1
     if c0 < 3:
@@ -309,7 +392,8 @@ def reconstruct_files(paths, target: str, cell=None, cell_scale: float = 1.0, k:
         xyz = torch.from_numpy(np.ascontiguousarray(rows[:, :3])).to(device)
         nrm = torch.from_numpy(np.ascontiguousarray(rows[:, c0:c0 + 3])).to(device)
         nrm = nrm / nrm.norm(dim=1, keepdim=True).clamp_min(1e-30)          # six printed decimals are not unit length
-        verts, faces, info = mesh_from_cloud(xyz, nrm, cell=cell, cell_scale=cell_scale, k=k, sigma=sigma, layout=layout)
+        verts, faces, info = mesh_from_cloud(xyz, nrm, cell=cell, cell_scale=cell_scale, k=k, sigma=sigma, layout=layout,
+                                             close_holes=close_holes)
         name = os.path.splitext(os.path.basename(p))[0] + ".off"
         write_off(os.path.join(target, name), verts, faces)
         if info["open_edges"] > 0:
@@ -332,12 +416,15 @@ def main(argv=None):
     parser.add_argument("--layout", type=str, default="dense", choices=LAYOUTS,
                         help="dense: arrays over the cloud's box; sparse: blocks around the band, for a box that is mostly empty; "
                              "auto: dense while the box is within the dense cap")
+    parser.add_argument("--close_holes", type=int, default=0, metavar="R",
+                        help=f"up to R (0 .. {GROW_MAX_ROUNDS}) rounds of band growth where the surface leaves the band: a hole closes "
+                             "by a cell per round from every side, a real boundary moves out by at most R cells; dense layout only")
     args = parser.parse_args(argv)
     paths = []
     for root, _dirs, files in os.walk(args.source):
         paths.extend([os.path.join(root, f) for f in files if ".xyz" in f])
     reconstruct_files(paths, args.target, cell=args.cell, cell_scale=args.cell_scale, k=args.k, sigma=args.sigma,
-                      normal_column=args.normal_column, layout=args.layout)
+                      normal_column=args.normal_column, layout=args.layout, close_holes=args.close_holes)
 
 
 if __name__ == "__main__":
