@@ -1,7 +1,10 @@
 // What the two layouts of the surface reconstruction share (csrc/recon.hip: dense arrays over the box; csrc/recon_sparse.hip:
 // 8 x 8 x 8 blocks around the band): the cell of a point, the generated triangle table of marching tetrahedra, the sign pattern of
-// a tet and the vertex arithmetic.  The contract is in puflow_hip.h.  Everything here has internal linkage: each source holds
-// its own copy of the table in constant memory.
+// a tet and - written once over "the flag and value at a corner, in this layout" (the last section) - the 4 x 4 x 4 stamp of a
+// point, the inside bits of a cell, the triangles of a cell and the vertex of an edge id.  A source keeps what is its layout's:
+// addressing, block keys and links, tiles.  The contract is in puflow_hip.h.  Everything here has internal linkage: each source
+// holds its own copy of the table in constant memory.  Like the kernels that use them the rules are one lane per item, without
+// atomics, with constant loop bounds, and check every index they form from a list (offsets, edge ids) before they use it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -122,6 +125,87 @@ __device__ __forceinline__ int mt_offset_bits(int cls) { return cls < 3 ? 1 << c
 __device__ __forceinline__ float mt_lerp(float ga, float gb, float t) {
 #pragma clang fp contract(off)
     return __fadd_rn(ga, __fmul_rn(t, __fsub_rn(gb, ga)));
+}
+
+// ---- written once over "the flag and value at a corner, in this layout" ------------------------------------------------------
+// A layout hands the three rules below a functor and keeps its addressing to itself:
+//   a cell:   flagged(b), inside(b) - corner b (x | y << 1 | z << 2) of the cell is in the band / has f < 0 there; inside(b) is
+//             asked only once all eight are flagged, so f is read at active corners only and the flags come first
+//   an edge:  ends(i, j, k, i2, j2, k2, fa, fb) - f at both end corners of an edge of the grid, false if one is not held
+//   a point:  put(i, j, k) - flag that corner of the grid
+// A further layout (a grown block list, say - not built) supplies these three and gets the extraction as it stands.
+
+// a point count that the kernels can index with int: N > 0 and 3 N <= INT_MAX
+inline bool rc_count_ok(int N) { return N > 0 && (long long)N * 3 <= 0x7fffffffll; }
+
+// the global index of corner b (x | y << 1 | z << 2) of the cell with lower corner c
+template <typename C, typename I>
+__device__ __forceinline__ C rc_corner(C c, int b, I Dx, I Dy) { return c + (b & 1) + ((b >> 1) & 1) * Dx + ((b >> 2) & 1) * Dx * Dy; }
+
+// the 4 x 4 x 4 corners around the cell of a point, those inside the box
+template <typename Put>
+__device__ __forceinline__ void rc_stamp(int cx, int cy, int cz, int Dx, int Dy, int Dz, Put put) {
+    for (int dz = -1; dz <= 2; ++dz)
+        for (int dy = -1; dy <= 2; ++dy)
+            for (int dx = -1; dx <= 2; ++dx) {
+                const int i = cx + dx, j = cy + dy, k = cz + dz;
+                if ((unsigned)i < (unsigned)Dx && (unsigned)j < (unsigned)Dy && (unsigned)k < (unsigned)Dz) put(i, j, k);
+            }
+}
+
+// the inside bits (f < 0) of a cell's 8 corners, bit x | y << 1 | z << 2; -1: one of them is not flagged - no active cell
+template <typename Cell>
+__device__ __forceinline__ int mt_cell_bits(const Cell& cell) {
+    bool all = true;
+#pragma unroll
+    for (int b = 0; b < 8; ++b) all = all && cell.flagged(b);
+    if (!all) return -1;
+    int bits = 0;
+#pragma unroll
+    for (int b = 0; b < 8; ++b) bits |= (cell.inside(b) ? 1 : 0) << b;
+    return bits;
+}
+
+// the triangles of the cell with GLOBAL corner index c and these inside bits, as edge ids 7 owner + class, from offset *first
+// on (read for a cell with triangles only)
+template <typename I>
+__device__ __forceinline__ void mt_emit_cell(int bits, I c, I Dx, I Dy, const long long* first, long long T, long long* edge_ids) {
+    if (bits <= 0 || bits >= 255) return;
+    long long t = *first;
+    for (int tet = 0; tet < 6; ++tet) {
+        const int mask = mt_mask(bits, tet), n = mt_table.ntri[tet][mask];
+        for (int s = 0; s < n; ++s, ++t) {
+            if (t < 0 || t >= T) return;                                    // offsets that are not this field's prefix sum: a wrong mesh
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const int e = mt_table.edge[tet][mask][s][k];
+                const long long owner = rc_corner((long long)c, e >> 3, Dx, Dy);
+                edge_ids[t * 3 + k] = 7 * owner + (e & 7);
+            }
+        }
+    }
+}
+
+// the vertex of edge id `id` of a D_x x D_y x D_z grid; (0, 0, 0) for an id that is no edge of it or whose ends are not held.
+// I: an integer that holds a corner index of the grid.
+template <typename I, typename Ends>
+__device__ __forceinline__ void mt_vertex_of(long long id, int Dx, int Dy, int Dz, const float* __restrict__ gx,
+                                             const float* __restrict__ gy, const float* __restrict__ gz, Ends ends,
+                                             float* __restrict__ vert) {
+    const I DxDy = (I)Dx * Dy;
+    float x = 0.f, y = 0.f, z = 0.f;
+    if (id >= 0 && id < 7ll * DxDy * Dz) {
+        const I a = (I)(id / 7);
+        const int ob = mt_offset_bits((int)(id % 7));
+        const int i = (int)(a % Dx), j = (int)((a / Dx) % Dy), k = (int)(a / DxDy);
+        const int i2 = i + (ob & 1), j2 = j + ((ob >> 1) & 1), k2 = k + ((ob >> 2) & 1);
+        float fa, fb;
+        if (i2 < Dx && j2 < Dy && k2 < Dz && ends(i, j, k, i2, j2, k2, fa, fb)) {
+            const float t = __fdiv_rn(fa, __fsub_rn(fa, fb));
+            x = mt_lerp(gx[i], gx[i2], t); y = mt_lerp(gy[j], gy[j2], t); z = mt_lerp(gz[k], gz[k2], t);
+        }
+    }
+    vert[0] = x; vert[1] = y; vert[2] = z;
 }
 
 }  // namespace

@@ -3,6 +3,11 @@
 // (pf_imls), and the zero set by marching tetrahedra with vertices named by grid-edge id (pf_mtet_count / _emit / _vertices).
 // Between the value and the extraction the host may grow the band where the zero set leaves it (pf_recon_grow, "closing holes").
 //
+// This is the dense layout: flags and values are arrays over the box, corner (i, j, k) at (k D_y + j) D_x + i, and every corner
+// of the box is held.  The stamp of a point, the inside bits and triangles of a cell and the vertex of an edge id are pf_recon.h's,
+// shared with csrc/recon_sparse.hip; the kernels here are index setup plus a call.  Band growth alone is written against dense
+// addresses (its neighbour reads are c +- a stride); growth over a block list is not built.
+//
 // Corner coordinates come from three fp32 tables the host made and are never recomputed here.  One lane per point, query, cell
 // or vertex; no LDS, no atomics, no lane-to-lane traffic; every loop has a constant or host-given bound.  All writers of the band
 // store the same byte, the triangles go where a host-side prefix sum put them and the vertices where torch.unique's order put
@@ -19,15 +24,8 @@ __global__ __launch_bounds__(RC_T) void recon_mark_kernel(const float* __restric
                                                           int Dz, unsigned char* __restrict__ flags) {
     const int p = blockIdx.x * RC_T + threadIdx.x;
     if (p >= N) return;
-    const int cx = rc_cell(gx, Dx, pts[(size_t)p * 3 + 0]), cy = rc_cell(gy, Dy, pts[(size_t)p * 3 + 1]),
-              cz = rc_cell(gz, Dz, pts[(size_t)p * 3 + 2]);
-    for (int dz = -1; dz <= 2; ++dz)
-        for (int dy = -1; dy <= 2; ++dy)
-            for (int dx = -1; dx <= 2; ++dx) {
-                const int i = cx + dx, j = cy + dy, k = cz + dz;
-                if ((unsigned)i < (unsigned)Dx && (unsigned)j < (unsigned)Dy && (unsigned)k < (unsigned)Dz)
-                    flags[((size_t)k * Dy + j) * Dx + i] = 1;
-            }
+    rc_stamp(rc_cell(gx, Dx, pts[(size_t)p * 3 + 0]), rc_cell(gy, Dy, pts[(size_t)p * 3 + 1]), rc_cell(gz, Dz, pts[(size_t)p * 3 + 2]),
+             Dx, Dy, Dz, [=](int i, int j, int k) { flags[((size_t)k * Dy + j) * Dx + i] = 1; });
 }
 
 // ---- the implicit value ------------------------------------------------------------------------------------------------------
@@ -54,34 +52,29 @@ __global__ __launch_bounds__(RC_T) void imls_kernel(const float* __restrict__ qu
     f[q] = (float)(num / den);
 }
 
-// ---- marching tetrahedra (the table, mt_mask and mt_lerp: pf_recon.h) --------------------------------------------------------
-// the inside bits (f < 0) of the 8 corners of cell c, bit x | y << 1 | z << 2; -1: c is no active cell
-__device__ __forceinline__ int mt_cell_bits(const float* __restrict__ f, const unsigned char* __restrict__ flags, int c, int Dx, int Dy,
+// ---- marching tetrahedra (the table and the rules over a cell, an edge: pf_recon.h) ------------------------------------------
+// the dense layout's cell: corner b of the cell with lower corner c is flags / f at rc_corner(c, b)
+struct RcCell {
+    const float* __restrict__ f;
+    const unsigned char* __restrict__ flags;
+    int c, Dx, Dy;
+    __device__ __forceinline__ bool flagged(int b) const { return flags[rc_corner(c, b, Dx, Dy)] != 0; }
+    __device__ __forceinline__ bool inside(int b) const { return f[rc_corner(c, b, Dx, Dy)] < 0.f; }
+};
+
+// the inside bits of cell c; -1: c is no cell of the box or no active one
+__device__ __forceinline__ int rc_cell_bits(const float* __restrict__ f, const unsigned char* __restrict__ flags, int c, int Dx, int Dy,
                                             int Dz) {
     const int i = c % Dx, j = (c / Dx) % Dy, k = c / (Dx * Dy);
     if (i >= Dx - 1 || j >= Dy - 1 || k >= Dz - 1) return -1;
-    int bits = 0;
-    bool all = true;
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-        const int o = c + (b & 1) + ((b >> 1) & 1) * Dx + ((b >> 2) & 1) * Dx * Dy;
-        all = all && flags[o] != 0;
-    }
-    if (!all) return -1;                                                    // f is read at active corners only
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-        const int o = c + (b & 1) + ((b >> 1) & 1) * Dx + ((b >> 2) & 1) * Dx * Dy;
-        bits |= (f[o] < 0.f ? 1 : 0) << b;
-    }
-    return bits;
+    return mt_cell_bits(RcCell{f, flags, c, Dx, Dy});
 }
 
 __global__ __launch_bounds__(RC_T) void mtet_count_kernel(const float* __restrict__ f, const unsigned char* __restrict__ flags,
                                                           int Dx, int Dy, int Dz, int* __restrict__ count) {
     const int c = blockIdx.x * RC_T + threadIdx.x;
     if (c >= Dx * Dy * Dz) return;
-    const int bits = mt_cell_bits(f, flags, c, Dx, Dy, Dz);
-    count[c] = mt_triangles(bits);
+    count[c] = mt_triangles(rc_cell_bits(f, flags, c, Dx, Dy, Dz));
 }
 
 __global__ __launch_bounds__(RC_T) void mtet_emit_kernel(const float* __restrict__ f, const unsigned char* __restrict__ flags, int Dx,
@@ -89,21 +82,7 @@ __global__ __launch_bounds__(RC_T) void mtet_emit_kernel(const float* __restrict
                                                          long long* __restrict__ edge_ids) {
     const int c = blockIdx.x * RC_T + threadIdx.x;
     if (c >= Dx * Dy * Dz) return;
-    const int bits = mt_cell_bits(f, flags, c, Dx, Dy, Dz);
-    if (bits <= 0 || bits >= 255) return;
-    long long t = first[c];
-    for (int tet = 0; tet < 6; ++tet) {
-        const int mask = mt_mask(bits, tet), n = mt_table.ntri[tet][mask];
-        for (int s = 0; s < n; ++s, ++t) {
-            if (t < 0 || t >= T) return;                                    // offsets that are not this field's prefix sum: a wrong mesh
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const int e = mt_table.edge[tet][mask][s][k], o = e >> 3;
-                const long long owner = (long long)c + (o & 1) + ((o >> 1) & 1) * Dx + ((o >> 2) & 1) * Dx * Dy;
-                edge_ids[t * 3 + k] = 7 * owner + (e & 7);
-            }
-        }
-    }
+    mt_emit_cell(rc_cell_bits(f, flags, c, Dx, Dy, Dz), c, Dx, Dy, first + c, T, edge_ids);
 }
 
 __global__ __launch_bounds__(RC_T) void mtet_vertices_kernel(const long long* __restrict__ edge_ids, long long V,
@@ -112,20 +91,10 @@ __global__ __launch_bounds__(RC_T) void mtet_vertices_kernel(const long long* __
                                                              int Dz, float* __restrict__ verts) {
     const long long v = (long long)blockIdx.x * RC_T + threadIdx.x;
     if (v >= V) return;
-    const long long id = edge_ids[v];
-    float x = 0.f, y = 0.f, z = 0.f;
-    if (id >= 0 && id < 7ll * Dx * Dy * Dz) {
-        const int a = (int)(id / 7), cls = (int)(id % 7);
-        const int ob = mt_offset_bits(cls);
-        const int i = a % Dx, j = (a / Dx) % Dy, k = a / (Dx * Dy);
-        const int i2 = i + (ob & 1), j2 = j + ((ob >> 1) & 1), k2 = k + ((ob >> 2) & 1);
-        if (i2 < Dx && j2 < Dy && k2 < Dz) {                                // an id that is no edge of the box: (0, 0, 0)
-            const float fa = f[a], fb = f[((size_t)k2 * Dy + j2) * Dx + i2];
-            const float t = __fdiv_rn(fa, __fsub_rn(fa, fb));
-            x = mt_lerp(gx[i], gx[i2], t); y = mt_lerp(gy[j], gy[j2], t); z = mt_lerp(gz[k], gz[k2], t);
-        }
-    }
-    verts[v * 3 + 0] = x; verts[v * 3 + 1] = y; verts[v * 3 + 2] = z;
+    mt_vertex_of<int>(edge_ids[v], Dx, Dy, Dz, gx, gy, gz, [=](int i, int j, int k, int i2, int j2, int k2, float& fa, float& fb) {
+        fa = f[((size_t)k * Dy + j) * Dx + i]; fb = f[((size_t)k2 * Dy + j2) * Dx + i2];           // every corner of the box is held
+        return true;
+    }, verts + v * 3);
 }
 
 // ---- band growth at the exits (the rule: puflow_hip.h "closing holes") --------------------------------------------------------
@@ -140,7 +109,7 @@ __global__ __launch_bounds__(RC_T) void recon_grow_kernel(const float* __restric
     if (pos[0] >= Dx - 1 || pos[1] >= Dy - 1 || pos[2] >= Dz - 1) return;
     int own = 0;                                                            // bit x | y << 1 | z << 2: that corner is flagged
 #pragma unroll
-    for (int b = 0; b < 8; ++b) own |= (flags[c + (b & 1) + ((b >> 1) & 1) * Dx + ((b >> 2) & 1) * Dx * Dy] != 0 ? 1 : 0) << b;
+    for (int b = 0; b < 8; ++b) own |= (flags[rc_corner(c, b, Dx, Dy)] != 0 ? 1 : 0) << b;
     if (own == 255) return;                                                 // active: no exit
     bool exit = false;
 #pragma unroll
@@ -157,16 +126,16 @@ __global__ __launch_bounds__(RC_T) void recon_grow_kernel(const float* __restric
             int inside = 0;
 #pragma unroll
             for (int b = 0; b < 8; ++b)
-                if (((b >> a) & 1) == s) all = all && flags[c + (b & 1) + ((b >> 1) & 1) * Dx + ((b >> 2) & 1) * Dx * Dy + far] != 0;
+                if (((b >> a) & 1) == s) all = all && flags[rc_corner(c, b, Dx, Dy) + far] != 0;
             if (!all) continue;                                             // f is read at the corners of an active cell only
 #pragma unroll
             for (int b = 0; b < 8; ++b)
-                if (((b >> a) & 1) == s) inside += f[c + (b & 1) + ((b >> 1) & 1) * Dx + ((b >> 2) & 1) * Dx * Dy] < 0.f ? 1 : 0;
+                if (((b >> a) & 1) == s) inside += f[rc_corner(c, b, Dx, Dy)] < 0.f ? 1 : 0;
             exit = exit || (inside != 0 && inside != 4);
         }
     if (!exit) return;
 #pragma unroll
-    for (int b = 0; b < 8; ++b) added[c + (b & 1) + ((b >> 1) & 1) * Dx + ((b >> 2) & 1) * Dx * Dy] = 1;
+    for (int b = 0; b < 8; ++b) added[rc_corner(c, b, Dx, Dy)] = 1;
 }
 
 // PF_OK, or what the entry points return for a box that is no box / over the cap
@@ -181,7 +150,7 @@ int rc_box(int Dx, int Dy, int Dz) {
 extern "C" int pf_recon_mark(const float* pts, int N, const float* gx, const float* gy, const float* gz, int Dx, int Dy, int Dz,
                              unsigned char* flags, void* stream) {
     if (!pts || !gx || !gy || !gz || !flags) return PF_ERR_NULL;
-    if (N <= 0 || (long long)N * 3 > 0x7fffffffll) return PF_ERR_SHAPE;
+    if (!rc_count_ok(N)) return PF_ERR_SHAPE;
     const int rc = rc_box(Dx, Dy, Dz);
     if (rc != PF_OK) return rc;
     if (hipMemsetAsync(flags, 0, (size_t)Dx * Dy * Dz, (hipStream_t)stream) != hipSuccess) return PF_ERR_LAUNCH;
@@ -193,7 +162,7 @@ extern "C" int pf_imls(const float* query, const float* pts, const float* normal
                        double sigma_h, float* f, void* stream) {
     if (!query || !pts || !normals || !idx || !f) return PF_ERR_NULL;
     if (K < 1 || K > PF_KNN_GRID_MAX_K) return PF_ERR_UNSUPPORTED;
-    if (Q <= 0 || N <= 0 || K > N || (long long)N * 3 > 0x7fffffffll || (long long)Q * 3 > 0x7fffffffll || !(sigma_h > 0.0) ||
+    if (!rc_count_ok(Q) || !rc_count_ok(N) || K > N || !(sigma_h > 0.0) ||
         !(1.0 / (sigma_h * sigma_h) < HUGE_VAL))
         return PF_ERR_SHAPE;
     hipLaunchKernelGGL(imls_kernel, dim3(rc_blocks(Q)), dim3(RC_T), 0, (hipStream_t)stream, query, pts, normals, idx, Q, N, K,

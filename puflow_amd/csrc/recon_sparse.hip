@@ -2,7 +2,10 @@
 // same virtual grid, cell rule, tets, edge ids and vertex arithmetic as csrc/recon.hip (shared through pf_recon.h), with the flags
 // and the implicit value held per 8 x 8 x 8 block of corners, [NB, 512], for the blocks that the band touches only.  The
 // ascending list of distinct block keys is the layout: a block is found by a binary search in it (32 halvings, a constant), its
-// 7 upper neighbours through a link table made once.  Memory and work follow the band, never D_x D_y D_z.
+// 7 upper neighbours through a link table made once.  Memory and work follow the band, never D_x D_y D_z.  What the layout
+// supplies to pf_recon.h's rules: the byte (flag, sign) of a corner of a block's 9 x 9 x 9 tile (rs_corner_byte, through the links),
+// f at both ends of an edge (one search, then a link), and the store of a stamped corner into one of a point's 8 blocks.  A grown
+// block list (band growth on this layout) would be one more writer of the list and is not built.
 //
 // One lane per point, block link, cell or vertex; pf_mtet_count_sparse is one workgroup per block with a 9 x 9 x 9 tile of
 // (flag, sign) bytes in LDS.  No atomics, no lane-to-lane traffic but that tile; every loop has a constant or host-given bound;
@@ -99,17 +102,13 @@ __global__ __launch_bounds__(RC_T) void mark_sparse_kernel(const float* __restri
         const bool here = (!(o & 1) || two_x) && (!(o & 2) || two_y) && (!(o & 4) || two_z);
         at[o] = here ? rs_find(blocks, g.NB, rs_key(g, bx + (o & 1), by + ((o >> 1) & 1), bz + ((o >> 2) & 1))) : -1;
     }
-    for (int dz = -1; dz <= 2; ++dz)
-        for (int dy = -1; dy <= 2; ++dy)
-            for (int dx = -1; dx <= 2; ++dx) {
-                const int i = cx + dx, j = cy + dy, k = cz + dz;
-                if ((unsigned)i >= (unsigned)g.Dx || (unsigned)j >= (unsigned)g.Dy || (unsigned)k >= (unsigned)g.Dz) continue;
-                const int o = ((i >> 3) - bx) | ((j >> 3) - by) << 1 | ((k >> 3) - bz) << 2;        // 4 corners span at most 2 blocks
-                int b = -1;
+    rc_stamp(cx, cy, cz, g.Dx, g.Dy, g.Dz, [=](int i, int j, int k) {
+        const int o = ((i >> 3) - bx) | ((j >> 3) - by) << 1 | ((k >> 3) - bz) << 2;                // 4 corners span at most 2 blocks
+        int b = -1;
 #pragma unroll
-                for (int q = 0; q < 8; ++q) b = (q == o) ? at[q] : b;       // a select chain: at[] stays in registers
-                if (b >= 0) flags[(size_t)b * RS_SLOTS + ((k & 7) << 6 | (j & 7) << 3 | (i & 7))] = 1;
-            }
+        for (int q = 0; q < 8; ++q) b = (q == o) ? at[q] : b;               // a select chain: at[] stays in registers
+        if (b >= 0) flags[(size_t)b * RS_SLOTS + ((k & 7) << 6 | (j & 7) << 3 | (i & 7))] = 1;
+    });
 }
 
 // ---- marching tetrahedra ---------------------------------------------------------------------------------------------------------
@@ -129,20 +128,20 @@ __device__ __forceinline__ int rs_corner_byte(const float* __restrict__ f, const
     return 1 | (f[at] < 0.f ? 2 : 0);
 }
 
-// inside bits of the cell with lower corner (x, y, z) of the tile, -1 if one of its corners is not flagged
-template <typename Corner>
-__device__ __forceinline__ int rs_cell_bits(Corner corner, int x, int y, int z) {
-    int bits = 0, all = 1;
+// the block layout's cell: the bytes of its 8 corners, fetched once from byte(x, y, z) over the tile's coordinates
+struct RsCell {
+    int v[8];
+    __device__ __forceinline__ bool flagged(int b) const { return (v[b] & 1) != 0; }
+    __device__ __forceinline__ bool inside(int b) const { return (v[b] & 2) != 0; }
+};
+template <typename Byte>
+__device__ __forceinline__ int rs_cell_bits(Byte byte, int x, int y, int z) {
+    RsCell cell;
 #pragma unroll
-    for (int c = 0; c < 8; ++c) {
-        const int v = corner(x + (c & 1), y + ((c >> 1) & 1), z + ((c >> 2) & 1));
-        all &= v;
-        bits |= ((v >> 1) & 1) << c;
-    }
-    return (all & 1) ? bits : -1;
+    for (int b = 0; b < 8; ++b) cell.v[b] = byte(x + (b & 1), y + ((b >> 1) & 1), z + ((b >> 2) & 1));
+    return mt_cell_bits(cell);
 }
 
-#ifndef PF_RECON_SPARSE_COUNT_DIRECT
 __global__ __launch_bounds__(RS_SLOTS) void count_sparse_kernel(const float* __restrict__ f, const unsigned char* __restrict__ flags,
                                                                 const long long* __restrict__ blocks, const int* __restrict__ links,
                                                                 RsGrid g, int* __restrict__ count) {
@@ -156,20 +155,6 @@ __global__ __launch_bounds__(RS_SLOTS) void count_sparse_kernel(const float* __r
     const int bits = rs_cell_bits([&](int x, int y, int z) { return (int)tile[(z * 9 + y) * 9 + x]; }, s & 7, (s >> 3) & 7, s >> 6);
     count[(size_t)b * RS_SLOTS + s] = mt_triangles(bits);
 }
-#else
-// the form without the tile, kept for measurement: every cell reads its 8 corners through the links
-__global__ __launch_bounds__(RS_SLOTS) void count_sparse_kernel(const float* __restrict__ f, const unsigned char* __restrict__ flags,
-                                                                const long long* __restrict__ blocks, const int* __restrict__ links,
-                                                                RsGrid g, int* __restrict__ count) {
-    const int b = blockIdx.x, s = threadIdx.x;
-    int bi = 0, bj = 0, bk = 0;
-    int bits = -1;
-    if (rs_block_of(g, blocks[b], bi, bj, bk))
-        bits = rs_cell_bits([&](int x, int y, int z) { return rs_corner_byte(f, flags, links, g, b, bi, bj, bk, x, y, z); }, s & 7,
-                            (s >> 3) & 7, s >> 6);
-    count[(size_t)b * RS_SLOTS + s] = mt_triangles(bits);
-}
-#endif
 
 // one lane per listed cell, in the order of the list
 __global__ __launch_bounds__(RC_T) void emit_sparse_kernel(const float* __restrict__ f, const unsigned char* __restrict__ flags,
@@ -186,22 +171,9 @@ __global__ __launch_bounds__(RC_T) void emit_sparse_kernel(const float* __restri
     const int x = s & 7, y = (s >> 3) & 7, z = s >> 6;
     const int bits = rs_cell_bits([&](int cx, int cy, int cz) { return rs_corner_byte(f, flags, links, g, b, bi, bj, bk, cx, cy, cz); },
                                   x, y, z);
-    if (bits <= 0 || bits >= 255) return;
     const long long Dx = g.Dx, DxDy = (long long)g.Dx * g.Dy;
     const long long c = (long long)(bk * 8 + z) * DxDy + (long long)(bj * 8 + y) * Dx + (bi * 8 + x);       // the GLOBAL corner index
-    long long t = first[m];
-    for (int tet = 0; tet < 6; ++tet) {
-        const int mask = mt_mask(bits, tet), n = mt_table.ntri[tet][mask];
-        for (int tr = 0; tr < n; ++tr, ++t) {
-            if (t < 0 || t >= T) return;                                    // offsets that are not this list's prefix sum: a wrong mesh
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const int e = mt_table.edge[tet][mask][tr][k], o = e >> 3;
-                const long long owner = c + (o & 1) + ((o >> 1) & 1) * Dx + ((o >> 2) & 1) * DxDy;
-                edge_ids[t * 3 + k] = 7 * owner + (e & 7);
-            }
-        }
-    }
+    mt_emit_cell(bits, c, Dx, (long long)g.Dy, first + m, T, edge_ids);
 }
 
 __global__ __launch_bounds__(RC_T) void vertices_sparse_kernel(const long long* __restrict__ edge_ids, long long V,
@@ -211,26 +183,14 @@ __global__ __launch_bounds__(RC_T) void vertices_sparse_kernel(const long long* 
                                                                float* __restrict__ verts) {
     const long long v = (long long)blockIdx.x * RC_T + threadIdx.x;
     if (v >= V) return;
-    const long long id = edge_ids[v];
-    const long long Dx = g.Dx, DxDy = (long long)g.Dx * g.Dy;
-    float x = 0.f, y = 0.f, z = 0.f;
-    if (id >= 0 && id < 7 * DxDy * g.Dz) {
-        const long long a = id / 7;
-        const int ob = mt_offset_bits((int)(id % 7));
-        const int i = (int)(a % Dx), j = (int)((a / Dx) % g.Dy), k = (int)(a / DxDy);
-        const int i2 = i + (ob & 1), j2 = j + ((ob >> 1) & 1), k2 = k + ((ob >> 2) & 1);
-        if (i2 < g.Dx && j2 < g.Dy && k2 < g.Dz) {                          // an id that is no edge of the grid: (0, 0, 0)
-            const int ba = rs_find(blocks, g.NB, rs_key(g, i >> 3, j >> 3, k >> 3));
-            const int bb = ba < 0 ? -1 : rs_link(links, g, ba, ((i2 >> 3) - (i >> 3)) | ((j2 >> 3) - (j >> 3)) << 1 | ((k2 >> 3) - (k >> 3)) << 2);
-            if (bb >= 0) {                                                  // both corners lie in listed blocks
-                const float fa = f[(size_t)ba * RS_SLOTS + ((k & 7) << 6 | (j & 7) << 3 | (i & 7))],
-                            fb = f[(size_t)bb * RS_SLOTS + ((k2 & 7) << 6 | (j2 & 7) << 3 | (i2 & 7))];
-                const float t = __fdiv_rn(fa, __fsub_rn(fa, fb));
-                x = mt_lerp(gx[i], gx[i2], t); y = mt_lerp(gy[j], gy[j2], t); z = mt_lerp(gz[k], gz[k2], t);
-            }
-        }
-    }
-    verts[v * 3 + 0] = x; verts[v * 3 + 1] = y; verts[v * 3 + 2] = z;
+    mt_vertex_of<long long>(edge_ids[v], g.Dx, g.Dy, g.Dz, gx, gy, gz, [=](int i, int j, int k, int i2, int j2, int k2, float& fa, float& fb) {
+        const int ba = rs_find(blocks, g.NB, rs_key(g, i >> 3, j >> 3, k >> 3));                    // one search: the upper end is a link away
+        const int bb = ba < 0 ? -1 : rs_link(links, g, ba, ((i2 >> 3) - (i >> 3)) | ((j2 >> 3) - (j >> 3)) << 1 | ((k2 >> 3) - (k >> 3)) << 2);
+        if (bb < 0) return false;                                           // a corner in no listed block
+        fa = f[(size_t)ba * RS_SLOTS + ((k & 7) << 6 | (j & 7) << 3 | (i & 7))];
+        fb = f[(size_t)bb * RS_SLOTS + ((k2 & 7) << 6 | (j2 & 7) << 3 | (i2 & 7))];
+        return true;
+    }, verts + v * 3);
 }
 
 // PF_OK and the grid, or what the entry points return for a grid that is none / over the caps
@@ -249,7 +209,7 @@ int rs_grid(int Dx, int Dy, int Dz, int NB, RsGrid* g) {
 extern "C" int pf_recon_block_keys(const float* pts, int N, const float* gx, const float* gy, const float* gz, int Dx, int Dy, int Dz,
                                    long long* keys, void* stream) {
     if (!pts || !gx || !gy || !gz || !keys) return PF_ERR_NULL;
-    if (N <= 0 || (long long)N * 3 > 0x7fffffffll) return PF_ERR_SHAPE;
+    if (!rc_count_ok(N)) return PF_ERR_SHAPE;
     RsGrid g;
     const int rc = rs_grid(Dx, Dy, Dz, 1, &g);
     if (rc != PF_OK) return rc;
@@ -269,7 +229,7 @@ extern "C" int pf_recon_block_links(const long long* blocks, int NB, int Dx, int
 extern "C" int pf_recon_mark_sparse(const float* pts, int N, const float* gx, const float* gy, const float* gz, int Dx, int Dy, int Dz,
                                     const long long* blocks, int NB, unsigned char* flags, void* stream) {
     if (!pts || !gx || !gy || !gz || !blocks || !flags) return PF_ERR_NULL;
-    if (N <= 0 || (long long)N * 3 > 0x7fffffffll) return PF_ERR_SHAPE;
+    if (!rc_count_ok(N)) return PF_ERR_SHAPE;
     RsGrid g;
     const int rc = rs_grid(Dx, Dy, Dz, NB, &g);
     if (rc != PF_OK) return rc;

@@ -671,13 +671,32 @@ def _recon_dense(t: torch.Tensor, dims, dtype, what: str) -> torch.Tensor:
     return t.contiguous()
 
 
+def _recon_dense_field(f, flags, what: str):
+    """f float32 / flags uint8 [D_z, D_y, D_x] -> (f, flags, (D_x, D_y, D_z)): the dims are the flags array's"""
+    if flags.dim() != 3:
+        raise _lib.PuflowHipError(f"{what}: flags [D_z, D_y, D_x], got {tuple(flags.shape)}")
+    dims = (int(flags.shape[2]), int(flags.shape[1]), int(flags.shape[0]))
+    return _recon_dense(f, dims, torch.float32, what), _recon_dense(flags, dims, torch.uint8, what), dims
+
+
+def _recon_pts(pts: torch.Tensor, what: str) -> torch.Tensor:
+    pts = _f32c(pts)
+    if pts.dim() != 2 or pts.shape[1] != 3 or pts.shape[0] <= 0:
+        raise _lib.PuflowHipError(f"{what}: pts [N,3], got {tuple(pts.shape)}")
+    return pts
+
+
+def _recon_edge_ids(edge_ids: torch.Tensor, what: str) -> torch.Tensor:
+    if not edge_ids.is_cuda or edge_ids.dtype != torch.int64 or edge_ids.dim() != 1 or edge_ids.shape[0] <= 0:
+        raise _lib.PuflowHipError(f"{what}: edge ids int64 [V] on the GPU, got {edge_ids.dtype} {tuple(edge_ids.shape)}")
+    return edge_ids.contiguous()
+
+
 def recon_mark(pts: torch.Tensor, tables) -> torch.Tensor:
     """pf_recon_mark: pts [N,3], the corner tables -> uint8 flags [D_z, D_y, D_x], 1 at the 4 x 4 x 4 corners around every
     point's cell"""
     lib = _lib.load()
-    pts = _f32c(pts)
-    if pts.dim() != 2 or pts.shape[1] != 3 or pts.shape[0] <= 0:
-        raise _lib.PuflowHipError(f"recon_mark: pts [N,3], got {tuple(pts.shape)}")
+    pts = _recon_pts(pts, "recon_mark")
     (gx, gy, gz), (Dx, Dy, Dz) = _recon_box(tables, "recon_mark")
     flags = torch.empty((Dz, Dy, Dx), dtype=torch.uint8, device=pts.device)
     _lib.check(lib.pf_recon_mark(pts.data_ptr(), pts.shape[0], gx.data_ptr(), gy.data_ptr(), gz.data_ptr(), Dx, Dy, Dz,
@@ -703,10 +722,7 @@ def recon_grow(f: torch.Tensor, flags: torch.Tensor) -> torch.Tensor:
     """pf_recon_grow: f float32 / flags uint8 [D_z, D_y, D_x] -> uint8 added [D_z, D_y, D_x], 1 at the 8 corners of every exit (an
     inactive cell that shares a face the zero set crosses with an active one)"""
     lib = _lib.load()
-    if flags.dim() != 3:
-        raise _lib.PuflowHipError(f"recon_grow: flags [D_z, D_y, D_x], got {tuple(flags.shape)}")
-    dims = (int(flags.shape[2]), int(flags.shape[1]), int(flags.shape[0]))
-    f, flags = _recon_dense(f, dims, torch.float32, "recon_grow"), _recon_dense(flags, dims, torch.uint8, "recon_grow")
+    f, flags, dims = _recon_dense_field(f, flags, "recon_grow")
     added = torch.empty(flags.shape, dtype=torch.uint8, device=f.device)
     _lib.check(lib.pf_recon_grow(f.data_ptr(), flags.data_ptr(), dims[0], dims[1], dims[2], added.data_ptr(), _stream()),
                "pf_recon_grow")
@@ -716,10 +732,7 @@ def recon_grow(f: torch.Tensor, flags: torch.Tensor) -> torch.Tensor:
 def mtet_count(f: torch.Tensor, flags: torch.Tensor) -> torch.Tensor:
     """pf_mtet_count: f float32 / flags uint8 [D_z, D_y, D_x] -> triangles per cell, int32 [D_z, D_y, D_x]"""
     lib = _lib.load()
-    if flags.dim() != 3:
-        raise _lib.PuflowHipError(f"mtet_count: flags [D_z, D_y, D_x], got {tuple(flags.shape)}")
-    dims = (int(flags.shape[2]), int(flags.shape[1]), int(flags.shape[0]))
-    f, flags = _recon_dense(f, dims, torch.float32, "mtet_count"), _recon_dense(flags, dims, torch.uint8, "mtet_count")
+    f, flags, dims = _recon_dense_field(f, flags, "mtet_count")
     count = torch.empty(flags.shape, dtype=torch.int32, device=f.device)
     _lib.check(lib.pf_mtet_count(f.data_ptr(), flags.data_ptr(), dims[0], dims[1], dims[2], count.data_ptr(), _stream()),
                "pf_mtet_count")
@@ -730,10 +743,7 @@ def mtet_emit(f: torch.Tensor, flags: torch.Tensor, first: torch.Tensor, total: 
     """pf_mtet_emit: first int64 [D_z, D_y, D_x] (the exclusive prefix sum of mtet_count), total its sum -> the triangles' edge
     ids, int64 [total, 3], in the order (cell, tet, triangle)"""
     lib = _lib.load()
-    if flags.dim() != 3:
-        raise _lib.PuflowHipError(f"mtet_emit: flags [D_z, D_y, D_x], got {tuple(flags.shape)}")
-    dims = (int(flags.shape[2]), int(flags.shape[1]), int(flags.shape[0]))
-    f, flags = _recon_dense(f, dims, torch.float32, "mtet_emit"), _recon_dense(flags, dims, torch.uint8, "mtet_emit")
+    f, flags, dims = _recon_dense_field(f, flags, "mtet_emit")
     first = _recon_dense(first, dims, torch.int64, "mtet_emit")
     ids = torch.empty((int(total), 3), dtype=torch.int64, device=f.device)
     _lib.check(lib.pf_mtet_emit(f.data_ptr(), flags.data_ptr(), dims[0], dims[1], dims[2], first.data_ptr(), int(total),
@@ -746,9 +756,7 @@ def mtet_vertices(edge_ids: torch.Tensor, f: torch.Tensor, tables) -> torch.Tens
     lib = _lib.load()
     (gx, gy, gz), dims = _recon_box(tables, "mtet_vertices")
     f = _recon_dense(f, dims, torch.float32, "mtet_vertices")
-    if not edge_ids.is_cuda or edge_ids.dtype != torch.int64 or edge_ids.dim() != 1 or edge_ids.shape[0] <= 0:
-        raise _lib.PuflowHipError(f"mtet_vertices: edge ids int64 [V] on the GPU, got {edge_ids.dtype} {tuple(edge_ids.shape)}")
-    edge_ids = edge_ids.contiguous()
+    edge_ids = _recon_edge_ids(edge_ids, "mtet_vertices")
     verts = torch.empty((edge_ids.shape[0], 3), dtype=torch.float32, device=f.device)
     _lib.check(lib.pf_mtet_vertices(edge_ids.data_ptr(), edge_ids.shape[0], f.data_ptr(), gx.data_ptr(), gy.data_ptr(),
                                     gz.data_ptr(), dims[0], dims[1], dims[2], verts.data_ptr(), _stream()), "pf_mtet_vertices")
@@ -788,9 +796,7 @@ def recon_block_keys(pts: torch.Tensor, tables) -> torch.Tensor:
     """pf_recon_block_keys: pts [N,3], the corner tables -> int64 [N, 8], the keys of the blocks every point's 4 x 4 x 4 corners
     touch; torch.unique of it is the block list"""
     lib = _lib.load()
-    pts = _f32c(pts)
-    if pts.dim() != 2 or pts.shape[1] != 3 or pts.shape[0] <= 0:
-        raise _lib.PuflowHipError(f"recon_block_keys: pts [N,3], got {tuple(pts.shape)}")
+    pts = _recon_pts(pts, "recon_block_keys")
     (gx, gy, gz), (Dx, Dy, Dz) = _recon_box(tables, "recon_block_keys")
     keys = torch.empty((pts.shape[0], 8), dtype=torch.int64, device=pts.device)
     _lib.check(lib.pf_recon_block_keys(pts.data_ptr(), pts.shape[0], gx.data_ptr(), gy.data_ptr(), gz.data_ptr(), Dx, Dy, Dz,
@@ -812,9 +818,7 @@ def recon_block_links(blocks: torch.Tensor, dims) -> torch.Tensor:
 def recon_mark_sparse(pts: torch.Tensor, tables, blocks: torch.Tensor) -> torch.Tensor:
     """pf_recon_mark_sparse: pts [N,3], the corner tables, the block list -> uint8 flags [NB, 512]"""
     lib = _lib.load()
-    pts = _f32c(pts)
-    if pts.dim() != 2 or pts.shape[1] != 3 or pts.shape[0] <= 0:
-        raise _lib.PuflowHipError(f"recon_mark_sparse: pts [N,3], got {tuple(pts.shape)}")
+    pts = _recon_pts(pts, "recon_mark_sparse")
     (gx, gy, gz), (Dx, Dy, Dz) = _recon_box(tables, "recon_mark_sparse")
     blocks = _recon_list(blocks, "recon_mark_sparse")
     flags = torch.empty((blocks.shape[0], RECON_SLOTS), dtype=torch.uint8, device=pts.device)
@@ -868,9 +872,7 @@ def mtet_vertices_sparse(edge_ids: torch.Tensor, f: torch.Tensor, blocks: torch.
     nb = int(blocks.shape[0])
     f = _recon_block(f, nb, RECON_SLOTS, torch.float32, "mtet_vertices_sparse")
     links = _recon_block(links, nb, 8, torch.int32, "mtet_vertices_sparse")
-    if not edge_ids.is_cuda or edge_ids.dtype != torch.int64 or edge_ids.dim() != 1 or edge_ids.shape[0] <= 0:
-        raise _lib.PuflowHipError(f"mtet_vertices_sparse: edge ids int64 [V] on the GPU, got {edge_ids.dtype} {tuple(edge_ids.shape)}")
-    edge_ids = edge_ids.contiguous()
+    edge_ids = _recon_edge_ids(edge_ids, "mtet_vertices_sparse")
     verts = torch.empty((edge_ids.shape[0], 3), dtype=torch.float32, device=f.device)
     _lib.check(lib.pf_mtet_vertices_sparse(edge_ids.data_ptr(), edge_ids.shape[0], f.data_ptr(), blocks.data_ptr(), links.data_ptr(), nb,
                                            gx.data_ptr(), gy.data_ptr(), gz.data_ptr(), dims[0], dims[1], dims[2], verts.data_ptr(),

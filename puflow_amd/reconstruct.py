@@ -96,6 +96,13 @@ def _rounds(close_holes, what: str) -> int:
     return int(close_holes)
 
 
+def _growth_is_dense(layout: str, rounds: int, what: str, how: str) -> None:
+    """the one decision about growth and layouts: band growth (pf_recon_grow) is written against dense addresses, so a call that
+    asks for rounds on the sparse layout is refused - in the caller's words: `how` names its way to the dense layout"""
+    if rounds and layout == "sparse":
+        raise _lib.PuflowHipError(f"{what}: close_holes = {rounds}: growth needs the dense layout{how}; a grown block list is not built")
+
+
 def _box(cells, rounds: int = 0) -> str:
     return " x ".join(str(int(c) + 2 * (PAD + rounds) + 1) if np.isfinite(c) else "inf" for c in cells)
 
@@ -110,17 +117,17 @@ def corner_tables(lo, hi, h: float, layout: str = "dense", rounds: int = 0):
     layout "dense": at most PF_RECON_MAX_CORNERS corners in the box; "sparse": at most PF_RECON_SPARSE_MAX_AXIS per axis; "auto":
     either.  rounds: that many more corners of padding per side for band growth (close_holes), dense only."""
     layout, rounds = _layout(layout, "corner_tables"), _rounds(rounds, "corner_tables")
+    _growth_is_dense(layout, rounds, "reconstruct", " (--layout dense, or auto)")
     lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
     o = lo - PAD * h
     cells = np.ceil((hi - lo) / h)
     unsupported = _lib.load().pf_error_string(_lib.PF_ERR_UNSUPPORTED).decode()
     dense = _within_dense_cap(cells, rounds)
-    if rounds and (layout == "sparse" or not dense):
+    if rounds and not dense:
         raise _lib.PuflowHipError(
-            f"reconstruct: close_holes = {rounds}: growth needs the dense layout" + (
-                " (--layout dense, or auto); a grown block list is not built" if layout == "sparse" else
-                f", and the padded box of {_box(cells, rounds)} corners at cell size {h:.6g} is over its cap of {MAX_CORNERS} "
-                f"({unsupported}): use a larger --cell (or --cell_scale) or fewer rounds"))
+            f"reconstruct: close_holes = {rounds}: growth needs the dense layout"
+            f", and the padded box of {_box(cells, rounds)} corners at cell size {h:.6g} is over its cap of {MAX_CORNERS} "
+            f"({unsupported}): use a larger --cell (or --cell_scale) or fewer rounds")
     if layout == "dense" and not dense:
         raise _lib.PuflowHipError(
             f"reconstruct: a box of {_box(cells)} corners at "
@@ -142,9 +149,7 @@ def implicit(points: torch.Tensor, normals: torch.Tensor, query: torch.Tensor, k
         raise _lib.PuflowHipError("implicit: query is a GPU tensor [Q,3] (no CPU path)")
     k = _k(k, points.shape[0], "implicit")
     h = cell_size(points) if h is None else _positive(h, "h", "implicit")
-    query = ops._f32c(query)
-    idx, _ = ops.knn_grid(points[None], query[None], k)
-    return ops.imls(query, points, normals, idx[0], _positive(sigma, "sigma", "implicit") * h)
+    return _values(None, points, normals, ops._f32c(query), k, _positive(sigma, "sigma", "implicit") * h)
 
 
 def _open_edges(faces: torch.Tensor, nv: int) -> torch.Tensor:
@@ -155,21 +160,7 @@ def _open_edges(faces: torch.Tensor, nv: int) -> torch.Tensor:
     return (n == 1).sum()
 
 
-def extract(f: torch.Tensor, flags: torch.Tensor, tables):
-    """marching tetrahedra over the active cells: f float32 / flags uint8 [D_z, D_y, D_x], the corner tables (device) ->
-    (verts float32 [V,3] in ascending edge id, faces int64 [T,3] in the order (cell, tet, triangle))"""
-    count = ops.mtet_count(f, flags)
-    incl = torch.cumsum(count.reshape(-1), dim=0)
-    total = int(incl[-1])                                                   # a size: the triangle array's
-    if total == 0:
-        return torch.zeros((0, 3), dtype=torch.float32, device=f.device), torch.zeros((0, 3), dtype=torch.int64, device=f.device)
-    first = (incl - count.reshape(-1)).reshape(count.shape)
-    ids = ops.mtet_emit(f, flags, first, total)
-    edge, inverse = torch.unique(ids.reshape(-1), sorted=True, return_inverse=True)
-    return ops.mtet_vertices(edge, f, tables), inverse.reshape(-1, 3)
-
-
-# ---- the block-sparse layout (the contract is in puflow_hip.h) ---------------------------------------------------------------
+# ---- the block-sparse layout's index arithmetic (the contract is in puflow_hip.h) ----------------------------------------------
 def block_dims(dims):
     """(D_x, D_y, D_z) -> blocks per axis (NB_x, NB_y, NB_z)"""
     return tuple((int(d) + BLOCK - 1) // BLOCK for d in dims)
@@ -214,23 +205,106 @@ def block_list(points: torch.Tensor, tables):
     return blocks, ops.recon_block_links(blocks, tuple(int(t.shape[0]) for t in tables))
 
 
+# ---- the seam: the flag and value at a corner, in this layout -----------------------------------------------------------------
+# A layout holds the corner tables and what addresses its flags / f arrays, and provides mark(points) -> flags, corners(index) ->
+# the (i, j, k) of entries of those arrays, triangles(f, flags, stage) -> the triangles' edge ids [T, 3] in the mesh's order
+# (ascending global cell, tet, triangle; None: no triangle), vertices(edge, f) and blocks (0 for dense).  Values, extraction
+# and mesh_from_cloud are written once on top of that.  Band growth is not part of it: pf_recon_grow reads dense addresses, and a
+# layout whose block list grows with the band is not built (_growth_is_dense).
+def _call(_name, thunk):
+    return thunk()
+
+
+class _Dense:
+    """arrays [D_z, D_y, D_x] over the box"""
+    blocks = 0
+
+    def __init__(self, tables, dims):
+        self.tables, self.dims = tables, dims
+
+    def mark(self, points):
+        return ops.recon_mark(points, self.tables)
+
+    def corners(self, index):
+        Dx, Dy, _ = self.dims
+        return index % Dx, (index // Dx) % Dy, index // (Dx * Dy)
+
+    def triangles(self, f, flags, stage=_call):
+        def count():
+            n = ops.mtet_count(f, flags)
+            incl = torch.cumsum(n.reshape(-1), dim=0)
+            return (incl - n.reshape(-1)).reshape(n.shape), int(incl[-1])   # a size: the triangle array's
+        first, total = stage("count", count)
+        return stage("emit", lambda: ops.mtet_emit(f, flags, first, total)) if total else None
+
+    def vertices(self, edge, f):
+        return ops.mtet_vertices(edge, f, self.tables)
+
+
+class _Blocks:
+    """arrays [NB, 512] over the listed 8 x 8 x 8 blocks: keys, the ascending block list, and its links"""
+
+    def __init__(self, tables, dims, keys, links):
+        self.tables, self.dims, self.keys, self.links, self.blocks = tables, dims, keys, links, int(keys.shape[0])
+
+    def mark(self, points):
+        return ops.recon_mark_sparse(points, self.tables, self.keys)
+
+    def corners(self, index):
+        return slot_corners(index, self.keys, self.dims)
+
+    def triangles(self, f, flags, stage=_call):
+        def count():
+            n = ops.mtet_count_sparse(f, flags, self.keys, self.links, self.dims).reshape(-1)
+            slots = torch.nonzero(n).reshape(-1)                            # block-major: not the order of the mesh
+            if slots.shape[0] == 0:                                         # a size
+                return None, None, 0
+            i, j, k = self.corners(slots)
+            _, order = torch.sort((k * self.dims[1] + j) * self.dims[0] + i)                        # distinct keys: the order is determined
+            cells = slots[order]
+            n = n[cells].to(torch.int64)
+            incl = torch.cumsum(n, dim=0)
+            return cells, incl - n, int(incl[-1])                           # a size: the triangle array's
+        cells, first, total = stage("count", count)
+        if not total:
+            return None
+        return stage("emit", lambda: ops.mtet_emit_sparse(f, flags, self.keys, self.links, self.dims, cells, first, total))
+
+    def vertices(self, edge, f):
+        return ops.mtet_vertices_sparse(edge, f, self.keys, self.links, self.tables)
+
+
+def _values(layout, points, normals, index, k: int, sigma_h: float, stage=_call):
+    """the IMLS value at entries `index` of a layout's arrays (layout None: at the points `index` [Q,3] themselves), float32 [Q]"""
+    if layout is None:
+        query = index
+    else:
+        i, j, kk = layout.corners(index)
+        query = torch.stack([layout.tables[0][i], layout.tables[1][j], layout.tables[2][kk]], dim=1)
+    idx, _ = stage("K search", lambda: ops.knn_grid(points[None], query[None], k))
+    return stage("IMLS", lambda: ops.imls(query, points, normals, idx[0], sigma_h))
+
+
+def _extract(layout, f: torch.Tensor, flags: torch.Tensor, stage=_call):
+    """marching tetrahedra over the active cells -> (verts float32 [V,3] in ascending edge id, faces int64 [T,3] in the order
+    (global cell, tet, triangle))"""
+    ids = layout.triangles(f, flags, stage)
+    if ids is None:
+        return torch.zeros((0, 3), dtype=torch.float32, device=f.device), torch.zeros((0, 3), dtype=torch.int64, device=f.device)
+    edge, inverse = stage("unique", lambda: torch.unique(ids.reshape(-1), sorted=True, return_inverse=True))
+    return stage("vertices", lambda: layout.vertices(edge, f)), inverse.reshape(-1, 3)
+
+
+def extract(f: torch.Tensor, flags: torch.Tensor, tables):
+    """marching tetrahedra over the active cells: f float32 / flags uint8 [D_z, D_y, D_x], the corner tables (device) ->
+    (verts float32 [V,3] in ascending edge id, faces int64 [T,3] in the order (cell, tet, triangle))"""
+    return _extract(_Dense(tables, tuple(int(t.shape[0]) for t in tables)), f, flags)
+
+
 def extract_sparse(f: torch.Tensor, flags: torch.Tensor, blocks: torch.Tensor, links: torch.Tensor, tables):
     """extract() over the block layout: f float32 / flags uint8 [NB, 512], the block list and its links, the corner tables
     (device) -> the same (verts, faces): triangles in ascending GLOBAL cell index, then tet, then triangle"""
-    dims = tuple(int(t.shape[0]) for t in tables)
-    empty = lambda: (torch.zeros((0, 3), dtype=torch.float32, device=f.device), torch.zeros((0, 3), dtype=torch.int64, device=f.device))
-    count = ops.mtet_count_sparse(f, flags, blocks, links, dims).reshape(-1)
-    slots = torch.nonzero(count).reshape(-1)                                # block-major: not the order of the mesh
-    if slots.shape[0] == 0:                                                 # a size
-        return empty()
-    i, j, k = slot_corners(slots, blocks, dims)
-    _, order = torch.sort((k * dims[1] + j) * dims[0] + i)                  # distinct keys: the order is determined
-    cells = slots[order]
-    n = count[cells].to(torch.int64)
-    incl = torch.cumsum(n, dim=0)
-    ids = ops.mtet_emit_sparse(f, flags, blocks, links, dims, cells, incl - n, int(incl[-1]))       # a size: the triangle array's
-    edge, inverse = torch.unique(ids.reshape(-1), sorted=True, return_inverse=True)
-    return ops.mtet_vertices_sparse(edge, f, blocks, links, tables), inverse.reshape(-1, 3)
+    return _extract(_Blocks(tables, tuple(int(t.shape[0]) for t in tables), blocks, links), f, flags)
 
 
 # ---- closing holes: the band grows at its exits (the rule is in puflow_hip.h) ---------------------------------------------------
@@ -276,7 +350,7 @@ def _exits(f: torch.Tensor, born: torch.Tensor, corners) -> list:
 
 
 def mesh_from_cloud(points: torch.Tensor, normals: torch.Tensor, cell: float = None, cell_scale: float = 1.0, k: int = 8,
-                    sigma: float = 1.0, layout: str = "dense", close_holes: int = 0):
+                    sigma: float = 1.0, layout: str = "dense", close_holes: int = 0, *, _stage=None):
     """points, normals [N,3] on the GPU (unit normals with consistent signs: estimate_normals(..., orient="propagate") or a
     scanner's) -> (verts [V,3] float32, faces [F,3] int32, info).  cell: the grid's cell size; default cell_scale x the median
     distance to the 6th nearest other point.  layout: "dense" - arrays over the cloud's box, refused over PF_RECON_MAX_CORNERS;
@@ -287,66 +361,46 @@ def mesh_from_cloud(points: torch.Tensor, normals: torch.Tensor, cell: float = N
     layout): up to R rounds in which the band grows by the cells into which the zero set leaves it (pf_recon_grow) - a hole
     shrinks from all sides by at most a cell per round, a real boundary moves outward by at most R cells and stays one; the
     filled patch follows the nearest points' tangent planes.  info then has grow_rounds, the rounds that added something, and
-    grown_cells, the exits of each.  R = 0 is the call without it, byte for byte."""
+    grown_cells, the exits of each.  R = 0 is the call without it, byte for byte.
+    _stage (the timing tools' hook): a callable (name, thunk) -> thunk() that every stage runs through, in this order - "cell-size
+    search", "block list" (sparse), "mark", "compaction", "K search", "IMLS"; per round of growth "grow", "compaction" and, if the
+    round added corners, "K search", "IMLS"; then "count" and, if there are triangles, "emit", "unique", "vertices"."""
     points, normals = _cloud(points, normals, "mesh_from_cloud")
     k = _k(k, points.shape[0], "mesh_from_cloud")
     sigma = _positive(sigma, "sigma", "mesh_from_cloud")
     layout, rounds = _layout(layout, "mesh_from_cloud"), _rounds(close_holes, "mesh_from_cloud")
-    if rounds and layout == "sparse":
-        raise _lib.PuflowHipError(f"mesh_from_cloud: close_holes = {rounds}: growth needs the dense layout (layout=\"dense\", or "
-                                  "\"auto\" while the padded box is within the dense cap); a grown block list is not built")
-    if cell is not None:
-        h = _positive(cell, "cell", "mesh_from_cloud")
-        _, lo, hi = _stats(points, False)
-    else:
-        scale = _positive(cell_scale, "cell_scale", "mesh_from_cloud")
-        m, lo, hi = _stats(points, True)
-        h = _positive(scale * float(np.sqrt(m)), "the cell size from the cloud's spacing", "mesh_from_cloud")
+    _growth_is_dense(layout, rounds, "mesh_from_cloud",
+                     " (layout=\"dense\", or \"auto\" while the padded box is within the dense cap)")
+    stage = _call if _stage is None else _stage
+    given = cell is not None                                                # the cell size, or a scale of the cloud's spacing
+    size = _positive(cell, "cell", "mesh_from_cloud") if given else _positive(cell_scale, "cell_scale", "mesh_from_cloud")
+    m, lo, hi = stage("cell-size search", lambda: _stats(points, not given))
+    h = size if given else _positive(size * float(np.sqrt(m)), "the cell size from the cloud's spacing", "mesh_from_cloud")
     if layout == "auto":
         layout = "dense" if rounds or _within_dense_cap(np.ceil((hi - lo) / h)) else "sparse"      # growth: dense, or refused
     dims, host_tables = corner_tables(lo, hi, h, layout, rounds)
-    grown = []
-    dev = points.device
-    tables = [torch.from_numpy(t).to(dev) for t in host_tables]
-    if layout == "sparse":
-        blocks, links = block_list(points, tables)
-        flags = ops.recon_mark_sparse(points, tables, blocks)
-        slot = torch.nonzero(flags.reshape(-1)).reshape(-1)                 # ascending slot number
-        i, j, kk = slot_corners(slot, blocks, dims)
-        query = torch.stack([tables[0][i], tables[1][j], tables[2][kk]], dim=1)
-        idx, _ = ops.knn_grid(points[None], query[None], k)
-        f = torch.empty(flags.shape, dtype=torch.float32, device=dev)       # unflagged slots are never read
-        f.reshape(-1)[slot] = ops.imls(query, points, normals, idx[0], sigma * h)
-        verts, faces = extract_sparse(f, flags, blocks, links, tables)
-        nblocks = int(blocks.shape[0])
-    else:
-        Dx, Dy = dims[0], dims[1]
-
-        def value(corner):
-            query = torch.stack([tables[0][corner % Dx], tables[1][(corner // Dx) % Dy], tables[2][corner // (Dx * Dy)]], dim=1)
-            idx, _ = ops.knn_grid(points[None], query[None], k)
-            return ops.imls(query, points, normals, idx[0], sigma * h)
-        flags = ops.recon_mark(points, tables)
-        corner = torch.nonzero(flags.reshape(-1)).reshape(-1)               # ascending corner index
-        f = torch.empty(flags.shape, dtype=torch.float32, device=dev)       # inactive corners are never read
-        f.reshape(-1)[corner] = value(corner)
-        born = None
-        for r in range(1, rounds + 1):
-            added = ops.recon_grow(f, flags)
-            corner = torch.nonzero((added & ~flags).reshape(-1)).reshape(-1)            # its size: the one host read of a round
-            if corner.shape[0] == 0:                                        # no new corner, no exit
-                break
-            if born is None:
-                born = (flags == 0).to(torch.int8) * 127
-            born.reshape(-1)[corner] = r
-            grown.append(corner)
-            f.reshape(-1)[corner] = value(corner)
-            flags |= added
-        grown = _exits(f, born, grown) if grown else []
-        verts, faces = extract(f, flags, tables)
-        nblocks = 0
+    tables = [torch.from_numpy(t).to(points.device) for t in host_tables]
+    grid = _Dense(tables, dims) if layout == "dense" else _Blocks(tables, dims, *stage("block list", lambda: block_list(points, tables)))
+    flags = stage("mark", lambda: grid.mark(points))
+    f = torch.empty(flags.shape, dtype=torch.float32, device=points.device)                        # read at flagged corners only
+    index = stage("compaction", lambda: torch.nonzero(flags.reshape(-1)).reshape(-1))              # ascending
+    f.reshape(-1)[index] = _values(grid, points, normals, index, k, sigma * h, stage)
+    born, grown = None, []
+    for r in range(1, rounds + 1):                                          # rounds: on the dense layout only (refused above)
+        added = stage("grow", lambda: ops.recon_grow(f, flags))
+        index = stage("compaction", lambda: torch.nonzero((added & ~flags).reshape(-1)).reshape(-1))   # its size: a round's one host read
+        if index.shape[0] == 0:                                             # no new corner, no exit
+            break
+        if born is None:
+            born = (flags == 0).to(torch.int8) * 127
+        born.reshape(-1)[index] = r
+        grown.append(index)
+        f.reshape(-1)[index] = _values(grid, points, normals, index, k, sigma * h, stage)
+        flags |= added
+    grown = _exits(f, born, grown) if grown else []
+    verts, faces = _extract(grid, f, flags, stage)
     open_edges = int(_open_edges(faces, verts.shape[0])) if faces.shape[0] else 0
-    return verts, faces.to(torch.int32), {"h": h, "dims": dims, "open_edges": open_edges, "layout": layout, "blocks": nblocks,
+    return verts, faces.to(torch.int32), {"h": h, "dims": dims, "open_edges": open_edges, "layout": layout, "blocks": grid.blocks,
                                           "grow_rounds": len(grown), "grown_cells": grown}
 
 

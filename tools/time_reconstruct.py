@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """What mesh_from_cloud costs, stage by stage, by device events: the median of --reps calls after one untimed call, with the
 spread, on one cloud of 20 000, 262 144 and 1 048 576 points (the bumpy sheet of tools/time_normals_orient.py with normals from
-estimate_normals(16, search="grid", orient="propagate"), K = 8, sigma = 1, the default cell size).  Stages: the cell-size search
-(K = 7 self-search, median, box - up to the one host read), mark, compaction (nonzero + corner coordinates), the K search, IMLS
-(with the scatter to the dense array), count (with the prefix sum), emit, unique, vertices.  There is no parent to compare with:
-absolute times only.
+estimate_normals(16, search="grid", orient="propagate"), K = 8, sigma = 1, the default cell size).  The stages are the library's
+own, timed through mesh_from_cloud's _stage hook: the cell-size search (K = 7 self-search, median, box - up to the one host read),
+mark, compaction (nonzero), the K search, IMLS, count (with the prefix sum), emit, unique, vertices.  What lies between the
+stages (the corner-coordinate gathers, the scatter of the values) is in no stage.  Absolute times only.
   python tools/time_reconstruct.py [--out-dir profiles/reconstruct] [--commit ID] [--reps 5]
   python tools/time_reconstruct.py --accuracy [--out-dir ...]       # accuracy.txt: vertex distances on the analytic test surfaces
 and the mesh of a 512-point torus against the mesh of its x4 upsampling with the trained weights of tests/golden"""
@@ -38,7 +38,7 @@ def write(name, record=None):
             json.dump(record, f, indent=1)
 
 
-from puflow_amd import _lib, attributes as A, ops, reconstruct as P
+from puflow_amd import _lib, attributes as A, reconstruct as P
 from puflow_amd.weights import synth_patches
 
 torch.zeros(1, device="cuda"); torch.cuda.synchronize()
@@ -90,47 +90,23 @@ if "--accuracy" in args:
     sys.exit(0)
 
 
-def event_ms(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record(); out = fn(); b.record(); torch.cuda.synchronize()
-    return out, a.elapsed_time(b)
-
-
 STAGES = ("cell-size search", "mark", "compaction", "K search", "IMLS", "count", "emit", "unique", "vertices")
 
 
 def staged(points, normals):
-    """mesh_from_cloud with an event pair around every stage: ({stage: ms}, info)"""
-    ms = {}
-    (m, lo, hi), ms["cell-size search"] = event_ms(lambda: P._stats(points, True))
-    h = float(np.sqrt(m))
-    dims, host_tables = P.corner_tables(lo, hi, h)
-    tables = [torch.from_numpy(t).cuda() for t in host_tables]
-    flags, ms["mark"] = event_ms(lambda: ops.recon_mark(points, tables))
+    """mesh_from_cloud with an event pair around every stage, through its _stage hook: ({stage: ms}, info)"""
+    ms, active = {}, []
 
-    def compact():
-        corner = torch.nonzero(flags.reshape(-1)).reshape(-1)
-        return corner, torch.stack([tables[0][corner % dims[0]], tables[1][(corner // dims[0]) % dims[1]],
-                                    tables[2][corner // (dims[0] * dims[1])]], dim=1)
-    (corner, query), ms["compaction"] = event_ms(compact)
-    (idx, _), ms["K search"] = event_ms(lambda: ops.knn_grid(points[None], query[None], K))
-
-    def value():
-        f = torch.empty(flags.shape, dtype=torch.float32, device="cuda")
-        f.reshape(-1)[corner] = ops.imls(query, points, normals, idx[0], SIGMA * h)
-        return f
-    f, ms["IMLS"] = event_ms(value)
-
-    def count():
-        c = ops.mtet_count(f, flags)
-        incl = torch.cumsum(c.reshape(-1), dim=0)
-        return (incl - c.reshape(-1)).reshape(c.shape), int(incl[-1])
-    (first, total), ms["count"] = event_ms(count)
-    ids, ms["emit"] = event_ms(lambda: ops.mtet_emit(f, flags, first, total))
-    (edge, inverse), ms["unique"] = event_ms(lambda: torch.unique(ids.reshape(-1), sorted=True, return_inverse=True))
-    verts, ms["vertices"] = event_ms(lambda: ops.mtet_vertices(edge, f, tables))
-    return ms, {"h": h, "dims": dims, "corners": int(np.prod(dims)), "active_corners": int(corner.shape[0]), "triangles": total,
-                "vertices": int(edge.shape[0])}
+    def stage(name, thunk):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(); out = thunk(); b.record(); torch.cuda.synchronize()
+        ms[name] = a.elapsed_time(b)
+        if name == "compaction":
+            active.append(int(out.shape[0]))
+        return out
+    verts, faces, info = P.mesh_from_cloud(points, normals, k=K, sigma=SIGMA, _stage=stage)
+    return ms, {"h": info["h"], "dims": info["dims"], "corners": int(np.prod(info["dims"])), "active_corners": active[0],
+                "triangles": int(faces.shape[0]), "vertices": int(verts.shape[0])}
 
 
 record = {"commit": commit, "k": K, "sigma": SIGMA, "reps": reps, "box": box, "rows": []}

@@ -1,14 +1,14 @@
 #!/usr/bin/env python3
 """mesh_from_cloud(close_holes=R) at R = 0, 2 and 8 side by side, by tools/time_reconstruct_sparse.py's method: device events per
-stage, the median of --reps calls after one untimed call; the legs alternate in FRESH processes over --rounds rounds; a leg's
+stage (the library's own stages, through mesh_from_cloud's _stage hook), the median of --reps calls after one untimed call; the legs alternate in FRESH processes over --rounds rounds; a leg's
 figure is the median over the rounds of its medians, its spread the largest minus the smallest of them.  By the project's rule a
 difference counts only beyond three spreads.  The growth stages are timed per round of growth and reported summed over the
-rounds: the grow sweep (pf_recon_grow with its memset), the compaction (added & ~flags, nonzero, the coordinate gathers), the K
-search and the IMLS stage with its scatters and flags |= added; then, once, the exit count for info["grown_cells"].
+rounds: the grow sweep (pf_recon_grow with its memset), the compaction (added & ~flags, nonzero), the K search and the IMLS
+stage.  The exit count for info["grown_cells"], once after the rounds, is in no stage: it shows in the whole call only.
 Shapes: the bumpy sheets of tools/time_reconstruct.py at 20 000, 262 144 and 1 048 576 points (normals from
 estimate_normals(16, search="grid", orient="propagate")).  They are open, so every round grows.
-The R = 0 leg runs the parent commit's code path.  --parent-root DIR adds a leg that runs the same stages on the package of
-another tree (a built checkout of the parent commit): R = 0 must stay within three spreads of it.
+--parent-root DIR adds a leg that runs the same hook on the package of another tree (a built checkout of a parent commit that
+has the hook): R = 0 must stay within three spreads of it.
   python tools/time_reconstruct_close.py [--out-dir profiles/reconstruct_close] [--commit ID] [--reps 5] [--rounds 3]
                                          [--parent-root DIR]
   python tools/time_reconstruct_close.py --accuracy [--out-dir ...]     # accuracy.txt: what the rounds do to the meshes of the
@@ -27,10 +27,10 @@ parent_root = opt("--parent-root", None)
 SHEETS = (20000, 262144, 1048576)
 K, SIGMA = 8, 1.0
 BASE = ("cell-size search", "mark", "compaction", "K search", "IMLS")
-GROW = ("grow sweep", "grow compaction", "grow K search", "grow IMLS", "exit count")
+GROW = ("grow sweep", "grow compaction", "grow K search", "grow IMLS")
 TAIL = ("count", "emit", "unique", "vertices")
 
-from puflow_amd import _lib, ops, reconstruct as P
+from puflow_amd import reconstruct as P
 
 
 def event_ms(fn):
@@ -40,68 +40,23 @@ def event_ms(fn):
 
 
 def staged(points, normals, R):
-    """mesh_from_cloud(close_holes=R) with an event pair around every stage: ({stage: ms}, info)"""
-    ms = {s: 0.0 for s in (GROW if R else ())}
-    (m, lo, hi), ms["cell-size search"] = event_ms(lambda: P._stats(points, True))
-    h = float(np.sqrt(m))
-    dims, host_tables = P.corner_tables(lo, hi, h, "dense", R) if R else P.corner_tables(lo, hi, h, "dense")
-    tables = [torch.from_numpy(t).cuda() for t in host_tables]
-    where = lambda corner: torch.stack([tables[0][corner % dims[0]], tables[1][(corner // dims[0]) % dims[1]],
-                                        tables[2][corner // (dims[0] * dims[1])]], dim=1)
-    flags, ms["mark"] = event_ms(lambda: ops.recon_mark(points, tables))
+    """mesh_from_cloud(close_holes=R) with an event pair around every stage, through its _stage hook: ({stage: ms}, info).  From
+    the first "grow" on, the stages up to the extraction belong to the rounds and are summed over them under GROW's names."""
+    ms, sizes = {s: 0.0 for s in BASE + (GROW if R else ()) + TAIL}, []     # in the order they run
+    in_rounds = {"grow": "grow sweep", "compaction": "grow compaction", "K search": "grow K search", "IMLS": "grow IMLS"}
 
-    def compact():
-        corner = torch.nonzero(flags.reshape(-1)).reshape(-1)
-        return corner, where(corner)
-    (corner, query), ms["compaction"] = event_ms(compact)
-    (idx, _), ms["K search"] = event_ms(lambda: ops.knn_grid(points[None], query[None], K))
-
-    def value():
-        f = torch.empty(flags.shape, dtype=torch.float32, device="cuda")
-        f.reshape(-1)[corner] = ops.imls(query, points, normals, idx[0], SIGMA * h)
-        return f
-    f, ms["IMLS"] = event_ms(value)
-    active0, born, grown = int(corner.shape[0]), None, []
-    for r in range(1, R + 1):
-        added, t = event_ms(lambda: ops.recon_grow(f, flags))
-        ms["grow sweep"] += t
-
-        def compact_new():
-            corner = torch.nonzero((added & ~flags).reshape(-1)).reshape(-1)
-            return corner, where(corner)
-        (corner, query), t = event_ms(compact_new)
-        ms["grow compaction"] += t
-        if corner.shape[0] == 0:
-            break
-        (idx, _), t = event_ms(lambda: ops.knn_grid(points[None], query[None], K))
-        ms["grow K search"] += t
-
-        def scatter():
-            b = (flags == 0).to(torch.int8) * 127 if born is None else born
-            b.reshape(-1)[corner] = r
-            f.reshape(-1)[corner] = ops.imls(query, points, normals, idx[0], SIGMA * h)
-            flags.__ior__(added)
-            return b
-        born, t = event_ms(scatter)
-        ms["grow IMLS"] += t
-        grown.append(corner)
-    if R:
-        exits, ms["exit count"] = event_ms(lambda: P._exits(f, born, grown) if grown else [])
-    else:
-        exits = []
-    new_corners = sum(int(c.shape[0]) for c in grown)
-
-    def count():
-        c = ops.mtet_count(f, flags)
-        incl = torch.cumsum(c.reshape(-1), dim=0)
-        return (incl - c.reshape(-1)).reshape(c.shape), int(incl[-1])
-    (first, total), ms["count"] = event_ms(count)
-    ids, ms["emit"] = event_ms(lambda: ops.mtet_emit(f, flags, first, total))
-    (edge, inverse), ms["unique"] = event_ms(lambda: torch.unique(ids.reshape(-1), sorted=True, return_inverse=True))
-    verts, ms["vertices"] = event_ms(lambda: ops.mtet_vertices(edge, f, tables))
-    ms = {s: ms[s] for s in BASE + (GROW if R else ()) + TAIL}              # in the order they run
-    return ms, {"h": h, "dims": dims, "corners": int(np.prod([int(d) for d in dims])), "active_corners": active0,
-                "new_corners": new_corners, "exits": exits, "triangles": total, "vertices": int(edge.shape[0])}
+    def stage(name, thunk):
+        out, t = event_ms(thunk)
+        if name == "compaction":
+            sizes.append(int(out.shape[0]))
+        stage.growing = (stage.growing or name == "grow") and name in in_rounds
+        ms[in_rounds[name] if stage.growing else name] += t
+        return out
+    stage.growing = False
+    verts, faces, info = P.mesh_from_cloud(points, normals, k=K, sigma=SIGMA, _stage=stage, **({"close_holes": R} if R else {}))
+    return ms, {"h": info["h"], "dims": info["dims"], "corners": int(np.prod([int(d) for d in info["dims"]])), "active_corners": sizes[0],
+                "new_corners": sum(sizes[1:]), "exits": info["grown_cells"], "triangles": int(faces.shape[0]),
+                "vertices": int(verts.shape[0])}
 
 
 def leg(R, cloud_dir, out_path):
@@ -254,10 +209,9 @@ for c, cloud in enumerate([str(n) for n in SHEETS]):
     for name in ("R = 2", "R = 8"):
         diff = L[name]["sum_median_ms"] - L["R = 0"]["sum_median_ms"]
         n = max(len(L[name]["exits"]), 1)
-        grow = sum(L[name]["stages"][s]["median_ms"] for s in GROW[:4])
+        grow = sum(L[name]["stages"][s]["median_ms"] for s in GROW)
         say(f"  {name} - R = 0: {diff:+.3f} ms on the sum ({100 * diff / L['R = 0']['sum_median_ms']:+.1f} %); the rounds "
-            f"{grow:.3f} ms = {grow / n:.3f} ms per round, of it the sweep {L[name]['stages']['grow sweep']['median_ms'] / n:.3f}; the exit "
-            f"count, once, {L[name]['stages']['exit count']['median_ms']:.3f}")
+            f"{grow:.3f} ms = {grow / n:.3f} ms per round, of it the sweep {L[name]['stages']['grow sweep']['median_ms'] / n:.3f}")
     record["clouds"].append(entry)
 say(f"medians over {rounds} rounds of fresh processes of the medians of {reps} calls after one untimed call, device events; "
     f"box: {box}   commit: {commit}")

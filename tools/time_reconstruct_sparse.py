@@ -1,15 +1,13 @@
 #!/usr/bin/env python3
-"""The two layouts of mesh_from_cloud side by side, by tools/time_reconstruct.py's method: device events per stage, the median
-of --reps calls after one untimed call.  layout="dense" and layout="sparse" legs alternate in FRESH processes over --rounds
-rounds; a leg's figure is the median over the rounds of its medians, its spread the largest minus the smallest of them.  By the
+"""The two layouts of mesh_from_cloud side by side, by tools/time_reconstruct.py's method: device events per stage (the library's
+own stages, through mesh_from_cloud's _stage hook), the median of --reps calls after one untimed call.  layout="dense" and
+layout="sparse" legs alternate in FRESH processes over --rounds rounds; a leg's figure is the median over the rounds of its medians, its spread the largest minus the smallest of them.  By the
 project's rule a difference counts only beyond three spreads of the dense leg.  Every leg also records its peak of allocated
 device memory over one whole mesh_from_cloud call (torch.cuda.max_memory_allocated above what the cloud itself holds).
 Shapes: the bumpy sheets of tools/time_reconstruct.py at 20 000, 262 144 and 1 048 576 points (normals from
 estimate_normals(16, search="grid", orient="propagate")), and a closed unit sphere of 4 194 304 points with analytic normals,
-whose box at the default cell the dense layout refuses.  The dense path's code is the parent commit's, so its leg is the parent.
-  python tools/time_reconstruct_sparse.py [--out-dir profiles/reconstruct_sparse] [--commit ID] [--reps 5] [--rounds 3]
-  ... --direct-lib PATH    a third leg: the sparse layout on a library whose count kernel has no LDS tile, built with
-      build.build(defines=["PF_RECON_SPARSE_COUNT_DIRECT"], tag="rsdirect", only=("recon_sparse.hip",))"""
+whose box at the default cell the dense layout refuses.
+  python tools/time_reconstruct_sparse.py [--out-dir profiles/reconstruct_sparse] [--commit ID] [--reps 5] [--rounds 3]"""
 import json, os, socket, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -20,18 +18,11 @@ args = sys.argv[1:]
 opt = lambda name, default: args[args.index(name) + 1] if name in args else default
 out_dir = opt("--out-dir", os.path.join(ROOT, "profiles", "reconstruct_sparse"))
 commit, reps, rounds = opt("--commit", "unknown"), int(opt("--reps", 5)), int(opt("--rounds", 3))
-direct_lib = opt("--direct-lib", None)
 SHEETS = (20000, 262144, 1048576)
 SPHERE = 4194304
 K, SIGMA = 8, 1.0
 
-from puflow_amd import _lib, ops, reconstruct as P
-
-
-def event_ms(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record(); out = fn(); b.record(); torch.cuda.synchronize()
-    return out, a.elapsed_time(b)
+from puflow_amd import _lib, reconstruct as P
 
 
 STAGES = {"dense": ("cell-size search", "mark", "compaction", "K search", "IMLS", "count", "emit", "unique", "vertices"),
@@ -39,60 +30,19 @@ STAGES = {"dense": ("cell-size search", "mark", "compaction", "K search", "IMLS"
 
 
 def staged(points, normals, layout):
-    """mesh_from_cloud with an event pair around every stage: ({stage: ms}, info)"""
-    ms = {}
-    (m, lo, hi), ms["cell-size search"] = event_ms(lambda: P._stats(points, True))
-    h = float(np.sqrt(m))
-    dims, host_tables = P.corner_tables(lo, hi, h, layout)
-    tables = [torch.from_numpy(t).cuda() for t in host_tables]
-    if layout == "dense":
-        flags, ms["mark"] = event_ms(lambda: ops.recon_mark(points, tables))
+    """mesh_from_cloud with an event pair around every stage, through its _stage hook: ({stage: ms}, info)"""
+    ms, active = {}, []
 
-        def compact():
-            corner = torch.nonzero(flags.reshape(-1)).reshape(-1)
-            return corner, torch.stack([tables[0][corner % dims[0]], tables[1][(corner // dims[0]) % dims[1]],
-                                        tables[2][corner // (dims[0] * dims[1])]], dim=1)
-    else:
-        (blocks, links), ms["block list"] = event_ms(lambda: P.block_list(points, tables))
-        flags, ms["mark"] = event_ms(lambda: ops.recon_mark_sparse(points, tables, blocks))
-
-        def compact():
-            slot = torch.nonzero(flags.reshape(-1)).reshape(-1)
-            i, j, k = P.slot_corners(slot, blocks, dims)
-            return slot, torch.stack([tables[0][i], tables[1][j], tables[2][k]], dim=1)
-    (corner, query), ms["compaction"] = event_ms(compact)
-    (idx, _), ms["K search"] = event_ms(lambda: ops.knn_grid(points[None], query[None], K))
-
-    def value():
-        f = torch.empty(flags.shape, dtype=torch.float32, device="cuda")
-        f.reshape(-1)[corner] = ops.imls(query, points, normals, idx[0], SIGMA * h)
-        return f
-    f, ms["IMLS"] = event_ms(value)
-    if layout == "dense":
-        def count():
-            c = ops.mtet_count(f, flags)
-            incl = torch.cumsum(c.reshape(-1), dim=0)
-            return (incl - c.reshape(-1)).reshape(c.shape), int(incl[-1])
-        (first, total), ms["count"] = event_ms(count)
-        ids, ms["emit"] = event_ms(lambda: ops.mtet_emit(f, flags, first, total))
-    else:
-        def count():                                                        # with the compaction, the sort and the prefix sum
-            c = ops.mtet_count_sparse(f, flags, blocks, links, dims).reshape(-1)
-            slots = torch.nonzero(c).reshape(-1)
-            i, j, k = P.slot_corners(slots, blocks, dims)
-            cells = slots[torch.sort((k * dims[1] + j) * dims[0] + i).indices]
-            n = c[cells].to(torch.int64)
-            incl = torch.cumsum(n, dim=0)
-            return cells, incl - n, int(incl[-1])
-        (cells, first, total), ms["count"] = event_ms(count)
-        ids, ms["emit"] = event_ms(lambda: ops.mtet_emit_sparse(f, flags, blocks, links, dims, cells, first, total))
-    (edge, inverse), ms["unique"] = event_ms(lambda: torch.unique(ids.reshape(-1), sorted=True, return_inverse=True))
-    if layout == "dense":
-        verts, ms["vertices"] = event_ms(lambda: ops.mtet_vertices(edge, f, tables))
-    else:
-        verts, ms["vertices"] = event_ms(lambda: ops.mtet_vertices_sparse(edge, f, blocks, links, tables))
-    return ms, {"h": h, "dims": dims, "corners": int(np.prod([int(d) for d in dims])), "active_corners": int(corner.shape[0]),
-                "blocks": int(blocks.shape[0]) if layout == "sparse" else 0, "triangles": total, "vertices": int(edge.shape[0])}
+    def stage(name, thunk):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(); out = thunk(); b.record(); torch.cuda.synchronize()
+        ms[name] = a.elapsed_time(b)
+        if name == "compaction":
+            active.append(int(out.shape[0]))
+        return out
+    verts, faces, info = P.mesh_from_cloud(points, normals, k=K, sigma=SIGMA, layout=layout, _stage=stage)
+    return ms, {"h": info["h"], "dims": info["dims"], "corners": int(np.prod([int(d) for d in info["dims"]])), "active_corners": active[0],
+                "blocks": info["blocks"], "triangles": int(faces.shape[0]), "vertices": int(verts.shape[0])}
 
 
 def leg(layout, cloud_dir, out_path):
@@ -149,8 +99,8 @@ def say(s):
 
 torch.zeros(1, device="cuda"); torch.cuda.synchronize()
 box = "%s / %s" % (socket.gethostname(), torch.cuda.get_device_name(0))
-legs = [("dense", None), ("sparse", None)] + ([("sparse, count without the LDS tile", direct_lib)] if direct_lib else [])
-results = {name: [] for name, _ in legs}
+legs = ("dense", "sparse")
+results = {name: [] for name in legs}
 with tempfile.TemporaryDirectory() as tmp:
     for n in SHEETS:
         points = synth_patches(1, n, seed=5, surface=True)[0].to("cuda:0")
@@ -163,11 +113,10 @@ with tempfile.TemporaryDirectory() as tmp:
     del v
     torch.cuda.empty_cache()
     for r in range(rounds):
-        for name, lib in legs:
+        for name in legs:
             path = os.path.join(tmp, "leg.json")
-            env = dict(os.environ, **({"PF_LIB_PATH": lib} if lib else {}))
-            subprocess.run([sys.executable, os.path.abspath(__file__), "--leg", name.split(",")[0], "--clouds", tmp, "--json", path,
-                            "--reps", str(reps)], check=True, env=env, timeout=600)
+            subprocess.run([sys.executable, os.path.abspath(__file__), "--leg", name, "--clouds", tmp, "--json", path,
+                            "--reps", str(reps)], check=True, timeout=600)
             with open(path) as fh:
                 results[name].append(json.load(fh))
 
@@ -179,14 +128,14 @@ for c, cloud in enumerate([str(n) for n in SHEETS] + ["sphere"]):
     entry = {"cloud": cloud, "legs": {}}
     first = results["dense"][0][c]
     say(f"{'bumpy sheet' if cloud != 'sphere' else 'unit sphere, analytic normals'}, {first['points']} points")
-    for name, _ in legs:
+    for name in legs:
         per_round = [results[name][r][c] for r in range(rounds)]
         if "refused" in per_round[0]:
             say(f"  {name}: refused - {per_round[0]['refused']}")
             entry["legs"][name] = {"refused": per_round[0]["refused"]}
             continue
         info = per_round[0]
-        stages = STAGES[name.split(",")[0]]
+        stages = STAGES[name]
         e = {k: info[k] for k in ("h", "dims", "corners", "active_corners", "blocks", "triangles", "vertices", "open_edges", "mesh_crc")}
         e["stages"] = {s: {"median_ms": mid([p["stages"][s] for p in per_round]), "spread_ms": spread([p["stages"][s] for p in per_round])}
                        for s in stages}
